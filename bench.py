@@ -10,15 +10,18 @@ BASELINE.json (B=1024 independent initial poses, reference tracking, horizon 30)
 every rank solves its own batch of the same size (weak scaling, no data-path collective; the
 instances are independent) and `value` is the whole-job rate.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--batch B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--batch B] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
   python bench.py --gpus N --single-process        # ONE process drives the N devices (no torch, no process group): same line schema
   python bench.py --gpus N [--single-process] --dry-run   # rehearsal of either multi-GPU path on a box without GPUs (value: null)
-  ... --no-extra-legs                               # under a profiler: the timed loop's kernels only
+  ... --full --no-extra-legs                        # under a profiler: the timed loop's kernels only
 
-Beside `value` (median of >= 25 regions of exactly K steps, four resident launches in flight) the line carries `value_200_step_regions`
-/ `ramp_drain_share` (the same loop in long regions), `value_one_launch_in_flight` (a caller whose step k + 1 needs step k),
-`admm_stock_mode` (the restated OSQP alone), `roofline` (HBM; + `roofline_fp64`, `roofline_assembly`), `cpu_baseline` (+ `_stock`).
+A plain run sets up, ramps the clocks, runs the W warm-up steps, times exactly K steps once (four resident launches in flight;
+`value`, `ms_per_step`), writes the last step's outputs with --dump-outputs DIR (DIR/z.npy, u0, status, iters, resid: float64),
+and prints the line.  With --full the timed region of K steps is repeated (`value` = median of >= --repeats regions) and the
+line also carries `value_200_step_regions` / `ramp_drain_share` (the same loop in long regions), `value_one_launch_in_flight` (a
+caller whose step k + 1 needs step k), `admm_stock_mode` (the restated OSQP alone), `roofline` (HBM; + `roofline_fp64`,
+`roofline_assembly`), the host-buffer paths, `cpu_baseline` (+ `_stock`) and the parity legs against the C port.
 
 `--gpus N` with N > 1 and no launcher environment (RANK / WORLD_SIZE unset) starts the N ranks itself: this
 process, which has not touched a GPU yet, runs `python -m torch.distributed.run --nproc-per-node N bench.py ...`
@@ -294,6 +297,25 @@ def pmc_traffic_bytes(kernel_prefix, B, lib_version, config=2):
         return None, "profiles/%s/pmc_summary.json has no counters for this kernel at B = %d" % (rnd, B)
 
 
+DUMP_LIMIT = 64_000_000    # bytes: all files --dump-outputs writes together
+
+
+def dump_outputs(dirname, sol, budget=DUMP_LIMIT, suffix=""):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step (z, u0, status, iters, resid of every
+    instance) as DIR/<name><suffix>.npy in float64.  Above `budget` bytes a fixed, seeded sample of the instances is written
+    instead, the same one every run; DIR/rows<suffix>.npy then holds their indices."""
+    arrs = {k: np.asarray(getattr(sol, k), np.float64) for k in ("z", "u0", "status", "iters", "resid")}
+    B = arrs["status"].shape[0]
+    per_row = sum(a[:1].nbytes for a in arrs.values())
+    if per_row * B > budget:
+        rows = np.sort(np.random.default_rng(0).choice(B, (budget - 4096) // (per_row + 8), replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(dirname, k + suffix + ".npy"), a)
+
+
 def check_ranks(args, dist, rank, world, ranks):
     """Every rank holds the same per-rank reports (bench_dist.rank_reports all-gathers them): all of them leave, non-zero and
     before rank 0 prints, unless the process group has --gpus ranks and every rank drives a device of its own."""
@@ -367,11 +389,15 @@ def single_process_bench(args, real_stdout):
     dts = timed(args.repeats)
     dt = float(np.median(dts))
     # per-device status counts of the timed launches' results (the torchrun line's `ranks`)
-    ranks = []
+    ranks, sols = [], []
     for r, h in enumerate(hs):
-        st = h.download(B, want_y=False).status
+        sols.append(h.download(B, want_y=False))
+        st = sols[-1].status
         ranks.append({"rank": r, "device": int(h.cfg.device), "solved": int(np.sum(st == 1)), "solved_inaccurate": int(np.sum(st == 2)),
                       "infeasible": int(np.sum(st == -3)), "other": int(np.sum((st != 1) & (st != 2) & (st != -3)))})
+    if args.dump_outputs:          # the whole world x B batch, shards in order
+        dump_outputs(args.dump_outputs, mpmpc.Solution(*[np.concatenate([getattr(s, k) for s in sols])
+                                                         for k in ("z", "u0", "status", "iters", "resid")], None))
     # the other operating point: one launch in flight per handle
     for h in hs:
         h.set_pipeline(1)
@@ -478,6 +504,14 @@ def _main(real_stdout):
                          "line it prints carries dry_run: true and value: null - nothing in it is a measurement")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="override any solver setting of the device path (exploration; the oracle keeps its defaults)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the timed region repeated (--repeats, value = median repeat), the "
+                         "200-step regions, one launch in flight, the restated OSQP at stock settings, the rooflines, the host-buffer "
+                         "paths, the CPU baseline and the parity legs, the multi-rank gather check.  Without it a run times exactly "
+                         "--steps steps once after the warm-up and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (z, u0, status, iters, resid) as DIR/<name>.npy, "
+                         "float64, at most 64 MB in all (a fixed, seeded sample of the instances above that)")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -585,14 +619,17 @@ def _main(real_stdout):
     # collective barrier) and the sync that ends them; the clock stops when this rank's device is idle, the collective
     # barrier that follows is timed on its own (`barrier_ms`) - it is launcher overhead, not solve time (VERDICT r3 "weak" 12).
     dev = "cuda" if (dist is not None and not args.dry_run) else None
-    # (at least --repeats, and enough of them for >= 30 ms of timed launches in total: a pilot region sizes it, every rank the same)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        h.solve_resident(B)
-    h.sync()
-    pilot = bench_dist.max_over_ranks(dist, time.perf_counter() - t0, device=dev)
-    repeats = int(min(400, max(1, args.repeats, -(-0.03 // max(pilot, 1e-6)))))
+    # Without --full the region runs once: exactly --steps timed steps.
+    repeats = 1
+    if args.full:
+        # (at least --repeats, and enough of them for >= 30 ms of timed launches in total: a pilot region sizes it, every rank the same)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            h.solve_resident(B)
+        h.sync()
+        pilot = bench_dist.max_over_ranks(dist, time.perf_counter() - t0, device=dev)
+        repeats = int(min(400, max(1, args.repeats, -(-0.03 // max(pilot, 1e-6)))))
     dts, mine, barrier_s = [], [], []
     for _ in range(repeats):
         barrier()
@@ -608,11 +645,15 @@ def _main(real_stdout):
     med = int(np.argsort(dts)[len(dts) // 2])
     dt = float(dts[med])                                                       # median repeat
     dt_ranks = bench_dist.all_ranks(dist, mine[med], device=dev)
+    # what the last timed step computed (the legs of --full below launch the same solves again, or other ones)
+    sol = h.download(B, want_y=False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sol, DUMP_LIMIT // world, "" if world == 1 else "_rank%d" % rank)
     # The same loop in regions of 200 steps: a region of K = 20 steps pays the ramp and the drain of the
     # launches in flight - the chip holds fewer kernels at its two ends - which a long-running caller does not.  Reported
     # beside `value` (value_200_step_regions, ramp_drain_share), never as it.
     dt200 = None
-    if not args.dry_run and args.steps < 200 and not args.no_extra_legs:          # (not under the profiler: 1 000 more launches per pass)
+    if args.full and not args.dry_run and args.steps < 200 and not args.no_extra_legs:   # (not under the profiler: 1 000 more launches per pass)
         d2 = []
         for _ in range(5):
             barrier()
@@ -626,8 +667,6 @@ def _main(real_stdout):
     if args.dry_run:
         # the rehearsal ends here: what the ranks exchange - the gathered result buffer against one process solving the whole
         # batch, the per-rank reports - and the line's multi-rank fields; no figure of it is a measurement
-        sol = h.download(B, want_y=False)
-
         def solve_whole_dry():
             cfg1 = mpmpc.make_config(N, Q, R, QN, scenarios.XMIN, scenarios.XMAX, scenarios.UMIN, scenarios.UMAX, scenarios.AY_MAX,
                                      scenarios.CAR_LENGTH, circular=True, max_batch=B * world, device=local_rank)
@@ -655,6 +694,54 @@ def _main(real_stdout):
             dist.destroy_process_group()
         return
 
+    nat_tt = native_tt_path(cfg, settings)
+    nat = native_path(cfg, settings) or nat_tt
+
+    def headline(ranks):
+        """the fields of every line: the figure, how it was taken, the workload, and what the timed launches returned"""
+        value = world * B * args.steps / dt
+        st, cnt = np.unique(sol.status, return_counts=True)
+        # iters[:, 0] is OSQP's iteration counter: 1 = the early attempt alone (general kernels: OSQP's first iterate, one KKT
+        # solve, as its start; reduced-native kernels: no OSQP iterate at all, the 1 marks the attempt); only an instance that
+        # fell back to the full OSQP run reports more
+        adm = np.where(sol.iters[:, 0] > settings.early_polish, sol.iters[:, 0], 0) if settings.polish and settings.early_polish > 0 else sol.iters[:, 0]
+        return {
+            "metric": "MPC QP solves/sec (batch, horizon N=%d)" % N,
+            "value": value, "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "world_size": int(dist.get_world_size()) if dist is not None else 1,
+            "ms_per_step_by_rank": [1e3 * t / args.steps for t in dt_ranks],
+            "repeats": repeats, "ms_per_step_min": 1e3 * float(min(dts)) / args.steps, "ms_per_step_max": 1e3 * float(max(dts)) / args.steps,
+            "value_from": "median of %d repeats of the timed region of exactly %d steps (max over ranks of every repeat)" % (repeats, args.steps),
+            "barrier_ms": 1e3 * float(np.median(barrier_s)),
+            "launches_in_flight": int(args.pipeline), "prewarm": int(n_prewarm), "prewarm_fixed": int(args.prewarm),
+            "config": {"workload": "config%d: batch=%d independent poses per GPU, %s weights, N=%d, %s corridor; %s" %
+                                   (args.config, B, sc_all.weights, N, "obstacle" if sc_all.obstacles else "free",
+                                    algorithm_text(cfg, settings)),
+                       "batch_per_gpu": B, "horizon": N, "parallelism": "batch-shard x%d" % world},
+            "rccl_world_size": int(dist.get_world_size()) if dist is not None else 0,      # 0: no process group (one process, no launcher)
+            "ranks": ranks,              # per rank: HIP device ordinal of its handle, status counts of its shard
+            "library": h.lib.mpmpc_version().decode(),
+            "status_counts": {int(s): int(c) for s, c in zip(st, cnt)},
+            "iters": {"start_steps_per_instance": 0 if (nat or not settings.early_start) else (int(settings.early_polish) if settings.polish else 0),
+                      "admm_loop_iterations_mean": float(adm.mean()), "admm_loop_iterations_max": int(adm.max()),
+                      "instances_in_admm_fallback": int(np.sum(adm > 0)),
+                      "ipm_mean": float(sol.iters[:, 1].mean()), "ipm_max": int(sol.iters[:, 1].max()),
+                      "ipm_histogram": {int(k): int(v) for k, v in zip(*np.unique(sol.iters[:, 1], return_counts=True))}},
+        }
+
+    if not args.full:
+        ranks = bench_dist.rank_reports(dist, cfg.device, sol.status, device=dev)
+        check_ranks(args, dist, rank, world, ranks)
+        if rank == 0:
+            real_stdout.write(json.dumps(headline(ranks)) + "\n")
+            real_stdout.flush()
+        h.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     # per-launch durations of the SAME launch pattern (double-buffered resident launches), HIP events on the streams the
     # kernels are launched on: what rocprofv3 --kernel-trace shows for the timed loop
     n_prof = max(8, min(args.steps, 64))
@@ -668,7 +755,6 @@ def _main(real_stdout):
         ks.append(s)
     ms_k1, ms_alone = float(np.mean(ka)), float(np.mean(ks))
     ms_k2 = float(np.mean(each[2:])) if each.size > 4 else float(np.mean(each))      # (the first two start on an empty chip)
-    sol = h.download(B, want_y=False)
 
     # The OTHER operating point (VERDICT r4 "weak" 4): ONE launch in flight - a caller whose step k + 1 needs the result of
     # step k (the reference's own loop, src/simulation.py:134-140) cannot pipeline.  Same K, same repeats, same clock.
@@ -772,18 +858,8 @@ def _main(real_stdout):
     check_ranks(args, dist, rank, world, ranks)
 
     if rank == 0:
-        value = world * B * args.steps / dt
-        out = {
-            "metric": "MPC QP solves/sec (batch, horizon N=%d)" % N,
-            "value": value, "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "world_size": int(dist.get_world_size()) if dist is not None else 1,
-            "ms_per_step_by_rank": [1e3 * t / args.steps for t in dt_ranks],
-            "repeats": repeats, "ms_per_step_min": 1e3 * float(min(dts)) / args.steps, "ms_per_step_max": 1e3 * float(max(dts)) / args.steps,
-            "value_from": "median of %d repeats of the timed region of exactly %d steps (max over ranks of every repeat)" % (repeats, args.steps),
-            "barrier_ms": 1e3 * float(np.median(barrier_s)),
-            "launches_in_flight": int(args.pipeline), "prewarm": int(n_prewarm), "prewarm_fixed": int(args.prewarm),
+        out = headline(ranks)
+        out.update({
             "value_200_step_regions": (world * B * 200 / dt200) if dt200 else world * B * args.steps / dt,
             "ramp_drain_share": (1.0 - (world * B * args.steps / dt) / (world * B * 200 / dt200)) if dt200 else 0.0,
             "value_one_launch_in_flight": (world * B * args.steps / dt1) if dt1 else None,
@@ -793,24 +869,14 @@ def _main(real_stdout):
                                      "note": "mpmpc_set_pipeline(h, 1): every launch waits for the one before, as in a loop whose step "
                                              "k + 1 needs step k's control (src/simulation.py:134-140); same K, same repeats as `value`"},
             "admm_stock_mode": admm_stock if admm_stock is not None else {"value": None, "note": "skipped: --no-extra-legs"},
-            "config": {"workload": "config%d: batch=%d independent poses per GPU, %s weights, N=%d, %s corridor; %s" %
-                                   (args.config, B, sc_all.weights, N, "obstacle" if sc_all.obstacles else "free",
-                                    algorithm_text(cfg, settings)),
-                       "batch_per_gpu": B, "horizon": N, "parallelism": "batch-shard x%d" % world},
-        }
+        })
         if pipelined:
             out["pipelined_two_handles"] = pipelined
-        out["rccl_world_size"] = int(dist.get_world_size()) if dist is not None else 0      # 0: no process group (one process, no launcher)
-        out["ranks"] = ranks              # per rank: HIP device ordinal of its handle, status counts of its shard
         if gather_check:
             out["gather_check"] = gather_check
-        lib_version = h.lib.mpmpc_version().decode()
-        out["library"] = lib_version
+        lib_version = out["library"]
         bytes_k2 = algorithmic_bytes_per_solve(N) * B
-        nat_tt = native_tt_path(cfg, settings)
-        nat = native_path(cfg, settings)
         k2_name = "mpmpc_reduced_t_kernel" if nat_tt else ("mpmpc_reduced_kernel" if nat else "mpmpc_solve_kernel")
-        nat = nat or nat_tt
         traffic, traffic_src = pmc_traffic_bytes(k2_name, B, lib_version, args.config)
         # ms_k2: average duration of a launch of the timed pattern (HIP events around each launch on its own stream; with two
         # launches in flight each takes longer than alone and two run side by side); span: first start to last end of the
@@ -869,17 +935,6 @@ def _main(real_stdout):
                                             "guide's measured-achievable HBM rate (6.29 TB/s = 79 % of the peak): a reading above it "
                                             "(above_achievable) means part of the stores was still in the 256 MB Infinity Cache when "
                                             "the event fired, not that HBM moved that much (VERDICT r4 \"weak\" 8)"}
-        st, cnt = np.unique(sol.status, return_counts=True)
-        out["status_counts"] = {int(s): int(c) for s, c in zip(st, cnt)}
-        # iters[:, 0] is OSQP's iteration counter: 1 = the early attempt alone (general kernels: OSQP's first iterate, one KKT
-        # solve, as its start; reduced-native kernels: no OSQP iterate at all, the 1 marks the attempt); only an instance that
-        # fell back to the full OSQP run reports more
-        adm = np.where(sol.iters[:, 0] > settings.early_polish, sol.iters[:, 0], 0) if settings.polish and settings.early_polish > 0 else sol.iters[:, 0]
-        out["iters"] = {"start_steps_per_instance": 0 if (nat or not settings.early_start) else (int(settings.early_polish) if settings.polish else 0),
-                        "admm_loop_iterations_mean": float(adm.mean()), "admm_loop_iterations_max": int(adm.max()),
-                        "instances_in_admm_fallback": int(np.sum(adm > 0)),
-                        "ipm_mean": float(sol.iters[:, 1].mean()), "ipm_max": int(sol.iters[:, 1].max()),
-                        "ipm_histogram": {int(k): int(v) for k, v in zip(*np.unique(sol.iters[:, 1], return_counts=True))}}
         # the same step from HOST buffers (mpmpc_solve: upload + assembly and solve in one launch + download): reported, never `value`
         t1 = time.perf_counter()
         for _ in range(5):

@@ -8,7 +8,7 @@ for v in "$@"; do
   [ -f profiles/_ab/$v.so ] || continue
   cp profiles/_ab/$v.so $D/libmpmpc.so
   for c in $CS; do
-    python bench.py --config $c --steps 10 --warmup 2 --no-cpu > /tmp/ab.json 2>/dev/null
+    python bench.py --full --config $c --steps 10 --warmup 2 --no-cpu > /tmp/ab.json 2>/dev/null
     python - "$v" "$c" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab.json"))

@@ -9,15 +9,15 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/$ROUND
 mkdir -p "$O"
 cd "$R"
-python bench.py > "$O/bench_cfg2.json" 2> "$O/bench_cfg2.err"
-for c in 3 4 5; do python bench.py --config $c --steps 20 --warmup 2 > "$O/bench_cfg$c.json" 2>/dev/null; done
+python bench.py --full > "$O/bench_cfg2.json" 2> "$O/bench_cfg2.err"
+for c in 3 4 5; do python bench.py --full --config $c --steps 20 --warmup 2 > "$O/bench_cfg$c.json" 2>/dev/null; done
 # the verdict semantics ADVICE r2 asked to see side by side: every proven infeasibility reported (phase1_accept = 0)
-for c in 4 5; do python bench.py --config $c --steps 20 --warmup 2 --no-cpu --set phase1_accept=0 > "$O/bench_cfg${c}_strict.json" 2>/dev/null; done
-python bench.py --batch 65536 --steps 5 --warmup 1 --no-cpu > "$O/bench_cfg2_b65536.json" 2>/dev/null
+for c in 4 5; do python bench.py --full --config $c --steps 20 --warmup 2 --no-cpu --set phase1_accept=0 > "$O/bench_cfg${c}_strict.json" 2>/dev/null; done
+python bench.py --full --batch 65536 --steps 5 --warmup 1 --no-cpu > "$O/bench_cfg2_b65536.json" 2>/dev/null
 cd /tmp; export TMPDIR=/tmp
 # (counter passes serialise the kernels and are slow per launch: few repeats, short clock ramp)
 PMC="--repeats 2 --prewarm 30"
-prof() { out=$1; shift; rocprofv3 "$@" --output-format csv -d "$O/$out" -- python3 "$R/bench.py" ${BENCH_ARGS:-} --no-cpu --no-extra-legs > "$O/$out.json" 2>/dev/null; }
+prof() { out=$1; shift; rocprofv3 "$@" --output-format csv -d "$O/$out" -- python3 "$R/bench.py" --full ${BENCH_ARGS:-} --no-cpu --no-extra-legs > "$O/$out.json" 2>/dev/null; }
 BENCH_ARGS="" prof trace --kernel-trace --stats
 # ... and of the driver's own command (20-step regions)
 BENCH_ARGS="--gpus 1 --steps 20 --warmup 5" prof trace_driver --kernel-trace --stats

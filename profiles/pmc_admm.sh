@@ -7,7 +7,7 @@ rm -rf "$O"; mkdir -p "$O"
 cd /tmp; export TMPDIR=/tmp
 for it in 100 300; do
   rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY \
-    --output-format csv -d "$O/it$it" -- python3 "$R/bench.py" --no-cpu --steps 3 --warmup 1 \
+    --output-format csv -d "$O/it$it" -- python3 "$R/bench.py" --full --no-cpu --steps 3 --warmup 1 \
     --set polish=0 --set check_termination=0 --set adaptive_rho=0 --set max_iter=$it > /dev/null 2>&1
 done
 python3 - "$O" <<'PY'

@@ -5,7 +5,7 @@ for v in "$@"; do
   ARGS=""
   for kv in $v; do ARGS="$ARGS --set $kv"; done
   for c in $CS; do
-    python bench.py --config $c --steps 10 --warmup 2 $ARGS > /tmp/sw.json 2>/dev/null
+    python bench.py --full --config $c --steps 10 --warmup 2 $ARGS > /tmp/sw.json 2>/dev/null
     python - "$v" "$c" <<'PY'
 import json, sys
 d = json.load(open("/tmp/sw.json"))

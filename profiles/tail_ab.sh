@@ -6,12 +6,12 @@ O=gpurun_out/$T
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 for c in 4 5; do
-  python bench.py --no-cpu --config $c --steps 20 --warmup 3 > $O/cfg${c}.json 2> $O/cfg${c}.err
-  python bench.py --no-cpu --config $c --steps 20 --warmup 3 --set phase1_accept=0 > $O/cfg${c}s.json 2> $O/cfg${c}s.err
+  python bench.py --full --no-cpu --config $c --steps 20 --warmup 3 > $O/cfg${c}.json 2> $O/cfg${c}.err
+  python bench.py --full --no-cpu --config $c --steps 20 --warmup 3 --set phase1_accept=0 > $O/cfg${c}s.json 2> $O/cfg${c}s.err
 done
-python bench.py --no-cpu --steps 200 > $O/cfg2.json 2> $O/cfg2.err
-rocprofv3 --kernel-trace --stats -d $O/prof4 -o p4 -- python3 bench.py --no-cpu --config 4 --steps 20 --warmup 3 > /dev/null 2> $O/prof4.err
-rocprofv3 --kernel-trace --stats -d $O/prof4s -o p4s -- python3 bench.py --no-cpu --config 4 --steps 20 --warmup 3 --set phase1_accept=0 > /dev/null 2> $O/prof4s.err
+python bench.py --full --no-cpu --steps 200 > $O/cfg2.json 2> $O/cfg2.err
+rocprofv3 --kernel-trace --stats -d $O/prof4 -o p4 -- python3 bench.py --full --no-cpu --config 4 --steps 20 --warmup 3 > /dev/null 2> $O/prof4.err
+rocprofv3 --kernel-trace --stats -d $O/prof4s -o p4s -- python3 bench.py --full --no-cpu --config 4 --steps 20 --warmup 3 --set phase1_accept=0 > /dev/null 2> $O/prof4s.err
 python - $O <<'PY'
 import json, sys, glob, csv, os
 O = sys.argv[1]
