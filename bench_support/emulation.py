@@ -192,8 +192,19 @@ class EmuBackend:
     def set_path(self, kappa, v_ref, ds_next):
         self.t.kappa, self.t.v_ref, self.t.ds_next = (np.ascontiguousarray(a, float) for a in (kappa, v_ref, ds_next))
 
+    def _check_wp(self, wp):
+        """what mpmpc_upload refuses, with its message: a start outside the path, or on an open path a horizon that passes
+        the last waypoint (the reference's get_waypoint exits there, src/reference_path.py:367-369)"""
+        n_wp = self.t.kappa.size
+        if np.any((wp < 0) | (wp >= n_wp)):
+            raise mpmpc.MpmpcError("mpmpc error -1: wp_id out of range")                 # MPMPC_E_ARG
+        if not self.cfg.circular and np.any(wp + self.cfg.N >= n_wp):
+            raise mpmpc.MpmpcError("mpmpc error -1: Reached end of path!")
+
     def solve(self, wp_id, x0, cc_prev, lb=None, ub=None, want_y=False):
-        qp = self.emu.assemble(self.cfg, self.t, (np.asarray(wp_id, np.int32), x0, cc_prev, lb, ub))
+        wp = np.asarray(wp_id, np.int32)
+        self._check_wp(wp)
+        qp = self.emu.assemble(self.cfg, self.t, (wp, x0, cc_prev, lb, ub))
         return self.emu.solve(self.cfg, self.settings, qp, G=64, want_y=want_y)
 
 
@@ -222,6 +233,7 @@ class DryHandle(EmuBackend):
         self.pipeline = int(depth)
 
     def upload(self, wp_id, x0, cc_prev, lb=None, ub=None):
+        self._check_wp(np.asarray(wp_id, np.int32))
         self.uploaded, self._sol = (np.asarray(wp_id, np.int32), x0, cc_prev, lb, ub), None
 
     def solve_resident(self, B):

@@ -245,7 +245,10 @@ int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, doubl
  *   init:  Ts = model.Ts; cum_lengths[n_wp] = cumsum(ReferencePath.segment_lengths); s[B] arc lengths;
  *          pose[B*3] = (x, y, psi); cc0[B*2N] previous plans or NULL for zeros (MPC.__init__).
  *   state: any output may be NULL.  alive: 1 running, 0 lap finished (s >= length), -1 ended by the
- *          reference's exit(1) after N-1 consecutive infeasible steps.
+ *          reference's exit(1) after N-1 consecutive infeasible steps, -2 ended by the reference's exit(1) at
+ *          the end of an OPEN path (circular = 0): the car's waypoint has wp_id + N >= n_wp, where
+ *          get_waypoint prints "Reached end of path!" (src/reference_path.py:367-369); wp_id and x0 hold the
+ *          state of that step, the car is not driven.  A circular path never ends a car with -2.
  * The rollout keeps its plans, waypoint ids and states in the handle's batch blocks: mpmpc_upload / mpmpc_solve /
  * mpmpc_assemble on the SAME handle overwrite them, after which mpmpc_rollout_step / _state / _set_counters return
  * MPMPC_E_STATE until mpmpc_rollout_init is called again.  (mpmpc_download and mpmpc_build_corridor are fine.) */

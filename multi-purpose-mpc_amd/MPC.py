@@ -7,6 +7,10 @@ src/MPC.py:14-257 so that src/simulation.py's body runs against it unchanged:
     u = mpc.get_control()            # np.array([v, delta]); u[0], u[1]
     mpc.show_prediction()
 
+On an open path (ReferencePath(..., circular=False)) `get_control()` ends the run where the reference does: when the
+horizon would read past the last waypoint (wp_id + N >= n_wp) it prints "Reached end of path!" and raises
+SystemExit(1) (src/reference_path.py:367-369), before any solve and whichever corridor the controller uses.
+
 What changed is where the work happens.  The reference rebuilds dense A/B, scipy.sparse P/A and a
 fresh OSQP workspace every step (src/MPC.py:61-159) and solves on one CPU thread
 (src/MPC.py:183).  Here the per-waypoint tables are uploaded once, and every step sends
@@ -137,6 +141,12 @@ class MPC:
         self.model.get_current_waypoint()
         self.model.spatial_state = self.model.t2s(reference_state=self.model.temporal_state,
                                                   reference_waypoint=self.model.current_waypoint)
+        rp = self.model.reference_path
+        if not rp.circular and self.model.wp_id + self.N >= rp.n_waypoints:
+            # the horizon passes the last waypoint of an open path: the reference's get_waypoint exits here
+            # (src/reference_path.py:367-369 via src/MPC.py:93-94), whichever way the corridor is computed
+            print('Reached end of path!')
+            raise SystemExit(1)
         wp, x0, cc, lb, ub = self._init_problem()
         sol = self.optimizer.solve(wp, x0, cc, lb, ub)
         self.last_solution = sol
@@ -287,7 +297,10 @@ class BatchMPC:
     def rollout(self, s, poses, n_steps, cc0=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
-        (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table."""
+        (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
+        alive: 1 running, 0 lap finished (s >= length), -1 ended after N - 1 consecutive infeasible steps
+        (src/MPC.py:218-220), -2 ended at the end of an open path (wp_id + N >= n_wp, where the reference's
+        get_waypoint exits: src/reference_path.py:367-369; wp_id and x0 are that step's, the car is not driven)."""
         rp = self._path
         if getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
             wps = rp.waypoints

@@ -668,7 +668,9 @@ __global__ __launch_bounds__(256) void mpmpc_corridor_select_kernel(PathGeom g, 
 }
 
 // K3a: where is each car on the path, and what is its path-relative state (one thread per car)
-__global__ __launch_bounds__(256) void mpmpc_localise_kernel(int B, int n_wp, const double* __restrict__ cum,
+// (alive: 0 = lap finished, s past the path's length; -2 = an open path's end reached, the reference's exit(1) in
+//  get_waypoint - wp_id and x0 are still written, they are the state the reference computed before it exited)
+__global__ __launch_bounds__(256) void mpmpc_localise_kernel(int B, int n_wp, int N, int circular, const double* __restrict__ cum,
                                                              const double* __restrict__ gx, const double* __restrict__ gy,
                                                              const double* __restrict__ gpsi, const double* __restrict__ s,
                                                              const double* __restrict__ pose, int* __restrict__ alive,
@@ -685,6 +687,7 @@ __global__ __launch_bounds__(256) void mpmpc_localise_kernel(int B, int n_wp, co
   }
   wp_id[i] = wp;
   ro_t2s(pose[3 * i], pose[3 * i + 1], pose[3 * i + 2], gx[wp], gy[wp], gpsi[wp], x0 + 3 * i);
+  if (ro_past_open_end(n_wp, N, circular != 0, wp)) alive[i] = -2;     // end of an open path
 }
 
 // K3b: use the solution (or the fallback plan), drive the plant one step (one thread per car)
@@ -1378,7 +1381,8 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int blocks = (B + 255) / 256;
   for (int t = 0; t < n_steps; ++t) {
-    hipLaunchKernelGGL(mpmpc_localise_kernel, dim3(blocks), dim3(256), 0, h->stream, B, h->n_wp, h->ro_cum, h->gx, h->gy,
+    hipLaunchKernelGGL(mpmpc_localise_kernel, dim3(blocks), dim3(256), 0, h->stream, B, h->n_wp, h->cfg.N,
+                       h->cfg.circular ? 1 : 0, h->ro_cum, h->gx, h->gy,
                        h->gpsi, h->ro_s, h->ro_pose, h->ro_alive, h->wp_id, h->x0, h->ro_shift);
     if (int rc = launch_solve(h, B, true, false)) return rc;      // (the plant step reads z and the status only)
     hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, h->stream, B, h->cfg.N, h->cfg.wheelbase, h->ro_Ts,

@@ -33,6 +33,11 @@ MPMPC_HD int ro_current_waypoint(const double* cum, int n_wp, double s) {
   return take_next ? nxt : (prv >= 0 ? prv : n_wp - 1);
 }
 
+// True when a car at waypoint wp can no longer be controlled on an OPEN path: the horizon's last stage would read
+// waypoint wp + N >= n_wp, where the reference's get_waypoint prints "Reached end of path!" and calls exit(1)
+// (src/reference_path.py:367-369, reached from MPC._init_problem, src/MPC.py:93-94).  A circular path never ends.
+MPMPC_HD bool ro_past_open_end(int n_wp, int N, bool circular, int wp) { return !circular && wp + N >= n_wp; }
+
 MPMPC_HD void ro_t2s(double px, double py, double ppsi, double wx, double wy, double wpsi, double* x0) {
   x0[0] = std::cos(wpsi) * (py - wy) - std::sin(wpsi) * (px - wx);
   double t = std::fmod(ppsi - wpsi + RO_PI, 2.0 * RO_PI);       // np.mod: result has the divisor's sign

@@ -321,6 +321,8 @@ class Handle:
         self._check(self.lib.mpmpc_rollout_step(self._h, self._ro_B, int(n_steps)))
 
     def rollout_state(self):
+        """-> dict(s, pose, cc, wp_id, x0, u, status, counter, alive) of the rollout's cars.  alive: 1 running, 0 lap
+        finished, -1 ended after N - 1 consecutive infeasible steps, -2 ended at the end of an open path (include/mpmpc.h)."""
         B, N = self._ro_B, self.N
         out = dict(s=np.zeros(B), pose=np.zeros((B, 3)), cc=np.zeros((B, 2 * N)), wp_id=np.zeros(B, np.int32),
                    x0=np.zeros((B, 3)), u=np.zeros((B, 2)), status=np.zeros(B, np.int32),

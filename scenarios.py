@@ -1,7 +1,8 @@
 """Seeded synthetic workloads for the batched QP path.
 
 Each scenario is a batch of independent controller instances on Sim_Track
-(src/simulation.py:20-35 of the reference): a waypoint index, a pose near that waypoint
+(src/simulation.py:20-35 of the reference; `make(..., track=real_track())`: on Real_Track, src/simulation.py:57-88, an
+open path whose starts stop N waypoints before its end): a waypoint index, a pose near that waypoint
 (turned into the spatial state the way MPC.get_control does, src/MPC.py:171-177) and a previous
 plan `cc_prev` (MPC.current_control).  Track tables come from the committed fixtures that the
 reference itself produced (tests/golden/make_golden.py).
@@ -24,6 +25,7 @@ UMIN = np.array([0.0, -math.tan(0.66) / CAR_LENGTH])      # simulation.py:108-10
 UMAX = np.array([1.0, math.tan(0.66) / CAR_LENGTH])
 XMIN, XMAX = np.full(3, -np.inf), np.full(3, np.inf)      # simulation.py:110-111
 AY_MAX = 4.0
+SIM_MAX_WIDTH = 0.23                                      # simulation.py:34
 WEIGHTS = {
     "stock": (np.array([1.0, 0.0, 0.0]), np.array([0.5, 0.0]), np.array([1.0, 0.0, 0.0])),  # simulation.py:101-103
     # the reference has no numeric time-optimal weights (README.md:56 is prose); build-defined:
@@ -56,10 +58,25 @@ class Track:
     lb_free: np.ndarray
     ub_obstacles: np.ndarray
     lb_obstacles: np.ndarray
+    # the car and the limits that come with the track (src/simulation.py:53-54 / :85-86 and :105-109)
+    car_length: float = CAR_LENGTH
+    car_width: float = CAR_WIDTH
+    umin: np.ndarray = dataclasses.field(default_factory=lambda: UMIN.copy())
+    umax: np.ndarray = dataclasses.field(default_factory=lambda: UMAX.copy())
+    circular: bool = True
+    max_width: float = SIM_MAX_WIDTH          # ReferencePath(max_width=...): the widest corridor of the track
+    # corridor columns the reference could build per start row (an open path ends: fewer than the table's width near
+    # the end); None = every column of every row
+    valid_cols_free: np.ndarray | None = None
+    valid_cols_obstacles: np.ndarray | None = None
 
     @property
     def n_wp(self):
         return self.x.size
+
+    def last_start(self, N):
+        """Last waypoint id a horizon of N stages may start at (an open path ends the run past it)."""
+        return self.n_wp - 1 if self.circular else self.n_wp - N - 1
 
 
 def sim_track(golden_dir: str = GOLDEN) -> Track:
@@ -69,6 +86,21 @@ def sim_track(golden_dir: str = GOLDEN) -> Track:
     return Track(g1["x"], g1["y"], g1["psi"], g1["kappa"], g1["ds_next"], g1["segment_lengths"],
                  g2["v_ref"], float(g1["length"][0]), g3["ub_free"], g3["lb_free"],
                  g3["ub_obstacles"], g3["lb_obstacles"])
+
+
+def real_track(golden_dir: str = GOLDEN) -> Track:
+    """Real_Track (src/simulation.py:57-88): an OPEN 302-waypoint path on a 767 x 867 grid, a 0.30 m car."""
+    g1 = np.load(os.path.join(golden_dir, "g1_path_real_track.npz"))
+    g2 = np.load(os.path.join(golden_dir, "g2_speed_profile_real.npz"))
+    g3 = np.load(os.path.join(golden_dir, "g3_corridor_real.npz"))
+    L, W = float(g1["car"][0]), float(g1["car"][1])
+    k = math.tan(0.66) / L
+    return Track(g1["x"], g1["y"], g1["psi"], g1["kappa"], g1["ds_next"], g1["segment_lengths"],
+                 g2["v_ref"], float(g1["length"][0]), g3["ub_free"], g3["lb_free"],
+                 g3["ub_obstacles"], g3["lb_obstacles"], car_length=L, car_width=W,
+                 umin=np.array([0.0, -k]), umax=np.array([1.0, k]), circular=bool(g1["circular"][0]),
+                 max_width=float(g1["max_width"][0]),
+                 valid_cols_free=g3["valid_cols_free"], valid_cols_obstacles=g3["valid_cols_obstacles"])
 
 
 @dataclasses.dataclass
@@ -105,15 +137,15 @@ def make(config: int, track: Track | None = None, B: int | None = None, N: int |
     N = int(N or spec["N"])
     rng = np.random.default_rng(spec["seed"])
     ubT, lbT = (tr.ub_obstacles, tr.lb_obstacles) if spec["obstacles"] else (tr.ub_free, tr.lb_free)
-    wp = rng.integers(0, tr.n_wp, B)
+    wp = rng.integers(0, tr.last_start(N) + 1, B)          # (an open path: only starts whose horizon stays on it)
     if N > ubT.shape[1]:
         raise ValueError("the corridor tables of the golden track hold %d stages; N = %d needs its own tables" % (ubT.shape[1], N))
     ub, lb = ubT[wp, :N], lbT[wp, :N]
     u1, u2 = rng.uniform(-1.0, 1.0, B), rng.uniform(-0.2, 0.2, B)
     if spec["obstacles"]:      # offset inside the first horizon corridor: most, not all, feasible
         e_y = (lb[:, 0] + ub[:, 0]) / 2 + 0.3 * u1 * (ub[:, 0] - lb[:, 0]) / 2
-    else:
-        e_y = 0.02 * u1
+    else:                      # 0.02 m on Sim_Track, in proportion to the track's corridor width elsewhere
+        e_y = 0.02 * u1 * (tr.max_width / SIM_MAX_WIDTH)
     e_psi = u2
     # pose via s2t, then back through t2s exactly as get_control does
     wx, wy, wpsi = tr.x[wp], tr.y[wp], tr.psi[wp]
@@ -123,7 +155,9 @@ def make(config: int, track: Track | None = None, B: int | None = None, N: int |
     delta = rng.uniform(-0.3, 0.3, (B, N))
     cc = np.zeros((B, 2 * N))
     warm = np.arange(B) >= B // 2          # first half cold (zeros), second half a warm previous plan
-    idx = np.mod(wp[:, None] + np.arange(N)[None, :], tr.n_wp)
+    idx = wp[:, None] + np.arange(N)[None, :]
+    if tr.circular:
+        idx = np.mod(idx, tr.n_wp)
     cc[:, 0::2] = np.where(warm[:, None], tr.v_ref[idx], 0.0)
     cc[:, 1::2] = np.where(warm[:, None], delta, 0.0)
     return Scenario("config%d" % config, N, spec["weights"], spec["obstacles"], wp.astype(np.int32), x0, cc,

@@ -510,10 +510,13 @@ extern "C" int emu_corridor(int height, int width, const int8_t* data, double ox
 }
 
 // host runs of the per-car rollout code that the K3 kernels execute per thread
-extern "C" int emu_localise(int n_wp, const double* cum, const double* gx, const double* gy, const double* gpsi, double s,
-                            const double* pose, double* x0) {
+// -> the car's waypoint (-1 past the path's length); *alive (may be NULL) as mpmpc_localise_kernel leaves it for a running car:
+// 1, 0 (s past the length) or -2 (the horizon passes the end of an open path)
+extern "C" int emu_localise(int n_wp, int N, int circular, const double* cum, const double* gx, const double* gy,
+                            const double* gpsi, double s, const double* pose, double* x0, int* alive) {
   int wp = ro_current_waypoint(cum, n_wp, s);
   if (wp >= 0) ro_t2s(pose[0], pose[1], pose[2], gx[wp], gy[wp], gpsi[wp], x0);
+  if (alive) *alive = wp < 0 ? 0 : (ro_past_open_end(n_wp, N, circular != 0, wp) ? -2 : 1);
   return wp;
 }
 extern "C" int emu_advance(int N, double L, double Ts, int status, const double* z, double* cc, int* counter,

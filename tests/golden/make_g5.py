@@ -6,7 +6,10 @@ HiGHS; a sanity cross-check of the optimum, not an oracle: SURVEY 8c).
 
     python tests/golden/make_g5.py          (system python; needs no reference and no GPU)
 
-Writes tests/golden/g5_solutions_N{3,10,30,50}.npz."""
+    python tests/golden/make_g5.py real     (only the Real_Track captures)
+
+Writes tests/golden/g5_solutions_N{3,10,30,50}.npz (Sim_Track, from g4_assembly_N*.npz) and
+tests/golden/g5_solutions_real_N{10,30,50}.npz (Real_Track, from g4_assembly_real_N*.npz)."""
 import os
 import sys
 
@@ -60,9 +63,13 @@ def highs_objective(P, q, A, l, u, time_limit=5.0):
         return np.nan
 
 
-def main():
-    for N in (3, 10, 30, 50):
-        g = np.load(os.path.join(HERE, "g4_assembly_N%d.npz" % N))
+SIM = [("", N) for N in (3, 10, 30, 50)]
+REAL = [("real_", N) for N in (10, 30, 50)]
+
+
+def main(which=SIM + REAL):
+    for tag, N in which:
+        g = np.load(os.path.join(HERE, "g4_assembly_%sN%d.npz" % (tag, N)))
         C = g["s"].size
         n, m = 5 * N + 3, 8 * N + 6
         X, Y = np.full((C, n), np.nan), np.full((C, m), np.nan)
@@ -92,11 +99,11 @@ def main():
                 assert f["ok"], (N, c, f)
             print("N=%d case %2d: status %2d, %4d ADMM + %2d interior-point iterations, certificate %.1e, obj %.9g (HiGHS %.9g)" %
                   (N, c, r.status, r.iters, r.ipm_iters, np.nanmax(cert[c]) if np.isfinite(cert[c]).any() else np.nan, obj[c], obj_highs[c]))
-        np.savez_compressed(os.path.join(HERE, "g5_solutions_N%d.npz" % N), x=X, y=Y, status=status, admm_iters=iters,
+        np.savez_compressed(os.path.join(HERE, "g5_solutions_%sN%d.npz" % (tag, N)), x=X, y=Y, status=status, admm_iters=iters,
                             ipm_iters=ipm, certificate=cert, obj=obj, obj_highs=obj_highs, farkas=farkas,
                             note=np.array(["certified optimum (or, status -3, least-violation point + Farkas ray) of the G4 capture "
                                            "of the same index; oracle/osqp_np.py polish=2, phase1=1"]))
 
 
 if __name__ == "__main__":
-    main()
+    main(REAL if sys.argv[1:] == ["real"] else SIM + REAL)

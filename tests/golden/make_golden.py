@@ -19,6 +19,8 @@ Stages
   assembly  G4  exact (P,q,A,l,u) the reference hands to osqp.setup for seeded cases
   assembly_full  G4f  the same with non-diagonal Q, R, QN (g4f_assembly_N*.npz: P as triplets)
   loop      G6  closed-loop lap, N=10, teacher-forced per-step record
+  real      G1r-G4r, G6r  the same on Real_Track (src/simulation.py:57-88): open path, non-square grid, 0.30 m car
+            (G5r: make_g5.py)
 """
 import os
 import sys
@@ -134,8 +136,8 @@ def stage_corridor():
           "| obst ub", np.nanmin(ub1), np.nanmax(ub1), "nan rows", np.isnan(ub1[:, 0]).sum())
 
 
-def make_controller(rp, N, weights):
-    car = BicycleModel(reference_path=rp, **CAR)
+def make_controller(rp, N, weights, car_dims=CAR):
+    car = BicycleModel(reference_path=rp, **car_dims)
     if weights == "stock":            # simulation.py:101-103
         Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     elif weights == "full":           # NON-diagonal Q, R, QN (round 5): the reference accepts any sparse matrices (src/MPC.py:150)
@@ -352,8 +354,212 @@ def stage_raster():
     print("G7:", len(ends), "lines,", ptr[-1], "cells")
 
 
+# ---------------------------------------------------------------- Real_Track (src/simulation.py:57-88)
+REAL_MAP = dict(file_path='maps/real_map.png', origin=(-30.0, -24.0), resolution=0.06)
+REAL_WP_X = [-9.169, 11.9, 7.3, -6.95]
+REAL_WP_Y = [-15.678, 10.9, 14.5, -3.31]
+REAL_OBSTACLES = [(-6.3, -11.1, 0.20), (-2.2, -6.8, 0.25), (2.0, -0.2, 0.25), (6.0, 5.0, 0.3), (7.42, 4.97, 0.3)]
+REAL_CAR = dict(length=0.30, width=0.20, Ts=0.05)
+
+
+def build_real_track(obstacles=False):
+    m = Map(**REAL_MAP)
+    rp = ReferencePath(m, REAL_WP_X, REAL_WP_Y, 0.20, smoothing_distance=5, max_width=1.50, circular=False)
+    if obstacles:
+        m.add_obstacles([Obstacle(cx=c[0], cy=c[1], radius=c[2]) for c in REAL_OBSTACLES])
+    return m, rp
+
+
+def real_path_table(rp):
+    """path_table for an OPEN path: the reference's get_waypoint(n_wp) exits, so the last ds_next is 0 (the successor of the
+    last waypoint is itself, as ReferencePath.tables() of the package has it; no legal horizon reads it)"""
+    wps = rp.waypoints
+    n = len(wps)
+    ds_next = np.array([wps[min(i + 1, n - 1)] - wps[i] for i in range(n)])
+    return dict(
+        x=np.array([w.x for w in wps], float), y=np.array([w.y for w in wps], float),
+        psi=np.array([w.psi for w in wps], float), kappa=np.array([float(w.kappa) for w in wps]),
+        kappa0_is_int=np.array([isinstance(wps[0].kappa, int)]),
+        ds_next=ds_next, segment_lengths=np.array(rp.segment_lengths, float),
+        length=np.array([rp.length]), lb_static=np.array([w.lb for w in wps], float),
+        ub_static=np.array([w.ub for w in wps], float),
+        border_ub=np.array([w.static_border_cells[0] for w in wps], float),
+        border_lb=np.array([w.static_border_cells[1] for w in wps], float))
+
+
+def real_corridor_table(rp, sm):
+    """corridor_table on an open path: a row whose horizon passes the last waypoint makes the reference exit(1)
+    (src/reference_path.py:367-369); such a row holds the longest prefix the reference builds,
+    update_path_constraints(w + 1, n_wp - 1 - w, ...), and NaN beyond it.  valid_cols[w] = length of that prefix (0 for a
+    row the reference cannot build at all: ValueError, no free segment at its first waypoint)."""
+    n = rp.n_waypoints
+    ub = np.full((n, NMAX), np.nan)
+    lb = np.full((n, NMAX), np.nan)
+    valid = np.zeros(n, np.int32)
+    value_error = np.zeros(n, bool)
+    for w in range(n):
+        try:
+            u, l, _ = rp.update_path_constraints(w + 1, NMAX, 2 * sm, sm)
+            ub[w], lb[w] = u, l
+            valid[w] = NMAX
+        except ValueError:
+            value_error[w] = True
+        except SystemExit:
+            k = n - 1 - w
+            if k > 0:
+                try:
+                    u, l, _ = rp.update_path_constraints(w + 1, k, 2 * sm, sm)
+                    ub[w, :k], lb[w, :k] = u, l
+                    valid[w] = k
+                except ValueError:
+                    value_error[w] = True
+    return ub, lb, valid, value_error
+
+
+def real_speed_profile(rp):
+    osqp.CAPTURES.clear()
+    rp.compute_speed_profile(dict(SPEED))
+    return osqp.CAPTURES[-1]
+
+
+def stage_real():
+    """Real_Track goldens: G1r (path, grids), G2r (speed profile), G3r (corridor tables), G4r (assembly captures,
+    N = 10 / 30 stock weights, N = 50 time-optimal), G6r (the reference's own loop at N = 30 without obstacles, teacher
+    forced, recorded until get_control exits at the end of the path)."""
+    from PIL import Image
+    # ---- G1r
+    m, rp = build_real_track()
+    t = real_path_table(rp)
+    raw = np.array(Image.open(REAL_MAP['file_path']))[:, :, 0]
+    t["grid_thresholded"] = np.packbits((raw >= m.threshold_occupied).astype(np.uint8))
+    grid_free = np.packbits(m.data.astype(np.uint8))
+    m.add_obstacles([Obstacle(cx=c[0], cy=c[1], radius=c[2]) for c in REAL_OBSTACLES])
+    grid_obs = np.packbits(m.data.astype(np.uint8))
+    np.savez_compressed(os.path.join(HERE, "g1_path_real_track.npz"), grid_shape=np.array(m.data.shape),
+                        grid_free=grid_free, grid_obstacles=grid_obs, origin=np.array(REAL_MAP['origin']),
+                        resolution=np.array([REAL_MAP['resolution']]), wp_x=np.array(REAL_WP_X), wp_y=np.array(REAL_WP_Y),
+                        obstacles=np.array(REAL_OBSTACLES), circular=np.array([False]), max_width=np.array([1.50]),
+                        car=np.array([REAL_CAR['length'], REAL_CAR['width'], REAL_CAR['Ts']]), **t)
+    print("G1r: grid", m.data.shape, "n_wp", t["x"].size, "length", t["length"][0], "ds", t["ds_next"][:-1].min(), t["ds_next"].max())
+    # ---- G2r
+    m, rp = build_real_track()
+    cap = real_speed_profile(rp)
+    res = cap["res"]
+    v_ref = np.array([w.v_ref for w in rp.waypoints], float)
+    A = cap["A"].tocoo()
+    np.savez_compressed(os.path.join(HERE, "g2_speed_profile_real.npz"),
+                        P_diag=cap["P"].diagonal(), q=cap["q"], l=cap["l"], u=cap["u"],
+                        A_row=A.row, A_col=A.col, A_val=A.data, A_shape=np.array(A.shape),
+                        x=res.x, y=res.y, status=np.array([res.status]), v_ref=v_ref,
+                        constraints=np.array([SPEED[k] for k in ('a_min', 'a_max', 'v_min', 'v_max', 'ay_max')]))
+    print("G2r: n", res.x.size, "status", res.status, "v_ref range", v_ref.min(), v_ref.max())
+    # ---- G3r
+    out = {}
+    for obst in (False, True):
+        m, rp = build_real_track(obst)
+        sm = BicycleModel(reference_path=rp, **REAL_CAR).safety_margin
+        ub, lb, valid, verr = real_corridor_table(rp, sm)
+        name = "obstacles" if obst else "free"
+        out.update({"ub_" + name: ub, "lb_" + name: lb, "valid_cols_" + name: valid, "value_error_" + name: verr})
+    np.savez_compressed(os.path.join(HERE, "g3_corridor_real.npz"), safety_margin=np.array([sm]), **out)
+    print("G3r: valid_cols<50 from row", int(np.argmax(out["valid_cols_free"] < NMAX)), "| ValueError rows free",
+          int(out["value_error_free"].sum()), "obstacles", int(out["value_error_obstacles"].sum()))
+    # ---- G4r
+    osqp.SOLVE = False
+    worlds = {}
+    for obst in (False, True):
+        m, rp = build_real_track(obst)
+        for w, v in zip(rp.waypoints, v_ref):
+            w.v_ref = v
+        worlds[obst] = rp
+    n_wp = len(v_ref)
+    for N, weights, ncase in ((10, "stock", 96), (30, "stock", 96), (50, "time_optimal", 64)):
+        rng = np.random.default_rng(2000 + N)
+        rec = {k: [] for k in ("s", "pose", "cc_prev", "obst", "wp_id", "x0", "lb", "ub", "q", "l", "u",
+                               "P_diag", "P_nnz", "A_indptr", "A_indices", "A_data")}
+        last = n_wp - N - 1                                    # the last start the reference accepts
+        edge = [0, 0] + [w for w in range(last - 4, last + 1) for _ in (0, 1)]    # each edge start with and without obstacles
+        for c in range(ncase):
+            obst = bool(c % 2)
+            rp = worlds[obst]
+            car, mpc = make_controller(rp, N, weights, REAL_CAR)
+            cum = np.cumsum(rp.segment_lengths)
+            wp = edge[c] if c < len(edge) else int(rng.integers(0, last + 1))
+            ds = rp.get_waypoint(wp + 1) - rp.get_waypoint(wp)
+            # (an offset toward the next waypoint only from an interior start: get_current_waypoint must return wp itself)
+            s = cum[wp] + (rng.uniform(-0.45, 0.45) * ds if (c >= len(edge) and wp > 0) else 0.0)
+            car.s = s
+            w = rp.waypoints[wp]
+            e_y, e_psi = rng.uniform(-0.1, 0.1), rng.uniform(-0.2, 0.2)
+            car.temporal_state.x = w.x - e_y * np.sin(w.psi)
+            car.temporal_state.y = w.y + e_y * np.cos(w.psi)
+            car.temporal_state.psi = w.psi + e_psi
+            cc = np.zeros(2 * N)
+            if c % 4 >= 2:
+                cc[0::2] = [rp.get_waypoint(wp + k).v_ref for k in range(N)]
+                cc[1::2] = rng.uniform(-0.3, 0.3, N)
+            mpc.current_control = cc.copy()
+            osqp.CAPTURES.clear()
+            try:
+                mpc.get_control()
+            except ValueError:
+                continue
+            assert car.wp_id == wp
+            cap = osqp.CAPTURES[-1]
+            ub, lb, _ = rp.update_path_constraints(car.wp_id + 1, N, 2 * car.safety_margin, car.safety_margin)
+            P, A = cap["P"], cap["A"]
+            A.sort_indices()
+            for k, v in (("s", s), ("pose", [car.temporal_state.x, car.temporal_state.y, car.temporal_state.psi]),
+                         ("cc_prev", cc), ("obst", obst), ("wp_id", car.wp_id), ("x0", car.spatial_state[:]), ("lb", lb),
+                         ("ub", ub), ("q", cap["q"]), ("l", cap["l"]), ("u", cap["u"]), ("P_diag", P.diagonal()),
+                         ("P_nnz", P.nnz), ("A_indptr", A.indptr), ("A_indices", A.indices), ("A_data", A.data)):
+                rec[k].append(v)
+        a_ptr = np.cumsum([0] + [d.size for d in rec["A_data"]])
+        out = {k: np.array(v) for k, v in rec.items() if not k.startswith("A_ind") and k != "A_data"}
+        out.update(A_indptr=np.array(rec["A_indptr"]), A_indices=np.concatenate(rec["A_indices"]),
+                   A_data=np.concatenate(rec["A_data"]), A_case_ptr=a_ptr, N=np.array([N]), weights=np.array([weights]))
+        np.savez_compressed(os.path.join(HERE, "g4_assembly_real_N%d.npz" % N), **out)
+        print("G4r N=%d: %d cases (%d with obstacles), max wp_id %d of %d" % (N, len(rec["s"]), sum(rec["obst"]),
+                                                                            max(rec["wp_id"]), n_wp))
+    osqp.SOLVE = True
+    # ---- G6r
+    N = 30
+    m, rp = build_real_track()
+    car, mpc = make_controller(rp, N, "stock", REAL_CAR)
+    rp.compute_speed_profile(dict(SPEED))
+    rec = {k: [] for k in ("s", "pose", "wp_id", "x0", "status", "u", "counter", "cc_next")}
+    s0 = pose0 = cc0 = None
+    exited, exit_state = False, None
+    while car.s < rp.length:
+        s, pose = car.s, [car.temporal_state.x, car.temporal_state.y, car.temporal_state.psi]
+        if s0 is None:
+            s0, pose0, cc0 = s, np.array(pose), mpc.current_control.copy()
+        osqp.CAPTURES.clear()
+        try:
+            u = mpc.get_control()
+        except SystemExit:
+            exited = True
+            exit_state = dict(exit_s=np.array([s]), exit_pose=np.array(pose), exit_wp_id=np.array([car.wp_id]),
+                              exit_x0=np.array(car.spatial_state[:]), exit_cc_prev=mpc.current_control.copy(),
+                              exit_counter=np.array([mpc.infeasibility_counter]))
+            assert car.wp_id + N >= rp.n_waypoints      # the end of the path, not N - 1 infeasible steps
+            break
+        res = osqp.CAPTURES[-1]["res"]
+        for k, v in (("s", s), ("pose", pose), ("wp_id", car.wp_id), ("x0", car.spatial_state[:]), ("status", res.status),
+                     ("u", np.array(u, float)), ("counter", mpc.infeasibility_counter), ("cc_next", mpc.current_control.copy())):
+            rec[k].append(v)
+        car.drive(u)
+    np.savez_compressed(os.path.join(HERE, "g6_closed_loop_real_N%d.npz" % N), **{k: np.array(v) for k, v in rec.items()},
+                        s0=np.array([s0]), pose0=pose0, cc_prev0=cc0, N=np.array([N]), exited_end_of_path=np.array([exited]),
+                        **exit_state)
+    st = np.array(rec["status"])
+    print("G6r N=%d: %d steps, statuses %s, exit at s %.4f wp %d" % (N, st.size, dict(zip(*np.unique(st, return_counts=True))),
+                                                                   exit_state["exit_s"][0], exit_state["exit_wp_id"][0]))
+
+
 STAGES = dict(raster=stage_raster, path=stage_path, speed=stage_speed, corridor=stage_corridor, assembly=stage_assembly,
-              loop=stage_loop, loop_stock=stage_loop_stock, assembly_full=stage_assembly_full)
+              loop=stage_loop, loop_stock=stage_loop_stock, assembly_full=stage_assembly_full,
+              real=stage_real)
 
 if __name__ == "__main__":
     assert os.getcwd().rstrip("/") == "/root/reference/src", "run with cwd=/root/reference/src"

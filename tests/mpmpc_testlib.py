@@ -29,10 +29,16 @@ def _i(a):
     return None if a is None else a.ctypes.data_as(_ip)
 
 
-def stock_config(N, weights="stock", max_batch=1, circular=True):
+def stock_config(N, weights="stock", max_batch=1, circular=None, track=None):
+    """The controller configuration of src/simulation.py:100-111 for `track` (default Sim_Track): its car's wheelbase and
+    input limits, and - unless `circular` says otherwise - whether its path is circular."""
     Q, R, QN = scenarios.WEIGHTS[weights]
-    return mpmpc.make_config(N, Q, R, QN, scenarios.XMIN, scenarios.XMAX, scenarios.UMIN, scenarios.UMAX,
-                             scenarios.AY_MAX, scenarios.CAR_LENGTH, circular=circular, max_batch=max_batch)
+    if track is None:
+        L, umin, umax, circ = scenarios.CAR_LENGTH, scenarios.UMIN, scenarios.UMAX, True
+    else:
+        L, umin, umax, circ = track.car_length, track.umin, track.umax, track.circular
+    return mpmpc.make_config(N, Q, R, QN, scenarios.XMIN, scenarios.XMAX, umin, umax, scenarios.AY_MAX, L,
+                             circular=circ if circular is None else circular, max_batch=max_batch)
 
 
 def qp_to_dense(qp_i, N):
@@ -329,7 +335,8 @@ def branch_compare(cfgid, B, settings=None):
     h.set_path(track.kappa, track.v_ref, track.ds_next)
     sol = h.solve(sc.wp_id, sc.x0, sc.cc_prev, sc.lb, sc.ub)
     h.close()
-    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], scenarios.UMIN, scenarios.UMAX, scenarios.XMIN, scenarios.XMAX, 4.0, 0.12)
+    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], track.umin, track.umax, scenarios.XMIN, scenarios.XMAX, 4.0,
+                      track.car_length)
     stock = OC.mpc_batch(ocfg, OC.settings(polish=0, early_polish=0, phase1=0), track.kappa, track.v_ref, track.ds_next, sc.wp_id,
                          sc.x0, sc.cc_prev, sc.lb, sc.ub)
 
@@ -340,4 +347,4 @@ def branch_compare(cfgid, B, settings=None):
             for i in dis]
     return dict(agreement=1.0 - dis.size / B, rows=rows, device=dict(zip(*map(lambda a: a.tolist(), np.unique(sol.status, return_counts=True)))),
                 stock=dict(zip(*map(lambda a: a.tolist(), np.unique(stock["status"], return_counts=True)))), B=B,
-                threshold=1e-3 + 1e-3 * float(scenarios.UMAX[1]))
+                threshold=1e-3 + 1e-3 * float(track.umax[1]))

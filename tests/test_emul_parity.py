@@ -145,8 +145,8 @@ def test_c_port_agrees_with_emulation_on_a_larger_sample(emu, track):
     cfg = T.stock_config(sc.N, sc.weights)
     qp = emu.assemble(cfg, track, _inputs(sc))
     sol = emu.solve(cfg, mpmpc.default_settings(phase1_accept=0), qp, G=64)
-    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], scenarios.UMIN, scenarios.UMAX, scenarios.XMIN,
-                      scenarios.XMAX, 4.0, 0.12)
+    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], track.umin, track.umax, scenarios.XMIN,
+                      scenarios.XMAX, 4.0, track.car_length)
     ref = OC.mpc_batch(ocfg, OC.settings(), track.kappa, track.v_ref, track.ds_next, sc.wp_id, sc.x0, sc.cc_prev,
                        sc.lb, sc.ub)
     assert np.array_equal(sol.status, ref["status"])
@@ -234,8 +234,8 @@ def test_phase1_certifies_every_infeasible_instance_without_admm(G, emu, track):
     cfg = T.stock_config(sc.N, sc.weights)
     qp = emu.assemble(cfg, track, _inputs(sc))
     sol, n_tail = emu.solve_launch(cfg, mpmpc.default_settings(phase1_accept=0), qp, G=G)
-    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], scenarios.UMIN, scenarios.UMAX, scenarios.XMIN,
-                      scenarios.XMAX, 4.0, 0.12)
+    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], track.umin, track.umax, scenarios.XMIN,
+                      scenarios.XMAX, 4.0, track.car_length)
     ref = OC.mpc_batch(ocfg, OC.settings(), track.kappa, track.v_ref, track.ds_next, sc.wp_id, sc.x0, sc.cc_prev,
                        sc.lb, sc.ub, want_y=True)
     assert np.array_equal(sol.status, ref["status"])
@@ -338,7 +338,7 @@ def test_default_branch_agreement_with_restated_stock_osqp_in_the_emulation(emu,
     import oracle_c as OC
     sc = scenarios.make(4, track, B=8192)
     cfg = T.stock_config(sc.N, sc.weights)
-    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], scenarios.UMIN, scenarios.UMAX, scenarios.XMIN, scenarios.XMAX, 4.0, 0.12)
+    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], track.umin, track.umax, scenarios.XMIN, scenarios.XMAX, 4.0, track.car_length)
     args = (track.kappa, track.v_ref, track.ds_next, sc.wp_id, sc.x0, sc.cc_prev, sc.lb, sc.ub)
     stock = OC.mpc_batch(ocfg, OC.settings(polish=0, early_polish=0, phase1=0), *args)
     cert = OC.mpc_batch(ocfg, OC.settings(), *args)

@@ -478,8 +478,8 @@ def test_full_batches_against_c_oracle(cfgid, B, track):
     h = _handle(track, sc.N, sc.weights, B, mpmpc.default_settings(**STRICT))
     qp = h.assemble(sc.wp_id, sc.x0, sc.cc_prev, sc.lb, sc.ub)
     sol = h.solve(sc.wp_id, sc.x0, sc.cc_prev, sc.lb, sc.ub, want_y=True)
-    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], scenarios.UMIN, scenarios.UMAX, scenarios.XMIN,
-                      scenarios.XMAX, 4.0, 0.12)
+    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], track.umin, track.umax, scenarios.XMIN,
+                      scenarios.XMAX, 4.0, track.car_length)
     ref = OC.mpc_batch(ocfg, OC.settings(), track.kappa, track.v_ref, track.ds_next, sc.wp_id, sc.x0, sc.cc_prev,
                        sc.lb, sc.ub, want_y=True)
     assert np.array_equal(sol.status, ref["status"])
@@ -515,8 +515,8 @@ def test_stock_mode_against_c_oracle(cfgid, B, track):
     sc = scenarios.make(cfgid, track, B=B)
     h = _handle(track, sc.N, sc.weights, B, mpmpc.default_settings(polish=0, early_polish=0))
     sol = h.solve(sc.wp_id, sc.x0, sc.cc_prev, sc.lb, sc.ub)
-    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], scenarios.UMIN, scenarios.UMAX, scenarios.XMIN,
-                      scenarios.XMAX, 4.0, 0.12)
+    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], track.umin, track.umax, scenarios.XMIN,
+                      scenarios.XMAX, 4.0, track.car_length)
     ref = OC.mpc_batch(ocfg, OC.settings(polish=0, early_polish=0), track.kappa, track.v_ref, track.ds_next, sc.wp_id,
                        sc.x0, sc.cc_prev, sc.lb, sc.ub)
     assert np.array_equal(sol.status, ref["status"])
@@ -633,7 +633,7 @@ def test_baseline_batch_sizes_carry_kkt_certificates(cfgid, B, track):
     # ... and the C oracle on the WHOLE batch (VERDICT r4 "weak" 9: it does 65 536 instances in seconds): every status of the
     # certified port (the device's strict verdicts), every control to 1e-6
     import oracle_c as OC
-    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], scenarios.UMIN, scenarios.UMAX, scenarios.XMIN, scenarios.XMAX, 4.0, 0.12)
+    ocfg = OC.mpc_cfg(sc.N, scenarios.WEIGHTS[sc.weights], track.umin, track.umax, scenarios.XMIN, scenarios.XMAX, 4.0, track.car_length)
     ref = OC.mpc_batch(ocfg, OC.settings(), track.kappa, track.v_ref, track.ds_next, sc.wp_id, sc.x0, sc.cc_prev, sc.lb, sc.ub, want_y=True)
     assert np.array_equal(ref["status"] == 1, ok) and np.array_equal(ref["status"] == -3, sol.status != 1)
     worst, alt = T.controls_vs_reference(qp, sc.N, sol, ref, 1e-6)

@@ -16,7 +16,7 @@ LONG = [(64, 2), (64, 4), (100, 4), (127, 2), (128, 4), (200, 2), (255, 4)]
 
 
 def _oracle(track, sc, weights, xmin=scenarios.XMIN, xmax=scenarios.XMAX, **st):
-    ocfg = OC.mpc_cfg(sc.N, weights, scenarios.UMIN, scenarios.UMAX, xmin, xmax, 4.0, 0.12)
+    ocfg = OC.mpc_cfg(sc.N, weights, track.umin, track.umax, xmin, xmax, 4.0, track.car_length)
     return OC.mpc_batch(ocfg, OC.settings(**st), track.kappa, track.v_ref, track.ds_next, sc.wp_id, sc.x0, sc.cc_prev, sc.lb, sc.ub, want_y=True)
 
 

@@ -27,8 +27,10 @@ def test_localise_and_advance_reproduce_reference_trace(emu):
     for t in range(steps - 1):
         pose = np.ascontiguousarray(g["pose"][t])
         x0 = np.zeros(3)
-        wp = emu.lib.emu_localise(C.c_int(200), _d(cum), _d(gx), _d(gy), _d(gpsi), C.c_double(float(g["s"][t])), _d(pose), _d(x0))
-        assert wp == g["wp_id"][t] and np.allclose(x0, g["x0"][t], rtol=0, atol=1e-14)
+        alive = C.c_int(7)
+        wp = emu.lib.emu_localise(C.c_int(200), C.c_int(N), C.c_int(1), _d(cum), _d(gx), _d(gy), _d(gpsi), C.c_double(float(g["s"][t])),
+                                  _d(pose), _d(x0), C.byref(alive))
+        assert wp == g["wp_id"][t] and np.allclose(x0, g["x0"][t], rtol=0, atol=1e-14) and alive.value == 1
         # feed the reference's own solution of this step and compare the plant / plan update
         cc = np.ascontiguousarray(g["cc_prev"][t].copy())
         z = np.ascontiguousarray(np.nan_to_num(g["z"][t]))
@@ -42,8 +44,10 @@ def test_localise_and_advance_reproduce_reference_trace(emu):
         assert np.allclose(cc, g["cc_next"][t], rtol=0, atol=1e-15)
         assert abs(s.value - g["s"][t + 1]) <= 1e-14 and np.allclose(pose, g["pose"][t + 1], rtol=0, atol=1e-14)
     # past the end of the path: reported, not wrapped
-    assert emu.lib.emu_localise(C.c_int(200), _d(cum), _d(gx), _d(gy), _d(gpsi), C.c_double(float(cum[-1]) + 1.0),
-                                _d(pose), _d(x0)) == -1
+    alive = C.c_int(7)
+    assert emu.lib.emu_localise(C.c_int(200), C.c_int(N), C.c_int(1), _d(cum), _d(gx), _d(gy), _d(gpsi), C.c_double(float(cum[-1]) + 1.0),
+                                _d(pose), _d(x0), C.byref(alive)) == -1
+    assert alive.value == 0
 
 
 def test_advance_ends_the_run_after_n_minus_one_fallbacks(emu):
