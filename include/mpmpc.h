@@ -249,6 +249,10 @@ int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, doubl
  *          the end of an OPEN path (circular = 0): the car's waypoint has wp_id + N >= n_wp, where
  *          get_waypoint prints "Reached end of path!" (src/reference_path.py:367-369); wp_id and x0 hold the
  *          state of that step, the car is not driven.  A circular path never ends a car with -2.
+ *          With per-car obstacles (mpmpc_rollout_set_obstacles) also: -3 the first horizon waypoint of the car's
+ *          world has no free segment (the reference raises in update_path_constraints), -4 a border line of the
+ *          car's world has more than 8 free segments (COR_MAXSEG, a limit of this library); wp_id and x0 hold
+ *          that step's state, the car is not driven, the other cars are unaffected.
  * The rollout keeps its plans, waypoint ids and states in the handle's batch blocks: mpmpc_upload / mpmpc_solve /
  * mpmpc_assemble on the SAME handle overwrite them, after which mpmpc_rollout_step / _state / _set_counters return
  * MPMPC_E_STATE until mpmpc_rollout_init is called again.  (mpmpc_download and mpmpc_build_corridor are fine.) */
@@ -266,6 +270,23 @@ int mpmpc_rollout_set_counters(mpmpc_handle h, int32_t B, const int32_t* counter
 int mpmpc_rollout_warm_start(mpmpc_handle h, int32_t enable);
 int mpmpc_rollout_state(mpmpc_handle h, int32_t B, double* s, double* pose, double* cc, int32_t* wp_id,
                         double* x0, double* u_last, int32_t* status, int32_t* counter, int32_t* alive);
+/* Per-car obstacles: a fleet of different worlds in one rollout.  Car b's world is the base map (mpmpc_set_map) with
+ * its own circular obstacles added as Map.add_obstacles rasterises them (src/map.py:116-137): disc j of car b is
+ * discs[3*(offsets[b] + j) + {0,1,2}] = (cx, cy, r) in map cells, r = ceil(radius / resolution), (cx, cy) = w2m(centre);
+ * it occupies (cx+dx, cy+dy) for dx, dy in [-r, r-1] with dx^2 + dy^2 <= r^2.  offsets [B+1] (offsets[0] = 0,
+ * non-decreasing, at most 64 discs per car; a car may have none).  Each rollout step then uses, for car b, the row
+ * update_path_constraints(wp_id_b + 1, N, min_width, safety_margin) of car b's world (min_width / safety_margin of the
+ * last mpmpc_build_corridor), bit-identical to the reference's, built on the device (K0c) - see alive -3 / -4 above.
+ *   Needs mpmpc_build_corridor on the current map, path and geometry (it reuses that build's per-waypoint segments):
+ *   MPMPC_E_STATE before one, or after mpmpc_set_map / mpmpc_set_path / mpmpc_set_path_geometry; a step after such a
+ *   change also fails with MPMPC_E_STATE until the obstacles are set again.  A disc whose square leaves the grid:
+ *   MPMPC_E_ARG.  offsets == NULL: back to the shared corridor table (the default).  May be called before
+ *   mpmpc_rollout_init or between mpmpc_rollout_step calls: it applies from the next step on and keeps the rollout's
+ *   state (worlds that change while the cars drive).  The B of the next step must equal this B. */
+int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* discs);
+/* ub / lb [B x N]: the rows the last rollout step used for each car (per-car obstacles only, else MPMPC_E_STATE), as the
+ * reference's update_path_constraints returns them; NaN rows for cars whose row was blocked (-3) or overflowed (-4). */
+int mpmpc_rollout_corridor(mpmpc_handle h, int32_t B, double* ub, double* lb);
 
 /* replaces MPC._init_problem (src/MPC.py:61-155) for B instances: LTV linearisation
  * (src/spatial_bicycle_models.py:391-417) around waypoints wp_id+0..N-1, offsets, speed cap from

@@ -189,7 +189,8 @@ class MPC:
 
 
 class BatchMPC:
-    """B independent controllers sharing one path, weights and limits; one launch per call."""
+    """B independent controllers sharing one path, weights and limits; one launch per call.  The map is shared too, except
+    in rollout(..., obstacles=...), where every car adds its own obstacles to it."""
 
     def __init__(self, model, N, Q, R, QN, StateConstraints, InputConstraints, ay_max, max_batch,
                  settings=None, device=0, corridor=None):
@@ -294,19 +295,32 @@ class BatchMPC:
         poses = np.asarray(poses, float)
         return wp.astype(np.int32), t2s_batch(poses[:, 0], poses[:, 1], poses[:, 2], wx, wy, wpsi)
 
-    def rollout(self, s, poses, n_steps, cc0=None):
+    def rollout(self, s, poses, n_steps, cc0=None, obstacles=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
+        obstacles: None (every car drives the path's map) or a length-B list of lists of Obstacle - car b drives the
+        path's map with ITS obstacles added (Map.add_obstacles), its corridor rebuilt on the device every step; needs
+        corridor='device' (the last update_corridor_from_map's map is the base every car's obstacles are added to).
         alive: 1 running, 0 lap finished (s >= length), -1 ended after N - 1 consecutive infeasible steps
         (src/MPC.py:218-220), -2 ended at the end of an open path (wp_id + N >= n_wp, where the reference's
-        get_waypoint exits: src/reference_path.py:367-369; wp_id and x0 are that step's, the car is not driven)."""
+        get_waypoint exits: src/reference_path.py:367-369; wp_id and x0 are that step's, the car is not driven),
+        -3 (obstacles) no free segment at the first horizon waypoint of the car's world (the reference raises in
+        update_path_constraints), -4 (obstacles) a border line of the car's world has more than 8 free segments (a
+        limit of this library); for -3 / -4 too wp_id and x0 are that step's and the car is not driven."""
         rp = self._path
+        if obstacles is not None:
+            if self.corridor_cols is None:
+                raise ValueError("per-car obstacles need corridor='device' (update_corridor_from_map)")
+            if len(obstacles) != np.asarray(s).size:
+                raise ValueError("obstacles must hold one list of Obstacle per car")
+            discs = [rp.map.obstacle_discs(obs) for obs in obstacles]
         if getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
             wps = rp.waypoints
             self.handle.set_path_geometry([w.x for w in wps], [w.y for w in wps], [w.psi for w in wps],
                                           [w.static_border_cells[0] for w in wps],
                                           [w.static_border_cells[1] for w in wps])
+        self.handle.rollout_set_obstacles(discs if obstacles is not None else None)
         self.handle.rollout_init(self.model.Ts, np.cumsum(rp.segment_lengths), s, poses, cc0)
         self.handle.rollout_step(n_steps)
         return self.handle.rollout_state()

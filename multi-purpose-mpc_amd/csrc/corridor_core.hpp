@@ -107,9 +107,11 @@ MPMPC_HD void cor_line_aa(int r0, int c0, int r1, int c1, F visit) {
 //   n_cells                      cells of the line after the skipped first one (the reference scans x_list[1:])
 //   cell(k, x, y)                coordinates of cell k
 //   is_free(k)                   occupancy of cell k
-template <class Cell, class Free>
-MPMPC_HD int cor_scan_cells(const MapView& m, int ux, int uy, int lx, int ly, double min_width, int n_cells, Cell cell,
-                            Free is_free_at, double* seg) {
+//   emit(s, sx, sy, x, y, ax, ay, bx, by)   segment s found: its end cells and their world coordinates
+// (cor_scan_cells: the same with the segments stored as world coordinates, K0a; K0c keeps the cells instead)
+template <class Cell, class Free, class Emit>
+MPMPC_HD int cor_scan_runs(const MapView& m, int ux, int uy, int lx, int ly, double min_width, int n_cells, Cell cell,
+                           Free is_free_at, Emit emit) {
   int count = 0;
   int sx = ux, sy = uy;       // start cell of the current run
   bool in_free = false;
@@ -125,7 +127,7 @@ MPMPC_HD int cor_scan_cells(const MapView& m, int ux, int uy, int lx, int ly, do
       const double len = std::sqrt((ax - bx) * (ax - bx) + (ay - by) * (ay - by));
       if (len > min_width) {
         if (count == COR_MAXSEG) return COR_E_SEGMENTS;
-        seg[4 * count + 0] = ax; seg[4 * count + 1] = ay; seg[4 * count + 2] = bx; seg[4 * count + 3] = by;
+        emit(count, sx, sy, x, y, ax, ay, bx, by);
         ++count;
       }
       sx = x; sy = y;
@@ -135,6 +137,15 @@ MPMPC_HD int cor_scan_cells(const MapView& m, int ux, int uy, int lx, int ly, do
     }
   }
   return count;
+}
+// the same, emitting (ub_x, ub_y, lb_x, lb_y) of segment s into seg[4*s ..]
+template <class Cell, class Free>
+MPMPC_HD int cor_scan_cells(const MapView& m, int ux, int uy, int lx, int ly, double min_width, int n_cells, Cell cell,
+                            Free is_free_at, double* seg) {
+  return cor_scan_runs(m, ux, uy, lx, ly, min_width, n_cells, cell, is_free_at,
+                       [&](int s, int, int, int, int, double ax, double ay, double bx, double by) {
+                         seg[4 * s + 0] = ax; seg[4 * s + 1] = ay; seg[4 * s + 2] = bx; seg[4 * s + 3] = by;
+                       });
 }
 // cells of the line (first one skipped) as 16-bit pairs (x + 1) | (y + 1) << 16 into idx[0..cap); returns how many
 // there are (possibly more than cap: the caller reports COR_E_CELLS)
@@ -223,27 +234,31 @@ MPMPC_HD void cor_bounds(double wx, double wy, const double* tr, double pux, dou
 // A waypoint with at most one free segment leaves nothing to choose, whatever the horizon did before it: its
 // bounds are computed once per waypoint (phase 1) instead of once per (start waypoint, column) - on Sim_Track
 // that is every waypoint of the free map and all but a handful with the obstacles.
-MPMPC_HD void cor_forced(const PathGeom& g, const double* segs, const int* nseg, int i, double safety_margin, double* o) {
+// (cnt = free segments of waypoint i, s = its first one when cnt == 1)
+MPMPC_HD void cor_forced_seg(const PathGeom& g, int i, int cnt, const double* s, double safety_margin, double* o) {
   const double wx = g.x[i], wy = g.y[i];
-  const double* s = segs + (long)i * 4 * COR_MAXSEG;
   const double* tr = g.trig + (long)i * COR_TRIG;
-  if (nseg[i] == 1) cor_bounds(wx, wy, tr, s[0], s[1], s[2], s[3], safety_margin, o);
+  if (cnt == 1) cor_bounds(wx, wy, tr, s[0], s[1], s[2], s[3], safety_margin, o);
   else cor_bounds(wx, wy, tr, wx, wy, wx, wy, safety_margin, o);
+}
+MPMPC_HD void cor_forced(const PathGeom& g, const double* segs, const int* nseg, int i, double safety_margin, double* o) {
+  cor_forced_seg(g, i, nseg[i], segs + (long)i * 4 * COR_MAXSEG, safety_margin, o);
 }
 
 // One column of phase 2 when the waypoint has several free segments: the largest one at the first waypoint of the
 // horizon, otherwise the one closest to the forward projection of the previous column's border cells (prev: rows 2..5
 // of its cor_bounds output; ip = previous waypoint).  o <- this column's cor_bounds output.
-MPMPC_HD void cor_choose(const PathGeom& g, const double* segs, const int* nseg, int i, int ip, bool first,
-                         const double* prev, double safety_margin, double* o) {
+template <class Seg>
+MPMPC_HD void cor_choose_acc(const PathGeom& g, int cnt, Seg seg, int i, int ip, bool first, const double* prev,
+                             double safety_margin, double* o) {
   const double wx = g.x[i], wy = g.y[i];
-  const double* s = segs + (long)i * 4 * COR_MAXSEG;
-  const int cnt = nseg[i];
   int best = 0;
   if (first) {
     double best_len = -1.0;
     for (int k = 0; k < cnt; ++k) {
-      const double dx = s[4 * k] - s[4 * k + 2], dy = s[4 * k + 1] - s[4 * k + 3];
+      double s[4];
+      seg(k, s);
+      const double dx = s[0] - s[2], dy = s[1] - s[3];
       const double len = std::sqrt(dx * dx + dy * dy);
       if (len > best_len) { best_len = len; best = k; }
     }
@@ -254,13 +269,23 @@ MPMPC_HD void cor_choose(const PathGeom& g, const double* segs, const int* nseg,
     const double qlx = prev[4] + shift * sp, qly = prev[5] + shift * sp;
     double best_off = 0.0;
     for (int k = 0; k < cnt; ++k) {
-      const double du = std::sqrt((s[4 * k] - qux) * (s[4 * k] - qux) + (s[4 * k + 1] - quy) * (s[4 * k + 1] - quy));
-      const double dl = std::sqrt((s[4 * k + 2] - qlx) * (s[4 * k + 2] - qlx) + (s[4 * k + 3] - qly) * (s[4 * k + 3] - qly));
+      double s[4];
+      seg(k, s);
+      const double du = std::sqrt((s[0] - qux) * (s[0] - qux) + (s[1] - quy) * (s[1] - quy));
+      const double dl = std::sqrt((s[2] - qlx) * (s[2] - qlx) + (s[3] - qly) * (s[3] - qly));
       const double off = (du + dl) / 2;
       if (k == 0 || off < best_off) { best_off = off; best = k; }
     }
   }
-  cor_bounds(wx, wy, g.trig + (long)i * COR_TRIG, s[4 * best], s[4 * best + 1], s[4 * best + 2], s[4 * best + 3], safety_margin, o);
+  double s[4];
+  seg(best, s);
+  cor_bounds(wx, wy, g.trig + (long)i * COR_TRIG, s[0], s[1], s[2], s[3], safety_margin, o);
+}
+MPMPC_HD void cor_choose(const PathGeom& g, const double* segs, const int* nseg, int i, int ip, bool first,
+                         const double* prev, double safety_margin, double* o) {
+  const double* sg = segs + (long)i * 4 * COR_MAXSEG;
+  cor_choose_acc(g, nseg[i], [&](int k, double* s) { for (int j = 0; j < 4; ++j) s[j] = sg[4 * k + j]; }, i, ip, first,
+                 prev, safety_margin, o);
 }
 MPMPC_HD int cor_wp(const PathGeom& g, int i) { return i >= g.n_wp ? (g.circular ? i % g.n_wp : g.n_wp - 1) : i; }
 
@@ -310,6 +335,117 @@ MPMPC_HD bool cor_select_one(const PathGeom& g, const double* segs, const int* n
   *ub = o[0];
   *lb = o[1];
   return true;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// K0c: the corridor of ONE car whose world is the base map plus its own obstacle discs, per rollout step.
+// A disc is Map.add_obstacles' rasterisation (src/map.py:116-137) in map cells: r = ceil(radius / resolution),
+// (cx, cy) = w2m(centre); it occupies (cx + dx, cy + dy) for dx, dy in [-r, r - 1] with dx^2 + dy^2 <= r^2.
+// Per (map, geometry, build) the device keeps every waypoint's rasterised border line (cor_line_cells, the cells K0a
+// scans) and a box: COR_LINE_BOX ints = n_cells, x_min, y_min, x_max, y_max (over the scanned cells), upper and lower
+// border cells (packed as the cells are).  A column of a car's horizon whose line box no disc meets keeps the base
+// waypoint's segments; the others rescan the cached cells with occupied = !base_free || in a disc, through the same
+// state machine (cor_scan_runs) - so the segments, and everything computed from them, are the same operations.
+constexpr int COR_MAX_DISCS = 64;       // discs per car (mpmpc_rollout_set_obstacles refuses more)
+constexpr int COR_LINE_BOX = 8;
+constexpr int COR_ROW_OK = 0, COR_ROW_BLOCKED = 1, COR_ROW_OVERFLOW = 2;   // per-car verdict of a step's row
+
+MPMPC_HD bool cor_in_disc(int x, int y, const int* d) {
+  const int dx = x - d[0], dy = y - d[1], r = d[2];
+  return dx >= -r && dx < r && dy >= -r && dy < r && dx * dx + dy * dy <= r * r;
+}
+MPMPC_HD bool cor_disc_meets_box(const int* d, const int* box) {
+  return d[0] - d[2] <= box[3] && d[0] + d[2] - 1 >= box[1] && d[1] - d[2] <= box[4] && d[1] + d[2] - 1 >= box[2];
+}
+// the box of a cached line (cells[0..n) of cor_line_cells; u / l = packed border cells)
+MPMPC_HD void cor_line_box(const int* cells, int n, int u, int l, int* box) {
+  int x0 = 1 << 30, y0 = 1 << 30, x1 = -(1 << 30), y1 = -(1 << 30);
+  for (int k = 0; k < n; ++k) {
+    int x, y;
+    cor_unpack_cell(cells[k], x, y);
+    x0 = x < x0 ? x : x0; y0 = y < y0 ? y : y0;
+    x1 = x > x1 ? x : x1; y1 = y > y1 ? y : y1;
+  }
+  box[0] = n; box[1] = x0; box[2] = y0; box[3] = x1; box[4] = y1; box[5] = u; box[6] = l; box[7] = 0;
+}
+// does any of a car's discs (disc(j) -> const int* {cx, cy, r}) meet the line box?
+template <class Disc>
+MPMPC_HD bool cor_car_touches(const int* box, int n_disc, Disc disc) {
+  for (int j = 0; j < n_disc; ++j)
+    if (cor_disc_meets_box(disc(j), box)) return true;
+  return false;
+}
+// occupancy of a (packed) cell in the car's world: free on the base map and in none of its discs
+template <class Disc>
+MPMPC_HD bool cor_car_cell_free(const MapView& m, int cell, int n_disc, Disc disc) {
+  int x, y;
+  cor_unpack_cell(cell, x, y);
+  if (!cor_cell_free(m, x, y)) return false;
+  for (int j = 0; j < n_disc; ++j)
+    if (cor_in_disc(x, y, disc(j))) return false;
+  return true;
+}
+// Free segments of a cached line in the car's world; emit as in cor_scan_runs.  -> count or COR_E_SEGMENTS
+template <class Disc, class Emit>
+MPMPC_HD int cor_car_scan(const MapView& m, double min_width, const int* cells, const int* box, int n_disc, Disc disc,
+                          Emit emit) {
+  int ux, uy, lx, ly;
+  cor_unpack_cell(box[5], ux, uy);
+  cor_unpack_cell(box[6], lx, ly);
+  return cor_scan_runs(m, ux, uy, lx, ly, min_width, box[0], [&](int k, int& x, int& y) { cor_unpack_cell(cells[k], x, y); },
+                       [&](int k) { return cor_car_cell_free(m, cells[k], n_disc, disc); }, emit);
+}
+// Column n of the horizon that starts at waypoint wp_id, over a car's per-column sources (cor_select_one's replay):
+//   cnt(c)          free segments of column c (COR_E_SEGMENTS: more than COR_MAXSEG)
+//   forced(c, o)    its cor_forced row (cnt(c) <= 1)
+//   seg(c, k, s)    segment k of column c as (ub_x, ub_y, lb_x, lb_y)
+// Returns COR_ROW_BLOCKED when the first column has no free segment (the reference raises there); the caller checks
+// cnt(c) < 0 for every column first (a car whose world overflows COR_MAXSEG anywhere in its horizon gets no row).
+template <class Cnt, class Forced, class Seg>
+MPMPC_HD int cor_select_car_one(const PathGeom& g, int wp_id, int n, double safety_margin, Cnt cnt, Forced forced, Seg seg,
+                                double* ub, double* lb) {
+  if (cnt(0) == 0) return COR_ROW_BLOCKED;
+  int m = n;
+  while (m > 0 && cnt(m) >= 2) --m;
+  double o[COR_WPC] = {0, 0, 0, 0, 0, 0};
+  for (int c = m; c <= n; ++c) {
+    const int i = cor_wp(g, wp_id + c);
+    if (cnt(c) <= 1) {
+      forced(c, o);
+    } else {
+      double prev[COR_WPC];
+      for (int k = 0; k < COR_WPC; ++k) prev[k] = o[k];
+      cor_choose_acc(g, cnt(c), [&](int k, double* s) { seg(c, k, s); }, i, cor_wp(g, wp_id + c - 1), c == 0, prev,
+                     safety_margin, o);
+    }
+  }
+  *ub = o[0];
+  *lb = o[1];
+  return COR_ROW_OK;
+}
+
+// Host-side validation of mpmpc_rollout_set_obstacles (offsets != NULL).  built: a mpmpc_build_corridor of the current
+// map and geometry exists.  Returns 0, -1 (MPMPC_E_ARG) or -3 (MPMPC_E_STATE) and the reason.
+inline int cor_check_obstacles(int B, int max_batch, const int32_t* off, const int32_t* discs, bool built, int map_w,
+                               int map_h, const char** why) {
+  if (!built) { *why = "needs mpmpc_build_corridor on the current map and path geometry first"; return -3; }
+  if (B < 1 || B > max_batch) { *why = "B must be in [1, max_batch]"; return -1; }
+  if (off[0] != 0) { *why = "offsets[0] must be 0"; return -1; }
+  for (int b = 0; b < B; ++b) {
+    const long k = (long)off[b + 1] - off[b];
+    if (k < 0) { *why = "offsets must not decrease"; return -1; }
+    if (k > COR_MAX_DISCS) { *why = "more than 64 discs for one car (COR_MAX_DISCS)"; return -1; }
+  }
+  if (off[B] > 0 && !discs) { *why = "discs is NULL"; return -1; }
+  for (long j = 0; j < off[B]; ++j) {
+    const long cx = discs[3 * j], cy = discs[3 * j + 1], r = discs[3 * j + 2];
+    if (r < 0) { *why = "a disc has a negative radius"; return -1; }
+    if (cx - r < 0 || cy - r < 0 || cx + r > map_w || cy + r > map_h) {
+      *why = "a disc's square leaves the map";
+      return -1;
+    }
+  }
+  return 0;
 }
 
 }  // namespace mpmpc

@@ -614,7 +614,8 @@ __global__ __launch_bounds__(64) void mpmpc_free_segments_kernel(MapView map, Pa
                                                                  const double* __restrict__ blb, double min_width,
                                                                  double safety_margin, double* __restrict__ segs,
                                                                  int* __restrict__ nseg, double* __restrict__ wpc,
-                                                                 int* __restrict__ err) {
+                                                                 int* __restrict__ err, int* __restrict__ line_cells,
+                                                                 int* __restrict__ line_box) {
   __shared__ int cells[COR_CELL_CAP];
   __shared__ unsigned char occ[COR_CELL_CAP];
   __shared__ int s_n;
@@ -634,9 +635,11 @@ __global__ __launch_bounds__(64) void mpmpc_free_segments_kernel(MapView map, Pa
       int x, y;
       cor_unpack_cell(cells[k], x, y);
       occ[k] = cor_cell_free(map, x, y) ? 1 : 0;
+      line_cells[(long)i * COR_CELL_CAP + k] = cells[k];      // K0c's cache of the line
     }
     __syncthreads();
     if (lane != 0) return;
+    cor_line_box(cells, n, (ux + 1) | ((uy + 1) << 16), (lx + 1) | ((ly + 1) << 16), line_box + (long)i * COR_LINE_BOX);
     cnt = cor_scan_cells(map, ux, uy, lx, ly, min_width, n, [&](int c, int& x, int& y) { cor_unpack_cell(cells[c], x, y); },
                          [&](int c) { return occ[c] != 0; }, seg);
     for (int k = 0; k < 4 * COR_MAXSEG; ++k) segs[(long)i * 4 * COR_MAXSEG + k] = (cnt > 0 && k < 4 * cnt) ? seg[k] : 0.0;
@@ -665,6 +668,137 @@ __global__ __launch_bounds__(256) void mpmpc_corridor_select_kernel(PathGeom g, 
   }
   ub_tab[(long)w * n_cols + n] = ub;
   lb_tab[(long)w * n_cols + n] = lb;
+}
+
+// K0c: the corridor rows of one rollout step when every car carries its own obstacle discs (mpmpc_rollout_set_obstacles).
+// One wavefront per car; lanes loop over the car's N columns (N up to 255).  Column n reads waypoint
+// cor_wp(wp_id + 1 + n): if none of the car's discs meets the box of that waypoint's cached border line, it keeps the
+// base segments of the last build (nseg / wpc / segs).  The others ("touched") are rescanned in the car's world: the
+// wave stages the cached cells of as many touched lines as fit COR_CELL_CAP cells in LDS together with their occupancy
+// (base map and discs, every lane fetching cells of its own - one memory round trip per batch of lines instead of one
+// per cell), then the lane of each staged column runs the state machine over its cells in LDS (cor_scan_runs) and keeps
+// the segment end cells as packed pairs plus the cor_forced row.  After a barrier every lane selects its columns as
+// K0b does (cor_select_car_one) and writes lb / ub into the per-instance rows the solve reads.  flag[b] = COR_ROW_*: a
+// car still running whose row is blocked / overflowing ends with alive = -3 / -4 (and gets a zero row, so that the
+// solve of a stopped car stays an ordinary QP).  Every car gets its row - the solve runs on stopped cars too, and their
+// status then matches the shared-table rollout's.
+// LDS: 5 KB of staged cells + 0.8 KB of discs + N * (COR_WPC doubles + (2 COR_MAXSEG + 3) ints) = 5.9 KB + 124 B per column.
+__global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, PathGeom g, int N, double min_width,
+                                                                double safety_margin, const double* __restrict__ segs,
+                                                                const int* __restrict__ nseg, const double* __restrict__ wpc,
+                                                                const int* __restrict__ line_cells,
+                                                                const int* __restrict__ line_box,
+                                                                const int* __restrict__ off, const int* __restrict__ discs,
+                                                                const int* __restrict__ wp_id, int* __restrict__ alive,
+                                                                int* __restrict__ flag, double* __restrict__ lb,
+                                                                double* __restrict__ ub) {
+  constexpr int PENDING = -1000000;
+  extern __shared__ double lds[];
+  double* col_o = lds;                                             // [N][COR_WPC]
+  int* col_seg = (int*)(col_o + (long)N * COR_WPC);                // [N][2 * COR_MAXSEG] packed end cells
+  int* col_cnt = col_seg + (long)N * 2 * COR_MAXSEG;               // [N]; < 0: COR_E_SEGMENTS; +1000: touched
+  int* col_aux = col_cnt + N;                                      // [N] touched: cells of the line
+  int* col_off = col_aux + N;                                      // [N] touched and staged: offset in stg_*, else -1
+  int* dsc = col_off + N;                                          // [COR_MAX_DISCS][3]
+  int* stg_cell = dsc + 3 * COR_MAX_DISCS;                         // [COR_CELL_CAP]
+  unsigned char* stg_free = (unsigned char*)(stg_cell + COR_CELL_CAP);   // [COR_CELL_CAP]
+  __shared__ int s_over;
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int d0 = off[b], nd = off[b + 1] - d0;
+  for (int k = lane; k < 3 * nd; k += 64) dsc[k] = discs[3L * d0 + k];
+  if (lane == 0) s_over = 0;
+  __syncthreads();
+  const int wp = wp_id[b] + 1;
+  auto disc = [&](int j) { return (const int*)(dsc + 3 * j); };
+  for (int n = lane; n < N; n += 64) {
+    const int i = cor_wp(g, wp + n);
+    const int* box = line_box + (long)i * COR_LINE_BOX;
+    col_off[n] = -1;
+    if (nd > 0 && cor_car_touches(box, nd, disc)) {
+      col_cnt[n] = PENDING;
+      col_aux[n] = box[0];
+    } else {
+      const int cnt = nseg[i];
+      if (cnt <= 1)
+        for (int k = 0; k < COR_WPC; ++k) col_o[(long)n * COR_WPC + k] = wpc[(long)i * COR_WPC + k];
+      col_cnt[n] = cnt;
+    }
+  }
+  __syncthreads();
+  for (int n = 0; n < N;) {            // (uniform: every lane reads the same LDS words)
+    int used = 0, e = n;
+    for (; e < N; ++e) {
+      if (col_cnt[e] != PENDING) continue;
+      const int nc = col_aux[e];
+      if (used > 0 && used + nc > COR_CELL_CAP) break;
+      used += nc;
+    }
+    used = 0;
+    for (int c = n; c < e; ++c) {
+      if (col_cnt[c] != PENDING) continue;
+      const int nc = col_aux[c];
+      if (lane == 0) col_off[c] = used;
+      const int* cells = line_cells + (long)cor_wp(g, wp + c) * COR_CELL_CAP;
+      for (int k = lane; k < nc; k += 64) {
+        const int cell = cells[k];
+        stg_cell[used + k] = cell;
+        stg_free[used + k] = cor_car_cell_free(map, cell, nd, disc) ? 1 : 0;
+      }
+      used += nc;
+    }
+    __syncthreads();
+    for (int c = n + lane; c < e; c += 64) {      // the lane of column c scans it
+      const int o0 = col_off[c];
+      if (o0 < 0) continue;
+      const int nc = col_aux[c];
+      const int i = cor_wp(g, wp + c);
+      const int* box = line_box + (long)i * COR_LINE_BOX;
+      int ux, uy, lx, ly;
+      cor_unpack_cell(box[5], ux, uy);
+      cor_unpack_cell(box[6], lx, ly);
+      int* cs = col_seg + (long)c * 2 * COR_MAXSEG;
+      double s0[4] = {0, 0, 0, 0};
+      const int cnt = cor_scan_runs(map, ux, uy, lx, ly, min_width, nc,
+                                    [&](int k, int& x, int& y) { cor_unpack_cell(stg_cell[o0 + k], x, y); },
+                                    [&](int k) { return stg_free[o0 + k] != 0; },
+                                    [&](int q, int sx, int sy, int x, int y, double ax, double ay, double bx, double by) {
+                                      cs[2 * q] = (sx + 1) | ((sy + 1) << 16);
+                                      cs[2 * q + 1] = (x + 1) | ((y + 1) << 16);
+                                      if (q == 0) { s0[0] = ax; s0[1] = ay; s0[2] = bx; s0[3] = by; }
+                                    });
+      if (cnt < 0) s_over = 1;
+      else if (cnt <= 1) cor_forced_seg(g, i, cnt, s0, safety_margin, col_o + (long)c * COR_WPC);
+      col_cnt[c] = cnt < 0 ? cnt : cnt + 1000;
+    }
+    __syncthreads();
+    n = e;
+  }
+  auto cnt = [&](int c) { const int v = col_cnt[c]; return v >= 1000 ? v - 1000 : v; };
+  auto forced = [&](int c, double* o) { for (int k = 0; k < COR_WPC; ++k) o[k] = col_o[(long)c * COR_WPC + k]; };
+  auto seg = [&](int c, int k, double* s) {
+    if (col_cnt[c] >= 1000) {
+      const int* cs = col_seg + (long)c * 2 * COR_MAXSEG;
+      int x, y;
+      cor_unpack_cell(cs[2 * k], x, y);
+      cor_m2w(map, x, y, s[0], s[1]);
+      cor_unpack_cell(cs[2 * k + 1], x, y);
+      cor_m2w(map, x, y, s[2], s[3]);
+    } else {
+      const double* sg = segs + (long)cor_wp(g, wp + c) * 4 * COR_MAXSEG + 4 * k;
+      for (int j = 0; j < 4; ++j) s[j] = sg[j];
+    }
+  };
+  const int verdict = cnt(0) == 0 ? COR_ROW_BLOCKED : (s_over ? COR_ROW_OVERFLOW : COR_ROW_OK);   // the reference raises at column 0 first
+  for (int n = lane; n < N; n += 64) {
+    double u = 0.0, l = 0.0;
+    if (verdict == COR_ROW_OK) cor_select_car_one(g, wp, n, safety_margin, cnt, forced, seg, &u, &l);
+    ub[(long)b * N + n] = u;
+    lb[(long)b * N + n] = l;
+  }
+  if (lane == 0) {
+    flag[b] = verdict;
+    if (verdict != COR_ROW_OK && alive[b] == 1) alive[b] = verdict == COR_ROW_BLOCKED ? -3 : -4;
+  }
 }
 
 // K3a: where is each car on the path, and what is its path-relative state (one thread per car)
@@ -742,6 +876,15 @@ struct mpmpc_handle_s {
   int *nseg = nullptr, *bad = nullptr;      // bad[0]: start waypoints without a free segment, bad[1]: K0a overflow code
   int geom_n = 0;
   std::vector<double> host_bub, host_blb;   // border points, kept to validate them against the map of the moment
+  // per-car obstacles (K0c): cached border lines of the last build, and what that build was made from
+  int *line_cells = nullptr, *line_box = nullptr;      // [n_wp x COR_CELL_CAP], [n_wp x COR_LINE_BOX]
+  unsigned base_gen = 1;        // bumped by mpmpc_set_path / _set_map / _set_path_geometry
+  unsigned built_gen = 0;       // base_gen of the last successful mpmpc_build_corridor (0: none)
+  double built_min_width = 0, built_sm = 0;
+  int *obst_off = nullptr, *obst_discs = nullptr, *ro_flag = nullptr;   // CSR lists on the device, per-car row verdicts
+  int obst_B = 0;               // > 0: the rollout's cars carry their own discs (mpmpc_rollout_set_obstacles)
+  unsigned obst_gen = 0;        // base_gen the discs were validated against
+  bool car_rows = false;        // the last rollout step built per-car rows
   // closed-loop rollout state
   double *ro_cum = nullptr, *ro_s = nullptr, *ro_pose = nullptr, *ro_u = nullptr;
   int *ro_counter = nullptr, *ro_alive = nullptr;
@@ -1035,7 +1178,8 @@ int mpmpc_destroy(mpmpc_handle h) {
   void* ptrs[] = {h->kappa, h->v_ref, h->ds_next, h->ub_tab, h->lb_tab, h->in_block, h->out_block,
                   h->qp,    h->map, h->gx,  h->gy,
                   h->gpsi,  h->bub,   h->blb,     h->segs,   h->nseg,   h->bad,    h->ro_cum, h->ro_s, h->ro_pose, h->gtrig,
-                  h->ro_u,  h->ro_counter, h->ro_alive, h->tail, h->ro_act, h->ro_shift};
+                  h->ro_u,  h->ro_counter, h->ro_alive, h->tail, h->ro_act, h->ro_shift, h->line_cells, h->line_box,
+                  h->obst_off, h->obst_discs, h->ro_flag};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& a : h->alt) {
@@ -1201,6 +1345,7 @@ int mpmpc_set_path(mpmpc_handle h, int32_t n_wp, const double* kappa, const doub
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (h->n_wp != n_wp) { h->n_cols = 0; }   // a corridor table of another path is void
   h->n_wp = n_wp;
+  ++h->base_gen;
   return MPMPC_OK;
 }
 
@@ -1229,6 +1374,7 @@ int mpmpc_set_map(mpmpc_handle h, int32_t height, int32_t width, const int8_t* d
   HIP_TRY(hipMemcpyAsync(h->map, data, (size_t)height * width, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->map_h = height; h->map_w = width; h->map_ox = origin_x; h->map_oy = origin_y; h->map_res = resolution;
+  ++h->base_gen;
   return MPMPC_OK;
 }
 
@@ -1258,8 +1404,13 @@ int mpmpc_set_path_geometry(mpmpc_handle h, int32_t n_wp, const double* x, const
   if (!h->bad) HIP_TRY(hipMalloc((void**)&h->bad, 2 * sizeof(int)));
   HIP_TRY(hipMalloc((void**)&h->segs, sizeof(double) * (4 * COR_MAXSEG + COR_WPC) * (size_t)n_wp));   // + cor_forced rows
   HIP_TRY(hipMalloc((void**)&h->nseg, sizeof(int) * (size_t)n_wp));
+  if (h->line_cells) { HIP_TRY(hipFree(h->line_cells)); h->line_cells = nullptr; }
+  if (h->line_box) { HIP_TRY(hipFree(h->line_box)); h->line_box = nullptr; }
+  HIP_TRY(hipMalloc((void**)&h->line_cells, sizeof(int) * COR_CELL_CAP * (size_t)n_wp));
+  HIP_TRY(hipMalloc((void**)&h->line_box, sizeof(int) * COR_LINE_BOX * (size_t)n_wp));
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->geom_n = n_wp;
+  ++h->base_gen;
   return MPMPC_OK;
 }
 
@@ -1293,7 +1444,7 @@ int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, doubl
   HIP_TRY(hipMemsetAsync(h->bad, 0, 2 * sizeof(int), h->stream));
   double* wpc = h->segs + (size_t)4 * COR_MAXSEG * n;
   hipLaunchKernelGGL(mpmpc_free_segments_kernel, dim3(n), dim3(64), 0, h->stream, mv, pg, h->bub, h->blb, min_width,
-                     safety_margin, h->segs, h->nseg, wpc, h->bad + 1);
+                     safety_margin, h->segs, h->nseg, wpc, h->bad + 1, h->line_cells, h->line_box);
   hipLaunchKernelGGL(mpmpc_corridor_select_kernel, dim3((n * n_cols + 255) / 256), dim3(256), 0, h->stream, pg, h->segs,
                      h->nseg, n_cols, safety_margin, h->ub_tab, h->lb_tab, h->bad, wpc);
   HIP_TRY(hipGetLastError());
@@ -1302,6 +1453,7 @@ int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, doubl
   if (ub_out) HIP_TRY(hipMemcpyAsync(ub_out, h->ub_tab, sizeof(double) * (size_t)n * n_cols, hipMemcpyDeviceToHost, h->stream));
   if (lb_out) HIP_TRY(hipMemcpyAsync(lb_out, h->lb_tab, sizeof(double) * (size_t)n * n_cols, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
+  h->built_gen = 0;
   if (bad2[1] != 0) {
     h->n_cols = 0;        // the table is not usable
     return fail(MPMPC_E_ARG, bad2[1] == 1 ? "a waypoint's border line has more than 1024 cells (COR_CELL_CAP)"
@@ -1310,6 +1462,9 @@ int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, doubl
   const int bad = bad2[0];
   if (bad_rows) *bad_rows = bad;
   h->n_cols = n_cols;
+  h->built_gen = h->base_gen;
+  h->built_min_width = min_width;
+  h->built_sm = safety_margin;
   return MPMPC_OK;
 }
 
@@ -1332,6 +1487,7 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
     HIP_TRY(hipMalloc((void**)&h->ro_act, sizeof(int) * mb * h->ld));
     HIP_TRY(hipMalloc((void**)&h->ro_shift, sizeof(int) * mb));
   }
+  if (!h->ro_flag) HIP_TRY(hipMalloc((void**)&h->ro_flag, sizeof(int) * mb));
   if (int rc = upload_table(h, &h->ro_cum, cum_lengths, h->n_wp)) return rc;
   const int N = h->cfg.N;
   if (B != h->laid_out) lay_out(h, B);
@@ -1354,6 +1510,7 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   h->ro_B = B;
   h->ro_valid = true;
   h->have_rows = false;       // the corridor comes from the table
+  h->car_rows = false;
   h->uploaded = B;
   return MPMPC_OK;
 }
@@ -1378,18 +1535,77 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     return fail(MPMPC_E_STATE, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
                                "call mpmpc_rollout_init again (or use a second handle for single solves)");
   if (n_steps < 0) return fail(MPMPC_E_ARG, "n_steps must be >= 0");
+  const bool per_car = h->obst_B > 0;
+  if (per_car) {
+    if (h->obst_B != B) return fail(MPMPC_E_STATE, "the per-car obstacles were set for another number of cars");
+    if (h->obst_gen != h->base_gen || h->built_gen != h->base_gen)
+      return fail(MPMPC_E_STATE, "map, path or geometry changed since mpmpc_rollout_set_obstacles / mpmpc_build_corridor");
+  }
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int blocks = (B + 255) / 256;
+  const int N = h->cfg.N;
+  const size_t car_lds = sizeof(double) * COR_WPC * N + sizeof(int) * (2 * COR_MAXSEG + 3) * N + sizeof(int) * 3 * COR_MAX_DISCS +
+                         (sizeof(int) + 1) * COR_CELL_CAP;
+  MapView mv{h->map, h->map_h, h->map_w, h->map_ox, h->map_oy, h->map_res};
+  PathGeom pg{h->gx, h->gy, h->gpsi, h->ds_next, h->n_wp, h->cfg.circular, h->gtrig};
+  h->have_rows = per_car;     // K1 / K2 read the per-instance rows K0c writes (else: the table)
   for (int t = 0; t < n_steps; ++t) {
     hipLaunchKernelGGL(mpmpc_localise_kernel, dim3(blocks), dim3(256), 0, h->stream, B, h->n_wp, h->cfg.N,
                        h->cfg.circular ? 1 : 0, h->ro_cum, h->gx, h->gy,
                        h->gpsi, h->ro_s, h->ro_pose, h->ro_alive, h->wp_id, h->x0, h->ro_shift);
+    if (per_car)
+      hipLaunchKernelGGL(mpmpc_car_corridor_kernel, dim3(B), dim3(64), car_lds, h->stream, mv, pg, N, h->built_min_width,
+                         h->built_sm, h->segs, h->nseg, h->segs + (size_t)4 * COR_MAXSEG * h->n_wp, h->line_cells,
+                         h->line_box, h->obst_off, h->obst_discs, h->wp_id, h->ro_alive, h->ro_flag, h->lb, h->ub);
     if (int rc = launch_solve(h, B, true, false)) return rc;      // (the plant step reads z and the status only)
     hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, h->stream, B, h->cfg.N, h->cfg.wheelbase, h->ro_Ts,
                        h->kappa, h->wp_id, h->x0, h->status, h->z, h->cc, h->ro_counter, h->ro_alive, h->ro_pose, h->ro_s,
                        h->ro_u);
   }
   HIP_TRY(hipGetLastError());
+  if (n_steps > 0) h->car_rows = per_car;
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* discs) {
+  if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
+  MPMPC_SETTLE(h);
+  if (!offsets) { h->obst_B = 0; return MPMPC_OK; }      // back to the shared table
+  const char* why = "";
+  const bool built = h->built_gen == h->base_gen && h->built_gen != 0 && h->n_cols > 0 && h->line_cells;
+  if (int rc = cor_check_obstacles(B, h->cfg.max_batch, offsets, discs, built, h->map_w, h->map_h, &why))
+    return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t mb = (size_t)h->cfg.max_batch;
+  if (!h->obst_off) {
+    HIP_TRY(hipMalloc((void**)&h->obst_off, sizeof(int) * (mb + 1)));
+    HIP_TRY(hipMalloc((void**)&h->obst_discs, sizeof(int) * 3 * COR_MAX_DISCS * mb));
+  }
+  if (!h->ro_flag) HIP_TRY(hipMalloc((void**)&h->ro_flag, sizeof(int) * mb));
+  HIP_TRY(hipMemcpyAsync(h->obst_off, offsets, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, h->stream));
+  if (offsets[B] > 0)
+    HIP_TRY(hipMemcpyAsync(h->obst_discs, discs, sizeof(int) * 3 * (size_t)offsets[B], hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->obst_B = B;
+  h->obst_gen = h->base_gen;
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_corridor(mpmpc_handle h, int32_t B, double* ub, double* lb) {
+  if (!h || !ub || !lb) return fail(MPMPC_E_ARG, "NULL argument");
+  MPMPC_SETTLE(h);
+  if (B < 1 || B > h->ro_B || !h->ro_valid) return fail(MPMPC_E_STATE, "call mpmpc_rollout_init for at least B cars first");
+  if (!h->car_rows) return fail(MPMPC_E_STATE, "the last rollout step did not build per-car rows (mpmpc_rollout_set_obstacles)");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t nb = (size_t)B * h->cfg.N;
+  std::vector<int> flag(B);
+  HIP_TRY(hipMemcpyAsync(ub, h->ub, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(lb, h->lb, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(flag.data(), h->ro_flag, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  for (int b = 0; b < B; ++b)
+    if (flag[b] != COR_ROW_OK)
+      for (int n = 0; n < h->cfg.N; ++n) ub[(size_t)b * h->cfg.N + n] = lb[(size_t)b * h->cfg.N + n] = std::nan("");
   return MPMPC_OK;
 }
 

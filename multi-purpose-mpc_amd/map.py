@@ -125,11 +125,19 @@ class Map:
         free = self.data >= self.threshold_occupied
         self.data = fill_small_holes(free, area_threshold=5).astype(np.int8)
 
+    def obstacle_discs(self, obstacles):
+        """-> int32 [k, 3]: (cx, cy, r) in map cells of each obstacle as add_obstacles rasterises it (src/map.py:129-133):
+        r = ceil(radius / resolution), (cx, cy) = w2m(centre); the disc is (cx + dx, cy + dy) for dx, dy in [-r, r - 1]
+        with dx^2 + dy^2 <= r^2.  What mpmpc.Handle.rollout_set_obstacles takes per car."""
+        out = np.zeros((len(obstacles), 3), np.int32)
+        for j, ob in enumerate(obstacles):
+            cx, cy = self.w2m(ob.cx, ob.cy)
+            out[j] = (cx, cy, int(np.ceil(ob.radius / self.resolution)))
+        return out
+
     def add_obstacles(self, obstacles):
         self.obstacles.extend(obstacles)
-        for ob in obstacles:
-            rad = int(np.ceil(ob.radius / self.resolution))
-            cx, cy = self.w2m(ob.cx, ob.cy)
+        for cx, cy, rad in self.obstacle_discs(obstacles).tolist():
             yy, xx = np.ogrid[-rad:rad, -rad:rad]
             disc = xx ** 2 + yy ** 2 <= rad ** 2
             self.data[cy - rad:cy + rad, cx - rad:cx + rad][disc] = 0

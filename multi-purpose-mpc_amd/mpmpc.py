@@ -158,6 +158,8 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_set_counters.argtypes = [h, C.c_int32, _ip]
     lib.mpmpc_rollout_warm_start.argtypes = [h, C.c_int32]
     lib.mpmpc_rollout_state.argtypes = [h, C.c_int32, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip]
+    lib.mpmpc_rollout_set_obstacles.argtypes = [h, C.c_int32, _ip, _ip]
+    lib.mpmpc_rollout_corridor.argtypes = [h, C.c_int32, _dp, _dp]
     lib.mpmpc_assemble.argtypes = [h, C.c_int32, _ip, _dp, _dp, _dp, _dp, _dp]
     lib.mpmpc_stage_ld.argtypes = [C.c_int32]
     lib.mpmpc_stage_ld.restype = C.c_int32
@@ -184,7 +186,7 @@ def load_library(path: str | None = None):
 EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_default_settings",
            "mpmpc_create", "mpmpc_destroy", "mpmpc_set_settings", "mpmpc_set_packing", "mpmpc_set_tail_kernel", "mpmpc_set_path", "mpmpc_set_corridor",
            "mpmpc_set_map", "mpmpc_set_path_geometry", "mpmpc_build_corridor", "mpmpc_rollout_init",
-           "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline",
+           "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline",
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_staging",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
@@ -322,7 +324,9 @@ class Handle:
 
     def rollout_state(self):
         """-> dict(s, pose, cc, wp_id, x0, u, status, counter, alive) of the rollout's cars.  alive: 1 running, 0 lap
-        finished, -1 ended after N - 1 consecutive infeasible steps, -2 ended at the end of an open path (include/mpmpc.h)."""
+        finished, -1 ended after N - 1 consecutive infeasible steps, -2 ended at the end of an open path, -3 / -4 (per-car
+        obstacles) no free segment at the first horizon waypoint of the car's world / more than 8 free segments on a border
+        line of it (include/mpmpc.h)."""
         B, N = self._ro_B, self.N
         out = dict(s=np.zeros(B), pose=np.zeros((B, 3)), cc=np.zeros((B, 2 * N)), wp_id=np.zeros(B, np.int32),
                    x0=np.zeros((B, 3)), u=np.zeros((B, 2)), status=np.zeros(B, np.int32),
@@ -331,6 +335,26 @@ class Handle:
                                                  _i(out["wp_id"]), _d(out["x0"]), _d(out["u"]), _i(out["status"]),
                                                  _i(out["counter"]), _i(out["alive"])))
         return out
+
+    def rollout_set_obstacles(self, discs):
+        """Per-car obstacle worlds: discs = one int [k_b, 3] array of (cx, cy, r) map cells per car (Map.obstacle_discs;
+        k_b may be 0, at most 64), or None for the shared corridor table.  Needs build_corridor on the current map; may be
+        called between rollout_step calls (applies from the next step, keeps the rollout's state)."""
+        if discs is None:
+            self._check(self.lib.mpmpc_rollout_set_obstacles(self._h, 0, None, None))
+            return
+        lists = [np.asarray(d, dtype=np.int32).reshape(-1, 3) for d in discs]
+        off = np.zeros(len(lists) + 1, np.int32)
+        off[1:] = np.cumsum([a.shape[0] for a in lists])
+        flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((0, 3), np.int32), dtype=np.int32)
+        self._check(self.lib.mpmpc_rollout_set_obstacles(self._h, len(lists), _i(off), _i(flat) if flat.size else None))
+
+    def rollout_corridor(self):
+        """-> (ub, lb) [B, N]: the rows the last rollout step used per car (per-car obstacles); NaN rows for alive -3 / -4"""
+        B, N = self._ro_B, self.N
+        ub, lb = np.zeros((B, N)), np.zeros((B, N))
+        self._check(self.lib.mpmpc_rollout_corridor(self._h, B, _d(ub), _d(lb)))
+        return ub, lb
 
     def _inputs(self, wp_id, x0, cc_prev, lb, ub):
         wp = np.ascontiguousarray(wp_id, dtype=np.int32).ravel()
