@@ -288,6 +288,46 @@ int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offset
  * reference's update_path_constraints returns them; NaN rows for cars whose row was blocked (-3) or overflowed (-4). */
 int mpmpc_rollout_corridor(mpmpc_handle h, int32_t B, double* ub, double* lb);
 
+/* Recorder: while the cars drive, the rollout appends one record per car and recorded step to a device-resident trace
+ * (what src/simulation.py:117-157 logs per step on the host: x_log / y_log / v_log and MPC.current_prediction), and
+ * mpmpc_rollout_trace brings any range of records back.  A rollout that does not ask for it launches what it always did.
+ *   mpmpc_rollout_record    reserves device memory for `capacity` records of B cars - the basic fields (s, pose, wp_id,
+ *                           x0, u, status, counter, alive: 88 bytes per car) plus those selected by `fields` - and switches
+ *                           recording on; capacity = 0 switches it off and frees the memory.  Rollout step k (0-based,
+ *                           counted from mpmpc_rollout_init) is recorded when k % stride == 0.  May be called before or
+ *                           after mpmpc_rollout_init (which keeps the configuration and empties the trace); the B of later
+ *                           mpmpc_rollout_init / _step calls must equal this B (MPMPC_E_STATE).  capacity < 0, stride < 1,
+ *                           unknown bits in fields, B outside [1, max_batch]: MPMPC_E_ARG; no memory: MPMPC_E_HIP, and
+ *                           recording is off.
+ *   mpmpc_rollout_step      never overwrites or drops records: a call whose records do not fit into what is left of
+ *                           `capacity` returns MPMPC_E_STATE before it launches anything.
+ *   mpmpc_rollout_recorded  records held, steps taken since mpmpc_rollout_init (either pointer may be NULL).
+ *   mpmpc_rollout_trace     records first .. first + count - 1 into host arrays [count][B][...]: pose 3, x0 3, u 2,
+ *                           plan 2N, pred_x / pred_y N-2, ub / lb N.  Any pointer may be NULL; a field that was not
+ *                           selected, or records beyond those held: MPMPC_E_STATE.  The trace has its own memory: it stays
+ *                           readable after mpmpc_upload / mpmpc_solve on the handle have invalidated the rollout's state,
+ *                           until the next mpmpc_rollout_init or mpmpc_rollout_record.
+ * A record, with a_in / a the car's `alive` before / after the step ("empty": NaN, wp_id -1, status 0):
+ *   s, pose        the state the step STARTED from (the state after the last step is mpmpc_rollout_state's); empty if
+ *                  a_in != 1 (the car had ended before)
+ *   wp_id, x0      this step's; empty if a_in != 1 or a == 0 (localise found the lap finished)
+ *   status, u, plan, ub, lb   this step's solver status, applied control (v, delta), MPC.current_control after the step,
+ *                  the corridor row the QP used; empty unless a is 1 or -1 (the solve launch also re-solves ended cars
+ *                  on stale inputs: their values are masked here)
+ *   pred_x, pred_y the predicted path, MPC.update_prediction (src/MPC.py:224-248): stage k = 2 .. N-1 of the step's
+ *                  solution at waypoint w = wp_id + k, x_w - e_y sin(psi_w), y_w + e_y cos(psi_w); empty unless the
+ *                  status is usable (1, 2, -2) - on a fallback step the reference keeps DISPLAYING the previous step's
+ *                  prediction, the trace holds none
+ *   counter, alive as they stand after the step, always */
+#define MPMPC_REC_PLAN 1   /* the car's plan after the step: MPC.current_control, [2N]               */
+#define MPMPC_REC_PRED 2   /* predicted path of the step, world x / y of stages 2 .. N-1, [N-2] each */
+#define MPMPC_REC_ROWS 4   /* the corridor row the step's QP used, ub / lb [N] each                  */
+int mpmpc_rollout_record(mpmpc_handle h, int32_t B, int32_t capacity, int32_t fields, int32_t stride);
+int mpmpc_rollout_recorded(mpmpc_handle h, int32_t* n_records, int32_t* n_steps);
+int mpmpc_rollout_trace(mpmpc_handle h, int32_t B, int32_t first, int32_t count, double* s, double* pose, int32_t* wp_id,
+                        double* x0, double* u, int32_t* status, int32_t* counter, int32_t* alive, double* plan,
+                        double* pred_x, double* pred_y, double* ub, double* lb);
+
 /* replaces MPC._init_problem (src/MPC.py:61-155) for B instances: LTV linearisation
  * (src/spatial_bicycle_models.py:391-417) around waypoints wp_id+0..N-1, offsets, speed cap from
  * the previous plan cc_prev (src/MPC.py:86-87,111-113), box bounds, references, cost vectors.

@@ -295,7 +295,7 @@ class BatchMPC:
         poses = np.asarray(poses, float)
         return wp.astype(np.int32), t2s_batch(poses[:, 0], poses[:, 1], poses[:, 2], wx, wy, wpsi)
 
-    def rollout(self, s, poses, n_steps, cc0=None, obstacles=None):
+    def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -307,7 +307,12 @@ class BatchMPC:
         get_waypoint exits: src/reference_path.py:367-369; wp_id and x0 are that step's, the car is not driven),
         -3 (obstacles) no free segment at the first horizon waypoint of the car's world (the reference raises in
         update_path_constraints), -4 (obstacles) a border line of the car's world has more than 8 free segments (a
-        limit of this library); for -3 / -4 too wp_id and x0 are that step's and the car is not driven."""
+        limit of this library); for -3 / -4 too wp_id and x0 are that step's and the car is not driven.
+        record: None - nothing is recorded; True or a dict of mpmpc.Handle.rollout_record's keyword arguments (capacity,
+        plan, prediction, rows, stride; capacity defaults to the records `n_steps` yields) - the run is recorded on the
+        device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of the whole run, arrays
+        [records, B, ...] with the state every recorded step started from, its control, status, ... (what
+        src/simulation.py:117-157 logs per step)."""
         rp = self._path
         if obstacles is not None:
             if self.corridor_cols is None:
@@ -321,9 +326,22 @@ class BatchMPC:
                                           [w.static_border_cells[0] for w in wps],
                                           [w.static_border_cells[1] for w in wps])
         self.handle.rollout_set_obstacles(discs if obstacles is not None else None)
-        self.handle.rollout_init(self.model.Ts, np.cumsum(rp.segment_lengths), s, poses, cc0)
-        self.handle.rollout_step(n_steps)
-        return self.handle.rollout_state()
+        if record is None or record is False:
+            self.handle.rollout_init(self.model.Ts, np.cumsum(rp.segment_lengths), s, poses, cc0)
+            self.handle.rollout_step(n_steps)
+            return self.handle.rollout_state()
+        kw = dict(record) if isinstance(record, dict) else {}
+        stride = int(kw.get("stride", 1))
+        kw.setdefault("capacity", max(1, -(-int(n_steps) // max(stride, 1))))
+        self.handle.rollout_record(B=np.asarray(s).size, **kw)
+        try:
+            self.handle.rollout_init(self.model.Ts, np.cumsum(rp.segment_lengths), s, poses, cc0)
+            self.handle.rollout_step(n_steps)
+            out = self.handle.rollout_state()
+            out["trace"] = self.handle.rollout_trace()
+        finally:
+            self.handle.rollout_record(0, B=np.asarray(s).size)      # later rollouts are unrecorded again
+        return out
 
     def staging(self, B):
         """numpy views of the handle's page-locked staging blocks for a batch of B (mpmpc.Handle.staging): a caller that builds

@@ -844,6 +844,27 @@ __global__ __launch_bounds__(256) void mpmpc_advance_kernel(int B, int N, double
     alive[i] = -1;
 }
 
+// K3r: the recorder of a rollout (mpmpc_rollout_record), two launches around a recorded step.  Both give every ENTRY of
+// a car's record its own thread, and the record's fields lie car-major ([B][len], the host's layout): consecutive threads
+// store consecutive words.  `rec` is the record's base address (64-bit arithmetic on the host).
+//   snapshot  before localise: s, pose, alive as the step finds them (4 entries per car)
+//   write     after advance: x0, u, wp_id, status, counter, alive, plan, predicted path, corridor row (ro_record_finish)
+__global__ __launch_bounds__(256) void mpmpc_record_snapshot_kernel(int B, const double* __restrict__ s,
+                                                                    const double* __restrict__ pose,
+                                                                    const int* __restrict__ alive, int* __restrict__ a_in,
+                                                                    char* __restrict__ rec, RoTraceLayout lay) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  const int i = (int)(g / RO_REC_BEGIN_ENTRIES), c = (int)(g - (long)i * RO_REC_BEGIN_ENTRIES);
+  if (i >= B) return;
+  ro_record_begin(s, pose, alive, a_in, rec, lay, i, c);
+}
+__global__ __launch_bounds__(256) void mpmpc_record_write_kernel(int B, RoRecSrc src, char* __restrict__ rec, RoTraceLayout lay) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  const int i = (int)(g / lay.entries), e = (int)(g - (long)i * lay.entries);
+  if (i >= B) return;
+  ro_record_finish(src, rec, lay, i, e);
+}
+
 // ------------------------------------------------------------------------------------ host side
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) {
@@ -893,6 +914,13 @@ struct mpmpc_handle_s {
   double ro_Ts = 0;
   int ro_B = 0;
   bool ro_valid = false;      // the batch blocks still hold the rollout's plans / waypoint ids / states
+  // recorder (mpmpc_rollout_record): the trace has its own memory, [rec_cap] records of rec_lay.bytes each
+  char* rec_buf = nullptr;
+  int* rec_ain = nullptr;       // [rec_B] alive before the step being recorded
+  RoTraceLayout rec_lay{};
+  int rec_cap = 0, rec_B = 0, rec_fields = 0, rec_stride = 1;
+  int rec_count = 0;            // records held
+  long long ro_steps = 0;       // rollout steps since mpmpc_rollout_init
   // per-batch inputs
   int* wp_id = nullptr;
   double *x0 = nullptr, *cc = nullptr, *lb = nullptr, *ub = nullptr;
@@ -1179,7 +1207,7 @@ int mpmpc_destroy(mpmpc_handle h) {
                   h->qp,    h->map, h->gx,  h->gy,
                   h->gpsi,  h->bub,   h->blb,     h->segs,   h->nseg,   h->bad,    h->ro_cum, h->ro_s, h->ro_pose, h->gtrig,
                   h->ro_u,  h->ro_counter, h->ro_alive, h->tail, h->ro_act, h->ro_shift, h->line_cells, h->line_box,
-                  h->obst_off, h->obst_discs, h->ro_flag};
+                  h->obst_off, h->obst_discs, h->ro_flag, h->rec_buf, h->rec_ain};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& a : h->alt) {
@@ -1476,6 +1504,7 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   if (!(Ts > 0)) return fail(MPMPC_E_ARG, "Ts must be > 0");
   if (h->n_wp == 0 || h->geom_n != h->n_wp) return fail(MPMPC_E_STATE, "needs mpmpc_set_path and mpmpc_set_path_geometry");
   if (h->n_cols == 0) return fail(MPMPC_E_STATE, "needs a corridor table (mpmpc_set_corridor / mpmpc_build_corridor)");
+  if (h->rec_cap > 0 && h->rec_B != B) return fail(MPMPC_E_STATE, "mpmpc_rollout_record was set up for another number of cars");
   HIP_TRY(hipSetDevice(h->cfg.device));
   const size_t mb = (size_t)h->cfg.max_batch;
   if (!h->ro_s) {
@@ -1512,6 +1541,85 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   h->have_rows = false;       // the corridor comes from the table
   h->car_rows = false;
   h->uploaded = B;
+  h->ro_steps = 0;            // the recorder keeps its configuration and starts over
+  h->rec_count = 0;
+  return MPMPC_OK;
+}
+
+// records that steps ro_steps .. ro_steps + n_steps - 1 add (every rec_stride-th step counted from mpmpc_rollout_init)
+static long long records_of(const mpmpc_handle_s* h, long long n_steps) {
+  const long long st = h->rec_stride, a = h->ro_steps, b = h->ro_steps + n_steps;
+  return (b + st - 1) / st - (a + st - 1) / st;
+}
+
+int mpmpc_rollout_record(mpmpc_handle h, int32_t B, int32_t capacity, int32_t fields, int32_t stride) {
+  if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
+  MPMPC_SETTLE(h);
+  if (capacity < 0) return fail(MPMPC_E_ARG, "capacity must be >= 0");
+  if (stride < 1) return fail(MPMPC_E_ARG, "stride must be >= 1");
+  if (fields & ~RO_REC_ALL) return fail(MPMPC_E_ARG, "unknown bits in fields");
+  if (B < 1 || B > h->cfg.max_batch) return fail(MPMPC_E_ARG, "B must be in [1, max_batch]");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (h->rec_buf) { (void)hipFree(h->rec_buf); h->rec_buf = nullptr; }
+  h->rec_cap = 0;
+  h->rec_count = 0;
+  if (capacity == 0) return MPMPC_OK;
+  const RoTraceLayout lay = ro_trace_layout(h->cfg.N, B, fields);
+  if (!h->rec_ain) HIP_TRY(hipMalloc((void**)&h->rec_ain, sizeof(int) * (size_t)h->cfg.max_batch));
+  if (hipMalloc((void**)&h->rec_buf, (size_t)lay.bytes * (size_t)capacity) != hipSuccess) {
+    (void)hipGetLastError();
+    h->rec_buf = nullptr;
+    return fail(MPMPC_E_HIP, "no device memory for " + std::to_string(capacity) + " records of " + std::to_string(lay.bytes) + " bytes");
+  }
+  h->rec_lay = lay;
+  h->rec_cap = capacity;
+  h->rec_B = B;
+  h->rec_fields = fields;
+  h->rec_stride = stride;
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_recorded(mpmpc_handle h, int32_t* n_records, int32_t* n_steps) {
+  if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
+  if (n_records) *n_records = h->rec_count;
+  if (n_steps) *n_steps = (int32_t)h->ro_steps;
+  return MPMPC_OK;
+}
+
+// field `off` of records first .. first + count - 1 -> host [count][bytes]: one strided copy
+static int pull_field(mpmpc_handle h, void* dst, long long off, size_t bytes, int first, int count) {
+  const char* src = h->rec_buf + (size_t)h->rec_lay.bytes * (size_t)first + off;
+  if (count == 1) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+  else HIP_TRY(hipMemcpy2DAsync(dst, bytes, src, (size_t)h->rec_lay.bytes, bytes, (size_t)count, hipMemcpyDeviceToHost, h->stream));
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_trace(mpmpc_handle h, int32_t B, int32_t first, int32_t count, double* s, double* pose, int32_t* wp_id,
+                        double* x0, double* u, int32_t* status, int32_t* counter, int32_t* alive, double* plan,
+                        double* pred_x, double* pred_y, double* ub, double* lb) {
+  if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
+  MPMPC_SETTLE(h);
+  if (first < 0 || count < 0) return fail(MPMPC_E_ARG, "first and count must be >= 0");
+  if (h->rec_cap == 0) return fail(MPMPC_E_STATE, "recording is off (mpmpc_rollout_record)");
+  if (B != h->rec_B) return fail(MPMPC_E_STATE, "mpmpc_rollout_record was set up for another number of cars");
+  if ((long long)first + count > h->rec_count)
+    return fail(MPMPC_E_STATE, "records " + std::to_string(first) + " .. " + std::to_string((long long)first + count - 1) +
+                                   " asked for, " + std::to_string(h->rec_count) + " held");
+  const RoTraceLayout& l = h->rec_lay;
+  if ((plan && l.plan < 0) || ((pred_x || pred_y) && l.pred_x < 0) || ((ub || lb) && l.ub < 0))
+    return fail(MPMPC_E_STATE, "a field was asked for that mpmpc_rollout_record did not select");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if (count > 0) {
+    const size_t N = (size_t)h->cfg.N, nb = (size_t)B;
+#define PULL(dst, off, per_car) if (dst) { if (int rc = pull_field(h, dst, off, (per_car) * nb, first, count)) return rc; }
+    PULL(s, l.s, 8); PULL(pose, l.pose, 24); PULL(wp_id, l.wp_id, 4); PULL(x0, l.x0, 24); PULL(u, l.u, 16);
+    PULL(status, l.status, 4); PULL(counter, l.counter, 4); PULL(alive, l.alive, 4);
+    PULL(plan, l.plan, 16 * N); PULL(pred_x, l.pred_x, 8 * (N - 2)); PULL(pred_y, l.pred_y, 8 * (N - 2));
+    PULL(ub, l.ub, 8 * N); PULL(lb, l.lb, 8 * N);
+#undef PULL
+  }
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return MPMPC_OK;
 }
 
@@ -1541,6 +1649,13 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     if (h->obst_gen != h->base_gen || h->built_gen != h->base_gen)
       return fail(MPMPC_E_STATE, "map, path or geometry changed since mpmpc_rollout_set_obstacles / mpmpc_build_corridor");
   }
+  const bool recording = h->rec_cap > 0;
+  if (recording) {
+    if (h->rec_B != B) return fail(MPMPC_E_STATE, "mpmpc_rollout_record was set up for another number of cars");
+    if (h->rec_count + records_of(h, n_steps) > h->rec_cap)
+      return fail(MPMPC_E_STATE, "the trace is full: " + std::to_string(h->rec_count) + " of " + std::to_string(h->rec_cap) +
+                                     " records held, this call would add " + std::to_string(records_of(h, n_steps)));
+  }
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int blocks = (B + 255) / 256;
   const int N = h->cfg.N;
@@ -1550,6 +1665,10 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   PathGeom pg{h->gx, h->gy, h->gpsi, h->ds_next, h->n_wp, h->cfg.circular, h->gtrig};
   h->have_rows = per_car;     // K1 / K2 read the per-instance rows K0c writes (else: the table)
   for (int t = 0; t < n_steps; ++t) {
+    char* rec = recording && h->ro_steps % h->rec_stride == 0 ? h->rec_buf + (size_t)h->rec_lay.bytes * (size_t)h->rec_count : nullptr;
+    if (rec)
+      hipLaunchKernelGGL(mpmpc_record_snapshot_kernel, dim3((unsigned)(((long)B * RO_REC_BEGIN_ENTRIES + 255) / 256)), dim3(256), 0,
+                         h->stream, B, h->ro_s, h->ro_pose, h->ro_alive, h->rec_ain, rec, h->rec_lay);
     hipLaunchKernelGGL(mpmpc_localise_kernel, dim3(blocks), dim3(256), 0, h->stream, B, h->n_wp, h->cfg.N,
                        h->cfg.circular ? 1 : 0, h->ro_cum, h->gx, h->gy,
                        h->gpsi, h->ro_s, h->ro_pose, h->ro_alive, h->wp_id, h->x0, h->ro_shift);
@@ -1561,6 +1680,15 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, h->stream, B, h->cfg.N, h->cfg.wheelbase, h->ro_Ts,
                        h->kappa, h->wp_id, h->x0, h->status, h->z, h->cc, h->ro_counter, h->ro_alive, h->ro_pose, h->ro_s,
                        h->ro_u);
+    if (rec) {
+      const RoRecSrc src{h->ro_alive, h->rec_ain, h->wp_id, h->status, h->ro_counter, h->x0, h->ro_u, h->cc, h->z,
+                         h->gx, h->gy, h->gtrig, per_car ? h->ub : h->ub_tab, per_car ? h->lb : h->lb_tab,
+                         per_car ? (long long)N : (long long)h->n_cols, per_car ? 1 : 0, COR_TRIG, N, h->n_wp, h->cfg.circular ? 1 : 0};
+      hipLaunchKernelGGL(mpmpc_record_write_kernel, dim3((unsigned)(((long)B * h->rec_lay.entries + 255) / 256)), dim3(256), 0,
+                         h->stream, B, src, rec, h->rec_lay);
+      ++h->rec_count;
+    }
+    ++h->ro_steps;
   }
   HIP_TRY(hipGetLastError());
   if (n_steps > 0) h->car_rows = per_car;

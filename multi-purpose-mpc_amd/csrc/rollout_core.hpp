@@ -88,4 +88,119 @@ MPMPC_HD bool ro_advance(int N, double L, double Ts, int status, const double* z
   return ro_drive(N, L, Ts, status, cc, counter, x0, kappa_wp, pose, s, u_out);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Recorder (mpmpc_rollout_record): one record per car and recorded step, written while the cars drive.
+//   ro_record_begin    before localise: s, pose and alive as the step finds them (localise / advance overwrite them)
+//   ro_record_finish   after advance: everything else, masked by how the step went for the car (include/mpmpc.h)
+// Both are written for ONE ENTRY of one car, so that the device gives every entry its own thread (consecutive
+// threads store consecutive words) and the host twin (tests/emul_trace) loops over the same code.
+// "Empty": NaN for doubles, -1 for wp_id, 0 for status.
+constexpr int RO_REC_PLAN = 1, RO_REC_PRED = 2, RO_REC_ROWS = 4, RO_REC_ALL = 7;
+constexpr int RO_REC_BEGIN_ENTRIES = 4;      // s, pose[3]
+constexpr int RO_REC_FIXED_ENTRIES = 9;      // x0[3], u[2], wp_id, status, counter, alive
+
+// Byte offsets of the fields inside one record of B cars; every field lies as the host arrays of mpmpc_rollout_trace
+// do ([B] or [B][len], car-major), so a range of records comes back with one strided copy per field.  -1: not recorded.
+struct RoTraceLayout {
+  long long s, pose, x0, u, wp_id, status, counter, alive, plan, pred_x, pred_y, ub, lb;
+  long long bytes;      // of one record (a multiple of 256)
+  int entries;          // per car in ro_record_finish
+};
+inline RoTraceLayout ro_trace_layout(int N, int B, int fields) {
+  RoTraceLayout l;
+  long long at = 0;
+  auto take = [&](long long per_car) { const long long o = at; at += (per_car * B + 255) / 256 * 256; return o; };
+  l.s = take(8); l.pose = take(24); l.x0 = take(24); l.u = take(16);
+  l.wp_id = take(4); l.status = take(4); l.counter = take(4); l.alive = take(4);
+  l.plan = (fields & RO_REC_PLAN) ? take(16LL * N) : -1;
+  l.pred_x = (fields & RO_REC_PRED) ? take(8LL * (N - 2)) : -1;
+  l.pred_y = (fields & RO_REC_PRED) ? take(8LL * (N - 2)) : -1;
+  l.ub = (fields & RO_REC_ROWS) ? take(8LL * N) : -1;
+  l.lb = (fields & RO_REC_ROWS) ? take(8LL * N) : -1;
+  l.bytes = at;
+  l.entries = RO_REC_FIXED_ENTRIES + ((fields & RO_REC_PLAN) ? 2 * N : 0) + ((fields & RO_REC_PRED) ? 2 * (N - 2) : 0) +
+              ((fields & RO_REC_ROWS) ? 2 * N : 0);
+  return l;
+}
+
+// what a record's fields may hold, from the car's alive before (a_in) and after (a) the step
+MPMPC_HD bool ro_rec_state(int a_in) { return a_in == 1; }                                   // s, pose
+MPMPC_HD bool ro_rec_input(int a_in, int a) { return a_in == 1 && a != 0; }                  // wp_id, x0
+MPMPC_HD bool ro_rec_solved(int a_in, int a) { return a_in == 1 && (a == 1 || a == -1); }    // status, u, plan, rows
+MPMPC_HD bool ro_rec_pred(int a_in, int a, int status) { return ro_rec_solved(a_in, a) && ro_usable(status); }
+MPMPC_HD double ro_rec_nan() { return __builtin_nan(""); }
+
+// BicycleModel.s2t of (e_y, waypoint), as MPC.update_prediction applies it (src/MPC.py:224-248): world x / y
+MPMPC_HD void ro_pred_point(double wx, double wy, double cos_w, double sin_w, double e_y, double* px, double* py) {
+  *px = wx - e_y * sin_w;
+  *py = wy + e_y * cos_w;
+}
+
+// entry c of car i: 0 = s, 1 .. 3 = pose; c == 0 also keeps a_in for ro_record_finish
+MPMPC_HD void ro_record_begin(const double* s, const double* pose, const int* alive, int* a_in, char* rec,
+                              const RoTraceLayout& l, int i, int c) {
+  const int a = alive[i];
+  const bool have = ro_rec_state(a);
+  if (c == 0) {
+    a_in[i] = a;
+    ((double*)(rec + l.s))[i] = have ? s[i] : ro_rec_nan();
+  } else {
+    ((double*)(rec + l.pose))[3LL * i + c - 1] = have ? pose[3LL * i + c - 1] : ro_rec_nan();
+  }
+}
+
+// what ro_record_finish reads: the rollout's state after advance, the step's solution, the path's tables
+struct RoRecSrc {
+  const int *alive, *a_in, *wp_id, *status, *counter;
+  const double *x0, *u, *cc, *z;            // z [B][5N+3]
+  const double *gx, *gy, *trig;             // per waypoint; trig [n_wp][trig_ld] = cos(psi), sin(psi), ...
+  const double *row_ub, *row_lb;            // corridor rows: row `wp_id` of the table, or row `car` of the per-car rows
+  long long row_ld;
+  int per_car, trig_ld, N, n_wp, circular;
+};
+
+// entry e of car i, in the order x0[3], u[2], wp_id, status, counter, alive, then plan / pred_x / pred_y / ub / lb as recorded
+MPMPC_HD void ro_record_finish(const RoRecSrc& r, char* rec, const RoTraceLayout& l, int i, int e) {
+  const int N = r.N;
+  const int a_in = r.a_in[i], a = r.alive[i];
+  const bool input = ro_rec_input(a_in, a), solved = ro_rec_solved(a_in, a);
+  const double nan = ro_rec_nan();
+  if (e < 3) { ((double*)(rec + l.x0))[3LL * i + e] = input ? r.x0[3LL * i + e] : nan; return; }
+  if (e < 5) { ((double*)(rec + l.u))[2LL * i + e - 3] = solved ? r.u[2LL * i + e - 3] : nan; return; }
+  if (e == 5) { ((int*)(rec + l.wp_id))[i] = input ? r.wp_id[i] : -1; return; }
+  if (e == 6) { ((int*)(rec + l.status))[i] = solved ? r.status[i] : 0; return; }
+  if (e == 7) { ((int*)(rec + l.counter))[i] = r.counter[i]; return; }
+  if (e == 8) { ((int*)(rec + l.alive))[i] = a; return; }
+  e -= RO_REC_FIXED_ENTRIES;
+  if (l.plan >= 0) {
+    if (e < 2 * N) { ((double*)(rec + l.plan))[2LL * N * i + e] = solved ? r.cc[2LL * N * i + e] : nan; return; }
+    e -= 2 * N;
+  }
+  if (l.pred_x >= 0) {
+    if (e < 2 * (N - 2)) {
+      const bool is_y = e >= N - 2;
+      const int k = (is_y ? e - (N - 2) : e) + 2;      // stage 2 .. N-1
+      double v = nan;
+      if (ro_rec_pred(a_in, a, r.status[i])) {
+        int w = r.wp_id[i] + k;
+        if (w >= r.n_wp) w = r.circular ? w % r.n_wp : r.n_wp - 1;
+        double px, py;
+        ro_pred_point(r.gx[w], r.gy[w], r.trig[(long long)w * r.trig_ld], r.trig[(long long)w * r.trig_ld + 1],
+                      r.z[(5LL * N + 3) * i + 3 * k], &px, &py);
+        v = is_y ? py : px;
+      }
+      ((double*)(rec + (is_y ? l.pred_y : l.pred_x)))[(long long)(N - 2) * i + k - 2] = v;
+      return;
+    }
+    e -= 2 * (N - 2);
+  }
+  if (l.ub >= 0 && e < 2 * N) {
+    const bool is_lb = e >= N;
+    const int k = is_lb ? e - N : e;
+    const long long row = r.per_car ? i : (solved ? r.wp_id[i] : 0);
+    const double* src = is_lb ? r.row_lb : r.row_ub;
+    ((double*)(rec + (is_lb ? l.lb : l.ub)))[(long long)N * i + k] = solved ? src[row * r.row_ld + k] : nan;
+  }
+}
+
 }  // namespace mpmpc

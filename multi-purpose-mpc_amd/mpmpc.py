@@ -19,6 +19,7 @@ MAX_HORIZON = 255
 
 SOLVED, SOLVED_INACCURATE = 1, 2
 MAX_ITER_REACHED, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE, UNSOLVED = -2, -3, -4, -10
+REC_PLAN, REC_PRED, REC_ROWS = 1, 2, 4      # optional fields of a rollout record (mpmpc_rollout_record)
 
 
 class Config(C.Structure):
@@ -160,6 +161,9 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_state.argtypes = [h, C.c_int32, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip]
     lib.mpmpc_rollout_set_obstacles.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_corridor.argtypes = [h, C.c_int32, _dp, _dp]
+    lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.mpmpc_rollout_recorded.argtypes = [h, _ip, _ip]
+    lib.mpmpc_rollout_trace.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
     lib.mpmpc_assemble.argtypes = [h, C.c_int32, _ip, _dp, _dp, _dp, _dp, _dp]
     lib.mpmpc_stage_ld.argtypes = [C.c_int32]
     lib.mpmpc_stage_ld.restype = C.c_int32
@@ -186,7 +190,8 @@ def load_library(path: str | None = None):
 EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_default_settings",
            "mpmpc_create", "mpmpc_destroy", "mpmpc_set_settings", "mpmpc_set_packing", "mpmpc_set_tail_kernel", "mpmpc_set_path", "mpmpc_set_corridor",
            "mpmpc_set_map", "mpmpc_set_path_geometry", "mpmpc_build_corridor", "mpmpc_rollout_init",
-           "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline",
+           "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor",
+           "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline",
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_staging",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
@@ -355,6 +360,58 @@ class Handle:
         ub, lb = np.zeros((B, N)), np.zeros((B, N))
         self._check(self.lib.mpmpc_rollout_corridor(self._h, B, _d(ub), _d(lb)))
         return ub, lb
+
+    # --- recorder of the rollout: one record per car and recorded step, kept on the device
+    TRACE_BASIC = ("s", "pose", "wp_id", "x0", "u", "status", "counter", "alive")
+
+    def rollout_record(self, capacity, plan=False, prediction=False, rows=False, stride=1, B=None):
+        """Record every `stride`-th step of the rollouts that follow into a device-resident trace of `capacity` records:
+        always s, pose (the state the step started from), wp_id, x0, u, status, counter, alive; optionally the plan after
+        the step, the predicted path (world x / y of stages 2 .. N-1, MPC.update_prediction) and the corridor row the QP
+        used.  capacity = 0 switches recording off and frees the memory.  B: cars per record (default: the rollout's, so
+        before the first rollout_init it must be given).  A rollout_step that would overflow the trace raises and does
+        nothing; rollout_init keeps the configuration and empties the trace."""
+        B = int(B if B is not None else getattr(self, "_ro_B", 0))
+        if B < 1:
+            raise ValueError("rollout_record before rollout_init needs B")
+        fields = (REC_PLAN if plan else 0) | (REC_PRED if prediction else 0) | (REC_ROWS if rows else 0)
+        self._check(self.lib.mpmpc_rollout_record(self._h, B, int(capacity), fields, int(stride)))
+        self._rec = (B, fields) if capacity else None
+
+    def rollout_recorded(self):
+        """-> (records held, rollout steps taken since rollout_init)"""
+        n, k = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.mpmpc_rollout_recorded(self._h, C.byref(n), C.byref(k)))
+        return n.value, k.value
+
+    def rollout_trace(self, first=0, count=None, fields=None):
+        """Records first .. first + count - 1 (default: all from `first`) -> dict of arrays [count, B, ...]: s, pose [.., 3],
+        wp_id, x0 [.., 3], u [.., 2], status, counter, alive, and - where recorded - plan [.., 2N], pred_x / pred_y [.., N-2],
+        ub / lb [.., N].  fields: names to fetch (default: everything recorded; asking for one that was not raises).  Entries
+        a step did not produce for a car are empty - NaN, wp_id -1, status 0 (include/mpmpc.h has the table)."""
+        if getattr(self, "_rec", None) is None:
+            raise MpmpcError("mpmpc error -3: recording is off (rollout_record)")
+        B, rec = self._rec
+        N = self.N
+        if count is None:
+            count = self.rollout_recorded()[0] - int(first)
+        count = int(count)
+        names = list(self.TRACE_BASIC) + (["plan"] if rec & REC_PLAN else []) + (["pred_x", "pred_y"] if rec & REC_PRED else []) + \
+            (["ub", "lb"] if rec & REC_ROWS else [])
+        if fields is not None:
+            names = list(fields)
+        shape = dict(s=(), pose=(3,), wp_id=(), x0=(3,), u=(2,), status=(), counter=(), alive=(), plan=(2 * N,),
+                     pred_x=(N - 2,), pred_y=(N - 2,), ub=(N,), lb=(N,))
+        ints = ("wp_id", "status", "counter", "alive")
+        for k in names:
+            if k not in shape:
+                raise ValueError("unknown trace field %r" % (k,))
+        out = {k: np.zeros((max(count, 0), B) + shape[k], np.int32 if k in ints else np.float64) for k in names}
+        a = {k: (_i(out[k]) if k in ints else _d(out[k])) if k in out else None for k in shape}
+        self._check(self.lib.mpmpc_rollout_trace(self._h, B, int(first), count, a["s"], a["pose"], a["wp_id"], a["x0"], a["u"],
+                                                 a["status"], a["counter"], a["alive"], a["plan"], a["pred_x"], a["pred_y"],
+                                                 a["ub"], a["lb"]))
+        return out
 
     def _inputs(self, wp_id, x0, cc_prev, lb, ub):
         wp = np.ascontiguousarray(wp_id, dtype=np.int32).ravel()
