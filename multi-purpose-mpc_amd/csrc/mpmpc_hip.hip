@@ -14,8 +14,14 @@
 //   K2t mpmpc_reduced_t_kernel  its twin for a terminal cost on the time state (rank-one term, Sherman-Morrison)
 //   K2p mpmpc_reduced_tail_kernel  the tail of a K2r launch (infeasible / marginal / capped instances) on the same footing:
 //                               phase 1 and one more attempt; K2 takes what it leaves
-//   K2b / K2rb                  horizons 64 .. 255: the general and the reduced-native solver on a WORKGROUP of 2 / 4 wavefronts
-//                               per instance (lane_gpu.hpp: LaneBlock)
+//   K2r2 / K2t2 / K2p2          mpmpc_reduced_pair_kernel, mpmpc_reduced_t_pair_kernel, mpmpc_reduced_tail_pair_kernel: the same
+//                               three solvers with TWO STAGES PER LANE (lane_pair.hpp) - 17 .. 32 stages in 16 lanes (K2r2<16>,
+//                               on request) and horizons 64 .. 127 in ONE wavefront (<64>)
+//   K2b / K2rb                  mpmpc_solve_block_kernel, mpmpc_reduced_block_kernel - horizons 64 .. 255: the general and the
+//                               reduced-native solver on a WORKGROUP of 2 / 4 wavefronts per instance (lane_gpu.hpp: LaneBlock)
+//   K2rb2                       mpmpc_reduced_pair_block_kernel, with mpmpc_reduced_tail_pair_block_kernel and
+//                               mpmpc_reduced_t_pair_block_kernel - horizons 128 .. 255: two stages per lane on a workgroup of two
+//   The twelve solve kernels (K2 ...) are the same steps around their solvers: "the steps of a solve kernel" below.
 //   K0 / K3 / K4                corridor tables from the map, closed-loop rollout, speed profile (see below).
 //
 // No CPU path exists in this library: every compute entry point needs a HIP device.
@@ -128,6 +134,69 @@ struct AssembleIn {
   const int* wp_id;
   const double *x0, *cc, *lb, *ub;
 };
+
+// ---------------------------------------------------------------------------------- the steps of a solve kernel
+// Every solve kernel below is the same eight steps around its solver; each step is written once here:
+//   1 empty_lists          the tail list(s) the NEXT launch appends to start empty
+//   2 inst_in_*            which instance this lane has - in batch order (a workgroup kernel is batch order with one
+//                          instance per group), or in the order of a tail list, one entry per group or packed - and
+//                          its stage, minus the lane offset of the layout
+//   3 the warm-start guess (K2 and K2r, written out there: as a function it changes the branches of both)
+//   4 assemble_in          the lane's 27 fields, in registers
+//   5 the solver's run     (the kernel's own: the solvers' signatures differ)
+//   6 *_again              instance and stage formed anew, so that they do not live in registers through the solve
+//   7 the solver's store   (the kernel's own)
+//   8 MPMPC_LEFT_UNSOLVED / leave_to_tail   stage 0 of an instance left MPMPC_UNSOLVED appends it to the list of the next kernel
+// (tests/emul/wave_loop.hpp is the same skeleton for the CPU emulation, with the same names)
+template <class... P>
+MPMPC_HD void empty_lists(P*... list) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) ((*list = 0), ...);
+}
+
+// batch order: group g carries the instances g * per_wave .. (the last group of a packed launch may carry ids >= B: "none")
+template <class L>
+MPMPC_HD typename L::ival inst_in_batch() { return L::slot() + (int)(blockIdx.x * L::per_wave); }
+template <class L>
+MPMPC_HD typename L::ival inst_in_batch_again() { return L::slot_again() + (int)(blockIdx.x * L::per_wave); }
+// list order: the groups take consecutive entries of list[1..], list[0] counts; groups beyond its end return at once
+#define MPMPC_PAST_LIST(list) ((int)blockIdx.x * L::per_wave >= (list)[0])          // (L: the kernel's lanes; a macro for the reason given at step 8)
+MPMPC_HD int inst_in_list(const int* list) { return list[1 + blockIdx.x]; }      // one instance per group
+// ... packed: the last wave may carry B = "none"
+template <class L>
+MPMPC_HD int inst_in_packed_list(const int* list, int B) {
+  const int e = blockIdx.x * L::per_wave + L::slot();
+  return e < list[0] ? list[1 + e] : B;
+}
+template <class L>
+MPMPC_HD int inst_in_packed_list_again(const int* list, int B) {
+  const int e = blockIdx.x * L::per_wave + L::slot_again();
+  return e < list[0] ? list[1 + e] : B;
+}
+// (the workgroup kernels keep the values of step 2 through the solve: LaneBlock's *_again are the same threadIdx.x)
+
+template <class L>
+MPMPC_HD void assemble_in(const mpmpc_config& cfg, const AssembleIn& ain, int B, const typename L::ival& inst,
+                          const typename L::ival& k, typename L::real* fields) {
+  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+}
+
+// Has this lane stage 0 of an instance of the batch that the solver left MPMPC_UNSOLVED?  For an `if`, on the scalars of the
+// lane's first stage (two stages per lane: component 0).
+// (Why the tests of steps 2 and 8 are macros and the stage line and step 3 are written out in the kernels: a function is
+//  optimised on its own before it is inlined - an && chain it returns becomes selects, `stage - lane_offset` is reassociated -
+//  and the branches and the register allocation of every kernel that calls it change; the pieces that are functions are
+//  those that leave every kernel's instructions as they were: profiles/kernel_resources.py --compare, docs/HISTORY.md.)
+#define MPMPC_LEFT_UNSOLVED(inst, k, status) ((k) == 0 && (inst) < B && (status) == MPMPC_UNSOLVED)
+// ... of a kernel that takes one instance per group from a list: its entries are always < B and no lane carries "none"
+#define MPMPC_LEFT_UNSOLVED_LISTED(k, status) ((k) == 0 && (status) == MPMPC_UNSOLVED)
+MPMPC_HD void leave_to_tail(int* list, int inst) { list[1 + atomicAdd(list, 1)] = inst; }
+// ... and "this launch left a tail": the launch's sequence number, in host memory the device writes through (read by the host
+// after the stream has drained: observe_tail)
+MPMPC_HD void leave_to_tail(int* list, int inst, unsigned* flag, unsigned seq) {
+  leave_to_tail(list, inst);
+  __hip_atomic_store(flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // VAR: 0 = the full problem with diagonal weights, 1 = full weights (FQ: Q, R, QN with off-diagonal entries), 2 = reduced polish (RED),
 //      3 = the full problem whose states e_psi and t have no bounds (FREEX; one-instance-per-wave kernels only)
 template <int G, int C, bool WARM, int VAR = 0>
@@ -139,12 +208,12 @@ __global__ __launch_bounds__(64) void mpmpc_solve_kernel(mpmpc_config cfg, Solve
                                                          int* __restrict__ act, const int* __restrict__ shift,
                                                          int* __restrict__ tail_reset) {
   using L = LaneGpu<G, C>;
-  int inst = blockIdx.x * L::per_wave + L::slot();
+  int inst = inst_in_batch<L>();
   if (mode == 2) {
     // the list the NEXT launch on this handle will fill starts empty (two lists, used in turn: no memset between launches)
-    if (blockIdx.x == 0 && threadIdx.x == 0) *tail_reset = 0;
-    if ((int)blockIdx.x >= tail[0]) return;       // wave-uniform: G = 64 here
-    inst = tail[1 + blockIdx.x];
+    empty_lists(tail_reset);
+    if (MPMPC_PAST_LIST(tail)) return;       // wave-uniform: G = 64 here
+    inst = inst_in_list(tail);
   }
   const int k = L::stage() - lane_offset(G, C, cfg.N);      // stage of this lane (negative / > N: none)
   // closed loop: the active set the previous step certified for this car, moved on by the waypoints it advanced
@@ -155,7 +224,7 @@ __global__ __launch_bounds__(64) void mpmpc_solve_kernel(mpmpc_config cfg, Solve
   }
   MPMPC_TICK_BEGIN(8);
   double fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   Solver<L, VAR == 1, VAR == 2, VAR == 3, VAR == 2> s;   // (the reduced variant factors its 16-lane chains by cyclic reduction, like the reduced-native kernels)
   // (second launch of a packed batch: the interior-point iterations the first launch spent on this instance)
   const int base_ipm = (mode == 2 && iters) ? iters[inst * 2 + 1] : 0;
@@ -167,7 +236,7 @@ __global__ __launch_bounds__(64) void mpmpc_solve_kernel(mpmpc_config cfg, Solve
   s.store(inst, k, cfg.wheelbase, z, u0, status, iters, resid, y, WARM ? act : nullptr, ld);
   MPMPC_TICK_END(7);
   MPMPC_TICK_END(8);
-  if (mode == 1 && k == 0 && inst < B && s.status == MPMPC_UNSOLVED) tail[1 + atomicAdd(tail, 1)] = inst;
+  if (mode == 1 && MPMPC_LEFT_UNSOLVED(inst, k, s.status)) leave_to_tail(tail, inst);
 }
 
 // K2b: the general solve kernel for horizons above 63 - one instance per WORKGROUP of G = 128 / 256 threads (2 / 4
@@ -184,11 +253,11 @@ __global__ __launch_bounds__(G) void mpmpc_solve_block_kernel(mpmpc_config cfg, 
   using L = LaneBlock<G>;
   // tail: the instances the reduced-native workgroup kernel (below) could not certify - one workgroup each, straight to
   // phase 1 and the full iteration (mode 2, as for the wavefront kernels); null: every instance, the whole solve
-  if (tail && (int)blockIdx.x >= tail[0]) return;
-  const int inst = tail ? tail[1 + blockIdx.x] : (int)blockIdx.x;
+  if (tail && MPMPC_PAST_LIST(tail)) return;
+  const int inst = tail ? inst_in_list(tail) : inst_in_batch<L>();
   const int k = L::stage() - lane_offset(G, G / 2, cfg.N);
   double fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   // (the reduced variant factors its chains of four / eight rows by cyclic reduction: Solver::kCR64)
   Solver<L, VAR == 1, VAR == 2, false, VAR == 2> s;
   double woff[7];
@@ -202,6 +271,7 @@ __global__ __launch_bounds__(G) void mpmpc_solve_block_kernel(mpmpc_config cfg, 
 // point from x = 0, active-set rounds, certificate) on a workgroup, for the reference's own weights at horizons above 63.
 // What it cannot certify is listed in `tail` for mpmpc_solve_block_kernel<G, 2>.
 // (40 cold slots like K2r instead of the general solver's 66: 50 KB of LDS per workgroup at G = 128 - three workgroups per CU)
+// (the workgroup kernels empty no list: launch_long_horizon does it with a memset in front of them)
 constexpr int RNB_SLOTS = 40;
 template <int G>
 __global__ __launch_bounds__(G) void mpmpc_reduced_block_kernel(mpmpc_config cfg, SolverParams st, int B, AssembleIn ain,
@@ -210,14 +280,14 @@ __global__ __launch_bounds__(G) void mpmpc_reduced_block_kernel(mpmpc_config cfg
                                                                 double* __restrict__ resid, double* __restrict__ y,
                                                                 int* __restrict__ tail) {
   using L = LaneBlock<G, RNB_SLOTS>;
-  const int inst = blockIdx.x;
+  const int inst = inst_in_batch<L>();
   const int k = L::stage() - lane_offset(G, G / 2, cfg.N);
   double fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   ReducedSolver<L> s;
   s.template run<false>(fields, B, inst, k, cfg.N, st, 0);
   s.store(inst, k, cfg.wheelbase, z, u0, status, iters, resid, y, nullptr, 0);
-  if (k == 0 && inst < B && s.status == MPMPC_UNSOLVED) tail[1 + atomicAdd(tail, 1)] = inst;
+  if (MPMPC_LEFT_UNSOLVED(inst, k, s.status)) leave_to_tail(tail, inst);
 }
 
 // K2r: the reduced-native solve kernel (mpmpc_reduced.hpp) - the batch path of every configuration whose time state
@@ -238,17 +308,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   using L = LaneGpu<G, C, RN_SLOTS>;
   // (the list of the NEXT launch is emptied here as well: the tail launch, which does it too, may be deferred - see
   //  launch_solve; and so is the list the reduced-native tail kernel of THIS launch appends to)
-  if (blockIdx.x == 0 && threadIdx.x == 0) { *tail_reset = 0; *tail2_reset = 0; }
+  empty_lists(tail_reset, tail2_reset);
+  // (the instance stays written out in K2r and K2t, which carry every headline number: a helper around these lines has
+  //  moved their instructions in every form tried - docs/HISTORY.md)
   const int inst = blockIdx.x * L::per_wave + L::slot();
   const int k = L::stage() - lane_offset(G, C, cfg.N);
-  int guess = 0;
+  int guess = 0;          // (step 3 as in mpmpc_solve_kernel, whose launch may come without the two arrays)
   if (WARM && inst < B && k >= 0 && k <= cfg.N) {
     const int kk = k + shift[inst];
     guess = act[inst * ld + (kk > cfg.N ? cfg.N : kk)];
   }
   MPMPC_TICK_BEGIN(8);
   double fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   ReducedSolver<L> s;
   s.template run<WARM>(fields, B, inst, k, cfg.N, st, guess);
   MPMPC_TICK_BEGIN(7);
@@ -258,12 +330,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   s.store(inst_o, k_o, cfg.wheelbase, z, u0, status, iters, resid, y, WARM ? act : nullptr, ld);
   MPMPC_TICK_END(7);
   MPMPC_TICK_END(8);
-  if (k_o == 0 && inst_o < B && s.status == MPMPC_UNSOLVED) {
-    tail[1 + atomicAdd(tail, 1)] = inst_o;
-    // "this launch left a tail": the launch's sequence number, in host memory the device writes through (read by the host
-    // after the stream has drained: observe_tail)
-    __hip_atomic_store(tail_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (MPMPC_LEFT_UNSOLVED(inst_o, k_o, s.status)) leave_to_tail(tail, inst_o, tail_flag, seq);
 }
 
 // K2r2: K2r with TWO STAGES PER LANE (lane_pair.hpp): an instance of 17 .. 32 stages takes 16 lanes, a
@@ -285,24 +352,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                                                            int* __restrict__ tail, int* __restrict__ tail_reset,
                                                            unsigned* __restrict__ tail_flag, unsigned seq, int* __restrict__ tail2_reset) {
   using L = LanePair<LaneGpu<GB, GB, RN2_SLOTS>>;
-  if (blockIdx.x == 0 && threadIdx.x == 0) { *tail_reset = 0; *tail2_reset = 0; }
-  const I2 inst = L::slot() + (int)(blockIdx.x * L::per_wave);
+  empty_lists(tail_reset, tail2_reset);
+  const I2 inst = inst_in_batch<L>();
   const I2 k = L::stage();          // (one chain, stage 0 on lane 0: no lane offset)
   MPMPC_TICK_BEGIN(8);
   D2 fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   ReducedSolver<L> s;
   s.template run<false>(fields, B, inst, k, cfg.N, st);
   MPMPC_TICK_BEGIN(7);
-  const I2 inst_o = L::slot_again() + (int)(blockIdx.x * L::per_wave);
+  const I2 inst_o = inst_in_batch_again<L>();
   const I2 k_o = L::stage_again();
   s.store(inst_o, k_o, cfg.wheelbase, z, u0, status, iters, resid, y, nullptr, ld);
   MPMPC_TICK_END(7);
   MPMPC_TICK_END(8);
-  if (k_o.v[0] == 0 && inst_o.v[0] < B && s.status.v[0] == MPMPC_UNSOLVED) {
-    tail[1 + atomicAdd(tail, 1)] = inst_o.v[0];
-    __hip_atomic_store(tail_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (MPMPC_LEFT_UNSOLVED(inst_o.v[0], k_o.v[0], s.status.v[0])) leave_to_tail(tail, inst_o.v[0], tail_flag, seq);
 }
 
 // K2rb2: horizons 128 .. 255 with two stages per lane - the instance on a workgroup of TWO wavefronts (128 lanes, one chain of
@@ -317,15 +381,15 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                                            double* __restrict__ resid, double* __restrict__ y,
                                                            int* __restrict__ tail) {
   using L = LanePairBlock;
-  const I2 inst((int)blockIdx.x);
+  const I2 inst = inst_in_batch<L>();
   const I2 k = L::stage();
   D2 fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   ReducedSolver<L> s;
   static_assert(ReducedSolver<L>::kLean, "37 pair slots: the lean cold storage");
   s.template run<false>(fields, B, inst, k, cfg.N, st);
   s.store(inst, k, cfg.wheelbase, z, u0, status, iters, resid, y, nullptr, 0);
-  if (k.v[0] == 0 && inst.v[0] < B && s.status.v[0] == MPMPC_UNSOLVED) tail[1 + atomicAdd(tail, 1)] = inst.v[0];
+  if (MPMPC_LEFT_UNSOLVED(inst.v[0], k.v[0], s.status.v[0])) leave_to_tail(tail, inst.v[0]);
 }
 
 // ... its tail (K2p's solver) and its twin for a terminal cost on the time state (K2t's solver) on the same workgroup layout, with
@@ -338,17 +402,17 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                                            double* __restrict__ resid, double* __restrict__ y,
                                                            const int* __restrict__ tail, int* __restrict__ tail2) {
   using L = LanePairBlockFull;
-  if ((int)blockIdx.x >= tail[0]) return;
-  const int in0 = tail[1 + blockIdx.x];
+  if (MPMPC_PAST_LIST(tail)) return;
+  const int in0 = inst_in_list(tail);
   const I2 inst(in0);
   const I2 k = L::stage();
   D2 fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   ReducedTailSolver<L> s;
   const int base = iters ? iters[in0 * 2 + 1] : 0;
   s.run(fields, B, inst, k, cfg.N, st, I2(base));
   s.store(inst, k, cfg.wheelbase, z, u0, status, iters, resid, y);
-  if (k.v[0] == 0 && s.status.v[0] == MPMPC_UNSOLVED) tail2[1 + atomicAdd(tail2, 1)] = in0;
+  if (MPMPC_LEFT_UNSOLVED_LISTED(k.v[0], s.status.v[0])) leave_to_tail(tail2, in0);
 }
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) void mpmpc_reduced_t_pair_block_kernel(mpmpc_config cfg, SolverParams st, int B, AssembleIn ain,
                                                            double* __restrict__ z, double* __restrict__ u0,
@@ -356,14 +420,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                                            double* __restrict__ resid, double* __restrict__ y,
                                                            int* __restrict__ tail) {
   using L = LanePairBlockFull;
-  const I2 inst((int)blockIdx.x);
+  const I2 inst = inst_in_batch<L>();
   const I2 k = L::stage();
   D2 fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   ReducedTSolver<L> s;
   s.run(fields, B, inst, k, cfg.N, st, cfg.QN[2]);
   s.store(inst, k, cfg.wheelbase, z, u0, status, iters, resid, y);
-  if (k.v[0] == 0 && inst.v[0] < B && s.status.v[0] == MPMPC_UNSOLVED) tail[1 + atomicAdd(tail, 1)] = inst.v[0];
+  if (MPMPC_LEFT_UNSOLVED(inst.v[0], k.v[0], s.status.v[0])) leave_to_tail(tail, inst.v[0]);
 }
 
 // K2p2: the reduced-native TAIL solver (mpmpc_reduced_tail.hpp: phase 1 / Farkas ray / relaxed plan, one more attempt) with two
@@ -377,18 +441,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                                                            const int* __restrict__ tail, int* __restrict__ tail2) {
   using L = LanePair<LaneGpu<GB, GB, RN2_SLOTS>>;
   static_assert(L::per_wave == 1, "one instance per wavefront");
-  if ((int)blockIdx.x >= tail[0]) return;
-  const int in0 = tail[1 + blockIdx.x];
+  if (MPMPC_PAST_LIST(tail)) return;
+  const int in0 = inst_in_list(tail);
   const I2 inst(in0, in0);
   const I2 k = L::stage();
   D2 fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   ReducedTailSolver<L> s;
   const int base = iters ? iters[in0 * 2 + 1] : 0;
   s.run(fields, B, inst, k, cfg.N, st, I2(base));
   const I2 k_o = L::stage_again();
   s.store(inst, k_o, cfg.wheelbase, z, u0, status, iters, resid, y);
-  if (k_o.v[0] == 0 && s.status.v[0] == MPMPC_UNSOLVED) tail2[1 + atomicAdd(tail2, 1)] = in0;
+  if (MPMPC_LEFT_UNSOLVED_LISTED(k_o.v[0], s.status.v[0])) leave_to_tail(tail2, in0);
 }
 
 // K2t2: K2t with two stages per lane, for horizons 64 .. 127 - ONE wavefront per instance where such weights used to run the
@@ -400,16 +464,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                                                            double* __restrict__ resid, double* __restrict__ y,
                                                            int* __restrict__ tail) {
   using L = LanePair<LaneGpu<GB, GB, RN2_SLOTS>>;
-  const I2 inst = L::slot() + (int)(blockIdx.x * L::per_wave);
+  const I2 inst = inst_in_batch<L>();
   const I2 k = L::stage();
   D2 fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   ReducedTSolver<L> s;
   s.run(fields, B, inst, k, cfg.N, st, cfg.QN[2]);
-  const I2 inst_o = L::slot_again() + (int)(blockIdx.x * L::per_wave);
+  const I2 inst_o = inst_in_batch_again<L>();
   const I2 k_o = L::stage_again();
   s.store(inst_o, k_o, cfg.wheelbase, z, u0, status, iters, resid, y);
-  if (k_o.v[0] == 0 && inst_o.v[0] < B && s.status.v[0] == MPMPC_UNSOLVED) tail[1 + atomicAdd(tail, 1)] = inst_o.v[0];
+  if (MPMPC_LEFT_UNSOLVED(inst_o.v[0], k_o.v[0], s.status.v[0])) leave_to_tail(tail, inst_o.v[0]);
 }
 
 // K2t: the reduced-native kernel of the weightings with a TERMINAL cost on the time state (mpmpc_reduced_t.hpp; BASELINE
@@ -423,24 +487,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                                                            int* __restrict__ tail, int* __restrict__ tail_reset,
                                                            unsigned* __restrict__ tail_flag, unsigned seq) {
   using L = LaneGpu<G, C, RN_SLOTS>;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *tail_reset = 0;
+  empty_lists(tail_reset);           // (no reduced-native tail kernel follows this one: one list)
+  // (the instance stays written out in K2r and K2t, which carry every headline number: a helper around these lines has
+  //  moved their instructions in every form tried - docs/HISTORY.md)
   const int inst = blockIdx.x * L::per_wave + L::slot();
   const int k = L::stage() - lane_offset(G, C, cfg.N);
   MPMPC_TICK_BEGIN(8);
   double fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   ReducedTSolver<L> s;
   s.run(fields, B, inst, k, cfg.N, st, cfg.QN[2]);
   MPMPC_TICK_BEGIN(7);
+  // (instance and stage are formed again rather than kept in registers through the solve)
   const int inst_o = blockIdx.x * L::per_wave + L::slot_again();
   const int k_o = L::stage_again() - lane_offset(G, C, cfg.N);
   s.store(inst_o, k_o, cfg.wheelbase, z, u0, status, iters, resid, y);
   MPMPC_TICK_END(7);
   MPMPC_TICK_END(8);
-  if (k_o == 0 && inst_o < B && s.status == MPMPC_UNSOLVED) {
-    tail[1 + atomicAdd(tail, 1)] = inst_o;
-    __hip_atomic_store(tail_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (MPMPC_LEFT_UNSOLVED(inst_o, k_o, s.status)) leave_to_tail(tail, inst_o, tail_flag, seq);
 }
 
 // K2p: the reduced-native TAIL kernel (mpmpc_reduced_tail.hpp): phase 1 and one more attempt of the certified polish on
@@ -455,28 +519,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                                                            const int* __restrict__ tail, int* __restrict__ tail_reset,
                                                            int* __restrict__ tail2, unsigned* __restrict__ tail2_flag, unsigned seq) {
   using L = LaneGpu<G, C, RN_SLOTS>;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *tail_reset = 0;
-  if ((int)blockIdx.x * L::per_wave >= tail[0]) return;
-  // (the instances of a wave: consecutive entries of the list; the last wave of a packed launch may carry B = "none")
-  const int e_ = blockIdx.x * L::per_wave + L::slot();
-  const int inst = e_ < tail[0] ? tail[1 + e_] : B;
+  empty_lists(tail_reset);
+  if (MPMPC_PAST_LIST(tail)) return;
+  const int inst = inst_in_packed_list<L>(tail, B);
   const int k = L::stage() - lane_offset(G, C, cfg.N);
   MPMPC_TICK_BEGIN(8);
   double fields[MPMPC_NUM_FIELDS];
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_in<L>(cfg, ain, B, inst, k, fields);
   ReducedTailSolver<L> s;
   s.run(fields, B, inst, k, cfg.N, st, (iters && inst < B) ? iters[inst * 2 + 1] : 0);
   MPMPC_TICK_BEGIN(7);
-  const int e_o = blockIdx.x * L::per_wave + L::slot_again();
-  const int inst_o = e_o < tail[0] ? tail[1 + e_o] : B;
+  const int inst_o = inst_in_packed_list_again<L>(tail, B);
   const int k_o = L::stage_again() - lane_offset(G, C, cfg.N);
   s.store(inst_o, k_o, cfg.wheelbase, z, u0, status, iters, resid, y);
   MPMPC_TICK_END(7);
   MPMPC_TICK_END(8);
-  if (k_o == 0 && inst_o < B && s.status == MPMPC_UNSOLVED) {
-    tail2[1 + atomicAdd(tail2, 1)] = inst_o;
-    __hip_atomic_store(tail2_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (MPMPC_LEFT_UNSOLVED(inst_o, k_o, s.status)) leave_to_tail(tail2, inst_o, tail2_flag, seq);
 }
 
 // K4: speed profile.  The kernel of choice is mpmpc_speed_profile_wave_kernel below (one wavefront per path); these
@@ -1874,12 +1932,48 @@ struct SolveLaunch {
   int* warm_act;
   const int* warm_shift;
 };
+// THE launcher: every solve kernel starts with the same arguments - cfg, prm, B, [ld,] ain, z, u0, status, iters, resid, y - which
+// come from the launch; `own` are the kernel's trailing ones.  (Whether the kernel takes ld is read off its parameter list.)
+template <class... K>
+constexpr bool takes_ld(void (*)(mpmpc_config, SolverParams, int, int, AssembleIn, K...)) { return true; }
+template <class... K>
+constexpr bool takes_ld(void (*)(mpmpc_config, SolverParams, int, AssembleIn, K...)) { return false; }
+template <auto KERNEL, class... T>
+static void go(const SolveLaunch& a, int grid, int block, size_t lds, T... own) {
+  mpmpc_handle h = a.h;
+  if constexpr (takes_ld(KERNEL))
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, h->stream, h->cfg, a.prm, a.B, h->ld, a.ain, h->z, h->u0, h->status, h->iters, h->resid,
+                       a.y_out, own...);
+  else
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0, h->status, h->iters, h->resid, a.y_out,
+                       own...);
+}
+// The workgroup kernels need more dynamic LDS than the default limit: the attribute is set once per function AND DEVICE (one
+// process may drive several - sharded.py, bench.py --single-process - and the attribute belongs to the function on the device
+// that is current; two threads may both set it once: the call is idempotent)
+constexpr int MAX_DEVICES = 64;
+static int device_slot(mpmpc_handle h) { return h->cfg.device >= 0 && h->cfg.device < MAX_DEVICES ? h->cfg.device : 0; }
+template <auto KERNEL>
+static int raise_lds_limit(mpmpc_handle h, size_t bytes) {
+  static std::atomic<bool> attr_set[MAX_DEVICES];
+  if (!attr_set[device_slot(h)]) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    attr_set[device_slot(h)] = true;
+  }
+  return MPMPC_OK;
+}
+// ... one instance per WORKGROUP of `block` lanes, every instance of the batch
+template <auto KERNEL, class... T>
+static int go_workgroups(const SolveLaunch& a, int block, size_t lds, T... own) {
+  if (int rc = raise_lds_limit<KERNEL>(a.h, lds)) return rc;
+  go<KERNEL>(a, a.B, block, lds, own...);
+  return MPMPC_OK;
+}
+
 // general kernel, one instance per wave: the whole solve (mode 0) or the tail of a reduced-native launch (mode 2, list `tail`)
 template <int C, bool WARM, int VAR>
 static void go_general(const SolveLaunch& a, int mode, int blocks, int* tail) {
-  mpmpc_handle h = a.h;
-  hipLaunchKernelGGL((mpmpc_solve_kernel<64, C, WARM, VAR>), dim3(blocks), dim3(64), 0, h->stream, h->cfg, a.prm, a.B, h->ld, a.ain, h->z, h->u0,
-                     h->status, h->iters, h->resid, a.y_out, mode, tail, WARM ? a.warm_act : nullptr, WARM ? a.warm_shift : nullptr, a.tail_next);
+  go<mpmpc_solve_kernel<64, C, WARM, VAR>>(a, blocks, 64, 0, mode, tail, WARM ? a.warm_act : nullptr, WARM ? a.warm_shift : nullptr, a.tail_next);
 }
 using GeneralFn = void (*)(const SolveLaunch&, int, int, int*);
 // [C == 32][warm][VAR: 0 full problem, 1 full weights, 2 reduced polish, 3 free e_psi / t]
@@ -1897,9 +1991,7 @@ static int rn_pad() {
 // K2r: the reduced-native batch kernel, 1 / 2 / 4 instances per wave
 template <int G, int C, bool WARM>
 static void go_reduced(const SolveLaunch& a, int blocks) {
-  mpmpc_handle h = a.h;
-  hipLaunchKernelGGL((mpmpc_reduced_kernel<G, C, WARM>), dim3(blocks), dim3(64), rn_pad(), h->stream, h->cfg, a.prm, a.B, h->ld, a.ain, h->z, h->u0,
-                     h->status, h->iters, h->resid, a.y_out, a.tail_cur, a.warm_act, a.warm_shift, a.tail_next, h->tail_flag, h->seq, a.tail2);
+  go<mpmpc_reduced_kernel<G, C, WARM>>(a, blocks, 64, rn_pad(), a.tail_cur, a.warm_act, a.warm_shift, a.tail_next, a.h->tail_flag, a.h->seq, a.tail2);
 }
 using ReducedFn = void (*)(const SolveLaunch&, int);
 // [layout: <64,16>, <64,32>, <32,16>, <16,16>][warm]
@@ -1909,106 +2001,41 @@ static int reduced_layout(int G, int C) { return G == 64 ? (C == 16 ? 0 : 1) : (
 // K2t: its twin for a terminal cost on the time state (one instance per wave)
 template <int C>
 static void go_reduced_t(const SolveLaunch& a, int blocks) {
-  mpmpc_handle h = a.h;
-  hipLaunchKernelGGL((mpmpc_reduced_t_kernel<64, C>), dim3(blocks), dim3(64), rn_pad(), h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0, h->status,
-                     h->iters, h->resid, a.y_out, a.tail_cur, a.tail_next, h->tail_flag, h->seq);
+  go<mpmpc_reduced_t_kernel<64, C>>(a, blocks, 64, rn_pad(), a.tail_cur, a.tail_next, a.h->tail_flag, a.h->seq);
 }
 // K2p: the reduced-native tail kernel on the list `tail_cur`; what it leaves goes to tail2
 template <int G, int C>
 static void go_reduced_tail(const SolveLaunch& a, int blocks) {
-  mpmpc_handle h = a.h;
-  hipLaunchKernelGGL((mpmpc_reduced_tail_kernel<G, C>), dim3(blocks), dim3(64), rn_pad(), h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0, h->status,
-                     h->iters, h->resid, a.y_out, a.tail_cur, a.tail_next, a.tail2, h->tail_flag + 1, h->seq);
+  go<mpmpc_reduced_tail_kernel<G, C>>(a, blocks, 64, rn_pad(), a.tail_cur, a.tail_next, a.tail2, a.h->tail_flag + 1, a.h->seq);
 }
 // K2r2 / K2t2 / K2p2: two stages per lane (lane_pair.hpp) - GB lanes per instance
 template <int GB>
 static void go_pair(const SolveLaunch& a, int blocks) {
-  mpmpc_handle h = a.h;
-  hipLaunchKernelGGL(mpmpc_reduced_pair_kernel<GB>, dim3(blocks), dim3(64), 0, h->stream, h->cfg, a.prm, a.B, h->ld, a.ain, h->z, h->u0, h->status,
-                     h->iters, h->resid, a.y_out, a.tail_cur, a.tail_next, h->tail_flag, h->seq, a.tail2);
+  go<mpmpc_reduced_pair_kernel<GB>>(a, blocks, 64, 0, a.tail_cur, a.tail_next, a.h->tail_flag, a.h->seq, a.tail2);
 }
 template <int GB>
-static void go_pair_t(const SolveLaunch& a) {
-  mpmpc_handle h = a.h;
-  hipLaunchKernelGGL(mpmpc_reduced_t_pair_kernel<GB>, dim3(a.B), dim3(64), 0, h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0, h->status, h->iters,
-                     h->resid, a.y_out, a.tail_cur);
-}
+static void go_pair_t(const SolveLaunch& a) { go<mpmpc_reduced_t_pair_kernel<GB>>(a, a.B, 64, 0, a.tail_cur); }
 template <int GB>
-static void go_pair_tail(const SolveLaunch& a) {
-  mpmpc_handle h = a.h;
-  hipLaunchKernelGGL(mpmpc_reduced_tail_pair_kernel<GB>, dim3(a.B), dim3(64), 0, h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0, h->status, h->iters,
-                     h->resid, a.y_out, a.tail_cur, a.tail_next);
-}
-// K2b / K2rb: one instance per WORKGROUP of G = 128 / 256 lanes.  The kernels need more dynamic LDS than the default limit: the
-// attribute is set once per function AND DEVICE (one process may drive several - sharded.py, bench.py --single-process - and the
-// attribute belongs to the function on the device that is current; two threads may both set it once: the call is idempotent)
-constexpr int MAX_DEVICES = 64;
-static int device_slot(mpmpc_handle h) { return h->cfg.device >= 0 && h->cfg.device < MAX_DEVICES ? h->cfg.device : 0; }
+static void go_pair_tail(const SolveLaunch& a) { go<mpmpc_reduced_tail_pair_kernel<GB>>(a, a.B, 64, 0, a.tail_cur, a.tail_next); }
+// K2b / K2rb and the pair kernels on a workgroup: one instance per WORKGROUP of G = 128 / 256 lanes
 template <int G, int VAR>
 static int go_block(const SolveLaunch& a, const int* tail) {
-  mpmpc_handle h = a.h;
-  static std::atomic<bool> attr_set[MAX_DEVICES];
-  if (!attr_set[device_slot(h)]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mpmpc_solve_block_kernel<G, VAR>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)LaneBlock<G>::lds_bytes));
-    attr_set[device_slot(h)] = true;
-  }
-  hipLaunchKernelGGL((mpmpc_solve_block_kernel<G, VAR>), dim3(a.B), dim3(G), LaneBlock<G>::lds_bytes, h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0,
-                     h->status, h->iters, h->resid, a.y_out, tail);
-  return MPMPC_OK;
+  return go_workgroups<mpmpc_solve_block_kernel<G, VAR>>(a, G, LaneBlock<G>::lds_bytes, tail);
 }
 using BlockFn = int (*)(const SolveLaunch&, const int*);
 static const BlockFn kBlock[2][3] = {{go_block<128, 0>, go_block<128, 1>, go_block<128, 2>}, {go_block<256, 0>, go_block<256, 1>, go_block<256, 2>}};
 template <int G>
 static int go_rblock(const SolveLaunch& a) {
-  mpmpc_handle h = a.h;
-  using LB = LaneBlock<G, RNB_SLOTS>;
-  static std::atomic<bool> attr_set[MAX_DEVICES];
-  if (!attr_set[device_slot(h)]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mpmpc_reduced_block_kernel<G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB::lds_bytes));
-    attr_set[device_slot(h)] = true;
-  }
-  hipLaunchKernelGGL((mpmpc_reduced_block_kernel<G>), dim3(a.B), dim3(G), LB::lds_bytes, h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0, h->status, h->iters,
-                     h->resid, a.y_out, a.tail_cur);
-  return MPMPC_OK;
+  return go_workgroups<mpmpc_reduced_block_kernel<G>>(a, G, LaneBlock<G, RNB_SLOTS>::lds_bytes, a.tail_cur);
 }
-
 static int go_pair_block(const SolveLaunch& a) {
-  mpmpc_handle h = a.h;
-  using LB = LaneBlock<128, RNB2_SLOTS, 128, RNB2_XR>;
-  static std::atomic<bool> attr_set[MAX_DEVICES];
-  if (!attr_set[device_slot(h)]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mpmpc_reduced_pair_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB::lds_bytes));
-    attr_set[device_slot(h)] = true;
-  }
-  hipLaunchKernelGGL(mpmpc_reduced_pair_block_kernel, dim3(a.B), dim3(128), LB::lds_bytes, h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0, h->status, h->iters,
-                     h->resid, a.y_out, a.tail_cur);
-  return MPMPC_OK;
+  return go_workgroups<mpmpc_reduced_pair_block_kernel>(a, 128, LanePairBlock::L1::lds_bytes, a.tail_cur);
 }
-
 static int go_pair_block_tail(const SolveLaunch& a) {
-  mpmpc_handle h = a.h;
-  using LB = LaneBlock<128, RN2_SLOTS, 128, RNB2_XR>;
-  static std::atomic<bool> attr_set[MAX_DEVICES];
-  if (!attr_set[device_slot(h)]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mpmpc_reduced_tail_pair_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB::lds_bytes));
-    attr_set[device_slot(h)] = true;
-  }
-  hipLaunchKernelGGL(mpmpc_reduced_tail_pair_block_kernel, dim3(a.B), dim3(128), LB::lds_bytes, h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0, h->status,
-                     h->iters, h->resid, a.y_out, a.tail_cur, a.tail_next);
-  return MPMPC_OK;
+  return go_workgroups<mpmpc_reduced_tail_pair_block_kernel>(a, 128, LanePairBlockFull::L1::lds_bytes, a.tail_cur, a.tail_next);
 }
 static int go_pair_block_t(const SolveLaunch& a) {
-  mpmpc_handle h = a.h;
-  using LB = LaneBlock<128, RN2_SLOTS, 128, RNB2_XR>;
-  static std::atomic<bool> attr_set[MAX_DEVICES];
-  if (!attr_set[device_slot(h)]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mpmpc_reduced_t_pair_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB::lds_bytes));
-    attr_set[device_slot(h)] = true;
-  }
-  hipLaunchKernelGGL(mpmpc_reduced_t_pair_block_kernel, dim3(a.B), dim3(128), LB::lds_bytes, h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0, h->status,
-                     h->iters, h->resid, a.y_out, a.tail_cur);
-  return MPMPC_OK;
+  return go_workgroups<mpmpc_reduced_t_pair_block_kernel>(a, 128, LanePairBlockFull::L1::lds_bytes, a.tail_cur);
 }
 
 // Horizons above 63.  65 .. 128 stages of the reference's own weights (or of a terminal cost on the time state): TWO stages per

@@ -3,6 +3,8 @@ inside multi-purpose-mpc_amd/csrc/libmpmpc.so (llvm-readelf --notes of the unbun
 
     python profiles/kernel_resources.py            # prints the table
     python profiles/kernel_resources.py r3         # ... and writes profiles/r3/kernel_resources.txt
+    python profiles/kernel_resources.py --compare OTHER.so   # table rows and kernels that differ from another build's
+                                                             # (exit status 1 if any: a refactor must leave none)
 
 tests/test_abi.py imports kernel_table() and fails when a batch-path solve kernel has scratch
 (private_segment_fixed_size != 0) or exceeds its register / LDS budget.
@@ -78,7 +80,45 @@ def render(rows, version=""):
     return "\n".join(lines) + "\n"
 
 
+def disassembly(so=SO):
+    """{mangled kernel name: its instructions as text} - comments and <symbol+offset> branch targets stripped, so that two
+    builds of the same kernel compare equal whatever surrounds it in the code object."""
+    co = code_object(so)
+    out = {}
+    for r in kernel_table(so):
+        txt = _run(os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", "--no-leading-addr",
+                   "--disassemble-symbols=" + r["mangled"], co)
+        lines = [re.sub(r"\s*<[^>]*>", "", re.sub(r"\s*//.*$", "", l)).strip() for l in txt.splitlines()]
+        out[r["mangled"]] = "\n".join(l for l in lines if l and not l.endswith(":") and "file format" not in l)
+    return out
+
+
+def compare(other, so=SO):
+    """Differences between the code object of `so` and that of `other`: table rows first, then kernels whose disassembly
+    differs.  -> the lines to print (none: the device code is the same)."""
+    mine, theirs = ({r["mangled"]: r for r in kernel_table(p)} for p in (so, other))
+    lines = []
+    for m in sorted(set(mine) | set(theirs)):
+        if m not in mine or m not in theirs:
+            lines.append("only in %s: %s" % (so if m in mine else other, (mine.get(m) or theirs[m])["name"]))
+            continue
+        for f in ("vgpr", "agpr", "sgpr", "scratch", "lds", "code_bytes"):
+            if mine[m][f] != theirs[m][f]:
+                lines.append("table: %s %s %d -> %d" % (mine[m]["name"], f, theirs[m][f], mine[m][f]))
+    da, db = disassembly(so), disassembly(other)
+    for m in sorted(set(da) & set(db)):
+        if da[m] != db[m]:
+            lines.append("disassembly differs: %s (code_bytes %d -> %d)" % (mine[m]["name"], theirs[m]["code_bytes"], mine[m]["code_bytes"]))
+    lines.append("%d kernels here, %d there, %d with identical instructions" %
+                 (len(mine), len(theirs), sum(da[m] == db[m] for m in set(da) & set(db))))
+    return lines, len(lines) > 1
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[1] == "--compare":
+        lines, differ = compare(sys.argv[2])
+        print("\n".join(lines))
+        sys.exit(1 if differ else 0)
     sys.path.insert(0, ROOT)
     import __graft_entry__ as g
     rows = kernel_table()

@@ -19,189 +19,94 @@ static long long g_emu_count[32];
 #include "corridor_core.hpp"
 #include "rollout_core.hpp"
 #include <limits>
-#include <vector>
 
 using namespace mpmpc;
+#include "wave_loop.hpp"
 
-// mode / tail as in mpmpc_solve_kernel: mode 1 appends the instances it leaves UNSOLVED to tail[1..] (tail[0] counts),
-// mode 2 runs one wave per listed instance
+// mode / tail as in mpmpc_solve_kernel: mode 1 appends the instances it leaves UNSOLVED to tail, mode 2 runs one wave per
+// instance listed in it
 template <int G, int C, bool FQ = false, bool RED = false, bool FREEX = false>
-static void solve_g(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z,
-                    double* u0, int* status, int* iters, double* resid, double* y, const int* guess = nullptr,
-                    int* act = nullptr, int mode = 0, int* tail = nullptr) {
+static void solve_g(const Problem& p, const Outputs& o, const int* guess = nullptr, int* act = nullptr, int mode = 0,
+                    std::vector<int>* tail = nullptr) {
   using L = LaneEmu<G, C>;
-  const int ld = stage_ld(cfg->N);
-  const int per = L::per_wave;
-  const int waves = mode == 2 ? tail[0] : (B + per - 1) / per;
-  for (int w = 0; w < waves; ++w) {
-    VI inst = L::slot() + w * per;
-    if (mode == 2) inst = VI(tail[1 + w]);
-    VI k = L::stage() - lane_offset(G, C, cfg->N);
-    VI gs, base(0);
-    for (int i = 0; i < EMU_W; ++i) {
-      const int in = inst.v[i], kk = k.v[i];
-      gs.v[i] = (guess && in < B && kk >= 0 && kk <= cfg->N) ? guess[in * ld + kk] : 0;
-      if (mode == 2) base.v[i] = iters[in * 2 + 1];
-    }
-    Solver<L, FQ, RED, FREEX, RED> s;
-    double woff7[7];
-    weight_offdiag(*cfg, woff7);
-    const double* woff = FQ ? woff7 : nullptr;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    Solver<L, FQ, RED, FREEX, RED>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
+  using S = Solver<L, FQ, RED, FREEX, RED>;
+  const int N = p.cfg->N, ld = stage_ld(N);
+  double woff7[7];
+  weight_offdiag(*p.cfg, woff7);
+  const double* woff = FQ ? woff7 : nullptr;
+  auto solve = [&](S& s, const VD* fields, const VI& inst, const VI& k) {
+    const VI base = mode == 2 ? spent_ipm(o.iters, inst, p.B) : VI(0);
     // (like the device: the packed kernels carry no phase-1 code when they run as the first of two launches)
-    if (guess) s.template run<true>(fields, B, inst, k, cfg->N, make_params(*st), mode, gs, base, woff);
-    else if (mode == 1) s.template run<false, (G == 64)>(fields, B, inst, k, cfg->N, make_params(*st), mode, VI(0), base, woff);
-    else s.template run<false, true>(fields, B, inst, k, cfg->N, make_params(*st), mode, VI(0), base, woff);
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y, act, ld);
-    if (mode == 1)
-      for (int i = 0; i < EMU_W; ++i)
-        if (k.v[i] == 0 && inst.v[i] < B && s.status.v[i] == MPMPC_UNSOLVED) tail[1 + tail[0]++] = inst.v[i];
-  }
+    if (guess) s.template run<true>(fields, p.B, inst, k, N, make_params(*p.st), mode, warm_guess(guess, ld, inst, k, p.B, N), base, woff);
+    else if (mode == 1) s.template run<false, (G == 64)>(fields, p.B, inst, k, N, make_params(*p.st), mode, VI(0), base, woff);
+    else s.template run<false, true>(fields, p.B, inst, k, N, make_params(*p.st), mode, VI(0), base, woff);
+    s.store(inst, k, p.cfg->wheelbase, o.z, o.u0, o.status, o.iters, o.resid, o.y, act, ld);
+  };
+  if (mode == 2) wave_loop<S, L>(p, ListOrder(*tail), nullptr, solve);
+  else wave_loop<S, L>(p, BatchOrder{}, mode == 1 ? tail : nullptr, solve);
 }
 
-// mpmpc_reduced_kernel: the reduced-native solver; instances it leaves UNSOLVED are appended to tail[1..]
-template <int G, int C, bool CR = true>
-static void solve_rn(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                     int* status, int* iters, double* resid, double* y, int* tail, const int* guess = nullptr, int* act = nullptr) {
-  using L = LaneEmu<G, C>;
-  const int ld = stage_ld(cfg->N);
-  const int per = L::per_wave;
-  for (int w = 0; w < (B + per - 1) / per; ++w) {
-    VI inst = L::slot() + w * per;
-    VI k = L::stage() - lane_offset(G, C, cfg->N);
-    VI gs(0);
-    for (int i = 0; i < EMU_W; ++i) {
-      const int in = inst.v[i], kk = k.v[i];
-      gs.v[i] = (guess && in < B && kk >= 0 && kk <= cfg->N) ? guess[in * ld + kk] : 0;
-    }
-    ReducedSolver<L, CR> s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    ReducedSolver<L, CR>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    if (guess) s.template run<true>(fields, B, inst, k, cfg->N, make_params(*st), gs);
-    else s.template run<false>(fields, B, inst, k, cfg->N, make_params(*st));
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y, act, ld);
-    for (int i = 0; i < EMU_W; ++i)
-      if (k.v[i] == 0 && inst.v[i] < B && s.status.v[i] == MPMPC_UNSOLVED) tail[1 + tail[0]++] = inst.v[i];
-  }
+// run-time (G, N) -> the <G, C> instantiation the launcher picks for G lanes per instance; -1: no such layout
+template <int G_, int C_> struct Layout { static constexpr int G = G_, C = C_; };
+template <class F>
+static int with_layout(int G, int N, F&& f) {
+  const int C = lane_split(G, N);
+  if (G == 64 && C == 16) f(Layout<64, 16>{});
+  else if (G == 64) f(Layout<64, 32>{});
+  else if (G == 32) f(Layout<32, 16>{});
+  else if (G == 16) f(Layout<16, 16>{});
+  else return -1;
+  return 0;
 }
-// mpmpc_reduced_pair_kernel: the same solver with TWO stages per lane (lane_pair.hpp) - 16 lanes per instance for N + 1 <= 32,
-// four instances per emulated wave
-// (GB = 64: horizons 64 .. 127 in ONE emulated wavefront - on the one-stage layout they take a workgroup of two, emul_wide.cpp)
-template <int GB>
-static void solve_rn2(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                      int* status, int* iters, double* resid, double* y, int* tail) {
-  using L = LanePair<LaneEmu<GB, GB>>;
-  const int ld = stage_ld(cfg->N);
-  const int per = L::per_wave;
-  for (int w = 0; w < (B + per - 1) / per; ++w) {
-    const I2 inst = L::slot() + w * per;
-    const I2 k = L::stage();
-    ReducedSolver<L> s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    ReducedSolver<L>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.template run<false>(fields, B, inst, k, cfg->N, make_params(*st));
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y, nullptr, ld);
-    for (int i = 0; i < EMU_W; ++i)
-      if (k.v[0].v[i] == 0 && inst.v[0].v[i] < B && s.status.v[0].v[i] == MPMPC_UNSOLVED) tail[1 + tail[0]++] = inst.v[0].v[i];
-  }
+// the general kernel in the variant the launcher would pick: reduced polish where the configuration allows it, free e_psi / t
+// (one instance per wave only)
+static int solve_general(int G, const Problem& p, const Outputs& o, const int* guess = nullptr, int* act = nullptr, int mode = 0,
+                         std::vector<int>* tail = nullptr) {
+  return with_layout(G, p.cfg->N, [&](auto l) {
+    constexpr int g = decltype(l)::G, c = decltype(l)::C;
+    if (reducible(*p.cfg, *p.st)) solve_g<g, c, false, true>(p, o, guess, act, mode, tail);
+    else if (g == 64 && free_states(*p.cfg)) solve_g<g, c, false, false, (g == 64)>(p, o, guess, act, mode, tail);
+    else solve_g<g, c>(p, o, guess, act, mode, tail);
+  });
 }
-// mpmpc_reduced_t_kernel: the reduced-native solver of the weightings with a terminal cost on the time state
-template <int G, int C, bool CR = true>
-static void solve_rnt(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                      int* status, int* iters, double* resid, double* y, int* tail) {
-  using L = LaneEmu<G, C>;
-  const int ld = stage_ld(cfg->N);
-  const int per = L::per_wave;
-  for (int w = 0; w < (B + per - 1) / per; ++w) {
-    VI inst = L::slot() + w * per;
-    VI k = L::stage() - lane_offset(G, C, cfg->N);
-    ReducedTSolver<L, CR> s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    ReducedTSolver<L, CR>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.run(fields, B, inst, k, cfg->N, make_params(*st), cfg->QN[2]);
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y);
-    for (int i = 0; i < EMU_W; ++i)
-      if (k.v[i] == 0 && inst.v[i] < B && s.status.v[i] == MPMPC_UNSOLVED) tail[1 + tail[0]++] = inst.v[i];
+// the reduced-native kernel for G lanes per instance (CR = false: the chain-sequential elimination, A/B in the tests)
+template <bool CR = true>
+static int solve_rn_g(int G, const Problem& p, const Outputs& o, std::vector<int>& tail, const int* guess = nullptr, int* act = nullptr) {
+  const int N = p.cfg->N;
+  // 16 lanes for more than 16 stages, 64 for more than 64 (mpmpc_reduced_pair_kernel; on the one-stage layout the latter take a
+  // workgroup of two, emul_wide.cpp): TWO stages per lane - cold starts only, like the launcher
+  if ((G == 16 || G == 64) && N + 1 > G) {
+    if (guess || N + 1 > 2 * G) return -1;
+    if (G == 16) solve_rn<LanePair<LaneEmu<16, 16>>>(p, o, tail);
+    else solve_rn<LanePair<LaneEmu<64, 64>>>(p, o, tail);
+    return 0;
   }
+  return with_layout(G, N, [&](auto l) { solve_rn<LaneEmu<decltype(l)::G, decltype(l)::C>, CR>(p, o, tail, guess, act); });
 }
-// ... with two stages per lane: horizons 64 .. 127 in one emulated wavefront (mpmpc_reduced_t_pair_kernel<64>)
-template <int GB>
-static void solve_rnt2(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                       int* status, int* iters, double* resid, double* y, int* tail) {
-  using L = LanePair<LaneEmu<GB, GB>>;
-  const int ld = stage_ld(cfg->N);
-  for (int w = 0; w < B; ++w) {
-    const I2 inst = L::slot() + w;
-    const I2 k = L::stage();
-    ReducedTSolver<L> s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    ReducedTSolver<L>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.run(fields, B, inst, k, cfg->N, make_params(*st), cfg->QN[2]);
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y);
-    for (int i = 0; i < EMU_W; ++i)
-      if (k.v[0].v[i] == 0 && inst.v[0].v[i] < B && s.status.v[0].v[i] == MPMPC_UNSOLVED) tail[1 + tail[0]++] = inst.v[0].v[i];
+// ... its twin for a terminal cost on the time state: one instance per wave whatever packing the caller asked for (the launcher
+// does the same); horizons 64 .. 127 with two stages per lane (mpmpc_reduced_t_pair_kernel<64>)
+template <bool CR = true>
+static int solve_rnt_g(const Problem& p, const Outputs& o, std::vector<int>& tail) {
+  const int N = p.cfg->N;
+  if (N + 1 > 64) {
+    if (N + 1 > 128) return -1;
+    solve_rnt<LanePair<LaneEmu<64, 64>>>(p, o, tail);
+    return 0;
   }
+  return with_layout(64, N, [&](auto l) { solve_rnt<LaneEmu<64, decltype(l)::C>, CR>(p, o, tail); });
 }
-// mpmpc_reduced_tail_kernel: the reduced-native tail solver on the instances listed in tail; what it leaves UNSOLVED is
-// appended to tail2[1..]
+
 static int g_emu_lean_tail = 1;          // emu_set_lean_tail, like mpmpc_set_tail_kernel: 0 = the general kernel takes the whole
                                          // tail (as before round 4); 1 = the tail solver, TWO instances per wave (32 lanes each,
                                          // three entries per lane: the device's default); 2 = the tail solver, one instance per wave
-template <int G, int C>
-static void solve_rn_tail(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                          int* status, int* iters, double* resid, double* y, const int* tail, int* tail2) {
-  using L = LaneEmu<G, C>;
-  const int ld = stage_ld(cfg->N);
-  const int per = L::per_wave;
-  for (int w = 0; w < (tail[0] + per - 1) / per; ++w) {
-    // (the instances of a wave: consecutive entries of the list; a wave of the last, partly filled group carries B = "none")
-    VI slot = L::slot(), inst, base(0);
-    for (int i = 0; i < EMU_W; ++i) {
-      const int e = w * per + slot.v[i];
-      inst.v[i] = e < tail[0] ? tail[1 + e] : B;
-      base.v[i] = inst.v[i] < B ? iters[inst.v[i] * 2 + 1] : 0;
-    }
-    VI k = L::stage() - lane_offset(G, C, cfg->N);
-    ReducedTailSolver<L> s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    ReducedTailSolver<L>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.run(fields, B, inst, k, cfg->N, make_params(*st), base);
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y);
-    for (int i = 0; i < EMU_W; ++i)
-      if (k.v[i] == 0 && inst.v[i] < B && s.status.v[i] == MPMPC_UNSOLVED) tail2[1 + tail2[0]++] = inst.v[i];
-  }
-}
-// ... with two stages per lane (mpmpc_reduced_tail_pair_kernel<64>: horizons 64 .. 127, one instance per emulated wavefront)
-template <int GB>
-static void solve_rn_tail2(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                           int* status, int* iters, double* resid, double* y, const int* tail, int* tail2) {
-  using L = LanePair<LaneEmu<GB, GB>>;
-  static_assert(L::per_wave == 1, "one instance per wavefront");
-  const int ld = stage_ld(cfg->N);
-  for (int w = 0; w < tail[0]; ++w) {
-    const int id = tail[1 + w];
-    const I2 inst = I2(id), base = I2(iters[id * 2 + 1]);
-    const I2 k = L::stage();
-    ReducedTailSolver<L> s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    ReducedTailSolver<L>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.run(fields, B, inst, k, cfg->N, make_params(*st), base);
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y);
-    for (int i = 0; i < EMU_W; ++i)
-      if (k.v[0].v[i] == 0 && s.status.v[0].v[i] == MPMPC_UNSOLVED) tail2[1 + tail2[0]++] = id;
-  }
-}
-// the reduced-native tail solver (pair layout) on a list of instances; ids2 <- what it leaves (n2 of them)
+// the reduced-native tail solver (pair layout: mpmpc_reduced_tail_pair_kernel<64>, horizons 64 .. 127, one instance per emulated
+// wavefront) on a list of instances; ids2 <- what it leaves (n2 of them)
 extern "C" int emu_solve_rn_tail_pair(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
                                       int* status, int* iters, double* resid, double* y, const int* ids, int n_ids, int* ids2, int* n2) {
   if (cfg->N + 1 <= 64 || cfg->N + 1 > 128 || !reduced_native_tail(*cfg, *st)) return -1;
-  std::vector<int> tail(n_ids + 1), tail2(n_ids + 1, 0);
-  tail[0] = n_ids;
-  for (int i = 0; i < n_ids; ++i) tail[1 + i] = ids[i];
-  solve_rn_tail2<64>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data(), tail2.data());
-  *n2 = tail2[0];
-  for (int i = 0; i < tail2[0]; ++i) ids2[i] = tail2[1 + i];
+  std::vector<int> tail2;
+  solve_rn_tail<LanePair<LaneEmu<64, 64>>>({cfg, st, qp, B}, {z, u0, status, iters, resid, y}, ListOrder(ids, n_ids), tail2);
+  list_out(tail2, ids2, n2);
   return 0;
 }
 extern "C" void emu_set_lean_tail(int on) { g_emu_lean_tail = on; }
@@ -209,126 +114,68 @@ extern "C" int emu_reduced_native_tail(const mpmpc_config* cfg, const mpmpc_sett
 static int g_emu_tail2 = 0;              // instances the last emu_solve_launch's reduced-native tail solver left to the general kernel
 extern "C" int emu_last_tail2() { return g_emu_tail2; }
 
-static int solve_rnt_g(int G, const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                       int* status, int* iters, double* resid, double* y, int* tail) {
-  const int C = lane_split(64, cfg->N);
-  // (one instance per wave whatever packing the caller asked for: the launcher does the same)
-  (void)G;
-  if (cfg->N + 1 > 64) { if (cfg->N + 1 > 128) return -1; solve_rnt2<64>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail); return 0; }
-  if (C == 16 && lane_split(64, cfg->N) == 16) solve_rnt<64, 16>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail);
-  else solve_rnt<64, 32>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail);
-  return 0;
-}
-static int solve_rn_g(int G, const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                      int* status, int* iters, double* resid, double* y, int* tail, const int* guess = nullptr, int* act = nullptr) {
-  const int C = lane_split(G, cfg->N);
-  // (16 lanes for more than 16 stages: two stages per lane - cold starts only, like the launcher)
-  if (G == 16 && cfg->N + 1 > 16) { if (guess || cfg->N + 1 > 32) return -1; solve_rn2<16>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail); return 0; }
-  if (G == 64 && cfg->N + 1 > 64) { if (guess || cfg->N + 1 > 128) return -1; solve_rn2<64>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail); return 0; }
-  if (G == 64 && C == 16) solve_rn<64, 16>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail, guess, act);
-  else if (G == 64) solve_rn<64, 32>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail, guess, act);
-  else if (G == 32) solve_rn<32, 16>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail, guess, act);
-  else if (G == 16) solve_rn<16, 16>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail, guess, act);
-  else return -1;
-  return 0;
-}
-
-// the variant the launcher would pick: reduced polish where the configuration allows it
-#define SOLVE_G(GG, CC, ...)                                                          \
-  do {                                                                                \
-    if (reducible(*cfg, *st)) solve_g<GG, CC, false, true>(__VA_ARGS__);              \
-    else if (GG == 64 && free_states(*cfg)) solve_g<GG, CC, false, false, (GG == 64)>(__VA_ARGS__);   \
-    else solve_g<GG, CC>(__VA_ARGS__);                                                \
-  } while (0)
-
 extern "C" int emu_solve(const mpmpc_config* cfg, const mpmpc_settings* st, int G, const double* qp, int B,
                          double* z, double* u0, int* status, int* iters, double* resid, double* y) {
+  const Problem p{cfg, st, qp, B};
+  const Outputs o{z, u0, status, iters, resid, y};
   if (cfg->N + 1 > G) return -1;
-  const int C = lane_split(G, cfg->N);       // same variant as the launcher picks
-  const bool fullqn = full_weights(*cfg);          // Q, R or QN with off-diagonal entries
-  if (fullqn && G != 64) return -1;          // the launcher gives such instances a wave each
-  if (fullqn && C == 16) solve_g<64, 16, true>(cfg, st, qp, B, z, u0, status, iters, resid, y);
-  else if (fullqn) solve_g<64, 32, true>(cfg, st, qp, B, z, u0, status, iters, resid, y);
-  else if (G == 64 && C == 16) SOLVE_G(64, 16, cfg, st, qp, B, z, u0, status, iters, resid, y);
-  else if (G == 64) SOLVE_G(64, 32, cfg, st, qp, B, z, u0, status, iters, resid, y);
-  else if (G == 32) SOLVE_G(32, 16, cfg, st, qp, B, z, u0, status, iters, resid, y);
-  else if (G == 16) SOLVE_G(16, 16, cfg, st, qp, B, z, u0, status, iters, resid, y);
-  else return -1;
-  return 0;
+  if (!full_weights(*cfg)) return solve_general(G, p, o);
+  if (G != 64) return -1;          // Q, R or QN with off-diagonal entries: the launcher gives such instances a wave each
+  return with_layout(64, cfg->N, [&](auto l) { solve_g<64, decltype(l)::C, true>(p, o); });
 }
 
 // what launch_solve does with a packed batch (G < 64 and an early polish attempt): the packed kernel in mode 1, then
 // the <64, C> kernel in mode 2 on the instances it left unsolved (phase 1, full ADMM run); otherwise one launch.
 extern "C" int emu_solve_launch(const mpmpc_config* cfg, const mpmpc_settings* st, int G, const double* qp, int B,
                                 double* z, double* u0, int* status, int* iters, double* resid, double* y, int* n_tail) {
-  if (cfg->N + 1 > G && !(G == 16 && cfg->N + 1 <= 32 && reduced_native(*cfg, *st))) return -1;      // (two stages per lane: solve_rn2)
+  const Problem p{cfg, st, qp, B};
+  const Outputs o{z, u0, status, iters, resid, y};
+  if (cfg->N + 1 > G && !(G == 16 && cfg->N + 1 <= 32 && reduced_native(*cfg, *st))) return -1;      // (two stages per lane)
   const bool early = st->polish && st->early_polish > 0 && st->early_polish < st->max_iter;
   if (n_tail) *n_tail = 0;
-  std::vector<int> tail(B + 1, 0);
+  std::vector<int> tail;
   if (reduced_native(*cfg, *st) || reduced_native_tt(*cfg, *st)) {
     // the reduced-native kernel for the whole batch (any packing), then the general kernel on its tail
-    if (reduced_native_tt(*cfg, *st) ? solve_rnt_g(G, cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data())
-                                     : solve_rn_g(G, cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data())) return -1;
-    if (n_tail) *n_tail = tail[0];
-    g_emu_tail2 = tail[0];
+    if (reduced_native_tt(*cfg, *st) ? solve_rnt_g(p, o, tail) : solve_rn_g(G, p, o, tail)) return -1;
+    if (n_tail) *n_tail = (int)tail.size();
     if (g_emu_lean_tail && !reduced_native_tt(*cfg, *st) && reduced_native_tail(*cfg, *st)) {
       // the reduced-native tail solver first; the general kernel on what that leaves
-      std::vector<int> tail2(B + 1, 0);
-      if (lane_split(64, cfg->N) == 32) solve_rn_tail<64, 32>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data(), tail2.data());
-      else if (g_emu_lean_tail != 2) solve_rn_tail<32, 16>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data(), tail2.data());
-      else solve_rn_tail<64, 16>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data(), tail2.data());
+      std::vector<int> tail2;
+      if (lane_split(64, cfg->N) == 32) solve_rn_tail<LaneEmu<64, 32>>(p, o, tail, tail2);
+      else if (g_emu_lean_tail != 2) solve_rn_tail<LaneEmu<32, 16>>(p, o, tail, tail2);
+      else solve_rn_tail<LaneEmu<64, 16>>(p, o, tail, tail2);
       tail.swap(tail2);
-      g_emu_tail2 = tail[0];
     }
-    if (lane_split(64, cfg->N) == 16) SOLVE_G(64, 16, cfg, st, qp, B, z, u0, status, iters, resid, y, nullptr, nullptr, 2, tail.data());
-    else SOLVE_G(64, 32, cfg, st, qp, B, z, u0, status, iters, resid, y, nullptr, nullptr, 2, tail.data());
-    return 0;
+    g_emu_tail2 = (int)tail.size();
+    return solve_general(64, p, o, nullptr, nullptr, 2, &tail);
   }
   if (G == 64 || !early) return emu_solve(cfg, st, G, qp, B, z, u0, status, iters, resid, y);
-  if (G == 32) SOLVE_G(32, 16, cfg, st, qp, B, z, u0, status, iters, resid, y, nullptr, nullptr, 1, tail.data());
-  else if (G == 16) SOLVE_G(16, 16, cfg, st, qp, B, z, u0, status, iters, resid, y, nullptr, nullptr, 1, tail.data());
-  else return -1;
-  if (n_tail) *n_tail = tail[0];
-  if (lane_split(64, cfg->N) == 16) SOLVE_G(64, 16, cfg, st, qp, B, z, u0, status, iters, resid, y, nullptr, nullptr, 2, tail.data());
-  else SOLVE_G(64, 32, cfg, st, qp, B, z, u0, status, iters, resid, y, nullptr, nullptr, 2, tail.data());
-  return 0;
+  if (G != 32 && G != 16) return -1;
+  solve_general(G, p, o, nullptr, nullptr, 1, &tail);
+  if (n_tail) *n_tail = (int)tail.size();
+  return solve_general(64, p, o, nullptr, nullptr, 2, &tail);
 }
 
 // the reduced-native kernel alone: what it cannot certify stays UNSOLVED and is counted in *n_tail
+template <bool CR>
+static int solve_rn_alone(int G, const Problem& p, const Outputs& o, int* n_tail) {
+  std::vector<int> tail;
+  if (reducible_tt(*p.cfg, *p.st)) {          // the terminal-time kernels (one instance per wave)
+    if (solve_rnt_g<CR>(p, o, tail)) return -1;
+  } else if (!reducible(*p.cfg, *p.st) || solve_rn_g<CR>(G, p, o, tail)) return -1;
+  if (n_tail) *n_tail = (int)tail.size();
+  return 0;
+}
 extern "C" int emu_solve_rn(const mpmpc_config* cfg, const mpmpc_settings* st, int G, const double* qp, int B,
                             double* z, double* u0, int* status, int* iters, double* resid, double* y, int* n_tail) {
   if (cfg->N + 1 > G && !((G == 16 || G == 64) && cfg->N + 1 <= 2 * G && (reducible(*cfg, *st) || (G == 64 && reducible_tt(*cfg, *st))))) return -1;
-  std::vector<int> tail(B + 1, 0);
-  if (reducible_tt(*cfg, *st)) {
-    if (solve_rnt_g(G, cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data())) return -1;
-    if (n_tail) *n_tail = tail[0];
-    return 0;
-  }
-  if (!reducible(*cfg, *st)) return -1;
-  if (solve_rn_g(G, cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data())) return -1;
-  if (n_tail) *n_tail = tail[0];
-  return 0;
+  return solve_rn_alone<true>(G, {cfg, st, qp, B}, {z, u0, status, iters, resid, y}, n_tail);
 }
 // the same kernel with the SEQUENTIAL elimination of the chains (the cyclic-reduction form is what ships): A/B in the tests
 extern "C" int emu_solve_rn_sequential(const mpmpc_config* cfg, const mpmpc_settings* st, int G, const double* qp, int B,
                                        double* z, double* u0, int* status, int* iters, double* resid, double* y, int* n_tail) {
   if (cfg->N + 1 > G) return -1;
-  std::vector<int> tail(B + 1, 0);
-  const int C = lane_split(G, cfg->N);
-  if (reducible_tt(*cfg, *st)) {          // the terminal-time kernels (one instance per wave)
-    if (lane_split(64, cfg->N) == 16) solve_rnt<64, 16, false>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data());
-    else solve_rnt<64, 32, false>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data());
-    if (n_tail) *n_tail = tail[0];
-    return 0;
-  }
-  if (!reducible(*cfg, *st)) return -1;
-  if (G == 64 && C == 32) solve_rn<64, 32, false>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data());
-  else if (G == 64 && C == 16) solve_rn<64, 16, false>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data());
-  else if (G == 32) solve_rn<32, 16, false>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data());
-  else if (G == 16) solve_rn<16, 16, false>(cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data());
-  else return -1;
-  if (n_tail) *n_tail = tail[0];
-  return 0;
+  return solve_rn_alone<false>(G, {cfg, st, qp, B}, {z, u0, status, iters, resid, y}, n_tail);
 }
 extern "C" int emu_reduced_native(const mpmpc_config* cfg, const mpmpc_settings* st) { return reduced_native(*cfg, *st) ? 1 : 0; }
 extern "C" int emu_reduced_native_tt(const mpmpc_config* cfg, const mpmpc_settings* st) { return reduced_native_tt(*cfg, *st) ? 1 : 0; }
@@ -338,24 +185,18 @@ extern "C" int emu_reduced_native_tt(const mpmpc_config* cfg, const mpmpc_settin
 extern "C" int emu_solve_warm(const mpmpc_config* cfg, const mpmpc_settings* st, int G, const double* qp, int B,
                               const int* guess, double* z, double* u0, int* status, int* iters, double* resid,
                               double* y, int* act) {
+  const Problem p{cfg, st, qp, B};
+  const Outputs o{z, u0, status, iters, resid, y};
   if (cfg->N + 1 > G) return -1;
-  const int C = lane_split(G, cfg->N);
   if (reduced_native(*cfg, *st)) {
     // what the launcher runs in a warm-started closed-loop step: the reduced-native kernel with the guesses, then the
     // general kernel (no guess) on its tail
-    std::vector<int> tail(B + 1, 0);
-    if (solve_rn_g(G, cfg, st, qp, B, z, u0, status, iters, resid, y, tail.data(), guess, act)) return -1;
-    if (lane_split(64, cfg->N) == 16) SOLVE_G(64, 16, cfg, st, qp, B, z, u0, status, iters, resid, y, nullptr, nullptr, 2, tail.data());
-    else SOLVE_G(64, 32, cfg, st, qp, B, z, u0, status, iters, resid, y, nullptr, nullptr, 2, tail.data());
-    return 0;
+    std::vector<int> tail;
+    if (solve_rn_g(G, p, o, tail, guess, act)) return -1;
+    return solve_general(64, p, o, nullptr, nullptr, 2, &tail);
   }
   if (G != 64) return -1;          // the general kernels run one instance per wave
-  if (G == 64 && C == 16) SOLVE_G(64, 16, cfg, st, qp, B, z, u0, status, iters, resid, y, guess, act);
-  else if (G == 64) SOLVE_G(64, 32, cfg, st, qp, B, z, u0, status, iters, resid, y, guess, act);
-  else if (G == 32) SOLVE_G(32, 16, cfg, st, qp, B, z, u0, status, iters, resid, y, guess, act);
-  else if (G == 16) SOLVE_G(16, 16, cfg, st, qp, B, z, u0, status, iters, resid, y, guess, act);
-  else return -1;
-  return 0;
+  return solve_general(64, p, o, guess, act);
 }
 
 extern "C" int emu_assemble(const mpmpc_config* cfg, int n_wp, const double* kappa, const double* v_ref,

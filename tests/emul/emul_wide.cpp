@@ -4,7 +4,6 @@
 // (mpmpc_core.hpp: Solver) runs on an emulated execution group of MPMPC_EMU_W = 128 / 256 lanes.  Built twice
 // (tests/emul/Makefile: libmpmpc_emul_w128.so, libmpmpc_emul_w256.so).  Never loaded by the product.
 #include <cstring>
-#include <vector>
 #define MPMPC_TICK_BEGIN(i) ((void)0)
 #define MPMPC_TICK_END(i) ((void)0)
 #define MPMPC_TICK_COUNT(i) ((void)0)
@@ -16,170 +15,91 @@
 #include "mpmpc_reduced_tail.hpp"
 
 using namespace mpmpc;
+#include "wave_loop.hpp"
 static_assert(EMU_W == 128 || EMU_W == 256, "build with -DMPMPC_EMU_W=128 or 256");
 
 // (a chain of the 128-lane workgroup is a wavefront: the reduced variant factors it by cyclic reduction, as on the device)
 static_assert(EMU_W != 128 || Solver<LaneEmu<EMU_W, EMU_W / 2>, false, true, false, true>::kCR64, "cyclic reduction of 64-lane chains");
 static_assert(EMU_W != 256 || Solver<LaneEmu<EMU_W, EMU_W / 2>, false, true, false, true>::kCRrows == 8, "256 lanes: chains of eight rows");
 
+using LW = LaneEmu<EMU_W, EMU_W / 2>;          // one lane per stage, two chains that meet in the middle (LaneBlock<EMU_W>)
+
+// mpmpc_solve_block_kernel<EMU_W, VAR>: every instance, the whole solve (list = null) - or, on the instances of a list, straight
+// to phase 1 and the full iteration (mode 2): what follows the reduced-native kernels
 template <int VAR>
-static void solve_wide(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                       int* status, int* iters, double* resid, double* y) {
-  constexpr int G = EMU_W, C = EMU_W / 2;
-  using L = LaneEmu<G, C>;
-  const int ld = stage_ld(cfg->N);
-  for (int w = 0; w < B; ++w) {
-    VI inst = L::slot() + w;
-    VI k = L::stage() - lane_offset(G, C, cfg->N);
-    using S = Solver<L, VAR == 1, VAR == 2, false, VAR == 2>;      // (as mpmpc_solve_block_kernel: cyclic reduction where a chain is a wavefront)
-    S s;
-    double woff7[7];
-    weight_offdiag(*cfg, woff7);
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    S::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.template run<false, true>(fields, B, inst, k, cfg->N, make_params(*st), 0, VI(0), VI(0), VAR == 1 ? woff7 : nullptr);
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y, nullptr, ld);
-  }
+static void solve_wide(const Problem& p, const Outputs& o, const ListOrder* list = nullptr) {
+  using S = Solver<LW, VAR == 1, VAR == 2, false, VAR == 2>;      // (cyclic reduction where a chain is a wavefront)
+  const int N = p.cfg->N, ld = stage_ld(N);
+  double woff7[7];
+  weight_offdiag(*p.cfg, woff7);
+  auto solve = [&](S& s, const VD* fields, const VI& inst, const VI& k) {
+    const VI base = list ? spent_ipm(o.iters, inst, p.B) : VI(0);
+    s.template run<false, true>(fields, p.B, inst, k, N, make_params(*p.st), list ? 2 : 0, VI(0), base, VAR == 1 ? woff7 : nullptr);
+    s.store(inst, k, p.cfg->wheelbase, o.z, o.u0, o.status, o.iters, o.resid, o.y, nullptr, ld);
+  };
+  if (list) wave_loop<S, LW>(p, *list, nullptr, solve);
+  else wave_loop<S, LW>(p, BatchOrder{}, nullptr, solve);
 }
 
-// the launcher's sequence for the reference's own weights at the default settings (reduced_native): the reduced-native solver
-// on the workgroup first (mpmpc_reduced_block_kernel), then the general one - straight to phase 1 and the full iteration, mode 2 -
-// on what that could not certify
-static void solve_wide_native(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                              int* status, int* iters, double* resid, double* y) {
-  constexpr int G = EMU_W, C = EMU_W / 2;
-  using L = LaneEmu<G, C>;
-  const int ld = stage_ld(cfg->N);
-  std::vector<int> tail;
-  for (int w = 0; w < B; ++w) {
-    VI inst = L::slot() + w;
-    VI k = L::stage() - lane_offset(G, C, cfg->N);
-    ReducedSolver<L> s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    ReducedSolver<L>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.template run<false>(fields, B, inst, k, cfg->N, make_params(*st), VI(0));
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y, nullptr, ld);
-    for (int i = 0; i < EMU_W; ++i)
-      if (k.v[i] == 0 && inst.v[i] < B && s.status.v[i] == MPMPC_UNSOLVED) tail.push_back(inst.v[i]);
-  }
-  for (int id : tail) {
-    VI inst = L::slot() + id;
-    VI k = L::stage() - lane_offset(G, C, cfg->N);
-    using S = Solver<L, false, true, false, true>;
-    S s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    S::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.template run<false, true>(fields, B, inst, k, cfg->N, make_params(*st), 2, VI(0), VI(iters[id * 2 + 1]), nullptr);
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y, nullptr, ld);
-  }
-}
-
-// the tail alone: mpmpc_solve_block_kernel<G, VAR> on the listed instances (mode 2: phase 1 and the full iteration) - what follows
-// the reduced-native kernels with two stages per lane (horizons 64 .. 127 in one wavefront: emul.cpp, solve_rn2<64> / solve_rnt2<64>)
-template <int VAR>
-static void solve_wide_tail(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
-                            int* status, int* iters, double* resid, double* y, const int* ids, int n_ids) {
-  constexpr int G = EMU_W, C = EMU_W / 2;
-  using L = LaneEmu<G, C>;
-  const int ld = stage_ld(cfg->N);
-  for (int j = 0; j < n_ids; ++j) {
-    const int id = ids[j];
-    VI inst = L::slot() + id;
-    VI k = L::stage() - lane_offset(G, C, cfg->N);
-    using S = Solver<L, false, VAR == 2, false, VAR == 2>;
-    S s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    S::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.template run<false, true>(fields, B, inst, k, cfg->N, make_params(*st), 2, VI(0), VI(iters[id * 2 + 1]), nullptr);
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y, nullptr, ld);
-  }
-}
+// the tail alone: mpmpc_solve_block_kernel<G, VAR> on the listed instances - what follows the reduced-native kernels with two
+// stages per lane (horizons 64 .. 127 in one wavefront: emul.cpp)
 extern "C" int emuw_solve_tail(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
                                int* status, int* iters, double* resid, double* y, const int* ids, int n_ids) {
   if (stage_ld(cfg->N) != EMU_W || full_weights(*cfg)) return -1;
-  if (reducible(*cfg, *st)) solve_wide_tail<2>(cfg, st, qp, B, z, u0, status, iters, resid, y, ids, n_ids);
-  else solve_wide_tail<0>(cfg, st, qp, B, z, u0, status, iters, resid, y, ids, n_ids);      // (the terminal-time kernel's tail: the full problem)
+  const Problem p{cfg, st, qp, B};
+  const Outputs o{z, u0, status, iters, resid, y};
+  const ListOrder list(ids, n_ids);
+  if (reducible(*cfg, *st)) solve_wide<2>(p, o, &list);
+  else solve_wide<0>(p, o, &list);      // (the terminal-time kernel's tail: the full problem)
   return 0;
 }
 
 // Horizons 128 .. 255 with TWO stages per lane: the instance on an emulated workgroup of 128 lanes - one chain of eight rows over
-// two wavefronts (mpmpc_reduced_pair_block_kernel; the 128-lane build only).  ids <- the instances it leaves UNSOLVED (*n of them):
-// they go to the general solver on 256 lanes (the 256-lane build's emuw_solve_tail).
+// two wavefronts (the 128-lane build only; -1 from the other).  ids <- the instances a kernel leaves UNSOLVED (*n of them): they
+// go to the general solver on 256 lanes (the 256-lane build's emuw_solve_tail).
+#if MPMPC_EMU_W == 128
+using LWPair = LanePair<LaneEmu<128, 128>>;                 // the full cold storage: one workgroup per CU
+using LWPairLean = LanePair<LaneEmu<128, 128, 74>>;         // 37 pair slots: the lean cold storage of the device kernel
+static_assert(ReducedSolver<LWPairLean>::kLean, "lean cold storage");
+#endif
+// mpmpc_reduced_pair_block_kernel
 extern "C" int emuw_solve_rn_pair(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
                                   int* status, int* iters, double* resid, double* y, int* ids, int* n) {
-#if MPMPC_EMU_W != 128
-  (void)cfg; (void)st; (void)qp; (void)B; (void)z; (void)u0; (void)status; (void)iters; (void)resid; (void)y; (void)ids; (void)n;
-  return -1;
+#if MPMPC_EMU_W == 128
+  if (stage_ld(cfg->N) != 256 || full_weights(*cfg) || !reduced_native(*cfg, *st)) return -1;
+  std::vector<int> tail;
+  solve_rn<LWPairLean>({cfg, st, qp, B}, {z, u0, status, iters, resid, y}, tail);
+  list_out(tail, ids, n);
+  return 0;
 #else
-  {
-    if (stage_ld(cfg->N) != 256 || full_weights(*cfg) || !reduced_native(*cfg, *st)) return -1;
-    using L = LanePair<LaneEmu<128, 128, 74>>;          // (37 pair slots: the lean cold storage of the device kernel, ReducedSolver::kLean)
-    static_assert(ReducedSolver<L>::kLean, "lean cold storage");
-    const int ld = stage_ld(cfg->N);
-    *n = 0;
-    for (int w = 0; w < B; ++w) {
-      const I2 inst = L::slot() + w;
-      const I2 k = L::stage();
-      ReducedSolver<L> s;
-      typename L::real fields[MPMPC_NUM_FIELDS];
-      ReducedSolver<L>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-      s.template run<false>(fields, B, inst, k, cfg->N, make_params(*st));
-      s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y, nullptr, ld);
-      if (s.status.v[0].v[0] == MPMPC_UNSOLVED) ids[(*n)++] = w;
-    }
-    return 0;
-  }
+  return -1;
 #endif
 }
-
-// ... its twin for a terminal cost on the time state (mpmpc_reduced_t_pair_block_kernel; full cold storage: one workgroup per CU)
+// ... its twin for a terminal cost on the time state (mpmpc_reduced_t_pair_block_kernel)
 extern "C" int emuw_solve_rnt_pair(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
                                    int* status, int* iters, double* resid, double* y, int* ids, int* n) {
-#if MPMPC_EMU_W != 128
-  (void)cfg; (void)st; (void)qp; (void)B; (void)z; (void)u0; (void)status; (void)iters; (void)resid; (void)y; (void)ids; (void)n;
-  return -1;
-#else
+#if MPMPC_EMU_W == 128
   if (stage_ld(cfg->N) != 256 || full_weights(*cfg) || !reduced_native_tt(*cfg, *st)) return -1;
-  using L = LanePair<LaneEmu<128, 128>>;
-  const int ld = stage_ld(cfg->N);
-  *n = 0;
-  for (int w = 0; w < B; ++w) {
-    const I2 inst = L::slot() + w;
-    const I2 k = L::stage();
-    ReducedTSolver<L> s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    ReducedTSolver<L>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.run(fields, B, inst, k, cfg->N, make_params(*st), cfg->QN[2]);
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y);
-    if (s.status.v[0].v[0] == MPMPC_UNSOLVED) ids[(*n)++] = w;
-  }
+  std::vector<int> tail;
+  solve_rnt<LWPair>({cfg, st, qp, B}, {z, u0, status, iters, resid, y}, tail);
+  list_out(tail, ids, n);
   return 0;
+#else
+  return -1;
 #endif
 }
 // ... and the reduced-native TAIL solver on the same workgroup, on a list of instances (mpmpc_reduced_tail_pair_block_kernel);
 // ids2 <- what it leaves
 extern "C" int emuw_solve_rn_tail_pair(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
                                        int* status, int* iters, double* resid, double* y, const int* ids, int n_ids, int* ids2, int* n2) {
-#if MPMPC_EMU_W != 128
-  (void)cfg; (void)st; (void)qp; (void)B; (void)z; (void)u0; (void)status; (void)iters; (void)resid; (void)y; (void)ids; (void)n_ids; (void)ids2; (void)n2;
-  return -1;
-#else
+#if MPMPC_EMU_W == 128
   if (stage_ld(cfg->N) != 256 || !reduced_native_tail(*cfg, *st)) return -1;
-  using L = LanePair<LaneEmu<128, 128>>;
-  const int ld = stage_ld(cfg->N);
-  *n2 = 0;
-  for (int j = 0; j < n_ids; ++j) {
-    const int id = ids[j];
-    const I2 inst = I2(id), base = I2(iters[id * 2 + 1]);
-    const I2 k = L::stage();
-    ReducedTailSolver<L> s;
-    typename L::real fields[MPMPC_NUM_FIELDS];
-    ReducedTailSolver<L>::fetch_fields(qp, B, ld, inst, k, cfg->N, fields);
-    s.run(fields, B, inst, k, cfg->N, make_params(*st), base);
-    s.store(inst, k, cfg->wheelbase, z, u0, status, iters, resid, y);
-    if (s.status.v[0].v[0] == MPMPC_UNSOLVED) ids2[(*n2)++] = id;
-  }
+  std::vector<int> tail2;
+  solve_rn_tail<LWPair>({cfg, st, qp, B}, {z, u0, status, iters, resid, y}, ListOrder(ids, n_ids), tail2);
+  list_out(tail2, ids2, n2);
   return 0;
+#else
+  return -1;
 #endif
 }
 
@@ -189,9 +109,17 @@ extern "C" int emuw_width() { return EMU_W; }
 extern "C" int emuw_solve(const mpmpc_config* cfg, const mpmpc_settings* st, const double* qp, int B, double* z, double* u0,
                           int* status, int* iters, double* resid, double* y) {
   if (stage_ld(cfg->N) != EMU_W) return -1;
-  if (!full_weights(*cfg) && reduced_native(*cfg, *st)) { solve_wide_native(cfg, st, qp, B, z, u0, status, iters, resid, y); return 0; }
-  if (full_weights(*cfg)) solve_wide<1>(cfg, st, qp, B, z, u0, status, iters, resid, y);
-  else if (reducible(*cfg, *st)) solve_wide<2>(cfg, st, qp, B, z, u0, status, iters, resid, y);      // (the launcher's choice: mpmpc_hip.hip, launch_solve)
-  else solve_wide<0>(cfg, st, qp, B, z, u0, status, iters, resid, y);
+  const Problem p{cfg, st, qp, B};
+  const Outputs o{z, u0, status, iters, resid, y};
+  if (full_weights(*cfg)) solve_wide<1>(p, o);
+  else if (reduced_native(*cfg, *st)) {
+    // the launcher's sequence for the reference's own weights at the default settings: the reduced-native solver on the workgroup
+    // first (mpmpc_reduced_block_kernel), then the general one (mode 2) on what that could not certify
+    std::vector<int> tail;
+    solve_rn<LW>(p, o, tail);
+    const ListOrder list(tail);
+    solve_wide<2>(p, o, &list);
+  } else if (reducible(*cfg, *st)) solve_wide<2>(p, o);      // (the launcher's choice: mpmpc_hip.hip, launch_solve)
+  else solve_wide<0>(p, o);
   return 0;
 }
