@@ -361,7 +361,7 @@ int mpmpc_upload(mpmpc_handle h, int32_t B, const int32_t* wp_id, const double* 
 /* The outputs of a resident launch are defined after the next mpmpc_sync / mpmpc_download on the handle (the only ways to
  * read them), and only for the LAST launch before it.  Resident launches are pipelined inside the handle (by default three
  * launch slots - stream, output block - used in turn: mpmpc_set_pipeline): launch k + 1, k + 2 run beside launch k, whose
- * outputs stay untouched until launch k + 3; mpmpc_sync / mpmpc_download and every other call on the handle wait for both.  The
+ * outputs stay untouched until launch k + 3; mpmpc_sync / mpmpc_download and every other call on the handle wait for all of them.  The
  * library also uses the freedom the first sentence leaves: the second kernel of a launch (the tail: instances the first kernel could not certify, usually none) is not
  * enqueued while the launches whose outcome the host has seen left no tail; a launch that does leave one has it run inside
  * the next mpmpc_sync / mpmpc_download / mpmpc_upload / mpmpc_set_* call, before that call does anything else. */
@@ -370,13 +370,25 @@ int mpmpc_solve_resident(mpmpc_handle h, int32_t B);
  * call (y == NULL: not stored), the closed-loop rollout never stores them.  mpmpc_download refuses a y the last launch
  * did not produce. */
 int mpmpc_set_outputs(mpmpc_handle h, int32_t want_y);
-/* Resident launches in flight, 1 .. 8: 3 (default) = pipelined as described above (launch k's outputs stay untouched until
- * launch k + depth); 1 = every launch on one stream and one output block, each waiting for the one before (what every other
- * entry point does anyway).  The HIP runtime spreads streams over GPU_MAX_HW_QUEUES hardware queues (default 4) and streams
- * that share a queue serialise: more than 3 launches in flight pay only in a process that exported GPU_MAX_HW_QUEUES=8 (or
- * more) before its first HIP call (bench.py does).  With depth > 1 the batch launches of the handle pack two / four instances into a wavefront from
+/* Resident launches in flight, 1 .. 8: 3 (default) = pipelined as described above; 1 = every launch on one stream and one output
+ * block, each waiting for the one before (what every other entry point does anyway).  Every launch in flight needs a stream of
+ * its own, and the HIP runtime spreads the streams of a process over GPU_MAX_HW_QUEUES hardware queues (4 when the variable is
+ * absent); streams that share a queue take turns, which costs more than the extra launch gains.  So the handle runs
+ *     s = mpmpc_pipeline_streams(depth, mpmpc_hw_queue_budget(getenv("GPU_MAX_HW_QUEUES")))  =  min(depth, queues)
+ * launch slots, whatever depth asks for beyond that: the library reads the variable (once per process), it never sets it, and a
+ * caller need not know about it.  What a caller may rely on: launch k's outputs stay untouched until launch k + s, 1 <= s <= depth;
+ * a slot's launches run in the order they were issued; mpmpc_sync / mpmpc_download see the LAST launch, after waiting for all.
+ * The library itself does nothing on the null stream, so that all of the process's queues are there for launch streams (a
+ * process that uses the null stream, or streams of its own, beside a handle gives one of them away: depth 3 then fits 4 queues).
+ * With depth > 1 (and more than one queue) the batch launches of the handle pack two / four instances into a wavefront from
  * 128 / 256 instances on (instead of 1 024 / 2 048): the handle is after throughput, several launches fill the chip. */
 int mpmpc_set_pipeline(mpmpc_handle h, int32_t depth);
+/* The two halves of that rule, pure functions (no device, no handle).  mpmpc_hw_queue_budget: the queue count a value of
+ * GPU_MAX_HW_QUEUES stands for - NULL (variable absent), text that is not one positive decimal number, zero or a negative
+ * number give the runtime's default, 4.  mpmpc_pipeline_streams: launch slots a handle uses for a depth asked of
+ * mpmpc_set_pipeline (clamped to 1 .. 8) in a process with hw_queues queues (below 1 counts as 1): min(depth, hw_queues). */
+int32_t mpmpc_hw_queue_budget(const char* text);
+int32_t mpmpc_pipeline_streams(int32_t depth, int32_t hw_queues);
 int mpmpc_sync(mpmpc_handle h);
 int mpmpc_download(mpmpc_handle h, int32_t B, double* z, double* u0, int32_t* status,
                    int32_t* iters, double* resid, double* y);

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1054,10 +1055,12 @@ struct mpmpc_handle_s {
   int ring = 0;             // alt slot the next resident launch swaps with: 0 .. pipeline - 2 in turn, which takes the launches
                             // through all `pipeline` slots round robin
   bool busy = false;        // ... the same for the slot of the last launch
-  int pipeline = 3;         // mpmpc_set_pipeline: resident launches in flight (1 = one slot only).  Three by default: the HIP
-                            // runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4, one of them taken), and two
-                            // streams on one queue serialise - measured, config 2: depth 2 / 3 / 4 = 38 / 49 / 36 M solves/s with
-                            // the default, 38 / 49 / 61.5 M with GPU_MAX_HW_QUEUES=8 (profiles/r4/depth_sweep.txt)
+  int pipeline = 3;         // launch slots in use = resident launches in flight (1 = one slot only): what mpmpc_set_pipeline asked
+                            // for, three by default, but never more than the process has hardware queues (launch_streams below:
+                            // GPU_MAX_HW_QUEUES, 4 if unset) - two streams on one queue take turns.  Measured, config 2, four
+                            // queues: depth 4 = 68.7 M solves/s with the four launch streams on four queues, 39.5 M while a
+                            // synchronous hipMemset of this file had made the null stream hold one of them (two launch streams
+                            // shared a queue: 2.0 instead of 3.85 solve kernels on the chip; profiles/hw_queues/)
   hipEvent_t ev_order = nullptr;
   bool order_pending = false;      // asynchronous work other than resident solves is queued on `stream`: the next resident launch
                                    // on the OTHER stream has to wait for it (uploads, closed-loop steps: they write what solves read)
@@ -1240,6 +1243,33 @@ static void lay_out(mpmpc_handle h, int B) {
   h->laid_out = B;
 }
 
+// ---- Launch streams and hardware queues.  The HIP runtime maps the streams of a process onto GPU_MAX_HW_QUEUES hardware queues
+// (4 when the variable is absent); two streams that land on one queue take turns, and a resident launch on such a stream
+// waits for a launch it was meant to run beside.  So a handle never drives more launch streams than the process has queues:
+// mpmpc_set_pipeline asks, mpmpc_pipeline_streams answers.  The variable is read once per process and never written.
+int32_t mpmpc_hw_queue_budget(const char* text) {
+  const int32_t runtime_default = 4;
+  if (!text) return runtime_default;
+  char* end = nullptr;
+  errno = 0;
+  const long v = std::strtol(text, &end, 10);
+  if (end == text || errno != 0) return runtime_default;      // no number at all, or out of range
+  while (*end == ' ' || *end == '\t') ++end;
+  if (*end != '\0' || v < 1) return runtime_default;           // trailing text, zero, negative: not a queue count
+  return v > 1024 ? 1024 : (int32_t)v;
+}
+int32_t mpmpc_pipeline_streams(int32_t depth, int32_t hw_queues) {
+  if (depth < 1) depth = 1;
+  if (depth > mpmpc_handle_s::MAX_PIPELINE) depth = mpmpc_handle_s::MAX_PIPELINE;
+  if (hw_queues < 1) hw_queues = 1;
+  return depth < hw_queues ? depth : hw_queues;
+}
+static int launch_streams(int depth) {
+  static const int32_t budget = mpmpc_hw_queue_budget(std::getenv("GPU_MAX_HW_QUEUES"));
+  return mpmpc_pipeline_streams(depth, budget);
+}
+static hipError_t create_launch_stream(hipStream_t* s) { return hipStreamCreate(s); }
+
 // launch slots beyond the first: stream, output block (laid out like the first), tail lists, tail flag
 static int grow_slots(mpmpc_handle h, int want) {
   const BlockLayout lay = block_layout(h->cfg.N, h->cfg.max_batch);
@@ -1247,9 +1277,10 @@ static int grow_slots(mpmpc_handle h, int want) {
     auto& a = h->alt[h->n_alt];
     const size_t nt = 3 * ((size_t)h->cfg.max_batch + 1);
     if (hipMalloc((void**)&a.out_block, lay.out_end) != hipSuccess || hipMalloc((void**)&a.tail, nt * sizeof(int)) != hipSuccess ||
-        hipMemset(a.tail, 0, nt * sizeof(int)) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(&a.tail_flag), 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess ||
-        hipStreamCreate(&a.stream) != hipSuccess)
+        create_launch_stream(&a.stream) != hipSuccess ||
+        // (on the slot's own stream, never the null stream: the slot's launches are ordered behind it)
+        hipMemsetAsync(a.tail, 0, nt * sizeof(int), a.stream) != hipSuccess || hipStreamSynchronize(a.stream) != hipSuccess)
       return fail(MPMPC_E_HIP, "allocation of a launch slot failed (stream / output block / tail list)");
     a.tail_flag[0] = a.tail_flag[1] = 0u;
     h->n_alt += 1;
@@ -1334,7 +1365,19 @@ int mpmpc_create(const mpmpc_config* cfg, const mpmpc_settings* settings, mpmpc_
   h->ld = host_stage_ld(cfg->N);
   h->n = 5 * cfg->N + 3;
   h->m = 8 * cfg->N + 6;
+  h->pipeline = launch_streams(h->pipeline);
   const size_t B = (size_t)cfg->max_batch;
+  // The handle's stream comes first: everything below that touches the device goes to it.  Nothing in this library may run on the
+  // null stream - its first use makes the runtime give it a hardware queue for the life of the process, one fewer for the
+  // launch streams (see launch_streams).
+  hipError_t e = create_launch_stream(&h->stream);
+  for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_order, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    mpmpc_destroy(h);
+    return fail(MPMPC_E_HIP, std::string("stream/event creation: ") + hipGetErrorString(e));
+  }
 #define ALLOC(ptr, count)                                                                \
   do {                                                                                   \
     hipError_t e_ = hipMalloc((void**)&(ptr), (count) * sizeof(*(ptr)));                 \
@@ -1349,7 +1392,11 @@ int mpmpc_create(const mpmpc_config* cfg, const mpmpc_settings* settings, mpmpc_
   lay_out(h, cfg->max_batch);
   ALLOC(h->qp, (size_t)MPMPC_NUM_FIELDS * B * h->ld);
   ALLOC(h->tail, 3 * (B + 1));
-  (void)hipMemset(h->tail, 0, 3 * (B + 1) * sizeof(int));
+  // (the lists are only ever used by launches on the stream of their slot: ordered behind this; the wait reports a failure here)
+  if (hipMemsetAsync(h->tail, 0, 3 * (B + 1) * sizeof(int), h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
+    mpmpc_destroy(h);
+    return fail(MPMPC_E_HIP, "clearing the tail lists failed");
+  }
   if (hipHostMalloc(reinterpret_cast<void**>(&h->tail_flag), 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) {
     h->tail_flag = nullptr;
     mpmpc_destroy(h);
@@ -1364,14 +1411,6 @@ int mpmpc_create(const mpmpc_config* cfg, const mpmpc_settings* settings, mpmpc_
     else h->stage_in = nullptr;
     if (out_b <= STAGE_LIMIT && hipHostMalloc((void**)&h->stage_out, out_b, hipHostMallocDefault) == hipSuccess) h->stage_out_bytes = out_b;
     else h->stage_out = nullptr;
-  }
-  hipError_t e = hipStreamCreate(&h->stream);
-  for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_order, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    mpmpc_destroy(h);
-    return fail(MPMPC_E_HIP, std::string("stream/event creation: ") + hipGetErrorString(e));
   }
   // (the further launch slots of pipelined resident launches are allocated by the first such launch: next_slot)
   *out = h;
@@ -2278,7 +2317,7 @@ int mpmpc_set_pipeline(mpmpc_handle h, int32_t depth) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
   MPMPC_SETTLE(h);
   if (depth < 1 || depth > mpmpc_handle_s::MAX_PIPELINE) return fail(MPMPC_E_ARG, "pipeline depth must be in [1, 8]");
-  h->pipeline = depth;
+  h->pipeline = launch_streams(depth);      // as many launch slots as the process has hardware queues for, at most
   h->ring = 0;
   return MPMPC_OK;
 }

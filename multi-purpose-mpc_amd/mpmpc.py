@@ -149,6 +149,10 @@ def load_library(path: str | None = None):
     lib.mpmpc_set_packing.argtypes = [h, C.c_int32]
     lib.mpmpc_set_tail_kernel.argtypes = [h, C.c_int32]
     lib.mpmpc_set_pipeline.argtypes = [h, C.c_int32]
+    lib.mpmpc_hw_queue_budget.argtypes = [C.c_char_p]
+    lib.mpmpc_hw_queue_budget.restype = C.c_int32
+    lib.mpmpc_pipeline_streams.argtypes = [C.c_int32, C.c_int32]
+    lib.mpmpc_pipeline_streams.restype = C.c_int32
     lib.mpmpc_set_path.argtypes = [h, C.c_int32, _dp, _dp, _dp]
     lib.mpmpc_set_corridor.argtypes = [h, C.c_int32, C.c_int32, _dp, _dp]
     lib.mpmpc_set_map.argtypes = [h, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double]
@@ -191,7 +195,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_create", "mpmpc_destroy", "mpmpc_set_settings", "mpmpc_set_packing", "mpmpc_set_tail_kernel", "mpmpc_set_path", "mpmpc_set_corridor",
            "mpmpc_set_map", "mpmpc_set_path_geometry", "mpmpc_build_corridor", "mpmpc_rollout_init",
            "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor",
-           "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline",
+           "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams",
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_staging",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
@@ -489,8 +493,10 @@ class Handle:
 
     def set_pipeline(self, depth=3):
         """resident launches in flight, 1 .. 8: 3 (default) = pipelined inside the handle (launch k + 1, k + 2 run beside
-        launch k, whose results stay readable until launch k + 3), 1 = one stream, one output block; more than 3 pay only with
-        GPU_MAX_HW_QUEUES >= 8 in the environment before the first HIP call (streams sharing a hardware queue serialise)"""
+        launch k), 1 = one stream, one output block.  Every launch in flight has a stream of its own and streams that share a
+        hardware queue take turns, so the handle uses s = min(depth, GPU_MAX_HW_QUEUES of this process; 4 if unset) launch
+        slots (mpmpc_pipeline_streams): results of launch k stay untouched until launch k + s.  The library reads the variable,
+        never sets it, and keeps off the null stream, so depth 4 runs four launches side by side on the runtime's default"""
         self._check(self.lib.mpmpc_set_pipeline(self._h, int(depth)))
 
     def sync(self):
