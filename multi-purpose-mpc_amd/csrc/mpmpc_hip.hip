@@ -941,7 +941,6 @@ struct mpmpc_handle_s {
   mpmpc_config cfg;
   mpmpc_settings st;
   int ld = 0, n = 0, m = 0;
-  hipStream_t stream = nullptr;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_in = nullptr;      // the last staged upload has left the pinned buffer
   bool in_flight = false;
@@ -986,13 +985,11 @@ struct mpmpc_handle_s {
   bool have_rows = false;     // per-instance corridor rows uploaded (else: table)
   int uploaded = 0;
   // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
-  // of the last upload), and so do the outputs (u0, resid, status, iters, z, y): an upload or a download through
-  // the pinned staging buffers is then a single copy instead of five or six - what a single-car call is made of
-  char *in_block = nullptr, *out_block = nullptr;
+  // of the last upload), and so do the outputs of every launch slot (Slot::out_block: u0, resid, status, iters, z, y): an upload
+  // or a download through the pinned staging buffers is then a single copy instead of five or six - what a single-car call is made of
+  char* in_block = nullptr;
   int laid_out = 0;
-  // stage-blocked QP and outputs
-  double *qp = nullptr, *z = nullptr, *u0 = nullptr, *resid = nullptr, *y = nullptr;
-  int *status = nullptr, *iters = nullptr;
+  double* qp = nullptr;      // stage-blocked QP
   // pinned host staging for mpmpc_upload / mpmpc_download (small copies from pageable memory are
   // synchronous and slow; nullptr above STAGE_LIMIT bytes: large batches amortise the direct path)
   char *stage_in = nullptr, *stage_out = nullptr;
@@ -1005,56 +1002,49 @@ struct mpmpc_handle_s {
   hipEvent_t ev_bounce[2] = {nullptr, nullptr};
   bool bounce_busy[2] = {false, false};
   int bounce_turn = 0;
-  // instances the early pass of a packed (2 or 4 per wave) launch could not certify: [0] = count, [1..] = ids
-  int* tail = nullptr;
-  int tail_flip = 0;          // which of the two lists the next reduced-native launch fills
-  // Deferred tail (batch launches of the reduced-native kernels, not the closed loop).  Launching the tail kernel costs
-  // 4.8 us even when its list is empty - 10 % of a 1 024-instance step - so when the last launch whose outcome the host
-  // has SEEN left no tail, the next launches do not enqueue one: the reduced-native kernel stamps its sequence number into
-  // tail_flag (host memory) if it appends anything, and every entry point through which results or state can be observed
-  // or changed (sync, download, upload, set_*, rollout, timed launches) first drains the stream, looks at the stamp and
-  // runs the tail of the LAST launch if it left one (observe_tail).  A launch that is followed by another launch without
-  // such a call in between has unobservable results either way (same output buffers).
-  unsigned* tail_flag = nullptr;      // hipHostMalloc'ed, device-visible
-  unsigned seq = 0;                   // sequence number of the last reduced-native launch
-  bool tail_expect_empty = false;     // the last observed launch left no tail
-  bool pend = false;                  // the last launch's tail launch was not enqueued
-  bool tail_ran_late = false;         // the last observe_tail had to run a deferred tail
-  // Second level (reduced_native_tail configurations): the tail goes to the reduced-native tail kernel first, which appends
-  // what IT leaves to a third list (tail + 2 (max_batch + 1)) and stamps tail_flag[1]; the general kernel on that list is
-  // deferred by the same rule.
-  bool tail2_expect_empty = false, pend2 = false;
-  size_t staged_bytes = 0;            // mpmpc_staged_begin without its mpmpc_staged_end: bytes of the output block on their way back
-  int pend_B = 0;
-  bool pend_y = false;
-  int *pend_cur = nullptr, *pend_next = nullptr;
-  // ---- further launch slots (pipelined resident launches, mpmpc_solve_resident): each its own stream, output block, tail
-  // lists and deferred-tail state.  The members above are those of the slot of the LAST launch; `alt` holds the other slots',
-  // and a resident launch swaps the next one in before it goes out, so that launch k + 1 .. k + pipeline - 1 run beside launch k
-  // (each on its own stream, writing its own outputs) and everything else in this file keeps working on "the last launch"
-  // unchanged.
+  size_t staged_bytes = 0;  // mpmpc_staged_begin without its mpmpc_staged_end: bytes of the output block on their way back
+  // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
+  // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that
+  // never pipelines; slot[1 .. n_slots - 1] are made by the first pipelined resident launch (next_slot).  `cur` is the slot of the
+  // LAST launch, and everything in this file that is not a resident launch - uploads, downloads, the staged calls, corridor build,
+  // rollout, recorder, timed launches - works on last(): its stream, its outputs.  A resident launch first moves `cur` one slot on
+  // (round robin over the `pipeline` slots in use), so that launches k + 1 .. k + pipeline - 1 run beside launch k, each on its
+  // own stream, writing its own outputs.  A function that acts on a slot is handed it; nothing is copied between slots.
   struct Slot {
     hipStream_t stream = nullptr;
-    char* out_block = nullptr;
+    char* out_block = nullptr;      // pointers into it (lay_out):
     double *z = nullptr, *u0 = nullptr, *resid = nullptr, *y = nullptr;
     int *status = nullptr, *iters = nullptr;
+    bool y_valid = false;     // the slot's last solve launch stored y
+    bool busy = false;        // resident launches in flight on the slot's stream that nothing has waited for yet
+    // instances the early pass of a packed (2 or 4 per wave) launch could not certify: [0] = count, [1..] = ids
     int* tail = nullptr;
-    int tail_flip = 0;
-    unsigned* tail_flag = nullptr;
-    unsigned seq = 0;
-    bool tail_expect_empty = false, pend = false, tail_ran_late = false, tail2_expect_empty = false, pend2 = false;
-    int pend_B = 0;
+    int tail_flip = 0;          // which of the two lists the next reduced-native launch fills
+    // Deferred tail (batch launches of the reduced-native kernels, not the closed loop).  Launching the tail kernel costs
+    // 4.8 us even when its list is empty - 10 % of a 1 024-instance step - so when the last launch whose outcome the host
+    // has SEEN left no tail, the next launches do not enqueue one: the reduced-native kernel stamps its sequence number into
+    // tail_flag (host memory) if it appends anything, and every entry point through which results or state can be observed
+    // or changed (sync, download, upload, set_*, rollout, timed launches) first drains the stream, looks at the stamp and
+    // runs the tail of the slot's LAST launch if it left one (observe_tail).  A launch that is followed by another launch on
+    // the slot without such a call in between has unobservable results either way (same output buffers).
+    unsigned* tail_flag = nullptr;      // hipHostMalloc'ed, device-visible
+    unsigned seq = 0;                   // sequence number of the last reduced-native launch
+    bool tail_expect_empty = false;     // the last observed launch left no tail
+    bool pend = false;                  // the last launch's tail launch was not enqueued
+    bool tail_ran_late = false;         // the last observe_tail had to run a deferred tail
+    // Second level (reduced_native_tail configurations): the tail goes to the reduced-native tail kernel first, which appends
+    // what IT leaves to a third list (tail + 2 (max_batch + 1)) and stamps tail_flag[1]; the general kernel on that list is
+    // deferred by the same rule.
+    bool tail2_expect_empty = false, pend2 = false;
+    int pend_B = 0;                     // what a deferred tail launch needs of the launch it belongs to
     bool pend_y = false;
     int *pend_cur = nullptr, *pend_next = nullptr;
-    bool y_valid = false;
-    bool busy = false;      // launches in flight on this slot's stream that nothing has waited for yet
   };
   static constexpr int MAX_PIPELINE = 8;
-  Slot alt[MAX_PIPELINE - 1];      // the other slots; alt[i] exists (is allocated) for i < n_alt
-  int n_alt = 0;
-  int ring = 0;             // alt slot the next resident launch swaps with: 0 .. pipeline - 2 in turn, which takes the launches
-                            // through all `pipeline` slots round robin
-  bool busy = false;        // ... the same for the slot of the last launch
+  Slot slot[MAX_PIPELINE];
+  int n_slots = 0;          // slots allocated: slot[0 .. n_slots - 1]
+  int cur = 0;              // the slot of the last launch
+  Slot& last() { return slot[cur]; }
   int pipeline = 3;         // launch slots in use = resident launches in flight (1 = one slot only): what mpmpc_set_pipeline asked
                             // for, three by default, but never more than the process has hardware queues (launch_streams below:
                             // GPU_MAX_HW_QUEUES, 4 if unset) - two streams on one queue take turns.  Measured, config 2, four
@@ -1062,56 +1052,48 @@ struct mpmpc_handle_s {
                             // synchronous hipMemset of this file had made the null stream hold one of them (two launch streams
                             // shared a queue: 2.0 instead of 3.85 solve kernels on the chip; profiles/hw_queues/)
   hipEvent_t ev_order = nullptr;
-  bool order_pending = false;      // asynchronous work other than resident solves is queued on `stream`: the next resident launch
-                                   // on the OTHER stream has to wait for it (uploads, closed-loop steps: they write what solves read)
+  bool order_pending = false;      // asynchronous work other than resident solves is queued on last().stream: the next resident launch
+                                   // goes to ANOTHER stream and has to wait for it (uploads, closed-loop steps: they write what solves read)
   int force_lanes = 0;      // mpmpc_set_packing: 0 = chosen from the batch size
   // mpmpc_set_tail_kernel (MPMPC_LEAN_TAIL=0 in the environment: off from the start, for A/B timings of whole programs)
   bool lean_tail = !(std::getenv("MPMPC_LEAN_TAIL") && std::atoi(std::getenv("MPMPC_LEAN_TAIL")) == 0);
   bool lean_tail_single = std::getenv("MPMPC_LEAN_TAIL") && std::atoi(std::getenv("MPMPC_LEAN_TAIL")) == 2;      // ONE tail instance per wave
   bool staged_async = true; // mpmpc_staged_begin was called as such (not as the first half of mpmpc_solve_staged)
   bool resident_y = true;   // mpmpc_set_outputs: do resident launches store the multipliers y (46 % of the output bytes)?
-  bool y_valid = false;     // the last solve launch stored y
 };
+using Slot = mpmpc_handle_s::Slot;
 
 static int host_stage_ld(int N) { return N + 1 <= 16 ? 16 : (N + 1 <= 32 ? 32 : (N + 1 <= 64 ? 64 : (N + 1 <= 128 ? 128 : 256))); }
 
-static int observe_tail(mpmpc_handle h);
-static void swap_slots(mpmpc_handle h, int i) {
-  auto& a = h->alt[i];
-  std::swap(h->stream, a.stream); std::swap(h->out_block, a.out_block);
-  std::swap(h->z, a.z); std::swap(h->u0, a.u0); std::swap(h->resid, a.resid); std::swap(h->y, a.y);
-  std::swap(h->status, a.status); std::swap(h->iters, a.iters);
-  std::swap(h->tail, a.tail); std::swap(h->tail_flip, a.tail_flip); std::swap(h->tail_flag, a.tail_flag); std::swap(h->seq, a.seq);
-  std::swap(h->tail_expect_empty, a.tail_expect_empty); std::swap(h->pend, a.pend); std::swap(h->tail_ran_late, a.tail_ran_late);
-  std::swap(h->tail2_expect_empty, a.tail2_expect_empty); std::swap(h->pend2, a.pend2);
-  std::swap(h->pend_B, a.pend_B); std::swap(h->pend_y, a.pend_y); std::swap(h->pend_cur, a.pend_cur); std::swap(h->pend_next, a.pend_next);
-  std::swap(h->y_valid, a.y_valid); std::swap(h->busy, a.busy);
-}
+static int observe_tail(mpmpc_handle h, Slot& s);
 // The other slots' launches are drained and their deferred tails, if any, are run (the slot of the last launch is left as it
 // is: what follows on its stream is ordered behind it anyway).
-static int settle_other_slot(mpmpc_handle h) {
-  for (int i = 0; i < h->n_alt; ++i) {
-    if (!h->alt[i].busy && !h->alt[i].pend && !h->alt[i].pend2) continue;
-    swap_slots(h, i);
-    const int rc = observe_tail(h);
-    swap_slots(h, i);
-    if (rc) return rc;
+static int settle_other_slots(mpmpc_handle h) {
+  for (int i = 0; i < h->n_slots; ++i) {
+    Slot& s = h->slot[i];
+    if (i == h->cur || (!s.busy && !s.pend && !s.pend2)) continue;
+    if (int rc = observe_tail(h, s)) return rc;
   }
   return MPMPC_OK;
 }
+// ... and then the slot of the last launch: every launch of the handle is done, deferred tails included
+static int drain(mpmpc_handle h) {
+  if (int rc = settle_other_slots(h)) return rc;
+  return observe_tail(h, h->last());
+}
 // first statement of every entry point that reads results or changes what a launch in flight - or a deferred tail launch -
-// works on
-#define MPMPC_SETTLE(h)                                      \
-  do {                                                       \
-    if ((h)->staged_bytes) {                                 \
-      if (int rc_ = mpmpc_staged_end(h)) return rc_;         \
-    }                                                        \
-    if (int rc_ = settle_other_slot(h)) return rc_;          \
-    if ((h)->pend || (h)->pend2) {                           \
-      if (int rc_ = observe_tail(h)) return rc_;             \
-    }                                                        \
-    (h)->order_pending = true;                               \
-  } while (0)
+// works on: `if (int rc = settle(h)) return rc;`
+static int settle(mpmpc_handle h) {
+  if (h->staged_bytes) {
+    if (int rc = mpmpc_staged_end(h)) return rc;
+  }
+  if (int rc = settle_other_slots(h)) return rc;
+  if (h->last().pend || h->last().pend2) {
+    if (int rc = observe_tail(h, h->last())) return rc;
+  }
+  h->order_pending = true;
+  return MPMPC_OK;
+}
 
 static int check_settings(const mpmpc_settings* s) {
   if (!s) return fail(MPMPC_E_ARG, "settings is NULL");
@@ -1145,7 +1127,7 @@ static int upload_through_bounce(mpmpc_handle h, void* dst, const void* src, siz
 static int launch_assemble(mpmpc_handle h, int B);
 // how a solve launch was asked for (decides the packing of the reduced-native kernels, see launch_solve)
 enum LaunchKind { LAUNCH_SINGLE = 0, LAUNCH_PIPELINED = 1 };
-static int launch_solve(mpmpc_handle h, int B, bool closed_loop = false, bool want_y = true, int tail_only = 0, LaunchKind kind = LAUNCH_SINGLE);
+static int launch_solve(mpmpc_handle h, Slot& sl, int B, bool closed_loop = false, bool want_y = true, int tail_only = 0, LaunchKind kind = LAUNCH_SINGLE);
 
 extern "C" {
 
@@ -1225,14 +1207,8 @@ static void lay_out(mpmpc_handle h, int B) {
   h->cc = (double*)(h->in_block + L.cc);
   h->lb = (double*)(h->in_block + L.lb);
   h->ub = (double*)(h->in_block + L.ub);
-  h->u0 = (double*)(h->out_block + L.u0);
-  h->resid = (double*)(h->out_block + L.resid);
-  h->status = (int*)(h->out_block + L.status);
-  h->iters = (int*)(h->out_block + L.iters);
-  h->z = (double*)(h->out_block + L.z);
-  h->y = (double*)(h->out_block + L.y);
-  for (int i = 0; i < h->n_alt; ++i) {
-    auto& a = h->alt[i];
+  for (int i = 0; i < h->n_slots; ++i) {
+    Slot& a = h->slot[i];
     a.u0 = (double*)(a.out_block + L.u0);
     a.resid = (double*)(a.out_block + L.resid);
     a.status = (int*)(a.out_block + L.status);
@@ -1270,21 +1246,34 @@ static int launch_streams(int depth) {
 }
 static hipError_t create_launch_stream(hipStream_t* s) { return hipStreamCreate(s); }
 
-// launch slots beyond the first: stream, output block (laid out like the first), tail lists, tail flag
-static int grow_slots(mpmpc_handle h, int want) {
-  const BlockLayout lay = block_layout(h->cfg.N, h->cfg.max_batch);
-  while (h->n_alt < want) {
-    auto& a = h->alt[h->n_alt];
-    const size_t nt = 3 * ((size_t)h->cfg.max_batch + 1);
-    if (hipMalloc((void**)&a.out_block, lay.out_end) != hipSuccess || hipMalloc((void**)&a.tail, nt * sizeof(int)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&a.tail_flag), 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess ||
-        create_launch_stream(&a.stream) != hipSuccess ||
-        // (on the slot's own stream, never the null stream: the slot's launches are ordered behind it)
-        hipMemsetAsync(a.tail, 0, nt * sizeof(int), a.stream) != hipSuccess || hipStreamSynchronize(a.stream) != hipSuccess)
-      return fail(MPMPC_E_HIP, "allocation of a launch slot failed (stream / output block / tail list)");
-    a.tail_flag[0] = a.tail_flag[1] = 0u;
-    h->n_alt += 1;
+static void free_slot(Slot& s) {
+  if (s.out_block) (void)hipFree(s.out_block);
+  if (s.tail) (void)hipFree(s.tail);
+  if (s.tail_flag) (void)hipHostFree(s.tail_flag);
+  if (s.stream) (void)hipStreamDestroy(s.stream);
+  s = Slot{};
+}
+// One launch slot: its stream FIRST (nothing in this library may run on the null stream - its first use makes the runtime give it
+// a hardware queue for the life of the process, one fewer for the launch streams, see launch_streams), the output block for
+// max_batch instances, the tail lists, the tail flag.  The lists are cleared on the slot's own stream: they are only ever used
+// by launches on it, which are ordered behind that; the wait reports a failure here.
+static int alloc_slot(mpmpc_handle h, Slot& s) {
+  const size_t out_bytes = block_layout(h->cfg.N, h->cfg.max_batch).out_end, tail_bytes = 3 * ((size_t)h->cfg.max_batch + 1) * sizeof(int);
+  if (create_launch_stream(&s.stream) != hipSuccess || hipMalloc((void**)&s.out_block, out_bytes) != hipSuccess ||
+      hipMalloc((void**)&s.tail, tail_bytes) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void**>(&s.tail_flag), 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess ||
+      hipMemsetAsync(s.tail, 0, tail_bytes, s.stream) != hipSuccess || hipStreamSynchronize(s.stream) != hipSuccess) {
+    const std::string why = hipGetErrorString(hipGetLastError());
+    free_slot(s);
+    return fail(MPMPC_E_HIP, "allocation of a launch slot failed (stream / output block / tail lists / tail flag): " + why);
   }
+  s.tail_flag[0] = s.tail_flag[1] = 0u;
+  return MPMPC_OK;
+}
+// launch slots up to `want`, in slot order (and so are their streams), laid out like the ones there are
+static int grow_slots(mpmpc_handle h, int want) {
+  for (; h->n_slots < want; ++h->n_slots)
+    if (int rc = alloc_slot(h, h->slot[h->n_slots])) return rc;
   lay_out(h, h->laid_out ? h->laid_out : h->cfg.max_batch);
   return MPMPC_OK;
 }
@@ -1292,30 +1281,23 @@ static int grow_slots(mpmpc_handle h, int want) {
 int mpmpc_destroy(mpmpc_handle h) {
   if (!h) return MPMPC_OK;
   (void)hipSetDevice(h->cfg.device);
-  void* ptrs[] = {h->kappa, h->v_ref, h->ds_next, h->ub_tab, h->lb_tab, h->in_block, h->out_block,
+  void* ptrs[] = {h->kappa, h->v_ref, h->ds_next, h->ub_tab, h->lb_tab, h->in_block,
                   h->qp,    h->map, h->gx,  h->gy,
                   h->gpsi,  h->bub,   h->blb,     h->segs,   h->nseg,   h->bad,    h->ro_cum, h->ro_s, h->ro_pose, h->gtrig,
-                  h->ro_u,  h->ro_counter, h->ro_alive, h->tail, h->ro_act, h->ro_shift, h->line_cells, h->line_box,
+                  h->ro_u,  h->ro_counter, h->ro_alive, h->ro_act, h->ro_shift, h->line_cells, h->line_box,
                   h->obst_off, h->obst_discs, h->ro_flag, h->rec_buf, h->rec_ain};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
-  for (auto& a : h->alt) {
-    if (a.out_block) (void)hipFree(a.out_block);
-    if (a.tail) (void)hipFree(a.tail);
-    if (a.tail_flag) (void)hipHostFree(a.tail_flag);
-    if (a.stream) (void)hipStreamDestroy(a.stream);
-  }
+  for (auto& s : h->slot) free_slot(s);
   if (h->ev_order) (void)hipEventDestroy(h->ev_order);
   if (h->bounce) (void)hipHostFree(h->bounce);
   for (auto& e : h->ev_bounce)
     if (e) (void)hipEventDestroy(e);
   if (h->stage_in) (void)hipHostFree(h->stage_in);
   if (h->stage_out) (void)hipHostFree(h->stage_out);
-  if (h->tail_flag) (void)hipHostFree(h->tail_flag);
   for (auto& e : h->ev)
     if (e) (void)hipEventDestroy(e);
   if (h->ev_in) (void)hipEventDestroy(h->ev_in);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return MPMPC_OK;
 }
@@ -1367,16 +1349,20 @@ int mpmpc_create(const mpmpc_config* cfg, const mpmpc_settings* settings, mpmpc_
   h->m = 8 * cfg->N + 6;
   h->pipeline = launch_streams(h->pipeline);
   const size_t B = (size_t)cfg->max_batch;
-  // The handle's stream comes first: everything below that touches the device goes to it.  Nothing in this library may run on the
-  // null stream - its first use makes the runtime give it a hardware queue for the life of the process, one fewer for the
-  // launch streams (see launch_streams).
-  hipError_t e = create_launch_stream(&h->stream);
+  // Slot 0 comes first, and its stream first of it: everything below that touches the device goes to that stream (alloc_slot).
+  // (the further launch slots of pipelined resident launches are allocated by the first such launch: next_slot)
+  if (int rc = alloc_slot(h, h->slot[0])) {
+    mpmpc_destroy(h);
+    return rc;
+  }
+  h->n_slots = 1;
+  hipError_t e = hipSuccess;
   for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_order, hipEventDisableTiming);
   if (e != hipSuccess) {
     mpmpc_destroy(h);
-    return fail(MPMPC_E_HIP, std::string("stream/event creation: ") + hipGetErrorString(e));
+    return fail(MPMPC_E_HIP, std::string("event creation: ") + hipGetErrorString(e));
   }
 #define ALLOC(ptr, count)                                                                \
   do {                                                                                   \
@@ -1388,21 +1374,8 @@ int mpmpc_create(const mpmpc_config* cfg, const mpmpc_settings* settings, mpmpc_
   } while (0)
   const BlockLayout lay = block_layout(cfg->N, cfg->max_batch);
   ALLOC(h->in_block, lay.in_end);
-  ALLOC(h->out_block, lay.out_end);
   lay_out(h, cfg->max_batch);
   ALLOC(h->qp, (size_t)MPMPC_NUM_FIELDS * B * h->ld);
-  ALLOC(h->tail, 3 * (B + 1));
-  // (the lists are only ever used by launches on the stream of their slot: ordered behind this; the wait reports a failure here)
-  if (hipMemsetAsync(h->tail, 0, 3 * (B + 1) * sizeof(int), h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
-    mpmpc_destroy(h);
-    return fail(MPMPC_E_HIP, "clearing the tail lists failed");
-  }
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->tail_flag), 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) {
-    h->tail_flag = nullptr;
-    mpmpc_destroy(h);
-    return fail(MPMPC_E_HIP, "hipHostMalloc tail_flag");
-  }
-  h->tail_flag[0] = h->tail_flag[1] = 0u;
 #undef ALLOC
   {
     const size_t STAGE_LIMIT = 64u << 20;
@@ -1412,14 +1385,13 @@ int mpmpc_create(const mpmpc_config* cfg, const mpmpc_settings* settings, mpmpc_
     if (out_b <= STAGE_LIMIT && hipHostMalloc((void**)&h->stage_out, out_b, hipHostMallocDefault) == hipSuccess) h->stage_out_bytes = out_b;
     else h->stage_out = nullptr;
   }
-  // (the further launch slots of pipelined resident launches are allocated by the first such launch: next_slot)
   *out = h;
   return MPMPC_OK;
 }
 
 int mpmpc_set_packing(mpmpc_handle h, int32_t lanes_per_instance) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   const int g = lanes_per_instance;
   if (g != 0 && g != 16 && g != 32 && g != 64 && !(g == 128 && h->cfg.N + 1 > 64) && !(g == 256 && h->cfg.N + 1 > 128))
     return fail(MPMPC_E_ARG, "lanes_per_instance must be 0 (auto), 16, 32 or 64 (128 / 256: the one-stage workgroup kernels of horizons 64 .. 127 / 128 .. 255)");
@@ -1434,7 +1406,7 @@ int mpmpc_set_packing(mpmpc_handle h, int32_t lanes_per_instance) {
 
 int mpmpc_set_tail_kernel(mpmpc_handle h, int32_t reduced_native) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (reduced_native < 0 || reduced_native > 2) return fail(MPMPC_E_ARG, "reduced_native must be 0, 1 or 2");
   h->lean_tail = reduced_native != 0;
   h->lean_tail_single = reduced_native == 2;
@@ -1443,7 +1415,7 @@ int mpmpc_set_tail_kernel(mpmpc_handle h, int32_t reduced_native) {
 
 int mpmpc_set_settings(mpmpc_handle h, const mpmpc_settings* settings) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (int rc = check_settings(settings)) return rc;
   h->st = *settings;
   return MPMPC_OK;
@@ -1452,13 +1424,13 @@ int mpmpc_set_settings(mpmpc_handle h, const mpmpc_settings* settings) {
 static int upload_table(mpmpc_handle h, double** dst, const double* src, size_t count) {
   if (*dst) { HIP_TRY(hipFree(*dst)); *dst = nullptr; }
   HIP_TRY(hipMalloc((void**)dst, count * sizeof(double)));
-  HIP_TRY(hipMemcpyAsync(*dst, src, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(*dst, src, count * sizeof(double), hipMemcpyHostToDevice, h->last().stream));
   return MPMPC_OK;
 }
 
 int mpmpc_set_path(mpmpc_handle h, int32_t n_wp, const double* kappa, const double* v_ref, const double* ds_next) {
   if (!h || !kappa || !v_ref || !ds_next) return fail(MPMPC_E_ARG, "NULL argument");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (n_wp < 2) return fail(MPMPC_E_ARG, "need at least 2 waypoints");
   for (int i = 0; i < n_wp; ++i)
     if (!(v_ref[i] > 0) || !std::isfinite(kappa[i]) || !(ds_next[i] >= 0))
@@ -1467,7 +1439,7 @@ int mpmpc_set_path(mpmpc_handle h, int32_t n_wp, const double* kappa, const doub
   if (int rc = upload_table(h, &h->kappa, kappa, n_wp)) return rc;
   if (int rc = upload_table(h, &h->v_ref, v_ref, n_wp)) return rc;
   if (int rc = upload_table(h, &h->ds_next, ds_next, n_wp)) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
   if (h->n_wp != n_wp) { h->n_cols = 0; }   // a corridor table of another path is void
   h->n_wp = n_wp;
   ++h->base_gen;
@@ -1476,13 +1448,13 @@ int mpmpc_set_path(mpmpc_handle h, int32_t n_wp, const double* kappa, const doub
 
 int mpmpc_set_corridor(mpmpc_handle h, int32_t n_wp, int32_t n_cols, const double* ub, const double* lb) {
   if (!h || !ub || !lb) return fail(MPMPC_E_ARG, "NULL argument");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (h->n_wp == 0 || n_wp != h->n_wp) return fail(MPMPC_E_STATE, "set the path first; n_wp must match it");
   if (n_cols < h->cfg.N) return fail(MPMPC_E_ARG, "corridor table needs n_cols >= N");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if (int rc = upload_table(h, &h->ub_tab, ub, (size_t)n_wp * n_cols)) return rc;
   if (int rc = upload_table(h, &h->lb_tab, lb, (size_t)n_wp * n_cols)) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
   h->n_cols = n_cols;
   return MPMPC_OK;
 }
@@ -1490,14 +1462,14 @@ int mpmpc_set_corridor(mpmpc_handle h, int32_t n_wp, int32_t n_cols, const doubl
 int mpmpc_set_map(mpmpc_handle h, int32_t height, int32_t width, const int8_t* data, double origin_x,
                   double origin_y, double resolution) {
   if (!h || !data) return fail(MPMPC_E_ARG, "NULL argument");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (height < 1 || width < 1 || !(resolution > 0)) return fail(MPMPC_E_ARG, "map needs positive size and resolution");
   if (height > COR_MAX_SIDE || width > COR_MAX_SIDE) return fail(MPMPC_E_ARG, "map sides are limited to 65534 cells");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if (h->map) { HIP_TRY(hipFree(h->map)); h->map = nullptr; }
   HIP_TRY(hipMalloc((void**)&h->map, (size_t)height * width));
-  HIP_TRY(hipMemcpyAsync(h->map, data, (size_t)height * width, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(h->map, data, (size_t)height * width, hipMemcpyHostToDevice, h->last().stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
   h->map_h = height; h->map_w = width; h->map_ox = origin_x; h->map_oy = origin_y; h->map_res = resolution;
   ++h->base_gen;
   return MPMPC_OK;
@@ -1506,7 +1478,7 @@ int mpmpc_set_map(mpmpc_handle h, int32_t height, int32_t width, const int8_t* d
 int mpmpc_set_path_geometry(mpmpc_handle h, int32_t n_wp, const double* x, const double* y, const double* psi,
                             const double* border_ub, const double* border_lb) {
   if (!h || !x || !y || !psi || !border_ub || !border_lb) return fail(MPMPC_E_ARG, "NULL argument");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (h->n_wp == 0 || n_wp != h->n_wp) return fail(MPMPC_E_STATE, "set the path first; n_wp must match it");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if (int rc = upload_table(h, &h->gx, x, n_wp)) return rc;
@@ -1520,7 +1492,7 @@ int mpmpc_set_path_geometry(mpmpc_handle h, int32_t n_wp, const double* x, const
     std::vector<double> trig((size_t)n_wp * COR_TRIG);
     for (int i = 0; i < n_wp; ++i) cor_trig_row(psi[i], trig.data() + (size_t)i * COR_TRIG);
     if (int rc = upload_table(h, &h->gtrig, trig.data(), trig.size())) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));      // `trig` leaves scope
+    HIP_TRY(hipStreamSynchronize(h->last().stream));      // `trig` leaves scope
   }
   h->host_bub.assign(border_ub, border_ub + 2 * (size_t)n_wp);
   h->host_blb.assign(border_lb, border_lb + 2 * (size_t)n_wp);
@@ -1533,7 +1505,7 @@ int mpmpc_set_path_geometry(mpmpc_handle h, int32_t n_wp, const double* x, const
   if (h->line_box) { HIP_TRY(hipFree(h->line_box)); h->line_box = nullptr; }
   HIP_TRY(hipMalloc((void**)&h->line_cells, sizeof(int) * COR_CELL_CAP * (size_t)n_wp));
   HIP_TRY(hipMalloc((void**)&h->line_box, sizeof(int) * COR_LINE_BOX * (size_t)n_wp));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
   h->geom_n = n_wp;
   ++h->base_gen;
   return MPMPC_OK;
@@ -1542,7 +1514,8 @@ int mpmpc_set_path_geometry(mpmpc_handle h, int32_t n_wp, const double* x, const
 int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, double safety_margin, double* ub_out,
                          double* lb_out, int32_t* bad_rows) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
+  Slot& sl = h->last();
   if (!h->map || h->geom_n == 0 || h->geom_n != h->n_wp)
     return fail(MPMPC_E_STATE, "needs mpmpc_set_path, mpmpc_set_map and mpmpc_set_path_geometry first");
   if (n_cols < h->cfg.N) return fail(MPMPC_E_ARG, "corridor table needs n_cols >= N");
@@ -1566,18 +1539,18 @@ int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, doubl
       if (cx[e] < 0 || cx[e] >= h->map_w || cy[e] < 0 || cy[e] >= h->map_h)
         return fail(MPMPC_E_ARG, "border cell of waypoint " + std::to_string(i) + " lies outside the map");
   }
-  HIP_TRY(hipMemsetAsync(h->bad, 0, 2 * sizeof(int), h->stream));
+  HIP_TRY(hipMemsetAsync(h->bad, 0, 2 * sizeof(int), sl.stream));
   double* wpc = h->segs + (size_t)4 * COR_MAXSEG * n;
-  hipLaunchKernelGGL(mpmpc_free_segments_kernel, dim3(n), dim3(64), 0, h->stream, mv, pg, h->bub, h->blb, min_width,
+  hipLaunchKernelGGL(mpmpc_free_segments_kernel, dim3(n), dim3(64), 0, sl.stream, mv, pg, h->bub, h->blb, min_width,
                      safety_margin, h->segs, h->nseg, wpc, h->bad + 1, h->line_cells, h->line_box);
-  hipLaunchKernelGGL(mpmpc_corridor_select_kernel, dim3((n * n_cols + 255) / 256), dim3(256), 0, h->stream, pg, h->segs,
+  hipLaunchKernelGGL(mpmpc_corridor_select_kernel, dim3((n * n_cols + 255) / 256), dim3(256), 0, sl.stream, pg, h->segs,
                      h->nseg, n_cols, safety_margin, h->ub_tab, h->lb_tab, h->bad, wpc);
   HIP_TRY(hipGetLastError());
   int bad2[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(bad2, h->bad, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (ub_out) HIP_TRY(hipMemcpyAsync(ub_out, h->ub_tab, sizeof(double) * (size_t)n * n_cols, hipMemcpyDeviceToHost, h->stream));
-  if (lb_out) HIP_TRY(hipMemcpyAsync(lb_out, h->lb_tab, sizeof(double) * (size_t)n * n_cols, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(bad2, h->bad, 2 * sizeof(int), hipMemcpyDeviceToHost, sl.stream));
+  if (ub_out) HIP_TRY(hipMemcpyAsync(ub_out, h->ub_tab, sizeof(double) * (size_t)n * n_cols, hipMemcpyDeviceToHost, sl.stream));
+  if (lb_out) HIP_TRY(hipMemcpyAsync(lb_out, h->lb_tab, sizeof(double) * (size_t)n * n_cols, hipMemcpyDeviceToHost, sl.stream));
+  HIP_TRY(hipStreamSynchronize(sl.stream));
   h->built_gen = 0;
   if (bad2[1] != 0) {
     h->n_cols = 0;        // the table is not usable
@@ -1596,7 +1569,8 @@ int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, doubl
 int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_lengths, const double* s,
                        const double* pose, const double* cc0) {
   if (!h || !cum_lengths || !s || !pose) return fail(MPMPC_E_ARG, "NULL argument");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
+  Slot& sl = h->last();
   if (B < 1 || B > h->cfg.max_batch) return fail(MPMPC_E_ARG, "B must be in [1, max_batch]");
   if (!(Ts > 0)) return fail(MPMPC_E_ARG, "Ts must be > 0");
   if (h->n_wp == 0 || h->geom_n != h->n_wp) return fail(MPMPC_E_STATE, "needs mpmpc_set_path and mpmpc_set_path_geometry");
@@ -1617,21 +1591,21 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   if (int rc = upload_table(h, &h->ro_cum, cum_lengths, h->n_wp)) return rc;
   const int N = h->cfg.N;
   if (B != h->laid_out) lay_out(h, B);
-  HIP_TRY(hipMemcpyAsync(h->ro_s, s, sizeof(double) * B, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->ro_pose, pose, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
-  if (cc0) HIP_TRY(hipMemcpyAsync(h->cc, cc0, sizeof(double) * 2 * N * B, hipMemcpyHostToDevice, h->stream));
-  else HIP_TRY(hipMemsetAsync(h->cc, 0, sizeof(double) * 2 * N * B, h->stream));
-  HIP_TRY(hipMemsetAsync(h->ro_counter, 0, sizeof(int) * B, h->stream));
-  HIP_TRY(hipMemsetAsync(h->ro_act, 0, sizeof(int) * (size_t)B * h->ld, h->stream));     // no guess yet
-  HIP_TRY(hipMemsetAsync(h->ro_shift, 0, sizeof(int) * B, h->stream));
-  HIP_TRY(hipMemsetAsync(h->ro_u, 0, sizeof(double) * 2 * B, h->stream));
-  HIP_TRY(hipMemsetAsync(h->wp_id, 0, sizeof(int) * B, h->stream));
-  HIP_TRY(hipMemsetAsync(h->x0, 0, sizeof(double) * 3 * B, h->stream));
-  HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(int) * B, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->ro_s, s, sizeof(double) * B, hipMemcpyHostToDevice, sl.stream));
+  HIP_TRY(hipMemcpyAsync(h->ro_pose, pose, sizeof(double) * 3 * B, hipMemcpyHostToDevice, sl.stream));
+  if (cc0) HIP_TRY(hipMemcpyAsync(h->cc, cc0, sizeof(double) * 2 * N * B, hipMemcpyHostToDevice, sl.stream));
+  else HIP_TRY(hipMemsetAsync(h->cc, 0, sizeof(double) * 2 * N * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(h->ro_counter, 0, sizeof(int) * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(h->ro_act, 0, sizeof(int) * (size_t)B * h->ld, sl.stream));     // no guess yet
+  HIP_TRY(hipMemsetAsync(h->ro_shift, 0, sizeof(int) * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(h->ro_u, 0, sizeof(double) * 2 * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(h->wp_id, 0, sizeof(int) * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(h->x0, 0, sizeof(double) * 3 * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(sl.status, 0, sizeof(int) * B, sl.stream));
   std::string ones(sizeof(int) * (size_t)B, '\0');
   for (int i = 0; i < B; ++i) ((int*)ones.data())[i] = 1;
-  HIP_TRY(hipMemcpyAsync(h->ro_alive, ones.data(), sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(h->ro_alive, ones.data(), sizeof(int) * B, hipMemcpyHostToDevice, sl.stream));
+  HIP_TRY(hipStreamSynchronize(sl.stream));
   h->ro_Ts = Ts;
   h->ro_B = B;
   h->ro_valid = true;
@@ -1651,13 +1625,13 @@ static long long records_of(const mpmpc_handle_s* h, long long n_steps) {
 
 int mpmpc_rollout_record(mpmpc_handle h, int32_t B, int32_t capacity, int32_t fields, int32_t stride) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (capacity < 0) return fail(MPMPC_E_ARG, "capacity must be >= 0");
   if (stride < 1) return fail(MPMPC_E_ARG, "stride must be >= 1");
   if (fields & ~RO_REC_ALL) return fail(MPMPC_E_ARG, "unknown bits in fields");
   if (B < 1 || B > h->cfg.max_batch) return fail(MPMPC_E_ARG, "B must be in [1, max_batch]");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
   if (h->rec_buf) { (void)hipFree(h->rec_buf); h->rec_buf = nullptr; }
   h->rec_cap = 0;
   h->rec_count = 0;
@@ -1687,8 +1661,8 @@ int mpmpc_rollout_recorded(mpmpc_handle h, int32_t* n_records, int32_t* n_steps)
 // field `off` of records first .. first + count - 1 -> host [count][bytes]: one strided copy
 static int pull_field(mpmpc_handle h, void* dst, long long off, size_t bytes, int first, int count) {
   const char* src = h->rec_buf + (size_t)h->rec_lay.bytes * (size_t)first + off;
-  if (count == 1) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-  else HIP_TRY(hipMemcpy2DAsync(dst, bytes, src, (size_t)h->rec_lay.bytes, bytes, (size_t)count, hipMemcpyDeviceToHost, h->stream));
+  if (count == 1) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->last().stream));
+  else HIP_TRY(hipMemcpy2DAsync(dst, bytes, src, (size_t)h->rec_lay.bytes, bytes, (size_t)count, hipMemcpyDeviceToHost, h->last().stream));
   return MPMPC_OK;
 }
 
@@ -1696,7 +1670,7 @@ int mpmpc_rollout_trace(mpmpc_handle h, int32_t B, int32_t first, int32_t count,
                         double* x0, double* u, int32_t* status, int32_t* counter, int32_t* alive, double* plan,
                         double* pred_x, double* pred_y, double* ub, double* lb) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (first < 0 || count < 0) return fail(MPMPC_E_ARG, "first and count must be >= 0");
   if (h->rec_cap == 0) return fail(MPMPC_E_STATE, "recording is off (mpmpc_rollout_record)");
   if (B != h->rec_B) return fail(MPMPC_E_STATE, "mpmpc_rollout_record was set up for another number of cars");
@@ -1716,25 +1690,26 @@ int mpmpc_rollout_trace(mpmpc_handle h, int32_t B, int32_t first, int32_t count,
     PULL(ub, l.ub, 8 * N); PULL(lb, l.lb, 8 * N);
 #undef PULL
   }
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
   return MPMPC_OK;
 }
 
 int mpmpc_rollout_set_counters(mpmpc_handle h, int32_t B, const int32_t* counter) {
   if (!h || !counter) return fail(MPMPC_E_ARG, "NULL argument");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (B < 1 || B > h->ro_B || !h->ro_valid) return fail(MPMPC_E_STATE, "call mpmpc_rollout_init for at least B cars first");
   for (int i = 0; i < B; ++i)
     if (counter[i] < 0 || counter[i] >= h->cfg.N - 1) return fail(MPMPC_E_ARG, "infeasibility counters must be in [0, N - 2]");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  HIP_TRY(hipMemcpyAsync(h->ro_counter, counter, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(h->ro_counter, counter, sizeof(int) * B, hipMemcpyHostToDevice, h->last().stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
   return MPMPC_OK;
 }
 
 int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
+  Slot& sl = h->last();
   if (B < 1 || B > h->ro_B) return fail(MPMPC_E_STATE, "call mpmpc_rollout_init for at least B cars first");
   if (!h->ro_valid)
     return fail(MPMPC_E_STATE, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
@@ -1765,24 +1740,24 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     char* rec = recording && h->ro_steps % h->rec_stride == 0 ? h->rec_buf + (size_t)h->rec_lay.bytes * (size_t)h->rec_count : nullptr;
     if (rec)
       hipLaunchKernelGGL(mpmpc_record_snapshot_kernel, dim3((unsigned)(((long)B * RO_REC_BEGIN_ENTRIES + 255) / 256)), dim3(256), 0,
-                         h->stream, B, h->ro_s, h->ro_pose, h->ro_alive, h->rec_ain, rec, h->rec_lay);
-    hipLaunchKernelGGL(mpmpc_localise_kernel, dim3(blocks), dim3(256), 0, h->stream, B, h->n_wp, h->cfg.N,
+                         sl.stream, B, h->ro_s, h->ro_pose, h->ro_alive, h->rec_ain, rec, h->rec_lay);
+    hipLaunchKernelGGL(mpmpc_localise_kernel, dim3(blocks), dim3(256), 0, sl.stream, B, h->n_wp, h->cfg.N,
                        h->cfg.circular ? 1 : 0, h->ro_cum, h->gx, h->gy,
                        h->gpsi, h->ro_s, h->ro_pose, h->ro_alive, h->wp_id, h->x0, h->ro_shift);
     if (per_car)
-      hipLaunchKernelGGL(mpmpc_car_corridor_kernel, dim3(B), dim3(64), car_lds, h->stream, mv, pg, N, h->built_min_width,
+      hipLaunchKernelGGL(mpmpc_car_corridor_kernel, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->built_min_width,
                          h->built_sm, h->segs, h->nseg, h->segs + (size_t)4 * COR_MAXSEG * h->n_wp, h->line_cells,
                          h->line_box, h->obst_off, h->obst_discs, h->wp_id, h->ro_alive, h->ro_flag, h->lb, h->ub);
-    if (int rc = launch_solve(h, B, true, false)) return rc;      // (the plant step reads z and the status only)
-    hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, h->stream, B, h->cfg.N, h->cfg.wheelbase, h->ro_Ts,
-                       h->kappa, h->wp_id, h->x0, h->status, h->z, h->cc, h->ro_counter, h->ro_alive, h->ro_pose, h->ro_s,
+    if (int rc = launch_solve(h, sl, B, true, false)) return rc;  // (the plant step reads z and the status only)
+    hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro_Ts,
+                       h->kappa, h->wp_id, h->x0, sl.status, sl.z, h->cc, h->ro_counter, h->ro_alive, h->ro_pose, h->ro_s,
                        h->ro_u);
     if (rec) {
-      const RoRecSrc src{h->ro_alive, h->rec_ain, h->wp_id, h->status, h->ro_counter, h->x0, h->ro_u, h->cc, h->z,
+      const RoRecSrc src{h->ro_alive, h->rec_ain, h->wp_id, sl.status, h->ro_counter, h->x0, h->ro_u, h->cc, sl.z,
                          h->gx, h->gy, h->gtrig, per_car ? h->ub : h->ub_tab, per_car ? h->lb : h->lb_tab,
                          per_car ? (long long)N : (long long)h->n_cols, per_car ? 1 : 0, COR_TRIG, N, h->n_wp, h->cfg.circular ? 1 : 0};
       hipLaunchKernelGGL(mpmpc_record_write_kernel, dim3((unsigned)(((long)B * h->rec_lay.entries + 255) / 256)), dim3(256), 0,
-                         h->stream, B, src, rec, h->rec_lay);
+                         sl.stream, B, src, rec, h->rec_lay);
       ++h->rec_count;
     }
     ++h->ro_steps;
@@ -1794,23 +1769,24 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
 
 int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* discs) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (!offsets) { h->obst_B = 0; return MPMPC_OK; }      // back to the shared table
   const char* why = "";
   const bool built = h->built_gen == h->base_gen && h->built_gen != 0 && h->n_cols > 0 && h->line_cells;
   if (int rc = cor_check_obstacles(B, h->cfg.max_batch, offsets, discs, built, h->map_w, h->map_h, &why))
     return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
   HIP_TRY(hipSetDevice(h->cfg.device));
+  Slot& sl = h->last();
   const size_t mb = (size_t)h->cfg.max_batch;
   if (!h->obst_off) {
     HIP_TRY(hipMalloc((void**)&h->obst_off, sizeof(int) * (mb + 1)));
     HIP_TRY(hipMalloc((void**)&h->obst_discs, sizeof(int) * 3 * COR_MAX_DISCS * mb));
   }
   if (!h->ro_flag) HIP_TRY(hipMalloc((void**)&h->ro_flag, sizeof(int) * mb));
-  HIP_TRY(hipMemcpyAsync(h->obst_off, offsets, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->obst_off, offsets, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, sl.stream));
   if (offsets[B] > 0)
-    HIP_TRY(hipMemcpyAsync(h->obst_discs, discs, sizeof(int) * 3 * (size_t)offsets[B], hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(h->obst_discs, discs, sizeof(int) * 3 * (size_t)offsets[B], hipMemcpyHostToDevice, sl.stream));
+  HIP_TRY(hipStreamSynchronize(sl.stream));
   h->obst_B = B;
   h->obst_gen = h->base_gen;
   return MPMPC_OK;
@@ -1818,16 +1794,17 @@ int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offset
 
 int mpmpc_rollout_corridor(mpmpc_handle h, int32_t B, double* ub, double* lb) {
   if (!h || !ub || !lb) return fail(MPMPC_E_ARG, "NULL argument");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
+  Slot& sl = h->last();
   if (B < 1 || B > h->ro_B || !h->ro_valid) return fail(MPMPC_E_STATE, "call mpmpc_rollout_init for at least B cars first");
   if (!h->car_rows) return fail(MPMPC_E_STATE, "the last rollout step did not build per-car rows (mpmpc_rollout_set_obstacles)");
   HIP_TRY(hipSetDevice(h->cfg.device));
   const size_t nb = (size_t)B * h->cfg.N;
   std::vector<int> flag(B);
-  HIP_TRY(hipMemcpyAsync(ub, h->ub, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(lb, h->lb, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(flag.data(), h->ro_flag, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(ub, h->ub, sizeof(double) * nb, hipMemcpyDeviceToHost, sl.stream));
+  HIP_TRY(hipMemcpyAsync(lb, h->lb, sizeof(double) * nb, hipMemcpyDeviceToHost, sl.stream));
+  HIP_TRY(hipMemcpyAsync(flag.data(), h->ro_flag, sizeof(int) * B, hipMemcpyDeviceToHost, sl.stream));
+  HIP_TRY(hipStreamSynchronize(sl.stream));
   for (int b = 0; b < B; ++b)
     if (flag[b] != COR_ROW_OK)
       for (int n = 0; n < h->cfg.N; ++n) ub[(size_t)b * h->cfg.N + n] = lb[(size_t)b * h->cfg.N + n] = std::nan("");
@@ -1836,7 +1813,7 @@ int mpmpc_rollout_corridor(mpmpc_handle h, int32_t B, double* ub, double* lb) {
 
 int mpmpc_rollout_warm_start(mpmpc_handle h, int32_t enable) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   h->ro_warm = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
   return MPMPC_OK;
 }
@@ -1844,32 +1821,33 @@ int mpmpc_rollout_warm_start(mpmpc_handle h, int32_t enable) {
 int mpmpc_rollout_state(mpmpc_handle h, int32_t B, double* s, double* pose, double* cc, int32_t* wp_id, double* x0,
                         double* u_last, int32_t* status, int32_t* counter, int32_t* alive) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
+  Slot& sl = h->last();
   if (B < 1 || B > h->ro_B) return fail(MPMPC_E_STATE, "call mpmpc_rollout_init for at least B cars first");
   if (!h->ro_valid)
     return fail(MPMPC_E_STATE, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
                                "call mpmpc_rollout_init again");
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int N = h->cfg.N;
-#define PULL(dst, src, bytes) if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream))
+#define PULL(dst, src, bytes) if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.stream))
   PULL(s, h->ro_s, sizeof(double) * B);
   PULL(pose, h->ro_pose, sizeof(double) * 3 * B);
   PULL(cc, h->cc, sizeof(double) * 2 * N * B);
   PULL(wp_id, h->wp_id, sizeof(int) * B);
   PULL(x0, h->x0, sizeof(double) * 3 * B);
   PULL(u_last, h->ro_u, sizeof(double) * 2 * B);
-  PULL(status, h->status, sizeof(int) * B);
+  PULL(status, sl.status, sizeof(int) * B);
   PULL(counter, h->ro_counter, sizeof(int) * B);
   PULL(alive, h->ro_alive, sizeof(int) * B);
 #undef PULL
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(sl.stream));
   return MPMPC_OK;
 }
 
 int mpmpc_upload(mpmpc_handle h, int32_t B, const int32_t* wp_id, const double* x0, const double* cc_prev,
                  const double* lb, const double* ub) {
   if (!h || !wp_id || !x0 || !cc_prev) return fail(MPMPC_E_ARG, "NULL argument");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (B < 1 || B > h->cfg.max_batch) return fail(MPMPC_E_ARG, "B must be in [1, max_batch]");
   if (h->n_wp == 0) return fail(MPMPC_E_STATE, "no path set (mpmpc_set_path)");
   if ((lb == nullptr) != (ub == nullptr)) return fail(MPMPC_E_ARG, "lb and ub must both be given or both NULL");
@@ -1897,8 +1875,8 @@ int mpmpc_upload(mpmpc_handle h, int32_t B, const int32_t* wp_id, const double* 
       std::memcpy(st + L.lb, lb, sizeof(double) * N * B);
       std::memcpy(st + L.ub, ub, sizeof(double) * N * B);
     }
-    HIP_TRY(hipMemcpyAsync(h->in_block, st, lb ? L.in_end : L.in_end_cc, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipEventRecord(h->ev_in, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->in_block, st, lb ? L.in_end : L.in_end_cc, hipMemcpyHostToDevice, h->last().stream));
+    HIP_TRY(hipEventRecord(h->ev_in, h->last().stream));
     h->in_flight = true;
   } else {
     // (no staging block of this size: through the bounce buffer - asynchronous on the device's side, the caller's buffers are
@@ -1928,8 +1906,8 @@ static int upload_through_bounce(mpmpc_handle h, void* dst, const void* src, siz
     const size_t n = bytes - off < BOUNCE_HALF ? bytes - off : BOUNCE_HALF;
     char* half = h->bounce + (size_t)k * BOUNCE_HALF;
     std::memcpy(half, static_cast<const char*>(src) + off, n);
-    HIP_TRY(hipMemcpyAsync(static_cast<char*>(dst) + off, half, n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipEventRecord(h->ev_bounce[k], h->stream));
+    HIP_TRY(hipMemcpyAsync(static_cast<char*>(dst) + off, half, n, hipMemcpyHostToDevice, h->last().stream));
+    HIP_TRY(hipEventRecord(h->ev_bounce[k], h->last().stream));
     h->bounce_busy[k] = true;
     h->bounce_turn = 1 - k;
   }
@@ -1945,7 +1923,7 @@ static int launch_assemble(mpmpc_handle h, int B) {
   const bool nt = force_nt != 0;
   const size_t k1_lds = h->n_wp <= K1_LDS_WP ? 3 * sizeof(double) * (size_t)h->n_wp : 0;
 #define K1_LAUNCH(V)                                                                                                       \
-  hipLaunchKernelGGL(mpmpc_assemble_kernel<V>, dim3(blocks), dim3(K1_THREADS), k1_lds, h->stream, h->cfg, t, B, h->ld, h->wp_id, \
+  hipLaunchKernelGGL(mpmpc_assemble_kernel<V>, dim3(blocks), dim3(K1_THREADS), k1_lds, h->last().stream, h->cfg, t, B, h->ld, h->wp_id, \
                      h->x0, h->cc, h->have_rows ? h->lb : nullptr, h->have_rows ? h->ub : nullptr, h->qp)
   if (nt) K1_LAUNCH(true);
   else K1_LAUNCH(false);
@@ -1963,6 +1941,7 @@ static int launch_assemble(mpmpc_handle h, int B) {
 // the six nested launch macros this replaces multiplied with every new layout).
 struct SolveLaunch {
   mpmpc_handle h;
+  Slot* slot;      // the launch slot it goes to: stream, outputs, tail flag
   SolverParams prm;
   AssembleIn ain;
   int B;
@@ -1980,11 +1959,12 @@ constexpr bool takes_ld(void (*)(mpmpc_config, SolverParams, int, AssembleIn, K.
 template <auto KERNEL, class... T>
 static void go(const SolveLaunch& a, int grid, int block, size_t lds, T... own) {
   mpmpc_handle h = a.h;
+  const Slot& s = *a.slot;
   if constexpr (takes_ld(KERNEL))
-    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, h->stream, h->cfg, a.prm, a.B, h->ld, a.ain, h->z, h->u0, h->status, h->iters, h->resid,
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, s.stream, h->cfg, a.prm, a.B, h->ld, a.ain, s.z, s.u0, s.status, s.iters, s.resid,
                        a.y_out, own...);
   else
-    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, h->stream, h->cfg, a.prm, a.B, a.ain, h->z, h->u0, h->status, h->iters, h->resid, a.y_out,
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, s.stream, h->cfg, a.prm, a.B, a.ain, s.z, s.u0, s.status, s.iters, s.resid, a.y_out,
                        own...);
 }
 // The workgroup kernels need more dynamic LDS than the default limit: the attribute is set once per function AND DEVICE (one
@@ -2030,7 +2010,7 @@ static int rn_pad() {
 // K2r: the reduced-native batch kernel, 1 / 2 / 4 instances per wave
 template <int G, int C, bool WARM>
 static void go_reduced(const SolveLaunch& a, int blocks) {
-  go<mpmpc_reduced_kernel<G, C, WARM>>(a, blocks, 64, rn_pad(), a.tail_cur, a.warm_act, a.warm_shift, a.tail_next, a.h->tail_flag, a.h->seq, a.tail2);
+  go<mpmpc_reduced_kernel<G, C, WARM>>(a, blocks, 64, rn_pad(), a.tail_cur, a.warm_act, a.warm_shift, a.tail_next, a.slot->tail_flag, a.slot->seq, a.tail2);
 }
 using ReducedFn = void (*)(const SolveLaunch&, int);
 // [layout: <64,16>, <64,32>, <32,16>, <16,16>][warm]
@@ -2040,17 +2020,17 @@ static int reduced_layout(int G, int C) { return G == 64 ? (C == 16 ? 0 : 1) : (
 // K2t: its twin for a terminal cost on the time state (one instance per wave)
 template <int C>
 static void go_reduced_t(const SolveLaunch& a, int blocks) {
-  go<mpmpc_reduced_t_kernel<64, C>>(a, blocks, 64, rn_pad(), a.tail_cur, a.tail_next, a.h->tail_flag, a.h->seq);
+  go<mpmpc_reduced_t_kernel<64, C>>(a, blocks, 64, rn_pad(), a.tail_cur, a.tail_next, a.slot->tail_flag, a.slot->seq);
 }
 // K2p: the reduced-native tail kernel on the list `tail_cur`; what it leaves goes to tail2
 template <int G, int C>
 static void go_reduced_tail(const SolveLaunch& a, int blocks) {
-  go<mpmpc_reduced_tail_kernel<G, C>>(a, blocks, 64, rn_pad(), a.tail_cur, a.tail_next, a.tail2, a.h->tail_flag + 1, a.h->seq);
+  go<mpmpc_reduced_tail_kernel<G, C>>(a, blocks, 64, rn_pad(), a.tail_cur, a.tail_next, a.tail2, a.slot->tail_flag + 1, a.slot->seq);
 }
 // K2r2 / K2t2 / K2p2: two stages per lane (lane_pair.hpp) - GB lanes per instance
 template <int GB>
 static void go_pair(const SolveLaunch& a, int blocks) {
-  go<mpmpc_reduced_pair_kernel<GB>>(a, blocks, 64, 0, a.tail_cur, a.tail_next, a.h->tail_flag, a.h->seq, a.tail2);
+  go<mpmpc_reduced_pair_kernel<GB>>(a, blocks, 64, 0, a.tail_cur, a.tail_next, a.slot->tail_flag, a.slot->seq, a.tail2);
 }
 template <int GB>
 static void go_pair_t(const SolveLaunch& a) { go<mpmpc_reduced_t_pair_kernel<GB>>(a, a.B, 64, 0, a.tail_cur); }
@@ -2082,20 +2062,20 @@ static int go_pair_block_t(const SolveLaunch& a) {
 // a workgroup; mpmpc_set_packing(h, 128) keeps round 5's workgroup kernels.  Everything else - longer horizons, full weights,
 // bounded e_psi / t - one instance per workgroup of 2 / 4 wavefronts (K2rb in front where the reduction applies).  No packing, no
 // deferred tail, cold starts in the closed loop too.
-static int launch_long_horizon(mpmpc_handle h, SolveLaunch& a, int tail_only) {
+static int launch_long_horizon(mpmpc_handle h, Slot& sl, SolveLaunch& a, int tail_only) {
   if (tail_only) return MPMPC_OK;
   const int N = h->cfg.N;
-  h->pend = h->pend2 = false;
+  sl.pend = sl.pend2 = false;
   const bool fullqn = full_weights(h->cfg);
   const int var = fullqn ? 1 : (reducible(h->cfg, h->st) ? 2 : 0);
   const bool one_wave = N + 1 <= 128 && h->force_lanes != 128;
-  int* list1 = h->tail;
-  int* list2 = h->tail + ((size_t)h->cfg.max_batch + 1);
+  int* list1 = sl.tail;
+  int* list2 = sl.tail + ((size_t)h->cfg.max_batch + 1);
   int* list3 = list2 + ((size_t)h->cfg.max_batch + 1);
   const int* tail_blk = nullptr;          // the list the general workgroup kernel works on (null: every instance, the whole solve)
   a.tail_cur = list1;
   if (!fullqn && reduced_native(h->cfg, h->st)) {
-    HIP_TRY(hipMemsetAsync(list1, 0, sizeof(int), h->stream));
+    HIP_TRY(hipMemsetAsync(list1, 0, sizeof(int), sl.stream));
     tail_blk = list1;
     if (one_wave) {
       // (the kernel empties "the lists of the next launch" - here the two lists behind the one it fills; the tail kernels below
@@ -2112,7 +2092,7 @@ static int launch_long_horizon(mpmpc_handle h, SolveLaunch& a, int tail_only) {
       // tail to the tail solver on the same layout (the list it fills is emptied first: no kernel of this sequence does it)
       if (int rc = go_pair_block(a)) return rc;
       if (h->lean_tail && reduced_native_tail(h->cfg, h->st)) {
-        HIP_TRY(hipMemsetAsync(list2, 0, sizeof(int), h->stream));
+        HIP_TRY(hipMemsetAsync(list2, 0, sizeof(int), sl.stream));
         a.tail_next = list2;
         if (int rc = go_pair_block_tail(a)) return rc;
         tail_blk = list2;
@@ -2121,7 +2101,7 @@ static int launch_long_horizon(mpmpc_handle h, SolveLaunch& a, int tail_only) {
   } else if (!fullqn && reduced_native_tt(h->cfg, h->st) && (one_wave || (N + 1 > 128 && h->force_lanes != 256))) {
     // a terminal cost on the time state: K2t's solver with two stages per lane - one wavefront per instance up to 128 stages, a
     // workgroup of two above - and the general workgroup kernel on what it lists
-    HIP_TRY(hipMemsetAsync(list1, 0, sizeof(int), h->stream));
+    HIP_TRY(hipMemsetAsync(list1, 0, sizeof(int), sl.stream));
     if (one_wave) go_pair_t<64>(a);
     else if (int rc = go_pair_block_t(a)) return rc;
     tail_blk = list1;
@@ -2131,20 +2111,21 @@ static int launch_long_horizon(mpmpc_handle h, SolveLaunch& a, int tail_only) {
   return MPMPC_OK;
 }
 
-// tail_only: 1 = the deferred tail launches of the last reduced-native launch (observe_tail), nothing else; 2 = of those,
+// A solve launch on slot `sl`.  tail_only: 1 = the deferred tail launches of its last reduced-native launch (observe_tail), nothing else; 2 = of those,
 // only the general kernel on what the reduced-native tail kernel left
-static int launch_solve(mpmpc_handle h, int B, bool closed_loop, bool want_y, int tail_only, LaunchKind kind) {
+static int launch_solve(mpmpc_handle h, Slot& sl, int B, bool closed_loop, bool want_y, int tail_only, LaunchKind kind) {
   const int N = h->cfg.N;
-  h->y_valid = want_y;
+  sl.y_valid = want_y;
   SolveLaunch a{};
   a.h = h;
+  a.slot = &sl;
   a.B = B;
   a.prm = make_params(h->st);
-  a.y_out = want_y ? h->y : nullptr;        // nobody wants the multipliers: the kernel skips their stores
+  a.y_out = want_y ? sl.y : nullptr;        // nobody wants the multipliers: the kernel skips their stores
   a.ain.tab = PathTables{h->kappa, h->v_ref, h->ds_next, h->n_wp, h->ub_tab, h->lb_tab, h->n_cols};
   a.ain.wp_id = h->wp_id; a.ain.x0 = h->x0; a.ain.cc = h->cc;
   a.ain.lb = h->have_rows ? h->lb : nullptr; a.ain.ub = h->have_rows ? h->ub : nullptr;
-  if (N + 1 > 64) return launch_long_horizon(h, a, tail_only);
+  if (N + 1 > 64) return launch_long_horizon(h, sl, a, tail_only);
   // Full weights (Q, R or QN with off-diagonal entries), bounds on e_psi / t or a cost on t rule the reduction out:
   // such configurations run the general kernels, one instance per wave.
   const bool fullqn = full_weights(h->cfg);
@@ -2192,11 +2173,11 @@ static int launch_solve(mpmpc_handle h, int B, bool closed_loop, bool want_y, in
   const int C64 = lane_split(64, N);     // ... of the one-instance-per-wave kernels that take a tail
   // tail lists ([0] = count, [1..] = instance ids), two of them used in turn: the tail launch of this step empties the
   // list of the next one, so that no memset has to sit between the launches of consecutive steps
-  a.tail_cur = h->tail + (size_t)h->tail_flip * (h->cfg.max_batch + 1);
-  a.tail_next = h->tail + (size_t)(1 - h->tail_flip) * (h->cfg.max_batch + 1);
-  a.tail2 = h->tail + 2 * ((size_t)h->cfg.max_batch + 1);      // what the reduced-native tail kernel leaves to the general one
-  if (tail_only) { a.tail_cur = h->pend_cur; a.tail_next = h->pend_next; }
-  else if (rn) { h->tail_flip = 1 - h->tail_flip; h->seq += 1; }
+  a.tail_cur = sl.tail + (size_t)sl.tail_flip * (h->cfg.max_batch + 1);
+  a.tail_next = sl.tail + (size_t)(1 - sl.tail_flip) * (h->cfg.max_batch + 1);
+  a.tail2 = sl.tail + 2 * ((size_t)h->cfg.max_batch + 1);      // what the reduced-native tail kernel leaves to the general one
+  if (tail_only) { a.tail_cur = sl.pend_cur; a.tail_next = sl.pend_next; }
+  else if (rn) { sl.tail_flip = 1 - sl.tail_flip; sl.seq += 1; }
   if (!rn) {
     // the general kernel, one instance per wave, the whole solve
     kGeneral[C == 32][warm][var](a, 0, blocks, a.tail_cur);
@@ -2218,10 +2199,10 @@ static int launch_solve(mpmpc_handle h, int B, bool closed_loop, bool want_y, in
   // object, not kept).  Its instances carry no guess for the next closed-loop step (act stays 0 from the first launch).
   // Deferred (see the handle): no tail launch is enqueued while the launches the host has seen leave none; the closed
   // loop consumes its results on the device and always launches it.
-  h->pend = !tail_only && !closed_loop && h->tail_expect_empty;
-  h->pend2 = false;
-  if (h->pend) {
-    h->pend_B = B; h->pend_y = want_y; h->pend_cur = a.tail_cur; h->pend_next = a.tail_next;
+  sl.pend = !tail_only && !closed_loop && sl.tail_expect_empty;
+  sl.pend2 = false;
+  if (sl.pend) {
+    sl.pend_B = B; sl.pend_y = want_y; sl.pend_cur = a.tail_cur; sl.pend_next = a.tail_next;
   } else if (lean) {
     if (tail_only != 2) {
       // (the list's order differs from run to run - atomic appends - and with it the two instances that share a wave of the
@@ -2231,9 +2212,9 @@ static int launch_solve(mpmpc_handle h, int B, bool closed_loop, bool want_y, in
       else go_reduced_tail<64, 16>(a, B);
     }
     // ... and the general kernel on what that left: deferred like the tail itself while the launches seen leave nothing
-    h->pend2 = tail_only != 2 && h->tail2_expect_empty;
-    if (h->pend2) {
-      h->pend_B = B; h->pend_y = want_y; h->pend_cur = a.tail_cur; h->pend_next = a.tail_next;
+    sl.pend2 = tail_only != 2 && sl.tail2_expect_empty;
+    if (sl.pend2) {
+      sl.pend_B = B; sl.pend_y = want_y; sl.pend_cur = a.tail_cur; sl.pend_next = a.tail_next;
     } else kGeneral[C64 == 32][0][var](a, 2, B, a.tail2);
   } else kGeneral[C64 == 32][0][var](a, 2, B, a.tail_cur);
   HIP_TRY(hipGetLastError());
@@ -2242,63 +2223,65 @@ static int launch_solve(mpmpc_handle h, int B, bool closed_loop, bool want_y, in
 
 extern "C" {
 
-// Drain the stream, see whether the last reduced-native launch left a tail, run it if its launch was deferred.
-static int observe_tail(mpmpc_handle h) {
+// Drain the slot's stream, see whether its last reduced-native launch left a tail, run it if its launch was deferred.
+static int observe_tail(mpmpc_handle h, Slot& sl) {
   HIP_TRY(hipSetDevice(h->cfg.device));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->busy = false;
+  HIP_TRY(hipStreamSynchronize(sl.stream));
+  sl.busy = false;
   h->order_pending = false;
-  if (h->seq == 0) return MPMPC_OK;
-  const bool left = *static_cast<volatile unsigned*>(h->tail_flag) == h->seq;
-  h->tail_ran_late = false;
-  if (h->pend) {
-    h->pend = false;
+  if (sl.seq == 0) return MPMPC_OK;
+  const bool left = *static_cast<volatile unsigned*>(sl.tail_flag) == sl.seq;
+  sl.tail_ran_late = false;
+  if (sl.pend) {
+    sl.pend = false;
     if (left) {
-      h->tail_ran_late = true;
-      if (int rc = launch_solve(h, h->pend_B, false, h->pend_y, 1)) return rc;
-      HIP_TRY(hipStreamSynchronize(h->stream));
+      sl.tail_ran_late = true;
+      if (int rc = launch_solve(h, sl, sl.pend_B, false, sl.pend_y, 1)) return rc;
+      HIP_TRY(hipStreamSynchronize(sl.stream));
     }
   }
-  h->tail_expect_empty = !left;
+  sl.tail_expect_empty = !left;
   // (second level: read after a tail that ran late has run)
-  const bool left2 = static_cast<volatile unsigned*>(h->tail_flag)[1] == h->seq;
-  if (h->pend2) {
-    h->pend2 = false;
+  const bool left2 = static_cast<volatile unsigned*>(sl.tail_flag)[1] == sl.seq;
+  if (sl.pend2) {
+    sl.pend2 = false;
     if (left2) {
-      h->tail_ran_late = true;
-      if (int rc = launch_solve(h, h->pend_B, false, h->pend_y, 2)) return rc;
-      HIP_TRY(hipStreamSynchronize(h->stream));
+      sl.tail_ran_late = true;
+      if (int rc = launch_solve(h, sl, sl.pend_B, false, sl.pend_y, 2)) return rc;
+      HIP_TRY(hipStreamSynchronize(sl.stream));
     }
   }
-  h->tail2_expect_empty = !left2;
+  sl.tail2_expect_empty = !left2;
   return MPMPC_OK;
 }
 
-// Resident launches are DOUBLE-BUFFERED: launch k + 1 goes to the other slot (stream, output block, tail lists) and runs
-// beside launch k - a batch launch fills one of the two wave slots of a SIMD (B <= 1 024) or leaves SIMDs idle while its last
-// waves and its tail launch run, and the next batch takes what is idle.  The results of launch k stay where they are until
-// launch k + 2; mpmpc_download / mpmpc_sync and every other call on the handle refer to the LAST launch and wait for both.
-// The next launch slot of a pipelined handle becomes "the slot of the last launch".  What the current stream still has queued
-// that solves read (an upload, closed-loop steps) must be done before ANY slot's next launch starts: an event goes to all
-// streams.  Shared by mpmpc_solve_resident and mpmpc_solve_resident_profile (the profile loop used to swap slots
-// without it, so an upload followed by it could be overtaken).  The further slots are allocated on first use: a handle that
-// never launches resident batches (single calls, host-buffer streams, the closed loop) holds one output block, not three.
+// Resident launches are PIPELINED over the `pipeline` launch slots in use: launch k + 1 goes to the next slot (stream, output
+// block, tail lists) and runs beside launch k - a batch launch fills one of the two wave slots of a SIMD (B <= 1 024) or leaves
+// SIMDs idle while its last waves and its tail launch run, and the next batches take what is idle.  The results of launch k stay
+// where they are until launch k + pipeline; mpmpc_download / mpmpc_sync and every other call on the handle refer to the LAST
+// launch and wait for all of them.
+// next_slot makes the next slot of the ring "the slot of the last launch": cur -> (cur + 1) % pipeline, which from slot 0 takes
+// the launches through slots 1, 2, .., pipeline - 1, 0, ..  That is also the whole rule after mpmpc_set_pipeline (which has
+// settled every slot): the ring goes on from wherever `cur` is.  If that is a slot the new ring no longer holds, the next launch
+// goes to (cur + 1) % pipeline all the same, and the slot left behind is not launched on again until a deeper ring reaches it.
+// At depth 1 `cur` stays: every launch on the one stream.  What the stream of the last launch still has queued that solves read (an upload, closed-loop steps) must be
+// done before ANY slot's next launch starts: an event goes to the streams of all slots in use.  Shared by mpmpc_solve_resident
+// and mpmpc_solve_resident_profile (the profile loop used to change slots without it, so an upload followed by it
+// could be overtaken).  The further slots are allocated on first use: a handle that never launches resident batches (single
+// calls, host-buffer streams, the closed loop) holds one output block, not three.
 static int next_slot(mpmpc_handle h) {
   if (h->pipeline > 1) {
-    if (h->n_alt < h->pipeline - 1) {
-      if (int rc = grow_slots(h, h->pipeline - 1)) return rc;
+    if (h->n_slots < h->pipeline) {
+      if (int rc = grow_slots(h, h->pipeline)) return rc;
     }
     const bool order = h->order_pending;
-    if (order) HIP_TRY(hipEventRecord(h->ev_order, h->stream));
-    swap_slots(h, h->ring);
-    h->ring = (h->ring + 1) % (h->pipeline - 1);
-    if (order) {
-      HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_order, 0));
-      for (int i = 0; i < h->pipeline - 1; ++i) HIP_TRY(hipStreamWaitEvent(h->alt[i].stream, h->ev_order, 0));
-    }
+    if (order) HIP_TRY(hipEventRecord(h->ev_order, h->last().stream));
+    h->cur = (h->cur + 1) % h->pipeline;
+    if (order)
+      for (int i = 0; i < h->pipeline; ++i) HIP_TRY(hipStreamWaitEvent(h->slot[i].stream, h->ev_order, 0));
     h->order_pending = false;
   }
-  h->busy = true;
+  h->last().busy = true;
   return MPMPC_OK;
 }
 
@@ -2310,44 +2293,44 @@ int mpmpc_solve_resident(mpmpc_handle h, int32_t B) {
   if (B < 1 || B > h->uploaded) return fail(MPMPC_E_STATE, "B exceeds the uploaded batch");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if (int rc = next_slot(h)) return rc;
-  return launch_solve(h, B, false, h->resident_y, 0, LAUNCH_PIPELINED);      // one launch: the assembly runs inside K2
+  return launch_solve(h, h->last(), B, false, h->resident_y, 0, LAUNCH_PIPELINED);      // one launch: the assembly runs inside K2
 }
 
 int mpmpc_set_pipeline(mpmpc_handle h, int32_t depth) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (depth < 1 || depth > mpmpc_handle_s::MAX_PIPELINE) return fail(MPMPC_E_ARG, "pipeline depth must be in [1, 8]");
-  h->pipeline = launch_streams(depth);      // as many launch slots as the process has hardware queues for, at most
-  h->ring = 0;
+  h->pipeline = launch_streams(depth);      // as many launch slots as the process has hardware queues for, at most (the ring: next_slot)
   return MPMPC_OK;
 }
 
 int mpmpc_set_outputs(mpmpc_handle h, int32_t want_y) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   h->resident_y = want_y != 0;
   return MPMPC_OK;
 }
 
 int mpmpc_solve_resident_timed(mpmpc_handle h, int32_t B, float* ms_assemble, float* ms_solve) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  MPMPC_SETTLE(h);          // (a timed launch runs alone: nothing of an earlier launch is left on the chip)
+  if (int rc = settle(h)) return rc;          // (a timed launch runs alone: nothing of an earlier launch is left on the chip)
+  Slot& sl = h->last();
   if (B < 1 || B > h->uploaded) return fail(MPMPC_E_STATE, "B exceeds the uploaded batch");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+  HIP_TRY(hipEventRecord(h->ev[0], sl.stream));
   if (int rc = launch_assemble(h, B)) return rc;
-  HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-  if (int rc = launch_solve(h, B, false, h->resident_y)) return rc;
-  HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+  HIP_TRY(hipEventRecord(h->ev[1], sl.stream));
+  if (int rc = launch_solve(h, sl, B, false, h->resident_y)) return rc;
+  HIP_TRY(hipEventRecord(h->ev[2], sl.stream));
   HIP_TRY(hipEventSynchronize(h->ev[2]));
   float a = 0.f, s = 0.f;
   HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
   HIP_TRY(hipEventElapsedTime(&s, h->ev[1], h->ev[2]));
   // a deferred tail this launch turns out to need runs now, and its time counts
-  HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-  if (int rc = observe_tail(h)) return rc;
-  if (h->tail_ran_late) {
-    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+  HIP_TRY(hipEventRecord(h->ev[1], sl.stream));
+  if (int rc = observe_tail(h, sl)) return rc;
+  if (sl.tail_ran_late) {
+    HIP_TRY(hipEventRecord(h->ev[2], sl.stream));
     HIP_TRY(hipEventSynchronize(h->ev[2]));
     float t = 0.f;
     HIP_TRY(hipEventElapsedTime(&t, h->ev[1], h->ev[2]));
@@ -2358,14 +2341,14 @@ int mpmpc_solve_resident_timed(mpmpc_handle h, int32_t B, float* ms_assemble, fl
   return MPMPC_OK;
 }
 
-// n resident launches exactly as mpmpc_solve_resident issues them (double-buffered unless mpmpc_set_pipeline(h, 1)), each
+// n resident launches exactly as mpmpc_solve_resident issues them (pipelined unless mpmpc_set_pipeline(h, 1)), each
 // bracketed by HIP events on the stream it goes to: ms_each[i] = duration of launch i (its kernels, with whatever else is on
-// the chip beside it - the other slot's launch), *ms_span = first start to last end.  For bench.py's roofline line: rocprofv3's
+// the chip beside it - the other slots' launches), *ms_span = first start to last end.  For bench.py's roofline line: rocprofv3's
 // per-kernel durations of the same loop must agree with ms_each.
 int mpmpc_solve_resident_profile(mpmpc_handle h, int32_t B, int32_t n, float* ms_each, float* ms_span) {
   if (!h || !ms_each) return fail(MPMPC_E_ARG, "NULL argument");
   if (n < 1 || n > 4096) return fail(MPMPC_E_ARG, "n must be in [1, 4096]");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (B < 1 || B > h->uploaded) return fail(MPMPC_E_STATE, "B exceeds the uploaded batch");
   HIP_TRY(hipSetDevice(h->cfg.device));
   std::vector<hipEvent_t> ev(2 * (size_t)n, nullptr);
@@ -2374,12 +2357,12 @@ int mpmpc_solve_resident_profile(mpmpc_handle h, int32_t B, int32_t n, float* ms
     if (hipEventCreate(&e) != hipSuccess) { rc = fail(MPMPC_E_HIP, "hipEventCreate"); break; }
   for (int i = 0; i < n && rc == MPMPC_OK; ++i) {
     if ((rc = next_slot(h)) != MPMPC_OK) break;
-    if (hipEventRecord(ev[2 * i], h->stream) != hipSuccess) { rc = fail(MPMPC_E_HIP, "hipEventRecord"); break; }
-    rc = launch_solve(h, B, false, h->resident_y, 0, LAUNCH_PIPELINED);
-    if (rc == MPMPC_OK && hipEventRecord(ev[2 * i + 1], h->stream) != hipSuccess) rc = fail(MPMPC_E_HIP, "hipEventRecord");
+    Slot& sl = h->last();
+    if (hipEventRecord(ev[2 * i], sl.stream) != hipSuccess) { rc = fail(MPMPC_E_HIP, "hipEventRecord"); break; }
+    rc = launch_solve(h, sl, B, false, h->resident_y, 0, LAUNCH_PIPELINED);
+    if (rc == MPMPC_OK && hipEventRecord(ev[2 * i + 1], sl.stream) != hipSuccess) rc = fail(MPMPC_E_HIP, "hipEventRecord");
   }
-  if (rc == MPMPC_OK) rc = settle_other_slot(h);
-  if (rc == MPMPC_OK) rc = observe_tail(h);
+  if (rc == MPMPC_OK) rc = drain(h);
   if (rc == MPMPC_OK) {
     for (int i = 0; i < n; ++i)
       if (hipEventElapsedTime(&ms_each[i], ev[2 * i], ev[2 * i + 1]) != hipSuccess) { rc = fail(MPMPC_E_HIP, "hipEventElapsedTime"); break; }
@@ -2402,19 +2385,20 @@ int mpmpc_solve_resident_profile(mpmpc_handle h, int32_t B, int32_t n, float* ms
 int mpmpc_assemble_resident_timed(mpmpc_handle h, int32_t B, int32_t n, float* ms_each) {
   if (!h || !ms_each) return fail(MPMPC_E_ARG, "NULL argument");
   if (n < 1 || n > 4096) return fail(MPMPC_E_ARG, "n must be in [1, 4096]");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
+  Slot& sl = h->last();
   if (B < 1 || B > h->uploaded) return fail(MPMPC_E_STATE, "B exceeds the uploaded batch");
   HIP_TRY(hipSetDevice(h->cfg.device));
   std::vector<hipEvent_t> ev((size_t)n + 1, nullptr);
   int rc = MPMPC_OK;
   for (auto& e : ev)
     if (hipEventCreate(&e) != hipSuccess) { rc = fail(MPMPC_E_HIP, "hipEventCreate"); break; }
-  if (rc == MPMPC_OK && hipEventRecord(ev[0], h->stream) != hipSuccess) rc = fail(MPMPC_E_HIP, "hipEventRecord");
+  if (rc == MPMPC_OK && hipEventRecord(ev[0], sl.stream) != hipSuccess) rc = fail(MPMPC_E_HIP, "hipEventRecord");
   for (int i = 0; i < n && rc == MPMPC_OK; ++i) {
     rc = launch_assemble(h, B);
-    if (rc == MPMPC_OK && hipEventRecord(ev[i + 1], h->stream) != hipSuccess) rc = fail(MPMPC_E_HIP, "hipEventRecord");
+    if (rc == MPMPC_OK && hipEventRecord(ev[i + 1], sl.stream) != hipSuccess) rc = fail(MPMPC_E_HIP, "hipEventRecord");
   }
-  if (rc == MPMPC_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(MPMPC_E_HIP, "hipStreamSynchronize");
+  if (rc == MPMPC_OK && hipStreamSynchronize(sl.stream) != hipSuccess) rc = fail(MPMPC_E_HIP, "hipStreamSynchronize");
   for (int i = 0; i < n && rc == MPMPC_OK; ++i)
     if (hipEventElapsedTime(&ms_each[i], ev[i], ev[i + 1]) != hipSuccess) rc = fail(MPMPC_E_HIP, "hipEventElapsedTime");
   for (auto& e : ev)
@@ -2492,8 +2476,7 @@ int mpmpc_speed_profile(int32_t device, int32_t B, int32_t n, const double* li, 
 int mpmpc_sync(mpmpc_handle h) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
   if (h->staged_bytes) return mpmpc_staged_end(h);
-  if (int rc = settle_other_slot(h)) return rc;
-  return observe_tail(h);
+  return drain(h);
 }
 
 int mpmpc_download(mpmpc_handle h, int32_t B, double* z, double* u0, int32_t* status, int32_t* iters,
@@ -2502,18 +2485,18 @@ int mpmpc_download(mpmpc_handle h, int32_t B, double* z, double* u0, int32_t* st
   if (h->staged_bytes) {
     if (int rc = mpmpc_staged_end(h)) return rc;
   }
-  if (int rc = settle_other_slot(h)) return rc;
-  if (int rc = observe_tail(h)) return rc;        // (also how the single-call path learns that its launches leave no tail)
+  if (int rc = drain(h)) return rc;               // (also how the single-call path learns that its launches leave no tail)
+  Slot& sl = h->last();
   if (B < 1 || B > h->uploaded) return fail(MPMPC_E_STATE, "B exceeds the uploaded batch");
-  if (y && !h->y_valid)
+  if (y && !sl.y_valid)
     return fail(MPMPC_E_STATE, "the last solve launch did not store the multipliers (mpmpc_set_outputs(h, 0) / closed loop)");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if (h->stage_out && B == h->laid_out) {
     // the whole batch was laid out for this B: one copy of the output block (without y, z when they are not wanted)
     const BlockLayout L = block_layout(h->cfg.N, B);
     char* st = h->stage_out;
-    HIP_TRY(hipMemcpyAsync(st, h->out_block, y ? L.out_end : (z ? L.out_end_z : L.z), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(st, sl.out_block, y ? L.out_end : (z ? L.out_end_z : L.z), hipMemcpyDeviceToHost, sl.stream));
+    HIP_TRY(hipStreamSynchronize(sl.stream));
     if (z) std::memcpy(z, st + L.z, sizeof(double) * h->n * B);
     if (u0) std::memcpy(u0, st + L.u0, sizeof(double) * 2 * B);
     if (status) std::memcpy(status, st + L.status, sizeof(int) * B);
@@ -2529,15 +2512,15 @@ int mpmpc_download(mpmpc_handle h, int32_t B, double* z, double* u0, int32_t* st
     if (!user) return hipSuccess;
     void* to = user;
     if (stage) { to = stage; pulls[np++] = Pull{user, stage, bytes}; stage += (bytes + 7) & ~size_t(7); }
-    return hipMemcpyAsync(to, dev, bytes, hipMemcpyDeviceToHost, h->stream);
+    return hipMemcpyAsync(to, dev, bytes, hipMemcpyDeviceToHost, sl.stream);
   };
-  HIP_TRY(pull(z, h->z, sizeof(double) * h->n * B));
-  HIP_TRY(pull(u0, h->u0, sizeof(double) * 2 * B));
-  HIP_TRY(pull(status, h->status, sizeof(int) * B));
-  HIP_TRY(pull(iters, h->iters, sizeof(int) * 2 * B));
-  HIP_TRY(pull(resid, h->resid, sizeof(double) * 2 * B));
-  HIP_TRY(pull(y, h->y, sizeof(double) * h->m * B));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(pull(z, sl.z, sizeof(double) * h->n * B));
+  HIP_TRY(pull(u0, sl.u0, sizeof(double) * 2 * B));
+  HIP_TRY(pull(status, sl.status, sizeof(int) * B));
+  HIP_TRY(pull(iters, sl.iters, sizeof(int) * 2 * B));
+  HIP_TRY(pull(resid, sl.resid, sizeof(double) * 2 * B));
+  HIP_TRY(pull(y, sl.y, sizeof(double) * h->m * B));
+  HIP_TRY(hipStreamSynchronize(sl.stream));
   for (int i = 0; i < np; ++i) std::memcpy(pulls[i].user, pulls[i].staged, pulls[i].bytes);
   return MPMPC_OK;
 }
@@ -2550,7 +2533,7 @@ int mpmpc_staging(mpmpc_handle h, int32_t B, int32_t** wp_id, double** x0, doubl
   if (!h->stage_in || !h->stage_out) return fail(MPMPC_E_STATE, "this handle has no staging blocks (max_batch above the staging limit)");
   // The blocks are the ones mpmpc_upload / mpmpc_download stage through: an upload still on its way out of the input block
   // must have left it before the caller may write there, and a begun staged call owns both blocks
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
   if (h->in_flight) { HIP_TRY(hipEventSynchronize(h->ev_in)); h->in_flight = false; }
   const BlockLayout L = block_layout(h->cfg.N, B);
   char *si = h->stage_in, *so = h->stage_out;
@@ -2572,12 +2555,12 @@ int mpmpc_staged_end(mpmpc_handle h) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
   if (!h->staged_bytes) return MPMPC_OK;
   const size_t out_bytes = h->staged_bytes;
-  if (int rc = settle_other_slot(h)) return rc;
-  if (int rc = observe_tail(h)) return rc;          // drains the stream; a launch that left a deferred tail has it run now
+  Slot& sl = h->last();
+  if (int rc = drain(h)) return rc;                 // drains the streams; a launch that left a deferred tail has it run now
   h->staged_bytes = 0;                              // (only now: an error above leaves the call begun)
-  if (h->tail_ran_late) {
-    HIP_TRY(hipMemcpyAsync(h->stage_out, h->out_block, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+  if (sl.tail_ran_late) {
+    HIP_TRY(hipMemcpyAsync(h->stage_out, sl.out_block, out_bytes, hipMemcpyDeviceToHost, sl.stream));
+    HIP_TRY(hipStreamSynchronize(sl.stream));
   }
   return MPMPC_OK;
 }
@@ -2594,7 +2577,8 @@ int mpmpc_solve_staged(mpmpc_handle h, int32_t B, int32_t with_rows, int32_t wan
 int mpmpc_staged_begin(mpmpc_handle h, int32_t B, int32_t with_rows, int32_t want_z, int32_t want_y) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
   if (h->staged_bytes) return fail(MPMPC_E_STATE, "mpmpc_staged_begin: the previous one has not been ended");
-  MPMPC_SETTLE(h);
+  if (int rc = settle(h)) return rc;
+  Slot& sl = h->last();
   if (B < 1 || B > h->cfg.max_batch) return fail(MPMPC_E_ARG, "B must be in [1, max_batch]");
   if (!h->stage_in || !h->stage_out) return fail(MPMPC_E_STATE, "this handle has no staging blocks (max_batch above the staging limit)");
   if (h->n_wp == 0) return fail(MPMPC_E_STATE, "no path set (mpmpc_set_path)");
@@ -2610,12 +2594,12 @@ int mpmpc_staged_begin(mpmpc_handle h, int32_t B, int32_t with_rows, int32_t wan
   if (h->in_flight) { HIP_TRY(hipEventSynchronize(h->ev_in)); h->in_flight = false; }
   h->ro_valid = false;
   if (B != h->laid_out) lay_out(h, B);
-  HIP_TRY(hipMemcpyAsync(h->in_block, h->stage_in, with_rows ? L.in_end : L.in_end_cc, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->in_block, h->stage_in, with_rows ? L.in_end : L.in_end_cc, hipMemcpyHostToDevice, sl.stream));
   h->have_rows = with_rows != 0;
   h->uploaded = B;
-  if (int rc = launch_solve(h, B, false, want_y != 0, 0, h->staged_async ? LAUNCH_PIPELINED : LAUNCH_SINGLE)) return rc;
+  if (int rc = launch_solve(h, sl, B, false, want_y != 0, 0, h->staged_async ? LAUNCH_PIPELINED : LAUNCH_SINGLE)) return rc;
   const size_t out_bytes = want_y ? L.out_end : (want_z ? L.out_end_z : L.z);
-  HIP_TRY(hipMemcpyAsync(h->stage_out, h->out_block, out_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->stage_out, sl.out_block, out_bytes, hipMemcpyDeviceToHost, sl.stream));
   h->staged_bytes = out_bytes;
   return MPMPC_OK;
 }
@@ -2627,9 +2611,9 @@ int mpmpc_assemble(mpmpc_handle h, int32_t B, const int32_t* wp_id, const double
   if (qp_out) {
     // device layout is [field][B][ld]; rows of B*ld doubles per field are contiguous
     HIP_TRY(hipMemcpyAsync(qp_out, h->qp, sizeof(double) * MPMPC_NUM_FIELDS * (size_t)B * h->ld,
-                           hipMemcpyDeviceToHost, h->stream));
+                           hipMemcpyDeviceToHost, h->last().stream));
   }
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
   return MPMPC_OK;
 }
 
@@ -2638,7 +2622,7 @@ int mpmpc_solve(mpmpc_handle h, int32_t B, const int32_t* wp_id, const double* x
                 double* resid, double* y) {
   if (int rc = mpmpc_upload(h, B, wp_id, x0, cc_prev, lb, ub)) return rc;
   HIP_TRY(hipSetDevice(h->cfg.device));
-  if (int rc = launch_solve(h, B, false, y != nullptr)) return rc;      // no y asked for: none stored
+  if (int rc = launch_solve(h, h->last(), B, false, y != nullptr)) return rc;      // no y asked for: none stored
   return mpmpc_download(h, B, z, u0, status, iters, resid, y);
 }
 

@@ -1088,6 +1088,81 @@ def test_pipelined_resident_launches_give_the_results_of_launches_done_one_at_a_
     one.close()
 
 
+def test_each_launch_slot_keeps_its_own_tail_state_through_depth_changes(track):
+    """The deferred-tail state belongs to the launch slot (mpmpc_hip.hip, Slot): after launches that leave the slots with
+    different histories - one expects a tail, its neighbour does not, a third owes a tail launch - and with the pipeline depth
+    changed in mid-rotation (3 -> 2 -> 4 -> 1 -> 3: slots leave the ring, new ones are allocated), every download gives, bit for
+    bit and for every instance, what a fresh handle gives for the batch last uploaded.  160 instances: the smallest round size
+    at which pipelined launches pack two instances per wave (from 128 on) and the hard batch leaves a real tail."""
+    N, B = 30, 160
+    feas = scenarios.make(2, track, B=B, N=N)             # every instance certified by the first kernel: no tail
+    hard = scenarios.make(4, track, B=B, N=N)             # 12 infeasible ones: a tail
+    assert feas.weights == hard.weights
+
+    def fresh(sc):
+        g = _handle(track, N, sc.weights, B)
+        try:
+            return g.solve(sc.wp_id, sc.x0, sc.cc_prev, sc.lb, sc.ub, want_y=True)
+        finally:
+            g.close()
+
+    ref_f, ref_h = fresh(feas), fresh(hard)
+    assert (ref_f.status == mpmpc.SOLVED).all() and (ref_h.status == mpmpc.PRIMAL_INFEASIBLE).sum() >= 8
+
+    def same(a, b):
+        for name in ("status", "iters", "z", "u0", "resid", "y"):
+            assert np.array_equal(getattr(a, name), getattr(b, name)), name
+
+    h = _handle(track, N, feas.weights, B)
+    h.set_outputs(True)
+
+    def run(sc, n_launch):
+        h.upload(sc.wp_id, sc.x0, sc.cc_prev, sc.lb, sc.ub)
+        for _ in range(n_launch):
+            h.solve_resident(B)
+
+    # depth 3, slots 1, 2, 0, 1, 2: slots 0 and 1 learn "no tail" on the feasible batch, slot 2 has seen one; the hard batch then
+    # meets slot 1 with its tail launch deferred and slot 2 with it enqueued
+    h.set_pipeline(3)
+    run(feas, 1)
+    run(hard, 1)
+    run(feas, 1)
+    h.sync()
+    run(hard, 2)
+    same(h.download(B, want_y=True), ref_h)
+    # 3 -> 2 in mid-rotation (the last launch sits in a slot the new ring does not hold)
+    h.set_pipeline(2)
+    run(feas, 3)
+    same(h.download(B, want_y=True), ref_f)
+    # 2 -> 4: a slot is allocated after the others have histories; a host-buffer call in the middle of the rotation
+    h.set_pipeline(4)
+    run(hard, 2)
+    same(h.solve(feas.wp_id, feas.x0, feas.cc_prev, feas.lb, feas.ub, want_y=True), ref_f)
+    h.solve_resident(B)                                   # (the batch of the host-buffer call is resident now)
+    same(h.download(B, want_y=True), ref_f)
+    run(hard, 3)
+    same(h.download(B, want_y=True), ref_h)
+    # 4 -> 1: every launch on the slot of the last one
+    h.set_pipeline(1)
+    run(feas, 2)
+    same(h.download(B, want_y=True), ref_f)
+    run(hard, 1)
+    same(h.download(B, want_y=True), ref_h)
+    # 1 -> 3: the slot of the last launch learns "no tail", and a timed launch on it turns out to need its deferred tail
+    h.set_pipeline(3)
+    run(feas, 1)
+    h.sync()
+    h.upload(hard.wp_id, hard.x0, hard.cc_prev, hard.lb, hard.ub)
+    ms = h.solve_resident_timed(B)
+    assert ms[1] > 0
+    same(h.download(B, want_y=True), ref_h)
+    run(feas, 2)
+    same(h.download(B, want_y=True), ref_f)
+    run(hard, 3)
+    same(h.download(B, want_y=True), ref_h)
+    h.close()
+
+
 def test_resident_launch_between_the_halves_of_a_staged_call(track):
     """a resident (or timed) launch issued between mpmpc_staged_begin and mpmpc_staged_end ends the begun call
     first - its deferred tail runs and its results are complete in the staging block - instead of overwriting its state."""
