@@ -192,11 +192,21 @@ void mpmpc_default_settings(mpmpc_settings* s);
 int mpmpc_create(const mpmpc_config* cfg, const mpmpc_settings* settings, mpmpc_handle* out);
 int mpmpc_destroy(mpmpc_handle h);
 int mpmpc_set_settings(mpmpc_handle h, const mpmpc_settings* settings);
-/* Lanes of a 64-lane wavefront given to one QP instance by the solve launches: 0 (default) = chosen from the batch
- * size (one instance per wave up to 1024 instances, then the smallest of 64 / 32 / 16 that holds the N + 1 stages);
- * 64 / 32 / 16 force that packing (parity tests and tuning; every packing returns the same answers).  16 with 17 .. 32
- * stages (16 <= N <= 31) selects the layout with TWO stages per lane - four instances per wavefront - for the batch launches
- * of the reference's own weights (cold starts; every other launch keeps one stage per lane). */
+/* Lanes given to one QP instance by the solve launches of the reference's own weights (the reduced-native kernels; every
+ * packing returns the same answers: parity tests and tuning).  A value the handle's horizon cannot take is MPMPC_E_ARG.
+ *     0    (default) chosen per launch.  N <= 63: one instance per 64-lane wavefront up to 1 024 instances, beyond that the
+ *          smallest of 32 / 16 lanes that holds the N + 1 stages from 1 025 / 2 049 instances on - from 129 / 257 on for
+ *          launches that are one of several in flight (mpmpc_set_pipeline).  N >= 64: two stages per lane (see 64, 128).
+ *    64    N <= 63: one instance per wavefront at any batch size.  64 <= N <= 127: TWO stages per lane, the instance in one
+ *          wavefront - what 0 selects there.
+ *    32    N <= 31: two instances per wavefront at any batch size.
+ *    16    N <= 15: four instances per wavefront at any batch size.  16 <= N <= 31: TWO stages per lane, four instances per
+ *          wavefront, for the batch launches (cold starts; the closed loop ignores it and keeps one stage per lane).
+ *   128    64 <= N <= 127: one stage per lane on a workgroup of two wavefronts instead of the two-stages-per-lane default.
+ *          128 <= N <= 255: two stages per lane on a workgroup of two wavefronts - what 0 selects there.
+ *   256    128 <= N <= 255: one stage per lane on a workgroup of four wavefronts instead.
+ * Configurations the reduction does not apply to (full weights, bounds on e_psi / t, a cost on t) run one instance per
+ * wavefront / workgroup whatever is set here. */
 int mpmpc_set_packing(mpmpc_handle h, int32_t lanes_per_instance);
 /* Which kernel takes the TAIL of a batch launch - the instances the reduced-native kernel could not certify: infeasible,
  * marginally infeasible and very hard ones.  1 (default) = the reduced-native tail kernel first (phase 1 and one more
@@ -389,6 +399,47 @@ int mpmpc_set_pipeline(mpmpc_handle h, int32_t depth);
  * mpmpc_set_pipeline (clamped to 1 .. 8) in a process with hw_queues queues (below 1 counts as 1): min(depth, hw_queues). */
 int32_t mpmpc_hw_queue_budget(const char* text);
 int32_t mpmpc_pipeline_streams(int32_t depth, int32_t hw_queues);
+/* Which solve kernels a launch runs, as the launcher itself decides it - a pure function (no device, no handle, no state;
+ * the launcher calls the same code): the plan of a launch of B instances on a handle with this configuration and these
+ * settings.  knobs[4] = what the policy reads of the handle: lanes per instance (mpmpc_set_packing), tail kernel
+ * (mpmpc_set_tail_kernel: 0 / 1 / 2), launch slots in use (mpmpc_pipeline_streams), warm start (mpmpc_rollout_warm_start:
+ * 0 / 1 / 2).  closed_loop: a step of mpmpc_rollout_step.  kind: 0 a launch that is waited for on its own (mpmpc_solve,
+ * mpmpc_solve_staged, timed launches, rollout steps), 1 one of several in flight (mpmpc_solve_resident, mpmpc_staged_begin).
+ * Returns the number of stages, 1 .. MPMPC_PLAN_MAX_STAGES, in stream order, and writes one row of MPMPC_PLAN_ROW int32 per stage
+ * to rows; MPMPC_E_ARG for arguments no handle can hold (horizon, B < 1, a packing mpmpc_set_packing refuses, ...).  A row:
+ *    0 family       MPMPC_K_*
+ *    1 G            lanes per instance          } template arguments of the instantiation; 0 where the family has none
+ *    2 C            chain split of the factorisation }
+ *    3 var          general kernels: 0 full problem, 1 full weights, 2 reduced polish, 3 free e_psi / t
+ *    4 warm         1: the closed loop's warm-started instantiation
+ *    5 mode         general kernels: 0 the whole solve of every instance, 2 the full run on the instances of a list
+ *    6 grid         workgroups
+ *    7 block        lanes per workgroup
+ *    8 reads        MPMPC_LIST_*: the list whose instances the stage takes (none: every instance of the batch)
+ *    9 fills        MPMPC_LIST_*: the list it appends what it cannot decide to
+ *   10 clear        1: the list it fills is emptied on the stream in front of it
+ *   11 deferrable   1: the launcher may hold the stage back while the launches it has seen left the list it reads empty
+ *   12 turn         1: the launch takes the slot's next flip list and a new sequence number */
+#define MPMPC_PLAN_ROW 13
+#define MPMPC_PLAN_MAX_STAGES 3
+#define MPMPC_K_GENERAL 0          /* mpmpc_solve_kernel<64, C, warm, var>          one instance per wavefront */
+#define MPMPC_K_REDUCED 1          /* mpmpc_reduced_kernel<G, C, warm>              64 / G instances per wavefront */
+#define MPMPC_K_REDUCED_T 2        /* mpmpc_reduced_t_kernel<64, C>                 terminal cost on the time state */
+#define MPMPC_K_REDUCED_TAIL 3     /* mpmpc_reduced_tail_kernel<G, C>               the tail solver; stamps tail_flag + 1 */
+#define MPMPC_K_PAIR 4             /* mpmpc_reduced_pair_kernel<G>                  two stages per lane, G lanes per instance */
+#define MPMPC_K_PAIR_T 5           /* mpmpc_reduced_t_pair_kernel<64> */
+#define MPMPC_K_PAIR_TAIL 6        /* mpmpc_reduced_tail_pair_kernel<64> */
+#define MPMPC_K_BLOCK 7            /* mpmpc_solve_block_kernel<G, var>              one instance per workgroup of G lanes */
+#define MPMPC_K_RBLOCK 8           /* mpmpc_reduced_block_kernel<G> */
+#define MPMPC_K_PAIR_BLOCK 9       /* mpmpc_reduced_pair_block_kernel               two stages per lane, workgroup of 128 */
+#define MPMPC_K_PAIR_BLOCK_TAIL 10 /* mpmpc_reduced_tail_pair_block_kernel */
+#define MPMPC_K_PAIR_BLOCK_T 11    /* mpmpc_reduced_t_pair_block_kernel */
+#define MPMPC_LIST_NONE 0
+#define MPMPC_LIST_THIS 1          /* the list this launch fills */
+#define MPMPC_LIST_NEXT 2          /* the list the slot's next launch fills (N <= 63: emptied by this launch's last kernel) */
+#define MPMPC_LIST_LEFT 3          /* what the tail solver leaves to the general kernel */
+int32_t mpmpc_launch_plan(const mpmpc_config* cfg, const mpmpc_settings* settings, const int32_t* knobs, int32_t B,
+                          int32_t closed_loop, int32_t kind, int32_t* rows);
 int mpmpc_sync(mpmpc_handle h);
 int mpmpc_download(mpmpc_handle h, int32_t B, double* z, double* u0, int32_t* status,
                    int32_t* iters, double* resid, double* y);

@@ -36,6 +36,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #define MPMPC_HD __device__ __forceinline__
@@ -53,6 +54,7 @@ __device__ long long g_phase[4096 * 32];
 #include "mpmpc_reduced.hpp"
 #include "mpmpc_reduced_t.hpp"
 #include "mpmpc_reduced_tail.hpp"
+#include "mpmpc_launch_plan.hpp"
 #include "corridor_core.hpp"
 #include "rollout_core.hpp"
 #include "speed_core.hpp"
@@ -272,7 +274,7 @@ __global__ __launch_bounds__(G) void mpmpc_solve_block_kernel(mpmpc_config cfg, 
 // point from x = 0, active-set rounds, certificate) on a workgroup, for the reference's own weights at horizons above 63.
 // What it cannot certify is listed in `tail` for mpmpc_solve_block_kernel<G, 2>.
 // (40 cold slots like K2r instead of the general solver's 66: 50 KB of LDS per workgroup at G = 128 - three workgroups per CU)
-// (the workgroup kernels empty no list: launch_long_horizon does it with a memset in front of them)
+// (the workgroup kernels empty no list: the launch plan has them emptied on the stream in front of them)
 constexpr int RNB_SLOTS = 40;
 template <int G>
 __global__ __launch_bounds__(G) void mpmpc_reduced_block_kernel(mpmpc_config cfg, SolverParams st, int B, AssembleIn ain,
@@ -308,7 +310,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                                                            unsigned* __restrict__ tail_flag, unsigned seq, int* __restrict__ tail2_reset) {
   using L = LaneGpu<G, C, RN_SLOTS>;
   // (the list of the NEXT launch is emptied here as well: the tail launch, which does it too, may be deferred - see
-  //  launch_solve; and so is the list the reduced-native tail kernel of THIS launch appends to)
+  //  run_stages; and so is the list the reduced-native tail kernel of THIS launch appends to)
   empty_lists(tail_reset, tail2_reset);
   // (the instance stays written out in K2r and K2t, which carry every headline number: a helper around these lines has
   //  moved their instructions in every form tried - docs/HISTORY.md)
@@ -968,7 +970,7 @@ struct mpmpc_handle_s {
   double *ro_cum = nullptr, *ro_s = nullptr, *ro_pose = nullptr, *ro_u = nullptr;
   int *ro_counter = nullptr, *ro_alive = nullptr;
   int *ro_act = nullptr, *ro_shift = nullptr;      // warm start: certified active sets [B x ld], waypoints advanced [B]
-  int ro_warm = 2;      // 0 off, 1 on, 2 where it pays (see launch_solve)
+  int ro_warm = 2;      // 0 off, 1 on, 2 where it pays (see plan_solve)
   double ro_Ts = 0;
   int ro_B = 0;
   bool ro_valid = false;      // the batch blocks still hold the rollout's plans / waypoint ids / states
@@ -1030,15 +1032,22 @@ struct mpmpc_handle_s {
     unsigned* tail_flag = nullptr;      // hipHostMalloc'ed, device-visible
     unsigned seq = 0;                   // sequence number of the last reduced-native launch
     bool tail_expect_empty = false;     // the last observed launch left no tail
-    bool pend = false;                  // the last launch's tail launch was not enqueued
     bool tail_ran_late = false;         // the last observe_tail had to run a deferred tail
     // Second level (reduced_native_tail configurations): the tail goes to the reduced-native tail kernel first, which appends
     // what IT leaves to a third list (tail + 2 (max_batch + 1)) and stamps tail_flag[1]; the general kernel on that list is
     // deferred by the same rule.
-    bool tail2_expect_empty = false, pend2 = false;
-    int pend_B = 0;                     // what a deferred tail launch needs of the launch it belongs to
-    bool pend_y = false;
-    int *pend_cur = nullptr, *pend_next = nullptr;
+    bool tail2_expect_empty = false;
+    // The slot's last solve launch: its plan (mpmpc_launch_plan.hpp), the first stage not yet enqueued, and what the stages
+    // still to come need of the launch they belong to - the batch size, whether y is stored, the solver parameters, the lists
+    // by role (MPMPC_LIST_*).  (The handle's input buffers and path tables are read when a stage is enqueued: every call that
+    // changes them settles first.)
+    SolvePlan plan{};
+    int next_stage = 0;
+    int launch_B = 0;
+    bool want_y = false;
+    SolverParams prm{};
+    int* list[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool deferred() const { return next_stage < plan.n; }      // stages of the last launch were held back
   };
   static constexpr int MAX_PIPELINE = 8;
   Slot slot[MAX_PIPELINE];
@@ -1071,7 +1080,7 @@ static int observe_tail(mpmpc_handle h, Slot& s);
 static int settle_other_slots(mpmpc_handle h) {
   for (int i = 0; i < h->n_slots; ++i) {
     Slot& s = h->slot[i];
-    if (i == h->cur || (!s.busy && !s.pend && !s.pend2)) continue;
+    if (i == h->cur || (!s.busy && !s.deferred())) continue;
     if (int rc = observe_tail(h, s)) return rc;
   }
   return MPMPC_OK;
@@ -1088,7 +1097,7 @@ static int settle(mpmpc_handle h) {
     if (int rc = mpmpc_staged_end(h)) return rc;
   }
   if (int rc = settle_other_slots(h)) return rc;
-  if (h->last().pend || h->last().pend2) {
+  if (h->last().deferred()) {
     if (int rc = observe_tail(h, h->last())) return rc;
   }
   h->order_pending = true;
@@ -1125,9 +1134,7 @@ static int check_settings(const mpmpc_settings* s) {
 static int grow_slots(mpmpc_handle h, int want);
 static int upload_through_bounce(mpmpc_handle h, void* dst, const void* src, size_t bytes);
 static int launch_assemble(mpmpc_handle h, int B);
-// how a solve launch was asked for (decides the packing of the reduced-native kernels, see launch_solve)
-enum LaunchKind { LAUNCH_SINGLE = 0, LAUNCH_PIPELINED = 1 };
-static int launch_solve(mpmpc_handle h, Slot& sl, int B, bool closed_loop = false, bool want_y = true, int tail_only = 0, LaunchKind kind = LAUNCH_SINGLE);
+static int launch_solve(mpmpc_handle h, Slot& sl, int B, bool closed_loop = false, bool want_y = true, LaunchKind kind = LAUNCH_SINGLE);
 
 extern "C" {
 
@@ -1239,6 +1246,20 @@ int32_t mpmpc_pipeline_streams(int32_t depth, int32_t hw_queues) {
   if (depth > mpmpc_handle_s::MAX_PIPELINE) depth = mpmpc_handle_s::MAX_PIPELINE;
   if (hw_queues < 1) hw_queues = 1;
   return depth < hw_queues ? depth : hw_queues;
+}
+// The plan of a solve launch (mpmpc_launch_plan.hpp: the launcher runs what plan_solve says), written out row by row.
+int32_t mpmpc_launch_plan(const mpmpc_config* cfg, const mpmpc_settings* settings, const int32_t* knobs, int32_t B, int32_t closed_loop,
+                          int32_t kind, int32_t* rows) {
+  if (!cfg || !settings || !knobs || !rows) return fail(MPMPC_E_ARG, "cfg, settings, knobs and rows must not be NULL");
+  if (cfg->N < 3 || cfg->N > MPMPC_MAX_HORIZON) return fail(MPMPC_E_ARG, "horizon N must satisfy 3 <= N <= 255");
+  if (B < 1 || kind < 0 || kind > 1) return fail(MPMPC_E_ARG, "need B >= 1 and kind 0 or 1");
+  if (!packing_valid(cfg->N, knobs[0]) || knobs[1] < 0 || knobs[1] > 2 || knobs[2] < 1 || knobs[2] > mpmpc_handle_s::MAX_PIPELINE ||
+      knobs[3] < 0 || knobs[3] > 2)
+    return fail(MPMPC_E_ARG, "knobs: a packing of this horizon, tail kernel 0 .. 2, 1 .. 8 launch slots, warm start 0 .. 2");
+  const SolvePlan p = plan_solve(*cfg, *settings, LaunchKnobs{knobs[0], knobs[1] != 0, knobs[1] == 2, knobs[2], knobs[3]}, B,
+                                 closed_loop != 0, kind ? LAUNCH_PIPELINED : LAUNCH_SINGLE);
+  std::memcpy(rows, p.stage, (size_t)p.n * sizeof(PlanStage));
+  return p.n;
 }
 static int launch_streams(int depth) {
   static const int32_t budget = mpmpc_hw_queue_budget(std::getenv("GPU_MAX_HW_QUEUES"));
@@ -1392,15 +1413,10 @@ int mpmpc_create(const mpmpc_config* cfg, const mpmpc_settings* settings, mpmpc_
 int mpmpc_set_packing(mpmpc_handle h, int32_t lanes_per_instance) {
   if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
   if (int rc = settle(h)) return rc;
-  const int g = lanes_per_instance;
-  if (g != 0 && g != 16 && g != 32 && g != 64 && !(g == 128 && h->cfg.N + 1 > 64) && !(g == 256 && h->cfg.N + 1 > 128))
-    return fail(MPMPC_E_ARG, "lanes_per_instance must be 0 (auto), 16, 32 or 64 (128 / 256: the one-stage workgroup kernels of horizons 64 .. 127 / 128 .. 255)");
-  // (16 lanes for 17 .. 32 stages: TWO stages per lane, four instances per wavefront - the reduced-native batch kernel only)
-  // (64 / 128 at 65 .. 128 stages: two stages per lane in one wavefront - the default there - or the workgroup kernel)
-  const bool two = (g == 16 && h->cfg.N + 1 > 16 && h->cfg.N + 1 <= 32) || ((g == 64 || g == 128) && h->cfg.N + 1 > 64 && h->cfg.N + 1 <= 128) ||
-                   ((g == 128 || g == 256) && h->cfg.N + 1 > 128);
-  if (g != 0 && h->cfg.N + 1 > g && !two) return fail(MPMPC_E_ARG, "lanes_per_instance must hold the N + 1 stages of an instance, or half of them at 16 (horizons above 63 take a workgroup: only 0)");
-  h->force_lanes = g;
+  if (!packing_valid(h->cfg.N, lanes_per_instance))
+    return fail(MPMPC_E_ARG, "lanes_per_instance must be 0 (auto) or 16, 32, 64 and hold the N + 1 stages of an instance - half of them at 16 / 64, two stages "
+                             "per lane - or 128 / 256: the workgroup kernels of horizons 64 .. 255");
+  h->force_lanes = lanes_per_instance;
   return MPMPC_OK;
 }
 
@@ -1935,20 +1951,16 @@ static int launch_assemble(mpmpc_handle h, int B) {
 }  // extern "C"  (the dispatch functions below are templates)
 
 // ---------------------------------------------------------------------------------------------------- launch dispatch
-// What a solve launch hands to its kernels, and ONE small function per kernel family that turns it into the launch of an
-// instantiation.  launch_solve below decides WHICH kernels run (policy: packing, warm start, tail deferral); the tables after
-// the families map that decision - (lanes per instance, chain split, variant, warm) - to the instantiation (VERDICT r5 item 8:
-// the six nested launch macros this replaces multiplied with every new layout).
+// What a solve launch hands to its kernels.  plan_solve (mpmpc_launch_plan.hpp) decides WHICH kernels run - policy: packing,
+// warm start, tail solver, what may be deferred; `enqueue` below maps a stage of that plan to the launch of an instantiation,
+// and run_stages enqueues the stages of the slot's plan in order, holding back what may be and need not run.
 struct SolveLaunch {
   mpmpc_handle h;
-  Slot* slot;      // the launch slot it goes to: stream, outputs, tail flag
+  Slot* slot;      // the launch slot it goes to: stream, outputs, tail flag, tail lists by role
   SolverParams prm;
   AssembleIn ain;
   int B;
   double* y_out;
-  int *tail_cur, *tail_next, *tail2;      // the list this launch fills / the next launch's (emptied here) / what the tail kernel leaves
-  int* warm_act;
-  const int* warm_shift;
 };
 // THE launcher: every solve kernel starts with the same arguments - cfg, prm, B, [ld,] ain, z, u0, status, iters, resid, y - which
 // come from the launch; `own` are the kernel's trailing ones.  (Whether the kernel takes ld is read off its parameter list.)
@@ -1969,37 +1981,27 @@ static void go(const SolveLaunch& a, int grid, int block, size_t lds, T... own) 
 }
 // The workgroup kernels need more dynamic LDS than the default limit: the attribute is set once per function AND DEVICE (one
 // process may drive several - sharded.py, bench.py --single-process - and the attribute belongs to the function on the device
-// that is current; two threads may both set it once: the call is idempotent)
+// that is current; two threads may both set it once: the call is idempotent).  A device ordinal beyond the table sets it
+// every time.
 constexpr int MAX_DEVICES = 64;
-static int device_slot(mpmpc_handle h) { return h->cfg.device >= 0 && h->cfg.device < MAX_DEVICES ? h->cfg.device : 0; }
 template <auto KERNEL>
 static int raise_lds_limit(mpmpc_handle h, size_t bytes) {
   static std::atomic<bool> attr_set[MAX_DEVICES];
-  if (!attr_set[device_slot(h)]) {
+  const int d = h->cfg.device;
+  const bool known = d >= 0 && d < MAX_DEVICES;
+  if (!known || !attr_set[d]) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    attr_set[device_slot(h)] = true;
+    if (known) attr_set[d] = true;
   }
   return MPMPC_OK;
 }
-// ... one instance per WORKGROUP of `block` lanes, every instance of the batch
+// ... one instance per WORKGROUP
 template <auto KERNEL, class... T>
-static int go_workgroups(const SolveLaunch& a, int block, size_t lds, T... own) {
+static int go_workgroups(const SolveLaunch& a, const PlanStage& s, size_t lds, T... own) {
   if (int rc = raise_lds_limit<KERNEL>(a.h, lds)) return rc;
-  go<KERNEL>(a, a.B, block, lds, own...);
+  go<KERNEL>(a, s.grid, s.block, lds, own...);
   return MPMPC_OK;
 }
-
-// general kernel, one instance per wave: the whole solve (mode 0) or the tail of a reduced-native launch (mode 2, list `tail`)
-template <int C, bool WARM, int VAR>
-static void go_general(const SolveLaunch& a, int mode, int blocks, int* tail) {
-  go<mpmpc_solve_kernel<64, C, WARM, VAR>>(a, blocks, 64, 0, mode, tail, WARM ? a.warm_act : nullptr, WARM ? a.warm_shift : nullptr, a.tail_next);
-}
-using GeneralFn = void (*)(const SolveLaunch&, int, int, int*);
-// [C == 32][warm][VAR: 0 full problem, 1 full weights, 2 reduced polish, 3 free e_psi / t]
-#define MPMPC_GENERAL_ROW(C, W) {go_general<C, W, 0>, go_general<C, W, 1>, go_general<C, W, 2>, go_general<C, W, 3>}
-static const GeneralFn kGeneral[2][2][4] = {{MPMPC_GENERAL_ROW(16, false), MPMPC_GENERAL_ROW(16, true)},
-                                            {MPMPC_GENERAL_ROW(32, false), MPMPC_GENERAL_ROW(32, true)}};
-#undef MPMPC_GENERAL_ROW
 // (knob of the occupancy experiment, profiles/r3/occupancy.txt: MPMPC_RN_OCC=1 pads every block of the one-stage reduced-native
 //  kernels with 20 KB of unused dynamic LDS - 40 KB per wave, four waves per CU, ONE per SIMD - so that the same code object can
 //  be timed at one and at two waves per SIMD)
@@ -2007,250 +2009,155 @@ static int rn_pad() {
   static const int pad = (std::getenv("MPMPC_RN_OCC") && std::atoi(std::getenv("MPMPC_RN_OCC")) == 1) ? 20 * 1024 : 0;
   return pad;
 }
-// K2r: the reduced-native batch kernel, 1 / 2 / 4 instances per wave
-template <int G, int C, bool WARM>
-static void go_reduced(const SolveLaunch& a, int blocks) {
-  go<mpmpc_reduced_kernel<G, C, WARM>>(a, blocks, 64, rn_pad(), a.tail_cur, a.warm_act, a.warm_shift, a.tail_next, a.slot->tail_flag, a.slot->seq, a.tail2);
+// A run-time value as a template argument: f(std::integral_constant<int, v>) for the one of V... that equals v (false: none does)
+template <int... V, class F>
+static bool pick(int v, F&& f) {
+  return ((v == V && f(std::integral_constant<int, V>{})) || ...);
 }
-using ReducedFn = void (*)(const SolveLaunch&, int);
-// [layout: <64,16>, <64,32>, <32,16>, <16,16>][warm]
-static const ReducedFn kReduced[4][2] = {{go_reduced<64, 16, false>, go_reduced<64, 16, true>}, {go_reduced<64, 32, false>, go_reduced<64, 32, true>},
-                                         {go_reduced<32, 16, false>, go_reduced<32, 16, true>}, {go_reduced<16, 16, false>, go_reduced<16, 16, true>}};
-static int reduced_layout(int G, int C) { return G == 64 ? (C == 16 ? 0 : 1) : (G == 32 ? 2 : 3); }
-// K2t: its twin for a terminal cost on the time state (one instance per wave)
-template <int C>
-static void go_reduced_t(const SolveLaunch& a, int blocks) {
-  go<mpmpc_reduced_t_kernel<64, C>>(a, blocks, 64, rn_pad(), a.tail_cur, a.tail_next, a.slot->tail_flag, a.slot->seq);
-}
-// K2p: the reduced-native tail kernel on the list `tail_cur`; what it leaves goes to tail2
-template <int G, int C>
-static void go_reduced_tail(const SolveLaunch& a, int blocks) {
-  go<mpmpc_reduced_tail_kernel<G, C>>(a, blocks, 64, rn_pad(), a.tail_cur, a.tail_next, a.tail2, a.slot->tail_flag + 1, a.slot->seq);
-}
-// K2r2 / K2t2 / K2p2: two stages per lane (lane_pair.hpp) - GB lanes per instance
-template <int GB>
-static void go_pair(const SolveLaunch& a, int blocks) {
-  go<mpmpc_reduced_pair_kernel<GB>>(a, blocks, 64, 0, a.tail_cur, a.tail_next, a.slot->tail_flag, a.slot->seq, a.tail2);
-}
-template <int GB>
-static void go_pair_t(const SolveLaunch& a) { go<mpmpc_reduced_t_pair_kernel<GB>>(a, a.B, 64, 0, a.tail_cur); }
-template <int GB>
-static void go_pair_tail(const SolveLaunch& a) { go<mpmpc_reduced_tail_pair_kernel<GB>>(a, a.B, 64, 0, a.tail_cur, a.tail_next); }
-// K2b / K2rb and the pair kernels on a workgroup: one instance per WORKGROUP of G = 128 / 256 lanes
-template <int G, int VAR>
-static int go_block(const SolveLaunch& a, const int* tail) {
-  return go_workgroups<mpmpc_solve_block_kernel<G, VAR>>(a, G, LaneBlock<G>::lds_bytes, tail);
-}
-using BlockFn = int (*)(const SolveLaunch&, const int*);
-static const BlockFn kBlock[2][3] = {{go_block<128, 0>, go_block<128, 1>, go_block<128, 2>}, {go_block<256, 0>, go_block<256, 1>, go_block<256, 2>}};
-template <int G>
-static int go_rblock(const SolveLaunch& a) {
-  return go_workgroups<mpmpc_reduced_block_kernel<G>>(a, G, LaneBlock<G, RNB_SLOTS>::lds_bytes, a.tail_cur);
-}
-static int go_pair_block(const SolveLaunch& a) {
-  return go_workgroups<mpmpc_reduced_pair_block_kernel>(a, 128, LanePairBlock::L1::lds_bytes, a.tail_cur);
-}
-static int go_pair_block_tail(const SolveLaunch& a) {
-  return go_workgroups<mpmpc_reduced_tail_pair_block_kernel>(a, 128, LanePairBlockFull::L1::lds_bytes, a.tail_cur, a.tail_next);
-}
-static int go_pair_block_t(const SolveLaunch& a) {
-  return go_workgroups<mpmpc_reduced_t_pair_block_kernel>(a, 128, LanePairBlockFull::L1::lds_bytes, a.tail_cur);
-}
-
-// Horizons above 63.  65 .. 128 stages of the reference's own weights (or of a terminal cost on the time state): TWO stages per
-// lane, the whole instance in ONE wavefront (K2r2<64> / K2t2<64>), its tail to K2p2<64>, what that leaves to the general solver on
-// a workgroup; mpmpc_set_packing(h, 128) keeps round 5's workgroup kernels.  Everything else - longer horizons, full weights,
-// bounded e_psi / t - one instance per workgroup of 2 / 4 wavefronts (K2rb in front where the reduction applies).  No packing, no
-// deferred tail, cold starts in the closed loop too.
-static int launch_long_horizon(mpmpc_handle h, Slot& sl, SolveLaunch& a, int tail_only) {
-  if (tail_only) return MPMPC_OK;
-  const int N = h->cfg.N;
-  sl.pend = sl.pend2 = false;
-  const bool fullqn = full_weights(h->cfg);
-  const int var = fullqn ? 1 : (reducible(h->cfg, h->st) ? 2 : 0);
-  const bool one_wave = N + 1 <= 128 && h->force_lanes != 128;
-  int* list1 = sl.tail;
-  int* list2 = sl.tail + ((size_t)h->cfg.max_batch + 1);
-  int* list3 = list2 + ((size_t)h->cfg.max_batch + 1);
-  const int* tail_blk = nullptr;          // the list the general workgroup kernel works on (null: every instance, the whole solve)
-  a.tail_cur = list1;
-  if (!fullqn && reduced_native(h->cfg, h->st)) {
-    HIP_TRY(hipMemsetAsync(list1, 0, sizeof(int), sl.stream));
-    tail_blk = list1;
-    if (one_wave) {
-      // (the kernel empties "the lists of the next launch" - here the two lists behind the one it fills; the tail kernels below
-      //  always run, so the host-side flag it stamps is not consulted)
-      a.tail_next = list2; a.tail2 = list3;
-      go_pair<64>(a, a.B);
-      if (h->lean_tail && reduced_native_tail(h->cfg, h->st)) {
-        a.tail_next = list2;          // K2p2 reads list 1, fills list 2
-        go_pair_tail<64>(a);
-        tail_blk = list2;
-      }
-    } else if (N + 1 > 128 && h->force_lanes != 256) {
-      // 129 .. 256 stages: two stages per lane on a workgroup of two wavefronts (K2rb2; mpmpc_set_packing(h, 256): K2rb<256>), its
-      // tail to the tail solver on the same layout (the list it fills is emptied first: no kernel of this sequence does it)
-      if (int rc = go_pair_block(a)) return rc;
-      if (h->lean_tail && reduced_native_tail(h->cfg, h->st)) {
-        HIP_TRY(hipMemsetAsync(list2, 0, sizeof(int), sl.stream));
-        a.tail_next = list2;
-        if (int rc = go_pair_block_tail(a)) return rc;
-        tail_blk = list2;
-      }
-    } else if (int rc = (N + 1 <= 128 ? go_rblock<128>(a) : go_rblock<256>(a))) return rc;
-  } else if (!fullqn && reduced_native_tt(h->cfg, h->st) && (one_wave || (N + 1 > 128 && h->force_lanes != 256))) {
-    // a terminal cost on the time state: K2t's solver with two stages per lane - one wavefront per instance up to 128 stages, a
-    // workgroup of two above - and the general workgroup kernel on what it lists
-    HIP_TRY(hipMemsetAsync(list1, 0, sizeof(int), sl.stream));
-    if (one_wave) go_pair_t<64>(a);
-    else if (int rc = go_pair_block_t(a)) return rc;
-    tail_blk = list1;
+// One stage of a plan -> the launch of its instantiation.  The instantiations named here are the solve kernels of the code
+// object; a stage that names none of them is an error, never another kernel.
+static int enqueue(const SolveLaunch& a, const PlanStage& s) {
+  mpmpc_handle h = a.h;
+  const Slot& sl = *a.slot;
+  int *const reads = sl.list[s.reads], *const fills = sl.list[s.fills];      // (none: null)
+  int *const next = sl.list[MPMPC_LIST_NEXT], *const left = sl.list[MPMPC_LIST_LEFT];
+  int* const act = s.warm ? h->ro_act : nullptr;
+  const int* const shift = s.warm ? h->ro_shift : nullptr;
+  int rc = MPMPC_OK;
+  bool found = false;
+  switch (s.family) {
+    case MPMPC_K_GENERAL:      // one instance per wave: the whole solve (mode 0) or the tail of a reduced-native launch (mode 2); empties `next`
+      found = pick<16, 32>(s.C, [&](auto C) { return pick<0, 1>(s.warm, [&](auto W) { return pick<0, 1, 2, 3>(s.var, [&](auto V) {
+        go<mpmpc_solve_kernel<64, C(), W() != 0, V()>>(a, s.grid, s.block, 0, s.mode, reads, act, shift, next);
+        return true; }); }); });
+      break;
+    case MPMPC_K_REDUCED:      // K2r: the reduced-native batch kernel, 1 / 2 / 4 instances per wave
+      found = pick<64, 32, 16>(s.G, [&](auto G) { return pick<16, 32>(s.C, [&](auto C) { return pick<0, 1>(s.warm, [&](auto W) {
+        if constexpr (G() == 64 || C() == 16) {      // (chains split at 32 need the 64 lanes)
+          go<mpmpc_reduced_kernel<G(), C(), W() != 0>>(a, s.grid, s.block, rn_pad(), fills, act, shift, next, sl.tail_flag, sl.seq, left);
+          return true;
+        } else return false; }); }); });
+      break;
+    case MPMPC_K_REDUCED_T:      // K2t: its twin for a terminal cost on the time state (one instance per wave)
+      found = s.G == 64 && pick<16, 32>(s.C, [&](auto C) {
+        go<mpmpc_reduced_t_kernel<64, C()>>(a, s.grid, s.block, rn_pad(), fills, next, sl.tail_flag, sl.seq);
+        return true; });
+      break;
+    case MPMPC_K_REDUCED_TAIL:      // K2p: the reduced-native tail solver on the list it reads; what it leaves goes to the list it fills
+      found = pick<64, 32>(s.G, [&](auto G) { return pick<16, 32>(s.C, [&](auto C) {
+        if constexpr (G() == 64 || C() == 16) {
+          go<mpmpc_reduced_tail_kernel<G(), C()>>(a, s.grid, s.block, rn_pad(), reads, next, fills, sl.tail_flag + 1, sl.seq);
+          return true;
+        } else return false; }); });
+      break;
+    case MPMPC_K_PAIR:      // K2r2 / K2t2 / K2p2: two stages per lane (lane_pair.hpp)
+      found = pick<16, 64>(s.G, [&](auto G) {
+        go<mpmpc_reduced_pair_kernel<G()>>(a, s.grid, s.block, 0, fills, next, sl.tail_flag, sl.seq, left);
+        return true; });
+      break;
+    case MPMPC_K_PAIR_T:
+      if ((found = s.G == 64)) go<mpmpc_reduced_t_pair_kernel<64>>(a, s.grid, s.block, 0, fills);
+      break;
+    case MPMPC_K_PAIR_TAIL:
+      if ((found = s.G == 64)) go<mpmpc_reduced_tail_pair_kernel<64>>(a, s.grid, s.block, 0, reads, fills);
+      break;
+    case MPMPC_K_BLOCK:      // K2b / K2rb and the pair kernels on a workgroup: one instance per WORKGROUP of 128 / 256 lanes
+      found = pick<128, 256>(s.G, [&](auto G) { return pick<0, 1, 2>(s.var, [&](auto V) {
+        rc = go_workgroups<mpmpc_solve_block_kernel<G(), V()>>(a, s, LaneBlock<G()>::lds_bytes, (const int*)reads);
+        return true; }); });
+      break;
+    case MPMPC_K_RBLOCK:
+      found = pick<128, 256>(s.G, [&](auto G) {
+        rc = go_workgroups<mpmpc_reduced_block_kernel<G()>>(a, s, LaneBlock<G(), RNB_SLOTS>::lds_bytes, fills);
+        return true; });
+      break;
+    case MPMPC_K_PAIR_BLOCK:
+      if ((found = s.G == 128)) rc = go_workgroups<mpmpc_reduced_pair_block_kernel>(a, s, LanePairBlock::L1::lds_bytes, fills);
+      break;
+    case MPMPC_K_PAIR_BLOCK_TAIL:
+      if ((found = s.G == 128)) rc = go_workgroups<mpmpc_reduced_tail_pair_block_kernel>(a, s, LanePairBlockFull::L1::lds_bytes, reads, fills);
+      break;
+    case MPMPC_K_PAIR_BLOCK_T:
+      if ((found = s.G == 128)) rc = go_workgroups<mpmpc_reduced_t_pair_block_kernel>(a, s, LanePairBlockFull::L1::lds_bytes, fills);
+      break;
   }
-  if (int rc = kBlock[N + 1 <= 128 ? 0 : 1][var](a, tail_blk)) return rc;
-  HIP_TRY(hipGetLastError());
-  return MPMPC_OK;
+  if (!found) return fail(MPMPC_E_STATE, "no solve kernel for a stage of the launch plan");
+  return rc;
 }
 
-// A solve launch on slot `sl`.  tail_only: 1 = the deferred tail launches of its last reduced-native launch (observe_tail), nothing else; 2 = of those,
-// only the general kernel on what the reduced-native tail kernel left
-static int launch_solve(mpmpc_handle h, Slot& sl, int B, bool closed_loop, bool want_y, int tail_only, LaunchKind kind) {
-  const int N = h->cfg.N;
-  sl.y_valid = want_y;
+// Enqueue the stages of the slot's plan from next_stage on.  A deferrable stage stops the run while the launches the host has
+// SEEN left the list it reads empty (Slot: deferred tail) - `late`: not the stage the run starts at, which observe_tail has just
+// found to be needed.  What is held back stays in the slot: next_stage.
+static int run_stages(mpmpc_handle h, Slot& sl, bool late) {
   SolveLaunch a{};
   a.h = h;
   a.slot = &sl;
-  a.B = B;
-  a.prm = make_params(h->st);
-  a.y_out = want_y ? sl.y : nullptr;        // nobody wants the multipliers: the kernel skips their stores
+  a.B = sl.launch_B;
+  a.prm = sl.prm;
+  a.y_out = sl.want_y ? sl.y : nullptr;        // nobody wants the multipliers: the kernel skips their stores
   a.ain.tab = PathTables{h->kappa, h->v_ref, h->ds_next, h->n_wp, h->ub_tab, h->lb_tab, h->n_cols};
   a.ain.wp_id = h->wp_id; a.ain.x0 = h->x0; a.ain.cc = h->cc;
   a.ain.lb = h->have_rows ? h->lb : nullptr; a.ain.ub = h->have_rows ? h->ub : nullptr;
-  if (N + 1 > 64) return launch_long_horizon(h, sl, a, tail_only);
-  // Full weights (Q, R or QN with off-diagonal entries), bounds on e_psi / t or a cost on t rule the reduction out:
-  // such configurations run the general kernels, one instance per wave.
-  const bool fullqn = full_weights(h->cfg);
-  const bool red = reducible(h->cfg, h->st);      // the polish may work on the (e_y, e_psi, kappa) problem
-  const bool freex = !fullqn && !red && free_states(h->cfg);
-  const int var = fullqn ? 1 : (red ? 2 : (freex ? 3 : 0));
-  // The reduced-native kernels (mpmpc_reduced.hpp) take the batch path of every configuration they apply to - cold and
-  // warm-started - and only they pack several instances into a wave; the general kernel then sees their tail.
-  const bool rnt = reduced_native_tt(h->cfg, h->st);      // ... or their twin for a terminal cost on the time state
-  const bool rn = rnt || reduced_native(h->cfg, h->st);
-  // lanes per instance: one instance per wave while there are no more instances than SIMDs (1024); beyond that the
-  // smallest power of two holding N + 1 stages, so that a wave carries 2 or 4 instances and a SIMD two such waves
-  int G = 64;
-  bool two = false;
-  if (rn && !rnt) {      // (the terminal-time kernels run one instance per wave)
-    // A launch that is one of several in flight - a pipelined resident launch (mpmpc_solve_resident with mpmpc_set_pipeline > 1:
-    // the default) or the begun half of a split host-buffer call (mpmpc_staged_begin: the caller keeps several handles busy) -
-    // is after throughput, and a packed wave does two or four instances for about the instructions of one: such launches pack
-    // from 128 instances on - the launches in flight fill the chip, not the waves of one launch (B = 1 024, four launches in
-    // flight: 36.5 M solves/s with one instance per wave, measured 41.4 M with two launches of the packed kernel, DESIGN.md
-    // section 4).  A launch that is waited for on its own - mpmpc_solve, mpmpc_solve_staged, the timed launch, a handle held at
-    // one launch in flight - and the closed loop (one launch per step, each waiting for the one before) keep one instance per
-    // wave up to the chip's 1 024 SIMDs: the latency of a single launch is 43 us against 52 (the decision used to
-    // follow the handle's pipeline depth alone, so single calls paid the packed kernel's latency).  The choice depends on the
-    // entry point, the handle's settings and the batch size only: a given call gives the same bits every time - and every
-    // packing returns the same bits anyway (tests).
-    const bool throughput = kind == LAUNCH_PIPELINED && h->pipeline > 1 && !closed_loop;
-    if (N + 1 <= 32 && B > (throughput ? 128 : 1024)) G = 32;
-    if (N + 1 <= 16 && B > (throughput ? 256 : 2048)) G = 16;
-    if (h->force_lanes && N + 1 <= h->force_lanes) G = h->force_lanes;      // mpmpc_set_packing
-    // TWO stages per lane (K2r2<16>): 17 .. 32 stages in 16 lanes, four instances per wavefront; cold starts only.  Measured
-    // slower than <32,16> at two waves per SIMD: never the automatic choice.
-    if (h->force_lanes == 16 && N + 1 > 16 && N + 1 <= 32 && !closed_loop) { G = 32; two = true; }
+  const int first = sl.next_stage, end = sl.plan.n;
+  for (int i = first; i < end; ++i) {
+    const PlanStage& s = sl.plan.stage[i];
+    const bool forced = late && i == first;
+    if (s.deferrable && !forced && (s.reads == MPMPC_LIST_THIS ? sl.tail_expect_empty : sl.tail2_expect_empty)) break;
+    sl.next_stage = end;      // (an error below leaves nothing held back)
+    if (s.clear) HIP_TRY(hipMemsetAsync(sl.list[s.fills], 0, sizeof(int), sl.stream));
+    if (int rc = enqueue(a, s)) return rc;
+    sl.next_stage = i + 1;
   }
-  // closed loop: the previous step's active sets as a first guess.  A launch with one instance per wave ends with
-  // its slowest car, and with more than a handful of cars one of them always misses its guess (hit rate 91-93 %
-  // per car and step: the miss pays for the attempt AND the normal path, 1024 cars -7 %), so "auto" warm-starts the
-  // packed launches (x1.5 at 8192 cars) and the very small fleets (x1.7 at 8 cars) only.
-  const bool warm = closed_loop && !rnt && (h->ro_warm == 1 || (h->ro_warm == 2 && (G < 64 || B <= 16)));
-  a.warm_act = warm ? h->ro_act : nullptr;
-  a.warm_shift = warm ? h->ro_shift : nullptr;
-  const int per = two ? 4 : 64 / G;
-  const int blocks = (B + per - 1) / per;
-  const int C = lane_split(G, N);        // where the two elimination chains of the factorisation meet
-  const int C64 = lane_split(64, N);     // ... of the one-instance-per-wave kernels that take a tail
-  // tail lists ([0] = count, [1..] = instance ids), two of them used in turn: the tail launch of this step empties the
-  // list of the next one, so that no memset has to sit between the launches of consecutive steps
-  a.tail_cur = sl.tail + (size_t)sl.tail_flip * (h->cfg.max_batch + 1);
-  a.tail_next = sl.tail + (size_t)(1 - sl.tail_flip) * (h->cfg.max_batch + 1);
-  a.tail2 = sl.tail + 2 * ((size_t)h->cfg.max_batch + 1);      // what the reduced-native tail kernel leaves to the general one
-  if (tail_only) { a.tail_cur = sl.pend_cur; a.tail_next = sl.pend_next; }
-  else if (rn) { sl.tail_flip = 1 - sl.tail_flip; sl.seq += 1; }
-  if (!rn) {
-    // the general kernel, one instance per wave, the whole solve
-    kGeneral[C == 32][warm][var](a, 0, blocks, a.tail_cur);
-    HIP_TRY(hipGetLastError());
-    return MPMPC_OK;
-  }
-  // The tail of a batch launch goes to the reduced-native tail kernel first (K2p: two waves per SIMD instead of one).  The
-  // closed loop keeps the general kernel for the whole tail: its step would pay for a third launch every time.
-  const bool lean = !rnt && !closed_loop && h->lean_tail && reduced_native_tail(h->cfg, h->st);
-  if (!tail_only) {
-    if (rnt) (C == 16 ? go_reduced_t<16> : go_reduced_t<32>)(a, blocks);
-    else if (two) go_pair<16>(a, blocks);
-    else kReduced[reduced_layout(G, C)][warm](a, blocks);
-  }
-  // The tail is short (infeasible / very hard instances).  One block per instance of the batch: blocks beyond the
-  // list's length return at once (an all-empty launch takes 4.8 us at 1 024 blocks, 15 us at 65 536: rocprofv3 kernel
-  // trace - which is why it is not enqueued when no tail is expected, below; a grid-stride loop over the list around the solver costs
-  // the general kernels 70 registers and puts 148-544 B of scratch into kernels that have none: measured on the code
-  // object, not kept).  Its instances carry no guess for the next closed-loop step (act stays 0 from the first launch).
-  // Deferred (see the handle): no tail launch is enqueued while the launches the host has seen leave none; the closed
-  // loop consumes its results on the device and always launches it.
-  sl.pend = !tail_only && !closed_loop && sl.tail_expect_empty;
-  sl.pend2 = false;
-  if (sl.pend) {
-    sl.pend_B = B; sl.pend_y = want_y; sl.pend_cur = a.tail_cur; sl.pend_next = a.tail_next;
-  } else if (lean) {
-    if (tail_only != 2) {
-      // (the list's order differs from run to run - atomic appends - and with it the two instances that share a wave of the
-      //  packed form: the solver's arithmetic does not depend on the partner, Solver::active_set)
-      if (C64 == 32) go_reduced_tail<64, 32>(a, B);          // horizons 32 .. 63: one lane per stage, one instance per wave
-      else if (!h->lean_tail_single) go_reduced_tail<32, 16>(a, (B + 1) / 2);
-      else go_reduced_tail<64, 16>(a, B);
-    }
-    // ... and the general kernel on what that left: deferred like the tail itself while the launches seen leave nothing
-    sl.pend2 = tail_only != 2 && sl.tail2_expect_empty;
-    if (sl.pend2) {
-      sl.pend_B = B; sl.pend_y = want_y; sl.pend_cur = a.tail_cur; sl.pend_next = a.tail_next;
-    } else kGeneral[C64 == 32][0][var](a, 2, B, a.tail2);
-  } else kGeneral[C64 == 32][0][var](a, 2, B, a.tail_cur);
   HIP_TRY(hipGetLastError());
   return MPMPC_OK;
+}
+
+// A solve launch on slot `sl`: plan it, bind the slot's lists to their roles, run the stages.
+static int launch_solve(mpmpc_handle h, Slot& sl, int B, bool closed_loop, bool want_y, LaunchKind kind) {
+  sl.y_valid = sl.want_y = want_y;
+  sl.launch_B = B;
+  sl.prm = make_params(h->st);
+  sl.plan = plan_solve(h->cfg, h->st, LaunchKnobs{h->force_lanes, h->lean_tail, h->lean_tail_single, h->pipeline, h->ro_warm}, B, closed_loop, kind);
+  sl.next_stage = 0;
+  // tail lists ([0] = count, [1..] = instance ids), two of them used in turn: the tail launch of this step empties the
+  // list of the next one, so that no memset has to sit between the launches of consecutive steps; the third is what the
+  // reduced-native tail kernel leaves to the general one.  (Horizons above 63 never turn: the same three lists every launch.)
+  const size_t stride = (size_t)h->cfg.max_batch + 1;
+  sl.list[MPMPC_LIST_NONE] = nullptr;
+  sl.list[MPMPC_LIST_THIS] = sl.tail + (size_t)sl.tail_flip * stride;
+  sl.list[MPMPC_LIST_NEXT] = sl.tail + (size_t)(1 - sl.tail_flip) * stride;
+  sl.list[MPMPC_LIST_LEFT] = sl.tail + 2 * stride;
+  if (sl.plan.stage[0].turn) { sl.tail_flip = 1 - sl.tail_flip; sl.seq += 1; }
+  return run_stages(h, sl, false);
 }
 
 extern "C" {
 
-// Drain the slot's stream, see whether its last reduced-native launch left a tail, run it if its launch was deferred.
+// Drain the slot's stream, see whether its last reduced-native launch left a tail, run the stages that were held back if it did.
+// Two levels: a late tail solver is followed by the general kernel unless tail2_expect_empty says to hold that back too, and a
+// general kernel held back on the tail solver's leftovers runs after the second stamp has been read.
 static int observe_tail(mpmpc_handle h, Slot& sl) {
   HIP_TRY(hipSetDevice(h->cfg.device));
   HIP_TRY(hipStreamSynchronize(sl.stream));
   sl.busy = false;
   h->order_pending = false;
   if (sl.seq == 0) return MPMPC_OK;
-  const bool left = *static_cast<volatile unsigned*>(sl.tail_flag) == sl.seq;
   sl.tail_ran_late = false;
-  if (sl.pend) {
-    sl.pend = false;
-    if (left) {
-      sl.tail_ran_late = true;
-      if (int rc = launch_solve(h, sl, sl.pend_B, false, sl.pend_y, 1)) return rc;
-      HIP_TRY(hipStreamSynchronize(sl.stream));
-    }
-  }
+  // stages held back in front of a stage that reads `list`: dropped if the launch left that list empty, else run now
+  auto resume = [&](int list, bool left) -> int {
+    if (!sl.deferred() || sl.plan.stage[sl.next_stage].reads != list) return MPMPC_OK;
+    if (!left) { sl.next_stage = sl.plan.n; return MPMPC_OK; }
+    sl.tail_ran_late = true;
+    if (int rc = run_stages(h, sl, true)) return rc;
+    HIP_TRY(hipStreamSynchronize(sl.stream));
+    return MPMPC_OK;
+  };
+  const bool left = *static_cast<volatile unsigned*>(sl.tail_flag) == sl.seq;
+  if (int rc = resume(MPMPC_LIST_THIS, left)) return rc;
   sl.tail_expect_empty = !left;
   // (second level: read after a tail that ran late has run)
   const bool left2 = static_cast<volatile unsigned*>(sl.tail_flag)[1] == sl.seq;
-  if (sl.pend2) {
-    sl.pend2 = false;
-    if (left2) {
-      sl.tail_ran_late = true;
-      if (int rc = launch_solve(h, sl, sl.pend_B, false, sl.pend_y, 2)) return rc;
-      HIP_TRY(hipStreamSynchronize(sl.stream));
-    }
-  }
+  if (int rc = resume(MPMPC_LIST_LEFT, left2)) return rc;
   sl.tail2_expect_empty = !left2;
   return MPMPC_OK;
 }
@@ -2293,7 +2200,7 @@ int mpmpc_solve_resident(mpmpc_handle h, int32_t B) {
   if (B < 1 || B > h->uploaded) return fail(MPMPC_E_STATE, "B exceeds the uploaded batch");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if (int rc = next_slot(h)) return rc;
-  return launch_solve(h, h->last(), B, false, h->resident_y, 0, LAUNCH_PIPELINED);      // one launch: the assembly runs inside K2
+  return launch_solve(h, h->last(), B, false, h->resident_y, LAUNCH_PIPELINED);      // one launch: the assembly runs inside K2
 }
 
 int mpmpc_set_pipeline(mpmpc_handle h, int32_t depth) {
@@ -2359,7 +2266,7 @@ int mpmpc_solve_resident_profile(mpmpc_handle h, int32_t B, int32_t n, float* ms
     if ((rc = next_slot(h)) != MPMPC_OK) break;
     Slot& sl = h->last();
     if (hipEventRecord(ev[2 * i], sl.stream) != hipSuccess) { rc = fail(MPMPC_E_HIP, "hipEventRecord"); break; }
-    rc = launch_solve(h, sl, B, false, h->resident_y, 0, LAUNCH_PIPELINED);
+    rc = launch_solve(h, sl, B, false, h->resident_y, LAUNCH_PIPELINED);
     if (rc == MPMPC_OK && hipEventRecord(ev[2 * i + 1], sl.stream) != hipSuccess) rc = fail(MPMPC_E_HIP, "hipEventRecord");
   }
   if (rc == MPMPC_OK) rc = drain(h);
@@ -2597,7 +2504,7 @@ int mpmpc_staged_begin(mpmpc_handle h, int32_t B, int32_t with_rows, int32_t wan
   HIP_TRY(hipMemcpyAsync(h->in_block, h->stage_in, with_rows ? L.in_end : L.in_end_cc, hipMemcpyHostToDevice, sl.stream));
   h->have_rows = with_rows != 0;
   h->uploaded = B;
-  if (int rc = launch_solve(h, sl, B, false, want_y != 0, 0, h->staged_async ? LAUNCH_PIPELINED : LAUNCH_SINGLE)) return rc;
+  if (int rc = launch_solve(h, sl, B, false, want_y != 0, h->staged_async ? LAUNCH_PIPELINED : LAUNCH_SINGLE)) return rc;
   const size_t out_bytes = want_y ? L.out_end : (want_z ? L.out_end_z : L.z);
   HIP_TRY(hipMemcpyAsync(h->stage_out, sl.out_block, out_bytes, hipMemcpyDeviceToHost, sl.stream));
   h->staged_bytes = out_bytes;

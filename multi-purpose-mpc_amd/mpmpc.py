@@ -153,6 +153,8 @@ def load_library(path: str | None = None):
     lib.mpmpc_hw_queue_budget.restype = C.c_int32
     lib.mpmpc_pipeline_streams.argtypes = [C.c_int32, C.c_int32]
     lib.mpmpc_pipeline_streams.restype = C.c_int32
+    lib.mpmpc_launch_plan.argtypes = [C.POINTER(Config), C.POINTER(Settings), _ip, C.c_int32, C.c_int32, C.c_int32, _ip]
+    lib.mpmpc_launch_plan.restype = C.c_int32
     lib.mpmpc_set_path.argtypes = [h, C.c_int32, _dp, _dp, _dp]
     lib.mpmpc_set_corridor.argtypes = [h, C.c_int32, C.c_int32, _dp, _dp]
     lib.mpmpc_set_map.argtypes = [h, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double]
@@ -195,13 +197,35 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_create", "mpmpc_destroy", "mpmpc_set_settings", "mpmpc_set_packing", "mpmpc_set_tail_kernel", "mpmpc_set_path", "mpmpc_set_corridor",
            "mpmpc_set_map", "mpmpc_set_path_geometry", "mpmpc_build_corridor", "mpmpc_rollout_init",
            "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor",
-           "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams",
+           "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams", "mpmpc_launch_plan",
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_staging",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
 class MpmpcError(RuntimeError):
     pass
+
+
+# mpmpc_launch_plan: the fields of a row, kernel families and list roles (include/mpmpc.h)
+PLAN_FIELDS = ("family", "G", "C", "var", "warm", "mode", "grid", "block", "reads", "fills", "clear", "deferrable", "turn")
+PLAN_MAX_STAGES = 3
+(K_GENERAL, K_REDUCED, K_REDUCED_T, K_REDUCED_TAIL, K_PAIR, K_PAIR_T, K_PAIR_TAIL, K_BLOCK, K_RBLOCK, K_PAIR_BLOCK,
+ K_PAIR_BLOCK_TAIL, K_PAIR_BLOCK_T) = range(12)
+LIST_NONE, LIST_THIS, LIST_NEXT, LIST_LEFT = range(4)
+
+
+def launch_plan(config: Config, settings: Settings, B: int, closed_loop=False, kind=0, packing=0, tail_kernel=1, pipeline=3,
+                warm_start=2):
+    """The stages of a solve launch of B instances as the launcher decides them (no device needed): a list of dicts keyed by
+    PLAN_FIELDS.  packing / tail_kernel / pipeline / warm_start: what mpmpc_set_packing, mpmpc_set_tail_kernel,
+    mpmpc_pipeline_streams and mpmpc_rollout_warm_start leave in a handle; kind 1: one of several launches in flight."""
+    lib = load_library()
+    knobs = np.array([packing, tail_kernel, pipeline, warm_start], np.int32)
+    rows = np.zeros((PLAN_MAX_STAGES, len(PLAN_FIELDS)), np.int32)
+    n = lib.mpmpc_launch_plan(C.byref(config), C.byref(settings), _i(knobs), int(B), int(bool(closed_loop)), int(kind), _i(rows))
+    if n < 0:
+        raise MpmpcError("mpmpc error %d: %s" % (n, lib.mpmpc_last_error().decode()))
+    return [dict(zip(PLAN_FIELDS, (int(v) for v in rows[i]))) for i in range(n)]
 
 
 class Solution:
