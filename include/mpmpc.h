@@ -297,6 +297,40 @@ int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offset
 /* ub / lb [B x N]: the rows the last rollout step used for each car (per-car obstacles only, else MPMPC_E_STATE), as the
  * reference's update_path_constraints returns them; NaN rows for cars whose row was blocked (-3) or overflowed (-4). */
 int mpmpc_rollout_corridor(mpmpc_handle h, int32_t B, double* ub, double* lb);
+/* Movers: per-car obstacles that move while the cars drive, advanced on the device (K0m) - a slower vehicle ahead,
+ * something crossing the track - so that mpmpc_rollout_step(h, B, n_steps) keeps its point with n_steps > 1.  A mover is a
+ * disc of constant radius (map cells, as above) whose centre is a closed-form function of the rollout step index k
+ * (0-based, counted from mpmpc_rollout_init: what mpmpc_rollout_recorded returns as n_steps), j = k - step0:
+ *   kind 0, params (x0, y0, dx, dy): a straight line, world start point and displacement per step [m]:
+ *           (x, y) = (x0 + j dx, y0 + j dy)
+ *   kind 1, params (s0, e, ds, 0): along the reference path, start arc length, lateral offset (positive = left, the sign
+ *           of e_y) and arc length per step: s = s0 + j ds, wrapped into [0, L) on a circular path (L = the last entry of
+ *           mpmpc_rollout_init's cum_lengths); the centre is the point at arc length s of the waypoint polyline, moved by
+ *           e along the normal of the segment's first waypoint.
+ * The disc of step k is (w2m(x, y), r).  A mover is ABSENT on a step - the disc (0, 0, 0), which occupies no cell - when
+ * its square leaves the grid, its centre is not finite or beyond 2^30 cells, or (kind 1, open path) s < 0 or s >= L.
+ * The exact operation order is stated in csrc/obstacle_motion_core.hpp; the positions of any step, recorded or not, can
+ * be recomputed from its index.
+ *   mpmpc_rollout_set_movers   mover q of car b is entry offsets[b] + q of kind[], radius_cells[] and params[][4]
+ *                           (offsets [B+1] as for the discs).  offsets == NULL: no movers.  Static discs and movers are
+ *                           two independent settings; K0c reads, per car, the static discs followed by the movers' discs
+ *                           of the step.  Together at most 64 per car (else MPMPC_E_ARG), and both settings must be for
+ *                           the same B (else MPMPC_E_STATE) - mpmpc_rollout_set_obstacles checks the same against the
+ *                           movers in force.  Also MPMPC_E_ARG: an unknown kind, a negative radius, a parameter that is
+ *                           not finite, offsets that decrease.  A refused call leaves the previous setting as it was.
+ *                           Needs mpmpc_build_corridor like the discs, and is void after a change of map, path or
+ *                           geometry in the same way.  May be called before mpmpc_rollout_init or between
+ *                           mpmpc_rollout_step calls: it applies from the next step on and keeps the rollout's state.
+ *                           step0 may be negative: a run resumed from a saved state of step k0 (mpmpc_rollout_init
+ *                           restarts k at 0) continues its movers with step0 - k0.
+ *   mpmpc_rollout_obstacles the disc lists the LAST rollout step used: offsets_out [B+1], discs_out [offsets_out[B]][3]
+ *                           (at most 64 B entries; either pointer may be NULL), per car the static discs and then the
+ *                           movers, absent ones as (0, 0, 0).  MPMPC_E_STATE if that step built no per-car rows (as
+ *                           mpmpc_rollout_corridor), or if either setting was changed since.
+ * A rollout without movers launches exactly what it launched before. */
+int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* kind,
+                             const int32_t* radius_cells, const double* params, int64_t step0);
+int mpmpc_rollout_obstacles(mpmpc_handle h, int32_t B, int32_t* discs_out, int32_t* offsets_out);
 
 /* Recorder: while the cars drive, the rollout appends one record per car and recorded step to a device-resident trace
  * (what src/simulation.py:117-157 logs per step on the host: x_log / y_log / v_log and MPC.current_prediction), and

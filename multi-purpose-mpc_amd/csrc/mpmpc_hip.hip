@@ -57,6 +57,7 @@ __device__ long long g_phase[4096 * 32];
 #include "mpmpc_launch_plan.hpp"
 #include "corridor_core.hpp"
 #include "rollout_core.hpp"
+#include "obstacle_motion_core.hpp"
 #include "speed_core.hpp"
 
 using namespace mpmpc;
@@ -862,6 +863,24 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
   }
 }
 
+// K0m: the movers of one rollout step (mpmpc_rollout_set_movers), launched between K3a and K0c when there are any.  One
+// thread per mover of the whole fleet; its parameters are structure-of-arrays ([n] each: a wavefront loads consecutive
+// words), its disc of step k (mov_disc: closed form in k; kind 1 searches ro_cum, ~9 probes that stay in L2) goes into
+// its slot of its car's disc list - dst[j], laid out on the host when either setting changes - where K0c reads it
+// behind the car's static discs.
+__global__ __launch_bounds__(256) void mpmpc_obstacle_move_kernel(int n, long long k, long long step0, MapView map,
+                                                                  MoverPath path, const int* __restrict__ kind,
+                                                                  const int* __restrict__ radius,
+                                                                  const double* __restrict__ prm,
+                                                                  const int* __restrict__ dst, int* __restrict__ discs) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  int d[3];
+  mov_disc(map, path, kind[j], radius[j], prm[j], prm[(long)n + j], prm[2L * n + j], prm[3L * n + j], k, step0, d);
+  int* o = discs + 3L * dst[j];
+  o[0] = d[0]; o[1] = d[1]; o[2] = d[2];
+}
+
 // K3a: where is each car on the path, and what is its path-relative state (one thread per car)
 // (alive: 0 = lap finished, s past the path's length; -2 = an open path's end reached, the reference's exit(1) in
 //  get_waypoint - wp_id and x0 are still written, they are the state the reference computed before it exited)
@@ -966,6 +985,17 @@ struct mpmpc_handle_s {
   int obst_B = 0;               // > 0: the rollout's cars carry their own discs (mpmpc_rollout_set_obstacles)
   unsigned obst_gen = 0;        // base_gen the discs were validated against
   bool car_rows = false;        // the last rollout step built per-car rows
+  // The two per-car settings, kept on the host: static discs (mpmpc_rollout_set_obstacles; st_B > 0: set; obst_gen) and
+  // movers (mpmpc_rollout_set_movers; mv_B > 0: set; mv_gen).  Whichever setter is called lays out ONE CSR list per car
+  // on the device (obst_off / obst_discs, what K0c reads: the static discs, then a slot per mover that K0m fills every
+  // step) - sync_disc_lists; obst_B is the B of whichever is set.
+  std::vector<int32_t> st_off, st_discs, mv_off, comb_off;
+  int st_B = 0, mv_B = 0;
+  int mv_n = 0, mv_cap = 0;     // movers of the fleet; movers the device block holds
+  unsigned mv_gen = 0;          // base_gen the movers were set against
+  long long mv_step0 = 0;
+  char* mv_block = nullptr;     // [4][mv_n] doubles (parameters), then [mv_n] ints each: kind, radius, slot
+  bool discs_live = false;      // obst_discs hold the lists the last rollout step used (mpmpc_rollout_obstacles)
   // closed-loop rollout state
   double *ro_cum = nullptr, *ro_s = nullptr, *ro_pose = nullptr, *ro_u = nullptr;
   int *ro_counter = nullptr, *ro_alive = nullptr;
@@ -1306,7 +1336,7 @@ int mpmpc_destroy(mpmpc_handle h) {
                   h->qp,    h->map, h->gx,  h->gy,
                   h->gpsi,  h->bub,   h->blb,     h->segs,   h->nseg,   h->bad,    h->ro_cum, h->ro_s, h->ro_pose, h->gtrig,
                   h->ro_u,  h->ro_counter, h->ro_alive, h->ro_act, h->ro_shift, h->line_cells, h->line_box,
-                  h->obst_off, h->obst_discs, h->ro_flag, h->rec_buf, h->rec_ain};
+                  h->obst_off, h->obst_discs, h->ro_flag, h->rec_buf, h->rec_ain, h->mv_block};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& s : h->slot) free_slot(s);
@@ -1627,6 +1657,7 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   h->ro_valid = true;
   h->have_rows = false;       // the corridor comes from the table
   h->car_rows = false;
+  h->discs_live = false;
   h->uploaded = B;
   h->ro_steps = 0;            // the recorder keeps its configuration and starts over
   h->rec_count = 0;
@@ -1734,7 +1765,7 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   const bool per_car = h->obst_B > 0;
   if (per_car) {
     if (h->obst_B != B) return fail(MPMPC_E_STATE, "the per-car obstacles were set for another number of cars");
-    if (h->obst_gen != h->base_gen || h->built_gen != h->base_gen)
+    if ((h->st_B > 0 && h->obst_gen != h->base_gen) || (h->mv_B > 0 && h->mv_gen != h->base_gen) || h->built_gen != h->base_gen)
       return fail(MPMPC_E_STATE, "map, path or geometry changed since mpmpc_rollout_set_obstacles / mpmpc_build_corridor");
   }
   const bool recording = h->rec_cap > 0;
@@ -1752,6 +1783,10 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   MapView mv{h->map, h->map_h, h->map_w, h->map_ox, h->map_oy, h->map_res};
   PathGeom pg{h->gx, h->gy, h->gpsi, h->ds_next, h->n_wp, h->cfg.circular, h->gtrig};
   h->have_rows = per_car;     // K1 / K2 read the per-instance rows K0c writes (else: the table)
+  const int movers = per_car && h->mv_B > 0 ? h->mv_n : 0;
+  const MoverPath mp{h->ro_cum, h->gx, h->gy, h->gtrig, h->n_wp, COR_TRIG, h->cfg.circular ? 1 : 0};
+  const double* mv_p = (const double*)h->mv_block;
+  const int* mv_i = (const int*)(mv_p + (size_t)MOV_PARAMS * movers);
   for (int t = 0; t < n_steps; ++t) {
     char* rec = recording && h->ro_steps % h->rec_stride == 0 ? h->rec_buf + (size_t)h->rec_lay.bytes * (size_t)h->rec_count : nullptr;
     if (rec)
@@ -1760,6 +1795,9 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     hipLaunchKernelGGL(mpmpc_localise_kernel, dim3(blocks), dim3(256), 0, sl.stream, B, h->n_wp, h->cfg.N,
                        h->cfg.circular ? 1 : 0, h->ro_cum, h->gx, h->gy,
                        h->gpsi, h->ro_s, h->ro_pose, h->ro_alive, h->wp_id, h->x0, h->ro_shift);
+    if (movers > 0)
+      hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->ro_steps,
+                         h->mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obst_discs);
     if (per_car)
       hipLaunchKernelGGL(mpmpc_car_corridor_kernel, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->built_min_width,
                          h->built_sm, h->segs, h->nseg, h->segs + (size_t)4 * COR_MAXSEG * h->n_wp, h->line_cells,
@@ -1779,18 +1817,19 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     ++h->ro_steps;
   }
   HIP_TRY(hipGetLastError());
-  if (n_steps > 0) h->car_rows = per_car;
+  if (n_steps > 0) h->car_rows = h->discs_live = per_car;
   return MPMPC_OK;
 }
 
-int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* discs) {
-  if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
-  if (int rc = settle(h)) return rc;
-  if (!offsets) { h->obst_B = 0; return MPMPC_OK; }      // back to the shared table
-  const char* why = "";
-  const bool built = h->built_gen == h->base_gen && h->built_gen != 0 && h->n_cols > 0 && h->line_cells;
-  if (int rc = cor_check_obstacles(B, h->cfg.max_batch, offsets, discs, built, h->map_w, h->map_h, &why))
-    return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+// Lays out the device's per-car disc lists from the two host-side settings (st_* / mv_*): combined offsets, the static
+// discs in place, every mover slot as the absent disc (K0m fills the slots in front of every K0c), and the movers' slot
+// indices.  new_mv: the movers' block as mpmpc_rollout_set_movers assembled it ([4][n] doubles, [2][n] ints kind / radius,
+// the slots follow on the device), or NULL when the movers did not change (only their slot indices are written anew).
+static int sync_disc_lists(mpmpc_handle h, std::vector<char>* new_mv) {
+  const int B = h->st_B > 0 ? h->st_B : h->mv_B;
+  h->obst_B = B;
+  h->discs_live = false;
+  if (B == 0) return MPMPC_OK;
   HIP_TRY(hipSetDevice(h->cfg.device));
   Slot& sl = h->last();
   const size_t mb = (size_t)h->cfg.max_batch;
@@ -1799,12 +1838,99 @@ int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offset
     HIP_TRY(hipMalloc((void**)&h->obst_discs, sizeof(int) * 3 * COR_MAX_DISCS * mb));
   }
   if (!h->ro_flag) HIP_TRY(hipMalloc((void**)&h->ro_flag, sizeof(int) * mb));
-  HIP_TRY(hipMemcpyAsync(h->obst_off, offsets, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, sl.stream));
-  if (offsets[B] > 0)
-    HIP_TRY(hipMemcpyAsync(h->obst_discs, discs, sizeof(int) * 3 * (size_t)offsets[B], hipMemcpyHostToDevice, sl.stream));
-  HIP_TRY(hipStreamSynchronize(sl.stream));
-  h->obst_B = B;
+  const int n = h->mv_B > 0 ? h->mv_n : 0;
+  h->comb_off.assign((size_t)B + 1, 0);
+  std::vector<int32_t> dst((size_t)n);
+  mov_combine(B, h->st_B > 0 ? h->st_off.data() : nullptr, h->mv_B > 0 ? h->mv_off.data() : nullptr, h->comb_off.data(),
+              dst.data());
+  const size_t total = (size_t)h->comb_off[B];
+  std::vector<int32_t> discs(3 * total, 0);
+  if (h->st_B > 0)
+    for (int b = 0; b < B; ++b)
+      std::memcpy(discs.data() + 3 * (size_t)h->comb_off[b], h->st_discs.data() + 3 * (size_t)h->st_off[b],
+                  sizeof(int32_t) * 3 * (size_t)(h->st_off[b + 1] - h->st_off[b]));
+  HIP_TRY(hipMemcpyAsync(h->obst_off, h->comb_off.data(), sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, sl.stream));
+  if (total > 0) HIP_TRY(hipMemcpyAsync(h->obst_discs, discs.data(), sizeof(int) * 3 * total, hipMemcpyHostToDevice, sl.stream));
+  if (n > 0) {
+    const size_t head = (sizeof(double) * MOV_PARAMS + 2 * sizeof(int)) * (size_t)n;      // parameters, kind, radius
+    if (new_mv) {
+      if (n > h->mv_cap) {
+        if (h->mv_block) { HIP_TRY(hipFree(h->mv_block)); h->mv_block = nullptr; h->mv_cap = 0; }
+        HIP_TRY(hipMalloc((void**)&h->mv_block, (sizeof(double) * MOV_PARAMS + 3 * sizeof(int)) * (size_t)n));
+        h->mv_cap = n;
+      }
+      HIP_TRY(hipMemcpyAsync(h->mv_block, new_mv->data(), head, hipMemcpyHostToDevice, sl.stream));
+    }
+    HIP_TRY(hipMemcpyAsync(h->mv_block + head, dst.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, sl.stream));
+  }
+  HIP_TRY(hipStreamSynchronize(sl.stream));      // the host vectors leave scope
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* discs) {
+  if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
+  if (int rc = settle(h)) return rc;
+  if (!offsets) {      // no static discs: back to the shared table, unless movers are set
+    h->st_B = 0;
+    return sync_disc_lists(h, nullptr);
+  }
+  const char* why = "";
+  const bool built = h->built_gen == h->base_gen && h->built_gen != 0 && h->n_cols > 0 && h->line_cells;
+  if (int rc = cor_check_obstacles(B, h->cfg.max_batch, offsets, discs, built, h->map_w, h->map_h, &why))
+    return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  if (int rc = mov_check_combined(B, offsets, h->mv_B, h->mv_off.data(), &why))
+    return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  h->st_off.assign(offsets, offsets + (size_t)B + 1);
+  h->st_discs.assign(discs, discs + 3 * (size_t)offsets[B]);
+  h->st_B = B;
   h->obst_gen = h->base_gen;
+  return sync_disc_lists(h, nullptr);
+}
+
+int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* kind,
+                             const int32_t* radius_cells, const double* params, int64_t step0) {
+  if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
+  if (int rc = settle(h)) return rc;
+  if (!offsets) {      // no movers
+    h->mv_B = 0;
+    h->mv_n = 0;
+    return sync_disc_lists(h, nullptr);
+  }
+  const char* why = "";
+  const bool built = h->built_gen == h->base_gen && h->built_gen != 0 && h->n_cols > 0 && h->line_cells;
+  if (int rc = mov_check_movers(B, h->cfg.max_batch, offsets, kind, radius_cells, params, built, h->st_B, h->st_off.data(), &why))
+    return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  const size_t n = (size_t)offsets[B];
+  std::vector<char> blk((sizeof(double) * MOV_PARAMS + 2 * sizeof(int)) * n);
+  double* p = (double*)blk.data();
+  int32_t* ki = (int32_t*)(p + MOV_PARAMS * n);
+  for (size_t j = 0; j < n; ++j) {
+    for (int t = 0; t < MOV_PARAMS; ++t) p[(size_t)t * n + j] = params[MOV_PARAMS * j + t];
+    ki[j] = kind[j];
+    ki[n + j] = radius_cells[j];
+  }
+  h->mv_off.assign(offsets, offsets + (size_t)B + 1);
+  h->mv_B = B;
+  h->mv_n = (int)n;
+  h->mv_step0 = step0;
+  h->mv_gen = h->base_gen;
+  return sync_disc_lists(h, &blk);
+}
+
+int mpmpc_rollout_obstacles(mpmpc_handle h, int32_t B, int32_t* discs_out, int32_t* offsets_out) {
+  if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
+  if (int rc = settle(h)) return rc;
+  Slot& sl = h->last();
+  if (B < 1 || B > h->ro_B || !h->ro_valid) return fail(MPMPC_E_STATE, "call mpmpc_rollout_init for at least B cars first");
+  if (!h->car_rows || !h->discs_live || B != h->obst_B)
+    return fail(MPMPC_E_STATE, "the last rollout step did not build per-car rows for B cars, or the obstacles / movers were set anew "
+                               "since (mpmpc_rollout_set_obstacles / mpmpc_rollout_set_movers)");
+  if (offsets_out) std::memcpy(offsets_out, h->comb_off.data(), sizeof(int32_t) * ((size_t)B + 1));
+  if (discs_out && h->comb_off[B] > 0) {
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(hipMemcpyAsync(discs_out, h->obst_discs, sizeof(int) * 3 * (size_t)h->comb_off[B], hipMemcpyDeviceToHost, sl.stream));
+    HIP_TRY(hipStreamSynchronize(sl.stream));
+  }
   return MPMPC_OK;
 }
 

@@ -167,6 +167,8 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_state.argtypes = [h, C.c_int32, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip]
     lib.mpmpc_rollout_set_obstacles.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_corridor.argtypes = [h, C.c_int32, _dp, _dp]
+    lib.mpmpc_rollout_set_movers.argtypes = [h, C.c_int32, _ip, _ip, _ip, _dp, C.c_int64]
+    lib.mpmpc_rollout_obstacles.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_recorded.argtypes = [h, _ip, _ip]
     lib.mpmpc_rollout_trace.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
@@ -197,6 +199,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_create", "mpmpc_destroy", "mpmpc_set_settings", "mpmpc_set_packing", "mpmpc_set_tail_kernel", "mpmpc_set_path", "mpmpc_set_corridor",
            "mpmpc_set_map", "mpmpc_set_path_geometry", "mpmpc_build_corridor", "mpmpc_rollout_init",
            "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor",
+           "mpmpc_rollout_set_movers", "mpmpc_rollout_obstacles",
            "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams", "mpmpc_launch_plan",
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_staging",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
@@ -388,6 +391,35 @@ class Handle:
         ub, lb = np.zeros((B, N)), np.zeros((B, N))
         self._check(self.lib.mpmpc_rollout_corridor(self._h, B, _d(ub), _d(lb)))
         return ub, lb
+
+    def rollout_set_movers(self, movers, step0=0):
+        """Per-car moving obstacles, advanced on the device every step (K0m): movers = one [k_b, 6] array per car of rows
+        (kind, radius in cells, p0, p1, p2, p3) - movers.Mover.row() - or None for no movers.  kind 0: (x0, y0, dx, dy), a
+        straight line; kind 1: (s0, e_y, ds, 0), along the reference path; displacements are per rollout step, counted from
+        step0 (which may be negative: resuming a run).  Combines with rollout_set_obstacles (together at most 64 per car,
+        the same number of cars); needs build_corridor on the current map; may be called between rollout_step calls."""
+        if movers is None:
+            self._check(self.lib.mpmpc_rollout_set_movers(self._h, 0, None, None, None, None, 0))
+            return
+        lists = [np.asarray(m, dtype=np.float64).reshape(-1, 6) for m in movers]
+        off = np.zeros(len(lists) + 1, np.int32)
+        off[1:] = np.cumsum([a.shape[0] for a in lists])
+        flat = np.concatenate(lists) if off[-1] else np.zeros((0, 6))
+        if not np.array_equal(flat[:, :2], np.floor(flat[:, :2])) or np.any(np.abs(flat[:, :2]) > 2 ** 30):
+            raise ValueError("mover kind and radius (cells) must be integers")
+        kind, rad = (np.ascontiguousarray(flat[:, c], dtype=np.int32) for c in (0, 1))
+        prm = np.ascontiguousarray(flat[:, 2:], dtype=np.float64)
+        self._check(self.lib.mpmpc_rollout_set_movers(self._h, len(lists), _i(off), _i(kind), _i(rad), _d(prm), int(step0)))
+
+    def rollout_obstacles(self):
+        """-> one int32 [k_b, 3] array of (cx, cy, r) per car: the discs the last rollout step used - the car's static discs,
+        then its movers where that step had them; an absent mover (off the map, past the end of an open path) is (0, 0, 0)"""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        off = np.zeros(B + 1, np.int32)
+        self._check(self.lib.mpmpc_rollout_obstacles(self._h, B, None, _i(off)))
+        flat = np.zeros((int(off[-1]), 3), np.int32)
+        self._check(self.lib.mpmpc_rollout_obstacles(self._h, B, _i(flat) if flat.size else None, None))
+        return [flat[off[b]:off[b + 1]] for b in range(B)]
 
     # --- recorder of the rollout: one record per car and recorded step, kept on the device
     TRACE_BASIC = ("s", "pose", "wp_id", "x0", "u", "status", "counter", "alive")
