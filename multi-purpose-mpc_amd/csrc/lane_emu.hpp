@@ -140,17 +140,20 @@ struct LaneEmu {
   static VD down(const VD& a) { MPMPC_OP(shift); VD r; for (int i = 0; i < EMU_W; ++i) r.v[i] = (i % G == G - 1) ? 0.0 : a.v[i + 1]; return r; }
 
   // chain layout: reversal of the lanes [C, 2C) and one-lane shifts with zero inflow at the chain ends
+  // (a workgroup, G > 64: the device's chain layout is the two halves of the workgroup whatever its CH - lane_gpu.hpp:
+  //  LaneBlock::mirror / cup / cdown use G / 2; with ONE chain, C = G, only lane_pair.hpp runs on it, which has its own)
+  static constexpr int CL = G > 64 ? G / 2 : C;
   static VD mirror(const VD& a) {
     MPMPC_OP(shift);
     VD r;
-    for (int i = 0; i < EMU_W; ++i) { int l = i % G; r.v[i] = (l >= C && l < 2 * C) ? a.v[i - l + 3 * C - 1 - l] : a.v[i]; }
+    for (int i = 0; i < EMU_W; ++i) { int l = i % G; r.v[i] = (l >= CL && l < 2 * CL) ? a.v[i - l + 3 * CL - 1 - l] : a.v[i]; }
     return r;
   }
   // (exactly what the device does: with C = 16 row shifts, every row of 16 lanes zero-filled, also the rows beyond
   //  2C; with C = 32 plain wavefront shifts, so lane 32 / lane 31 do receive their neighbour's value - which the
   //  zero coupling block of the meeting stage multiplies away, see lane_gpu.hpp)
-  static VD cup(const VD& a) { MPMPC_OP(shift); VD r; for (int i = 0; i < EMU_W; ++i) { int l = i % G; r.v[i] = (l == 0 || (l == C && C != 32) || (C == 16 && l % 16 == 0)) ? 0.0 : a.v[i - 1]; } return r; }
-  static VD cdown(const VD& a) { MPMPC_OP(shift); VD r; for (int i = 0; i < EMU_W; ++i) { int l = i % G; r.v[i] = ((l == C - 1 && C != 32) || l == 2 * C - 1 || l == G - 1 || (C == 16 && l % 16 == 15)) ? 0.0 : a.v[i + 1]; } return r; }
+  static VD cup(const VD& a) { MPMPC_OP(shift); VD r; for (int i = 0; i < EMU_W; ++i) { int l = i % G; r.v[i] = (l == 0 || (l == CL && CL != 32) || (CL == 16 && l % 16 == 0)) ? 0.0 : a.v[i - 1]; } return r; }
+  static VD cdown(const VD& a) { MPMPC_OP(shift); VD r; for (int i = 0; i < EMU_W; ++i) { int l = i % G; r.v[i] = ((l == CL - 1 && CL != 32) || l == 2 * CL - 1 || l == G - 1 || (CL == 16 && l % 16 == 15)) ? 0.0 : a.v[i + 1]; } return r; }
 
   // shifts by D lanes inside each row of 16 lanes, zero inflow (see lane_gpu.hpp)
   template <int D>
@@ -187,14 +190,21 @@ struct LaneEmu {
 
   // ---- chains of four / eight rows (a 128- / 256-lane workgroup; lane_gpu.hpp: LaneBlock, Solver::kCR64): position of a lane in
   // its chain = lane % C; step r works on the survivor X of row r, the survivor Y of row r + 1 and that row's lanes 0, 1, 3, 7
-  static VB cr64_x(int r) { VB m; for (int i = 0; i < EMU_W; ++i) m.v[i] = (i % C) == 16 * r + 15; return m; }
-  static VB cr64_special(int r) { VB m; for (int i = 0; i < EMU_W; ++i) { const int p = i & 15; m.v[i] = ((i % C) >> 4) == r + 1 && ((p & (p + 1)) == 0) && p != 15; } return m; }
+  // (the device's wavefront backends count the rows of the WAVEFRONT, lane & 63: the chain where these are used, C = 64)
+  static constexpr int CR = C < 64 ? 64 : C;
+  static VB cr64_x(int r) { VB m; for (int i = 0; i < EMU_W; ++i) m.v[i] = (i % CR) == 16 * r + 15; return m; }
+  static VB cr64_special(int r) { VB m; for (int i = 0; i < EMU_W; ++i) { const int p = i & 15; m.v[i] = ((i % CR) >> 4) == r + 1 && ((p & (p + 1)) == 0) && p != 15; } return m; }
   // pull: every lane gets v of the same position one row up the chain; push: one row down; down: of the next lane; bcast: of
-  // position 15 of the row below (what a lane without such a source gets is not used: 0 here)
-  template <int NV> static void cr_pull(int, const VD* v, VD* o) { MPMPC_OP(shift); for (int k = 0; k < NV; ++k) for (int i = 0; i < EMU_W; ++i) o[k].v[i] = ((i % C) + 16 < C) ? v[k].v[i + 16] : 0.0; }
-  template <int NV> static void cr_push(int, const VD* v, VD* o) { MPMPC_OP(shift); for (int k = 0; k < NV; ++k) for (int i = 0; i < EMU_W; ++i) o[k].v[i] = ((i % C) >= 16) ? v[k].v[i - 16] : 0.0; }
-  template <int NV> static void cr_down(int, const VD* v, VD* o) { MPMPC_OP(shift); for (int k = 0; k < NV; ++k) for (int i = 0; i < EMU_W; ++i) o[k].v[i] = ((i % C) != C - 1) ? v[k].v[i + 1] : 0.0; }
-  template <int NV> static void cr_bcast(int, const VD* v, VD* o) { MPMPC_OP(shift); for (int k = 0; k < NV; ++k) for (int i = 0; i < EMU_W; ++i) o[k].v[i] = ((i % C) >= 16) ? v[k].v[((i & ~15) - 16) | 15] : 0.0; }
+  // position 15 of the row below (what a lane without such a source gets is not used: 0 here).  A chain of more than four rows
+  // spans wavefronts, and only the crossing step (r = 3 mod 4) moves values between them: at every other step the device's
+  // moves stay inside the wavefront (lane_gpu.hpp: LaneBlock::cr_crosses - pull / push rotate the wavefront's four rows, down
+  // and bcast fill its lane 63 / its first row with 0), and so do these - what the lanes next to a wavefront edge get at a
+  // step that does not work on them is the device's, lane for lane (tests/test_lane_backends.py).
+  static bool cr_crosses(int r) { return C > 64 && (r & 3) == 3; }
+  template <int NV> static void cr_pull(int r, const VD* v, VD* o) { MPMPC_OP(shift); const bool x = cr_crosses(r); for (int k = 0; k < NV; ++k) for (int i = 0; i < EMU_W; ++i) o[k].v[i] = ((i % C) + 16 < C) ? v[k].v[x ? i + 16 : (i & ~63) | ((i + 16) & 63)] : 0.0; }
+  template <int NV> static void cr_push(int r, const VD* v, VD* o) { MPMPC_OP(shift); const bool x = cr_crosses(r); for (int k = 0; k < NV; ++k) for (int i = 0; i < EMU_W; ++i) o[k].v[i] = ((i % C) >= 16) ? v[k].v[x ? i - 16 : (i & ~63) | ((i - 16) & 63)] : 0.0; }
+  template <int NV> static void cr_down(int r, const VD* v, VD* o) { MPMPC_OP(shift); const bool x = cr_crosses(r); for (int k = 0; k < NV; ++k) for (int i = 0; i < EMU_W; ++i) o[k].v[i] = ((i % C) != C - 1 && (x || (i & 63) != 63)) ? v[k].v[i + 1] : 0.0; }
+  template <int NV> static void cr_bcast(int r, const VD* v, VD* o) { MPMPC_OP(shift); const bool x = cr_crosses(r); for (int k = 0; k < NV; ++k) for (int i = 0; i < EMU_W; ++i) o[k].v[i] = ((i % C) >= 16 && (x || (i & 63) >= 16)) ? v[k].v[((i & ~15) - 16) | 15] : 0.0; }
 
   // half-wave exchange (see lane_gpu.hpp)
   static VD from_upper(const VD& a) { MPMPC_OP(shift); VD r; for (int i = 0; i < EMU_W; ++i) r.v[i] = a.v[i | 32]; return r; }
