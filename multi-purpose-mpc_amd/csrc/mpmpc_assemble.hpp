@@ -11,6 +11,12 @@
 #ifndef MPMPC_UNROLL
 #define MPMPC_UNROLL _Pragma("unroll")
 #endif
+// MPMPC_UNROLL_BY(n): n copies of the body per trip, n a constant expression (it may depend on template parameters).  n = the
+// trip count: straight-line code; n = 1: the loop stays a loop.  For loops whose form is chosen per kernel family.
+#ifndef MPMPC_UNROLL_BY
+#define MPMPC_PRAGMA_(x) _Pragma(#x)
+#define MPMPC_UNROLL_BY(n) MPMPC_PRAGMA_(unroll n)
+#endif
 
 namespace mpmpc {
 

@@ -119,6 +119,14 @@ struct Solver {
   static_assert(!(FQ && RED), "the reduced problem needs a diagonal terminal weight");
   // kS2: TWO stages per lane (lane_pair.hpp) - the reduced problem's factorisation is factor_core2_s2 / s_solve_s2 (mpmpc_solver_s2.hpp)
   static constexpr bool kS2 = (L::stages_per_lane == 2);
+  // Predictor and corrector of an interior-point iteration as straight-line code (2 copies of the pass) or as a loop of two trips
+  // (1): the same operations either way; which one is decided per kernel family by what its instantiations cost in registers and
+  // scratch (tests/test_abi.py; the table is in docs/HISTORY.md).  kPassesGeneral: Solver::ipm - straight-line on the workgroup
+  // backends (mpmpc_solve_block_kernel: less scratch in every instantiation), a loop in a wavefront (the <64,32> general kernels
+  // and the split <64,16> reduced-native ones would spill 4 - 84 B more).  kPassesReduced: ReducedSolver::ipm3 and the terminal-time
+  // interior point - straight-line everywhere but in the pair layout on a workgroup (mpmpc_reduced_tail_pair_block_kernel: 36 B).
+  static constexpr int kPassesGeneral = (L::batched && !kS2) ? 2 : 1;
+  static constexpr int kPassesReduced = (L::batched && kS2) ? 1 : 2;
   static constexpr bool kCR = CR && !kS2 && (L::split == 16 || L::split == 32 || L::split == 64 || L::split == 128);
   static constexpr bool kCR32 = kCR && L::split == 32;      // a chain is TWO rows of 16 lanes (see factor_cr2)
   // ... FOUR rows - a whole wavefront of a 128-lane workgroup - or EIGHT, two wavefronts of a 256-lane one (LaneBlock): the

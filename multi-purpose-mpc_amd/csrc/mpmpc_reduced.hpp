@@ -406,9 +406,16 @@ struct ReducedSolver : Solver<L, false, true, false, CR> {
         }
       }
       R alpha_aff(1.0);
+      // predictor (pass 0) and corrector (pass 1) as straight-line code: `pass` is a constant in each copy, so each keeps
+      // its own branch only and alpha_aff, rcl, rcu, dx, dnu cross from one to the other in the registers they were made in
+      // (as a run-time loop of two trips: both branches in a 558-instruction body, the crossing values through copies and
+      // selects - 154 VALU instructions more per iteration, docs/HISTORY.md).  A hint: tests/test_abi.py has the registers,
+      // profiles/ipm_passes/census.py shows that no loop is left inside the iteration.  (S::kPassesReduced: the pair layout
+      // on a workgroup keeps the loop.)
+      MPMPC_UNROLL_BY(S::kPassesReduced)
       for (int pass = 0; pass < 2; ++pass) {
         R dx[3], dnu[2];
-        [[maybe_unused]] R cul[2];          // phase 1: cu - cl of the boxed entries
+        [[maybe_unused]] R cul[2];         // phase 1: cu - cl of the boxed entries
         {
           L::fence();
           R rhs[3], nreq[2];

@@ -294,6 +294,8 @@ struct ReducedTSolver : Solver<L, false, true, false, CR, 11> {
       }
       MPMPC_TICK_END(11);
       R alpha_aff(1.0);
+      // (predictor and corrector as straight-line code, like ReducedSolver::ipm3 - and a loop where that one keeps it)
+      MPMPC_UNROLL_BY(S::kPassesReduced)
       for (int pass = 0; pass < 2; ++pass) {
         R dx[4], dnu[2];
         {

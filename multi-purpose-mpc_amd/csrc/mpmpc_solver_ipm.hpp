@@ -199,6 +199,8 @@
       MPMPC_UNROLL
       for (int j = 0; j < E; ++j) if (boxed(j)) { rcl[j] = s.sl[j] * s.zl[j]; rcu[j] = s.su[j] * s.zu[j]; }
       R alpha_aff(1.0);
+      // (straight-line code or a loop of two trips, per kernel family: kPassesGeneral, mpmpc_core.hpp)
+      MPMPC_UNROLL_BY(kPassesGeneral)
       for (int pass = 0; pass < 2; ++pass) {
         R rhs[E], nreq[NQ];
         [[maybe_unused]] R cul[E];          // phase 1: cu - cl of the entry
