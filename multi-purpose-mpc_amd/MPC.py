@@ -230,7 +230,7 @@ class BatchMPC:
     # stale corridor or stale settings (a call on `self.handle` alone reaches only the first handle of the ring).
     def _quiesce_stream(self):
         """nothing of a stream may still be in flight on a handle whose settings, packing, tail kernel or corridor change: the
-        C side would settle the staged call (`settle` in mpmpc_hip.hip) and a live get_control_stream generator would then yield fewer or
+        C side would settle the staged call (`settle` in mpmpc_handle.hpp) and a live get_control_stream generator would then yield fewer or
         stale batches - what is in flight is waited for and dropped, the generator ends at its next step"""
         if self._stream is not None:
             self._stream.discard()

@@ -1,5 +1,5 @@
 // Dynamic drivable corridor per waypoint (e_y bounds of the horizon), scalar per-thread code that
-// compiles for gfx950 (K0 kernels in mpmpc_hip.hip) and for the host (tests/emul, CPU check).
+// compiles for gfx950 (K0 kernels in mpmpc_closed_loop.hpp) and for the host (tests/emul, CPU check).
 //
 // Replaces, for every start waypoint of the path at once,
 //   ReferencePath.update_path_constraints(wp_id, N, min_width, safety_margin)   src/reference_path.py:522-648

@@ -1,0 +1,720 @@
+// The closed loop of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind mpmpc_set_corridor):
+// the kernels K0a / K0b (corridor tables from the map), K0c (per-car corridor rows), K0m (movers), K3a / K3b (localise, advance)
+// and the two recorder kernels, and their entry points - mpmpc_set_map, mpmpc_set_path_geometry, mpmpc_build_corridor and every
+// mpmpc_rollout_*.  The state they work on: the sub-states cor, obs, ro, rec of the handle (mpmpc_handle.hpp).
+#pragma once
+
+// K0a: free segments of every waypoint's border line, one WAVEFRONT per waypoint.  Lane 0 walks Zingl's anti-aliased
+// line (a float32 recurrence in skimage's exact cell order: inherently serial, ~95 cells on Sim_Track) and leaves the
+// cells in LDS; all 64 lanes then fetch the occupancies (one memory round trip for the whole line instead of one per
+// cell; cells outside the grid count as occupied); lane 0 runs the run-length state machine over the LDS copy and, for
+// a waypoint with at most one free segment, computes its bounds once (cor_forced) instead of once per start waypoint
+// and column in K0b.  A line longer than COR_CELL_CAP cells or with more than COR_MAXSEG free segments raises *err
+// (1 / 2) - mpmpc_build_corridor then fails instead of working with a truncated list.
+__global__ __launch_bounds__(64) void mpmpc_free_segments_kernel(MapView map, PathGeom g, const double* __restrict__ bub,
+                                                                 const double* __restrict__ blb, double min_width,
+                                                                 double safety_margin, double* __restrict__ segs,
+                                                                 int* __restrict__ nseg, double* __restrict__ wpc,
+                                                                 int* __restrict__ err, int* __restrict__ line_cells,
+                                                                 int* __restrict__ line_box) {
+  __shared__ int cells[COR_CELL_CAP];
+  __shared__ unsigned char occ[COR_CELL_CAP];
+  __shared__ int s_n;
+  __shared__ double seg[4 * COR_MAXSEG];      // lane 0's segment list (in LDS: a per-lane array would live in scratch)
+  const int i = blockIdx.x, lane = threadIdx.x;
+  int ux, uy, lx, ly;
+  cor_w2m(map, bub[2 * i], bub[2 * i + 1], ux, uy);
+  cor_w2m(map, blb[2 * i], blb[2 * i + 1], lx, ly);
+  if (lane == 0) s_n = cor_line_cells(ux, uy, lx, ly, cells, COR_CELL_CAP);
+  __syncthreads();
+  const int n = s_n;
+  int cnt;
+  if (n > COR_CELL_CAP) {
+    cnt = COR_E_CELLS;
+  } else {
+    for (int k = lane; k < n; k += 64) {
+      int x, y;
+      cor_unpack_cell(cells[k], x, y);
+      occ[k] = cor_cell_free(map, x, y) ? 1 : 0;
+      line_cells[(long)i * COR_CELL_CAP + k] = cells[k];      // K0c's cache of the line
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    cor_line_box(cells, n, (ux + 1) | ((uy + 1) << 16), (lx + 1) | ((ly + 1) << 16), line_box + (long)i * COR_LINE_BOX);
+    cnt = cor_scan_cells(map, ux, uy, lx, ly, min_width, n, [&](int c, int& x, int& y) { cor_unpack_cell(cells[c], x, y); },
+                         [&](int c) { return occ[c] != 0; }, seg);
+    for (int k = 0; k < 4 * COR_MAXSEG; ++k) segs[(long)i * 4 * COR_MAXSEG + k] = (cnt > 0 && k < 4 * cnt) ? seg[k] : 0.0;
+  }
+  if (lane != 0) return;
+  if (cnt < 0) { atomicMax(err, cnt == COR_E_CELLS ? 1 : 2); cnt = 0; }
+  nseg[i] = cnt;
+  if (cnt <= 1) cor_forced(g, segs, nseg, i, safety_margin, wpc + (long)i * COR_WPC);
+}
+
+// K0b: horizon walk for every start waypoint w (table row w = update_path_constraints(w + 1, ...)).
+// K0b: one thread per (start waypoint, column): cor_select_one replays only the short run of multi-segment waypoints
+// right before its column, everything else is a row of K0a's per-waypoint table.
+__global__ __launch_bounds__(256) void mpmpc_corridor_select_kernel(PathGeom g, const double* __restrict__ segs,
+                                                                    const int* __restrict__ nseg, int n_cols,
+                                                                    double safety_margin, double* __restrict__ ub_tab,
+                                                                    double* __restrict__ lb_tab, int* __restrict__ bad,
+                                                                    const double* __restrict__ wpc) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int w = t / n_cols, n = t - w * n_cols;
+  if (w >= g.n_wp) return;
+  double ub, lb;
+  if (!cor_select_one(g, segs, nseg, w + 1, n, safety_margin, wpc, &ub, &lb)) {
+    ub = lb = __builtin_nan("");
+    if (n == 0) atomicAdd(bad, 1);
+  }
+  ub_tab[(long)w * n_cols + n] = ub;
+  lb_tab[(long)w * n_cols + n] = lb;
+}
+
+// K0c: the corridor rows of one rollout step when every car carries its own obstacle discs (mpmpc_rollout_set_obstacles).
+// One wavefront per car; lanes loop over the car's N columns (N up to 255).  Column n reads waypoint
+// cor_wp(wp_id + 1 + n): if none of the car's discs meets the box of that waypoint's cached border line, it keeps the
+// base segments of the last build (nseg / wpc / segs).  The others ("touched") are rescanned in the car's world: the
+// wave stages the cached cells of as many touched lines as fit COR_CELL_CAP cells in LDS together with their occupancy
+// (base map and discs, every lane fetching cells of its own - one memory round trip per batch of lines instead of one
+// per cell), then the lane of each staged column runs the state machine over its cells in LDS (cor_scan_runs) and keeps
+// the segment end cells as packed pairs plus the cor_forced row.  After a barrier every lane selects its columns as
+// K0b does (cor_select_car_one) and writes lb / ub into the per-instance rows the solve reads.  flag[b] = COR_ROW_*: a
+// car still running whose row is blocked / overflowing ends with alive = -3 / -4 (and gets a zero row, so that the
+// solve of a stopped car stays an ordinary QP).  Every car gets its row - the solve runs on stopped cars too, and their
+// status then matches the shared-table rollout's.
+// LDS: 5 KB of staged cells + 0.8 KB of discs + N * (COR_WPC doubles + (2 COR_MAXSEG + 3) ints) = 5.9 KB + 124 B per column.
+__global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, PathGeom g, int N, double min_width,
+                                                                double safety_margin, const double* __restrict__ segs,
+                                                                const int* __restrict__ nseg, const double* __restrict__ wpc,
+                                                                const int* __restrict__ line_cells,
+                                                                const int* __restrict__ line_box,
+                                                                const int* __restrict__ off, const int* __restrict__ discs,
+                                                                const int* __restrict__ wp_id, int* __restrict__ alive,
+                                                                int* __restrict__ flag, double* __restrict__ lb,
+                                                                double* __restrict__ ub) {
+  constexpr int PENDING = -1000000;
+  extern __shared__ double lds[];
+  double* col_o = lds;                                             // [N][COR_WPC]
+  int* col_seg = (int*)(col_o + (long)N * COR_WPC);                // [N][2 * COR_MAXSEG] packed end cells
+  int* col_cnt = col_seg + (long)N * 2 * COR_MAXSEG;               // [N]; < 0: COR_E_SEGMENTS; +1000: touched
+  int* col_aux = col_cnt + N;                                      // [N] touched: cells of the line
+  int* col_off = col_aux + N;                                      // [N] touched and staged: offset in stg_*, else -1
+  int* dsc = col_off + N;                                          // [COR_MAX_DISCS][3]
+  int* stg_cell = dsc + 3 * COR_MAX_DISCS;                         // [COR_CELL_CAP]
+  unsigned char* stg_free = (unsigned char*)(stg_cell + COR_CELL_CAP);   // [COR_CELL_CAP]
+  __shared__ int s_over;
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int d0 = off[b], nd = off[b + 1] - d0;
+  for (int k = lane; k < 3 * nd; k += 64) dsc[k] = discs[3L * d0 + k];
+  if (lane == 0) s_over = 0;
+  __syncthreads();
+  const int wp = wp_id[b] + 1;
+  auto disc = [&](int j) { return (const int*)(dsc + 3 * j); };
+  for (int n = lane; n < N; n += 64) {
+    const int i = cor_wp(g, wp + n);
+    const int* box = line_box + (long)i * COR_LINE_BOX;
+    col_off[n] = -1;
+    if (nd > 0 && cor_car_touches(box, nd, disc)) {
+      col_cnt[n] = PENDING;
+      col_aux[n] = box[0];
+    } else {
+      const int cnt = nseg[i];
+      if (cnt <= 1)
+        for (int k = 0; k < COR_WPC; ++k) col_o[(long)n * COR_WPC + k] = wpc[(long)i * COR_WPC + k];
+      col_cnt[n] = cnt;
+    }
+  }
+  __syncthreads();
+  for (int n = 0; n < N;) {            // (uniform: every lane reads the same LDS words)
+    int used = 0, e = n;
+    for (; e < N; ++e) {
+      if (col_cnt[e] != PENDING) continue;
+      const int nc = col_aux[e];
+      if (used > 0 && used + nc > COR_CELL_CAP) break;
+      used += nc;
+    }
+    used = 0;
+    for (int c = n; c < e; ++c) {
+      if (col_cnt[c] != PENDING) continue;
+      const int nc = col_aux[c];
+      if (lane == 0) col_off[c] = used;
+      const int* cells = line_cells + (long)cor_wp(g, wp + c) * COR_CELL_CAP;
+      for (int k = lane; k < nc; k += 64) {
+        const int cell = cells[k];
+        stg_cell[used + k] = cell;
+        stg_free[used + k] = cor_car_cell_free(map, cell, nd, disc) ? 1 : 0;
+      }
+      used += nc;
+    }
+    __syncthreads();
+    for (int c = n + lane; c < e; c += 64) {      // the lane of column c scans it
+      const int o0 = col_off[c];
+      if (o0 < 0) continue;
+      const int nc = col_aux[c];
+      const int i = cor_wp(g, wp + c);
+      const int* box = line_box + (long)i * COR_LINE_BOX;
+      int ux, uy, lx, ly;
+      cor_unpack_cell(box[5], ux, uy);
+      cor_unpack_cell(box[6], lx, ly);
+      int* cs = col_seg + (long)c * 2 * COR_MAXSEG;
+      double s0[4] = {0, 0, 0, 0};
+      const int cnt = cor_scan_runs(map, ux, uy, lx, ly, min_width, nc,
+                                    [&](int k, int& x, int& y) { cor_unpack_cell(stg_cell[o0 + k], x, y); },
+                                    [&](int k) { return stg_free[o0 + k] != 0; },
+                                    [&](int q, int sx, int sy, int x, int y, double ax, double ay, double bx, double by) {
+                                      cs[2 * q] = (sx + 1) | ((sy + 1) << 16);
+                                      cs[2 * q + 1] = (x + 1) | ((y + 1) << 16);
+                                      if (q == 0) { s0[0] = ax; s0[1] = ay; s0[2] = bx; s0[3] = by; }
+                                    });
+      if (cnt < 0) s_over = 1;
+      else if (cnt <= 1) cor_forced_seg(g, i, cnt, s0, safety_margin, col_o + (long)c * COR_WPC);
+      col_cnt[c] = cnt < 0 ? cnt : cnt + 1000;
+    }
+    __syncthreads();
+    n = e;
+  }
+  auto cnt = [&](int c) { const int v = col_cnt[c]; return v >= 1000 ? v - 1000 : v; };
+  auto forced = [&](int c, double* o) { for (int k = 0; k < COR_WPC; ++k) o[k] = col_o[(long)c * COR_WPC + k]; };
+  auto seg = [&](int c, int k, double* s) {
+    if (col_cnt[c] >= 1000) {
+      const int* cs = col_seg + (long)c * 2 * COR_MAXSEG;
+      int x, y;
+      cor_unpack_cell(cs[2 * k], x, y);
+      cor_m2w(map, x, y, s[0], s[1]);
+      cor_unpack_cell(cs[2 * k + 1], x, y);
+      cor_m2w(map, x, y, s[2], s[3]);
+    } else {
+      const double* sg = segs + (long)cor_wp(g, wp + c) * 4 * COR_MAXSEG + 4 * k;
+      for (int j = 0; j < 4; ++j) s[j] = sg[j];
+    }
+  };
+  const int verdict = cnt(0) == 0 ? COR_ROW_BLOCKED : (s_over ? COR_ROW_OVERFLOW : COR_ROW_OK);   // the reference raises at column 0 first
+  for (int n = lane; n < N; n += 64) {
+    double u = 0.0, l = 0.0;
+    if (verdict == COR_ROW_OK) cor_select_car_one(g, wp, n, safety_margin, cnt, forced, seg, &u, &l);
+    ub[(long)b * N + n] = u;
+    lb[(long)b * N + n] = l;
+  }
+  if (lane == 0) {
+    flag[b] = verdict;
+    if (verdict != COR_ROW_OK && alive[b] == 1) alive[b] = verdict == COR_ROW_BLOCKED ? -3 : -4;
+  }
+}
+
+// K0m: the movers of one rollout step (mpmpc_rollout_set_movers), launched between K3a and K0c when there are any.  One
+// thread per mover of the whole fleet; its parameters are structure-of-arrays ([n] each: a wavefront loads consecutive
+// words), its disc of step k (mov_disc: closed form in k; kind 1 searches ro_cum, ~9 probes that stay in L2) goes into
+// its slot of its car's disc list - dst[j], laid out on the host when either setting changes - where K0c reads it
+// behind the car's static discs.
+__global__ __launch_bounds__(256) void mpmpc_obstacle_move_kernel(int n, long long k, long long step0, MapView map,
+                                                                  MoverPath path, const int* __restrict__ kind,
+                                                                  const int* __restrict__ radius,
+                                                                  const double* __restrict__ prm,
+                                                                  const int* __restrict__ dst, int* __restrict__ discs) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  int d[3];
+  mov_disc(map, path, kind[j], radius[j], prm[j], prm[(long)n + j], prm[2L * n + j], prm[3L * n + j], k, step0, d);
+  int* o = discs + 3L * dst[j];
+  o[0] = d[0]; o[1] = d[1]; o[2] = d[2];
+}
+
+// K3a: where is each car on the path, and what is its path-relative state (one thread per car)
+// (alive: 0 = lap finished, s past the path's length; -2 = an open path's end reached, the reference's exit(1) in
+//  get_waypoint - wp_id and x0 are still written, they are the state the reference computed before it exited)
+__global__ __launch_bounds__(256) void mpmpc_localise_kernel(int B, int n_wp, int N, int circular, const double* __restrict__ cum,
+                                                             const double* __restrict__ gx, const double* __restrict__ gy,
+                                                             const double* __restrict__ gpsi, const double* __restrict__ s,
+                                                             const double* __restrict__ pose, int* __restrict__ alive,
+                                                             int* __restrict__ wp_id, double* __restrict__ x0,
+                                                             int* __restrict__ shift) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B || alive[i] != 1) return;
+  const int wp = ro_current_waypoint(cum, n_wp, s[i]);
+  if (wp < 0) { alive[i] = 0; return; }              // lap finished
+  if (shift) {                                        // waypoints advanced since the last step (warm start)
+    int d = wp - wp_id[i];
+    if (d < 0) d += n_wp;
+    shift[i] = d;
+  }
+  wp_id[i] = wp;
+  ro_t2s(pose[3 * i], pose[3 * i + 1], pose[3 * i + 2], gx[wp], gy[wp], gpsi[wp], x0 + 3 * i);
+  if (ro_past_open_end(n_wp, N, circular != 0, wp)) alive[i] = -2;     // end of an open path
+}
+
+// K3b: use the solution (or the fallback plan), drive the plant one step (one thread per car)
+__global__ __launch_bounds__(256) void mpmpc_advance_kernel(int B, int N, double L, double Ts, const double* __restrict__ kappa,
+                                                            const int* __restrict__ wp_id, const double* __restrict__ x0,
+                                                            const int* __restrict__ status, const double* __restrict__ z,
+                                                            double* __restrict__ cc, int* __restrict__ counter,
+                                                            int* __restrict__ alive, double* __restrict__ pose,
+                                                            double* __restrict__ s, double* __restrict__ u_last) {
+  // one thread per (car, plan entry): the N arctangents of a car's new plan are independent; the thread of entry 0
+  // then drives the car (it reads only plan entries it wrote itself, or - fallback - entries nobody writes)
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  const int i = g / N, k = g - i * N;
+  if (i >= B || alive[i] != 1) return;
+  const int n = 5 * N + 3;
+  const int st = status[i];
+  if (ro_usable(st)) ro_plan_entry(N, L, z + (long)i * n, cc + (long)i * 2 * N, k);
+  if (k == 0 && !ro_drive(N, L, Ts, st, cc + (long)i * 2 * N, counter + i, x0 + 3 * i, kappa[wp_id[i]], pose + 3 * i,
+                          s + i, u_last + 2 * i))
+    alive[i] = -1;
+}
+
+// K3r: the recorder of a rollout (mpmpc_rollout_record), two launches around a recorded step.  Both give every ENTRY of
+// a car's record its own thread, and the record's fields lie car-major ([B][len], the host's layout): consecutive threads
+// store consecutive words.  `rec` is the record's base address (64-bit arithmetic on the host).
+//   snapshot  before localise: s, pose, alive as the step finds them (4 entries per car)
+//   write     after advance: x0, u, wp_id, status, counter, alive, plan, predicted path, corridor row (ro_record_finish)
+__global__ __launch_bounds__(256) void mpmpc_record_snapshot_kernel(int B, const double* __restrict__ s,
+                                                                    const double* __restrict__ pose,
+                                                                    const int* __restrict__ alive, int* __restrict__ a_in,
+                                                                    char* __restrict__ rec, RoTraceLayout lay) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  const int i = (int)(g / RO_REC_BEGIN_ENTRIES), c = (int)(g - (long)i * RO_REC_BEGIN_ENTRIES);
+  if (i >= B) return;
+  ro_record_begin(s, pose, alive, a_in, rec, lay, i, c);
+}
+__global__ __launch_bounds__(256) void mpmpc_record_write_kernel(int B, RoRecSrc src, char* __restrict__ rec, RoTraceLayout lay) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  const int i = (int)(g / lay.entries), e = (int)(g - (long)i * lay.entries);
+  if (i >= B) return;
+  ro_record_finish(src, rec, lay, i, e);
+}
+
+extern "C" {
+
+int mpmpc_set_map(mpmpc_handle h, int32_t height, int32_t width, const int8_t* data, double origin_x,
+                  double origin_y, double resolution) {
+  if (int rc = enter(h, data)) return rc;
+  if (height < 1 || width < 1 || !(resolution > 0)) return fail(MPMPC_E_ARG, "map needs positive size and resolution");
+  if (height > COR_MAX_SIDE || width > COR_MAX_SIDE) return fail(MPMPC_E_ARG, "map sides are limited to 65534 cells");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  HIP_TRY(h->cor.map.alloc((size_t)height * width));
+  HIP_TRY(hipMemcpyAsync(h->cor.map, data, (size_t)height * width, hipMemcpyHostToDevice, h->last().stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
+  h->cor.map_h = height; h->cor.map_w = width; h->cor.map_ox = origin_x; h->cor.map_oy = origin_y; h->cor.map_res = resolution;
+  ++h->cor.base_gen;
+  return MPMPC_OK;
+}
+
+int mpmpc_set_path_geometry(mpmpc_handle h, int32_t n_wp, const double* x, const double* y, const double* psi,
+                            const double* border_ub, const double* border_lb) {
+  if (int rc = enter(h, x && y && psi && border_ub && border_lb)) return rc;
+  if (h->tab.n_wp == 0 || n_wp != h->tab.n_wp) return fail(MPMPC_E_STATE, "set the path first; n_wp must match it");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  h->cor.geom_n = 0;      // a failure below leaves "no geometry set"
+  if (int rc = upload_table(h, h->cor.gx, x, n_wp)) return rc;
+  if (int rc = upload_table(h, h->cor.gy, y, n_wp)) return rc;
+  if (int rc = upload_table(h, h->cor.gpsi, psi, n_wp)) return rc;
+  if (int rc = upload_table(h, h->cor.bub, border_ub, 2 * (size_t)n_wp)) return rc;
+  if (int rc = upload_table(h, h->cor.blb, border_lb, 2 * (size_t)n_wp)) return rc;
+  {
+    // everything of a waypoint that needs libm, from the HOST's libm: the device tables then hold no device-libm
+    // result (bit-exact against the reference's tables, golden G3)
+    std::vector<double> trig((size_t)n_wp * COR_TRIG);
+    for (int i = 0; i < n_wp; ++i) cor_trig_row(psi[i], trig.data() + (size_t)i * COR_TRIG);
+    if (int rc = upload_table(h, h->cor.gtrig, trig.data(), trig.size())) return rc;
+    HIP_TRY(hipStreamSynchronize(h->last().stream));      // `trig` leaves scope
+  }
+  h->cor.host_bub.assign(border_ub, border_ub + 2 * (size_t)n_wp);
+  h->cor.host_blb.assign(border_lb, border_lb + 2 * (size_t)n_wp);
+  const size_t nw = (size_t)n_wp;
+  if (!h->cor.bad) HIP_TRY(h->cor.bad.alloc(2));
+  HIP_TRY(alloc_all(Want{h->cor.segs, (4 * COR_MAXSEG + COR_WPC) * nw} /* + cor_forced rows */, Want{h->cor.nseg, nw},
+                    Want{h->cor.line_cells, COR_CELL_CAP * nw}, Want{h->cor.line_box, COR_LINE_BOX * nw}));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
+  h->cor.geom_n = n_wp;
+  ++h->cor.base_gen;
+  return MPMPC_OK;
+}
+
+int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, double safety_margin, double* ub_out,
+                         double* lb_out, int32_t* bad_rows) {
+  if (int rc = enter(h)) return rc;
+  Slot& sl = h->last();
+  if (!h->cor.map || h->cor.geom_n == 0 || h->cor.geom_n != h->tab.n_wp)
+    return fail(MPMPC_E_STATE, "needs mpmpc_set_path, mpmpc_set_map and mpmpc_set_path_geometry first");
+  if (n_cols < h->cfg.N) return fail(MPMPC_E_ARG, "corridor table needs n_cols >= N");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const int n = h->tab.n_wp;
+  if (h->tab.n_cols != n_cols || !h->tab.ub_tab || !h->tab.lb_tab) {
+    h->tab.n_cols = 0;      // a failure here leaves no table and no build
+    h->cor.built_gen = 0;
+    HIP_TRY(alloc_all(Want{h->tab.ub_tab, (size_t)n * n_cols}, Want{h->tab.lb_tab, (size_t)n * n_cols}));
+  }
+  const MapView mv = h->cor.map_view();
+  const PathGeom pg = h->cor.path_geom(h->tab, h->cfg.circular);
+  // the border cells of every waypoint must lie on the map of the moment (numpy indexing in the reference raises
+  // IndexError past the upper edges and silently wraps around below zero: here both are an error)
+  for (int i = 0; i < n; ++i) {
+    int cx[2], cy[2];
+    cor_w2m(mv, h->cor.host_bub[2 * i], h->cor.host_bub[2 * i + 1], cx[0], cy[0]);
+    cor_w2m(mv, h->cor.host_blb[2 * i], h->cor.host_blb[2 * i + 1], cx[1], cy[1]);
+    for (int e = 0; e < 2; ++e)
+      if (cx[e] < 0 || cx[e] >= h->cor.map_w || cy[e] < 0 || cy[e] >= h->cor.map_h)
+        return fail(MPMPC_E_ARG, "border cell of waypoint " + std::to_string(i) + " lies outside the map");
+  }
+  HIP_TRY(hipMemsetAsync(h->cor.bad, 0, 2 * sizeof(int), sl.stream));
+  double* wpc = h->cor.forced_rows(h->tab);
+  hipLaunchKernelGGL(mpmpc_free_segments_kernel, dim3(n), dim3(64), 0, sl.stream, mv, pg, h->cor.bub, h->cor.blb, min_width,
+                     safety_margin, h->cor.segs, h->cor.nseg, wpc, h->cor.bad + 1, h->cor.line_cells, h->cor.line_box);
+  hipLaunchKernelGGL(mpmpc_corridor_select_kernel, dim3((n * n_cols + 255) / 256), dim3(256), 0, sl.stream, pg, h->cor.segs,
+                     h->cor.nseg, n_cols, safety_margin, h->tab.ub_tab, h->tab.lb_tab, h->cor.bad, wpc);
+  HIP_TRY(hipGetLastError());
+  int bad2[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(bad2, h->cor.bad, 2 * sizeof(int), hipMemcpyDeviceToHost, sl.stream));
+  if (ub_out) HIP_TRY(hipMemcpyAsync(ub_out, h->tab.ub_tab, sizeof(double) * (size_t)n * n_cols, hipMemcpyDeviceToHost, sl.stream));
+  if (lb_out) HIP_TRY(hipMemcpyAsync(lb_out, h->tab.lb_tab, sizeof(double) * (size_t)n * n_cols, hipMemcpyDeviceToHost, sl.stream));
+  HIP_TRY(hipStreamSynchronize(sl.stream));
+  h->cor.built_gen = 0;
+  if (bad2[1] != 0) {
+    h->tab.n_cols = 0;        // the table is not usable
+    return fail(MPMPC_E_ARG, bad2[1] == 1 ? "a waypoint's border line has more than 1024 cells (COR_CELL_CAP)"
+                                           : "a waypoint's border line has more than 8 free segments (COR_MAXSEG)");
+  }
+  const int bad = bad2[0];
+  if (bad_rows) *bad_rows = bad;
+  h->tab.n_cols = n_cols;
+  h->cor.built_gen = h->cor.base_gen;
+  h->cor.built_min_width = min_width;
+  h->cor.built_sm = safety_margin;
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_lengths, const double* s,
+                       const double* pose, const double* cc0) {
+  if (int rc = enter(h, cum_lengths && s && pose)) return rc;
+  Slot& sl = h->last();
+  if (B < 1 || B > h->cfg.max_batch) return fail(MPMPC_E_ARG, "B must be in [1, max_batch]");
+  if (!(Ts > 0)) return fail(MPMPC_E_ARG, "Ts must be > 0");
+  if (h->tab.n_wp == 0 || h->cor.geom_n != h->tab.n_wp) return fail(MPMPC_E_STATE, "needs mpmpc_set_path and mpmpc_set_path_geometry");
+  if (h->tab.n_cols == 0) return fail(MPMPC_E_STATE, "needs a corridor table (mpmpc_set_corridor / mpmpc_build_corridor)");
+  if (h->rec.cap > 0 && h->rec.B != B) return fail(MPMPC_E_STATE, "mpmpc_rollout_record was set up for another number of cars");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t mb = (size_t)h->cfg.max_batch;
+  if (!h->ro.s)      // (all seven or none)
+    HIP_TRY(alloc_all(Want{h->ro.s, mb}, Want{h->ro.pose, 3 * mb}, Want{h->ro.u, 2 * mb}, Want{h->ro.counter, mb}, Want{h->ro.alive, mb},
+                      Want{h->ro.act, mb * h->ld}, Want{h->ro.shift, mb}));
+  if (!h->obs.ro_flag) HIP_TRY(h->obs.ro_flag.alloc(mb));
+  if (int rc = upload_table(h, h->ro.cum, cum_lengths, h->tab.n_wp)) return rc;
+  const int N = h->cfg.N;
+  if (B != h->io.laid_out) lay_out(h, B);
+  HIP_TRY(hipMemcpyAsync(h->ro.s, s, sizeof(double) * B, hipMemcpyHostToDevice, sl.stream));
+  HIP_TRY(hipMemcpyAsync(h->ro.pose, pose, sizeof(double) * 3 * B, hipMemcpyHostToDevice, sl.stream));
+  if (cc0) HIP_TRY(hipMemcpyAsync(h->io.cc, cc0, sizeof(double) * 2 * N * B, hipMemcpyHostToDevice, sl.stream));
+  else HIP_TRY(hipMemsetAsync(h->io.cc, 0, sizeof(double) * 2 * N * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(h->ro.counter, 0, sizeof(int) * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(h->ro.act, 0, sizeof(int) * (size_t)B * h->ld, sl.stream));     // no guess yet
+  HIP_TRY(hipMemsetAsync(h->ro.shift, 0, sizeof(int) * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(h->ro.u, 0, sizeof(double) * 2 * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(h->io.wp_id, 0, sizeof(int) * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(h->io.x0, 0, sizeof(double) * 3 * B, sl.stream));
+  HIP_TRY(hipMemsetAsync(sl.status, 0, sizeof(int) * B, sl.stream));
+  const std::vector<int> ones((size_t)B, 1);
+  HIP_TRY(hipMemcpyAsync(h->ro.alive, ones.data(), sizeof(int) * B, hipMemcpyHostToDevice, sl.stream));
+  HIP_TRY(hipStreamSynchronize(sl.stream));
+  h->ro.Ts = Ts;
+  h->ro.B = B;
+  h->ro.valid = true;
+  h->io.have_rows = false;       // the corridor comes from the table
+  h->obs.car_rows = false;
+  h->obs.discs_live = false;
+  h->io.uploaded = B;
+  h->rec.ro_steps = 0;            // the recorder keeps its configuration and starts over
+  h->rec.count = 0;
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_record(mpmpc_handle h, int32_t B, int32_t capacity, int32_t fields, int32_t stride) {
+  if (int rc = enter(h)) return rc;
+  if (capacity < 0) return fail(MPMPC_E_ARG, "capacity must be >= 0");
+  if (stride < 1) return fail(MPMPC_E_ARG, "stride must be >= 1");
+  if (fields & ~RO_REC_ALL) return fail(MPMPC_E_ARG, "unknown bits in fields");
+  if (B < 1 || B > h->cfg.max_batch) return fail(MPMPC_E_ARG, "B must be in [1, max_batch]");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
+  h->rec.buf.reset();
+  h->rec.cap = h->rec.count = 0;
+  if (capacity == 0) return MPMPC_OK;
+  const RoTraceLayout lay = ro_trace_layout(h->cfg.N, B, fields);
+  if (!h->rec.ain) HIP_TRY(h->rec.ain.alloc((size_t)h->cfg.max_batch));
+  if (h->rec.buf.alloc((size_t)lay.bytes * (size_t)capacity)) {
+    (void)hipGetLastError();
+    return fail(MPMPC_E_HIP, "no device memory for " + std::to_string(capacity) + " records of " + std::to_string(lay.bytes) + " bytes");
+  }
+  h->rec.lay = lay;
+  h->rec.cap = capacity;
+  h->rec.B = B;
+  h->rec.fields = fields;
+  h->rec.stride = stride;
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_recorded(mpmpc_handle h, int32_t* n_records, int32_t* n_steps) {
+  if (!h) return fail(MPMPC_E_ARG, "handle is NULL");
+  if (n_records) *n_records = h->rec.count;
+  if (n_steps) *n_steps = (int32_t)h->rec.ro_steps;
+  return MPMPC_OK;
+}
+
+// field `off` of records first .. first + count - 1 -> host [count][bytes]: one strided copy
+static int pull_field(mpmpc_handle h, void* dst, long long off, size_t bytes, int first, int count) {
+  const char* src = h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)first + off;
+  if (count == 1) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->last().stream));
+  else HIP_TRY(hipMemcpy2DAsync(dst, bytes, src, (size_t)h->rec.lay.bytes, bytes, (size_t)count, hipMemcpyDeviceToHost, h->last().stream));
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_trace(mpmpc_handle h, int32_t B, int32_t first, int32_t count, double* s, double* pose, int32_t* wp_id,
+                        double* x0, double* u, int32_t* status, int32_t* counter, int32_t* alive, double* plan,
+                        double* pred_x, double* pred_y, double* ub, double* lb) {
+  if (int rc = enter(h)) return rc;
+  if (first < 0 || count < 0) return fail(MPMPC_E_ARG, "first and count must be >= 0");
+  if (h->rec.cap == 0) return fail(MPMPC_E_STATE, "recording is off (mpmpc_rollout_record)");
+  if (B != h->rec.B) return fail(MPMPC_E_STATE, "mpmpc_rollout_record was set up for another number of cars");
+  if ((long long)first + count > h->rec.count)
+    return fail(MPMPC_E_STATE, "records " + std::to_string(first) + " .. " + std::to_string((long long)first + count - 1) +
+                                   " asked for, " + std::to_string(h->rec.count) + " held");
+  const RoTraceLayout& l = h->rec.lay;
+  if ((plan && l.plan < 0) || ((pred_x || pred_y) && l.pred_x < 0) || ((ub || lb) && l.ub < 0))
+    return fail(MPMPC_E_STATE, "a field was asked for that mpmpc_rollout_record did not select");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if (count > 0) {
+    const size_t N = (size_t)h->cfg.N, nb = (size_t)B;
+#define PULL(dst, off, per_car) if (dst) { if (int rc = pull_field(h, dst, off, (per_car) * nb, first, count)) return rc; }
+    PULL(s, l.s, 8); PULL(pose, l.pose, 24); PULL(wp_id, l.wp_id, 4); PULL(x0, l.x0, 24); PULL(u, l.u, 16);
+    PULL(status, l.status, 4); PULL(counter, l.counter, 4); PULL(alive, l.alive, 4);
+    PULL(plan, l.plan, 16 * N); PULL(pred_x, l.pred_x, 8 * (N - 2)); PULL(pred_y, l.pred_y, 8 * (N - 2));
+    PULL(ub, l.ub, 8 * N); PULL(lb, l.lb, 8 * N);
+#undef PULL
+  }
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_set_counters(mpmpc_handle h, int32_t B, const int32_t* counter) {
+  if (int rc = enter(h, counter)) return rc;
+  if (int rc = h->ro.check(B)) return rc;
+  for (int i = 0; i < B; ++i)
+    if (counter[i] < 0 || counter[i] >= h->cfg.N - 1) return fail(MPMPC_E_ARG, "infeasibility counters must be in [0, N - 2]");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  HIP_TRY(hipMemcpyAsync(h->ro.counter, counter, sizeof(int) * B, hipMemcpyHostToDevice, h->last().stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
+  if (int rc = enter(h)) return rc;
+  Slot& sl = h->last();
+  if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
+                              "call mpmpc_rollout_init again (or use a second handle for single solves)")) return rc;
+  if (n_steps < 0) return fail(MPMPC_E_ARG, "n_steps must be >= 0");
+  const bool per_car = h->obs.obst_B > 0;
+  if (per_car) {
+    if (h->obs.obst_B != B) return fail(MPMPC_E_STATE, "the per-car obstacles were set for another number of cars");
+    if ((h->obs.st_B > 0 && h->obs.obst_gen != h->cor.base_gen) || (h->obs.mv_B > 0 && h->obs.mv_gen != h->cor.base_gen) || h->cor.built_gen != h->cor.base_gen)
+      return fail(MPMPC_E_STATE, "map, path or geometry changed since mpmpc_rollout_set_obstacles / mpmpc_build_corridor");
+  }
+  const bool recording = h->rec.cap > 0;
+  if (recording) {
+    if (h->rec.B != B) return fail(MPMPC_E_STATE, "mpmpc_rollout_record was set up for another number of cars");
+    if (h->rec.count + h->rec.records_of(n_steps) > h->rec.cap)
+      return fail(MPMPC_E_STATE, "the trace is full: " + std::to_string(h->rec.count) + " of " + std::to_string(h->rec.cap) +
+                                     " records held, this call would add " + std::to_string(h->rec.records_of(n_steps)));
+  }
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const int N = h->cfg.N;
+  const size_t car_lds = sizeof(double) * COR_WPC * N + sizeof(int) * (2 * COR_MAXSEG + 3) * N + sizeof(int) * 3 * COR_MAX_DISCS +
+                         (sizeof(int) + 1) * COR_CELL_CAP;
+  const MapView mv = h->cor.map_view();
+  const PathGeom pg = h->cor.path_geom(h->tab, h->cfg.circular);
+  h->io.have_rows = per_car;     // K1 / K2 read the per-instance rows K0c writes (else: the table)
+  const int movers = per_car && h->obs.mv_B > 0 ? h->obs.mv_n : 0;
+  const MoverPath mp{h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gtrig, h->tab.n_wp, COR_TRIG, h->cfg.circular ? 1 : 0};
+  const double* mv_p = (const double*)h->obs.mv_block.get();
+  const int* mv_i = (const int*)(mv_p + (size_t)MOV_PARAMS * movers);
+  for (int t = 0; t < n_steps; ++t) {
+    char* rec = recording && h->rec.ro_steps % h->rec.stride == 0 ? h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)h->rec.count : nullptr;
+    if (rec)
+      hipLaunchKernelGGL(mpmpc_record_snapshot_kernel, dim3((unsigned)(((long)B * RO_REC_BEGIN_ENTRIES + 255) / 256)), dim3(256), 0,
+                         sl.stream, B, h->ro.s, h->ro.pose, h->ro.alive, h->rec.ain, rec, h->rec.lay);
+    hipLaunchKernelGGL(mpmpc_localise_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.N, h->cfg.circular ? 1 : 0,
+                       h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, h->ro.s, h->ro.pose, h->ro.alive, h->io.wp_id, h->io.x0, h->ro.shift);
+    if (movers > 0)
+      hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
+                         h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs);
+    if (per_car)
+      hipLaunchKernelGGL(mpmpc_car_corridor_kernel, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
+                         h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells,
+                         h->cor.line_box, h->obs.obst_off, h->obs.obst_discs, h->io.wp_id, h->ro.alive, h->obs.ro_flag, h->io.lb, h->io.ub);
+    if (int rc = launch_solve(h, sl, B, true, false)) return rc;  // (the plant step reads z and the status only)
+    hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro.Ts,
+                       h->tab.kappa, h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter, h->ro.alive, h->ro.pose, h->ro.s, h->ro.u);
+    if (rec) {
+      const RoRecSrc src{h->ro.alive, h->rec.ain, h->io.wp_id, sl.status, h->ro.counter, h->io.x0, h->ro.u, h->io.cc, sl.z,
+                         h->cor.gx, h->cor.gy, h->cor.gtrig, per_car ? h->io.ub : h->tab.ub_tab, per_car ? h->io.lb : h->tab.lb_tab,
+                         per_car ? (long long)N : (long long)h->tab.n_cols, per_car ? 1 : 0, COR_TRIG, N, h->tab.n_wp, h->cfg.circular ? 1 : 0};
+      hipLaunchKernelGGL(mpmpc_record_write_kernel, dim3((unsigned)(((long)B * h->rec.lay.entries + 255) / 256)), dim3(256), 0,
+                         sl.stream, B, src, rec, h->rec.lay);
+      ++h->rec.count;
+    }
+    ++h->rec.ro_steps;
+  }
+  HIP_TRY(hipGetLastError());
+  if (n_steps > 0) h->obs.car_rows = h->obs.discs_live = per_car;
+  return MPMPC_OK;
+}
+
+// Lays out the device's per-car disc lists from the two host-side settings (st_* / mv_*): combined offsets, the static
+// discs in place, every mover slot as the absent disc (K0m fills the slots in front of every K0c), and the movers' slot
+// indices.  new_mv: the movers' block as mpmpc_rollout_set_movers assembled it ([4][n] doubles, [2][n] ints kind / radius,
+// the slots follow on the device), or NULL when the movers did not change (only their slot indices are written anew).
+static int sync_disc_lists(mpmpc_handle h, std::vector<char>* new_mv) {
+  const int B = h->obs.st_B > 0 ? h->obs.st_B : h->obs.mv_B;
+  h->obs.obst_B = B;
+  h->obs.discs_live = false;
+  if (B == 0) return MPMPC_OK;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  Slot& sl = h->last();
+  const size_t mb = (size_t)h->cfg.max_batch;
+  if (!h->obs.obst_off) HIP_TRY(alloc_all(Want{h->obs.obst_off, mb + 1}, Want{h->obs.obst_discs, 3 * COR_MAX_DISCS * mb}));      // (both or neither)
+  if (!h->obs.ro_flag) HIP_TRY(h->obs.ro_flag.alloc(mb));
+  const int n = h->obs.mv_B > 0 ? h->obs.mv_n : 0;
+  h->obs.comb_off.assign((size_t)B + 1, 0);
+  std::vector<int32_t> dst((size_t)n);
+  mov_combine(B, h->obs.st_B > 0 ? h->obs.st_off.data() : nullptr, h->obs.mv_B > 0 ? h->obs.mv_off.data() : nullptr, h->obs.comb_off.data(),
+              dst.data());
+  const size_t total = (size_t)h->obs.comb_off[B];
+  std::vector<int32_t> discs(3 * total, 0);
+  if (h->obs.st_B > 0)
+    for (int b = 0; b < B; ++b)
+      std::memcpy(discs.data() + 3 * (size_t)h->obs.comb_off[b], h->obs.st_discs.data() + 3 * (size_t)h->obs.st_off[b],
+                  sizeof(int32_t) * 3 * (size_t)(h->obs.st_off[b + 1] - h->obs.st_off[b]));
+  HIP_TRY(hipMemcpyAsync(h->obs.obst_off, h->obs.comb_off.data(), sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, sl.stream));
+  if (total > 0) HIP_TRY(hipMemcpyAsync(h->obs.obst_discs, discs.data(), sizeof(int) * 3 * total, hipMemcpyHostToDevice, sl.stream));
+  if (n > 0) {
+    const size_t head = (sizeof(double) * MOV_PARAMS + 2 * sizeof(int)) * (size_t)n;      // parameters, kind, radius
+    if (new_mv) {
+      const size_t bytes = (sizeof(double) * MOV_PARAMS + 3 * sizeof(int)) * (size_t)n;      // + the slots
+      if (bytes > h->obs.mv_block.count()) HIP_TRY(h->obs.mv_block.alloc(bytes));             // (only grows)
+      HIP_TRY(hipMemcpyAsync(h->obs.mv_block, new_mv->data(), head, hipMemcpyHostToDevice, sl.stream));
+    }
+    HIP_TRY(hipMemcpyAsync(h->obs.mv_block + head, dst.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, sl.stream));
+  }
+  HIP_TRY(hipStreamSynchronize(sl.stream));      // the host vectors leave scope
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* discs) {
+  if (int rc = enter(h)) return rc;
+  if (!offsets) {      // no static discs: back to the shared table, unless movers are set
+    h->obs.st_B = 0;
+    return sync_disc_lists(h, nullptr);
+  }
+  const char* why = "";
+  if (int rc = cor_check_obstacles(B, h->cfg.max_batch, offsets, discs, h->cor.built(h->tab), h->cor.map_w, h->cor.map_h, &why))
+    return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  if (int rc = mov_check_combined(B, offsets, h->obs.mv_B, h->obs.mv_off.data(), &why))
+    return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  h->obs.st_off.assign(offsets, offsets + (size_t)B + 1);
+  h->obs.st_discs.assign(discs, discs + 3 * (size_t)offsets[B]);
+  h->obs.st_B = B;
+  h->obs.obst_gen = h->cor.base_gen;
+  return sync_disc_lists(h, nullptr);
+}
+
+int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* kind,
+                             const int32_t* radius_cells, const double* params, int64_t step0) {
+  if (int rc = enter(h)) return rc;
+  if (!offsets) {      // no movers
+    h->obs.mv_B = 0;
+    h->obs.mv_n = 0;
+    return sync_disc_lists(h, nullptr);
+  }
+  const char* why = "";
+  if (int rc = mov_check_movers(B, h->cfg.max_batch, offsets, kind, radius_cells, params, h->cor.built(h->tab), h->obs.st_B, h->obs.st_off.data(), &why))
+    return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  const size_t n = (size_t)offsets[B];
+  std::vector<char> blk((sizeof(double) * MOV_PARAMS + 2 * sizeof(int)) * n);
+  double* p = (double*)blk.data();
+  int32_t* ki = (int32_t*)(p + MOV_PARAMS * n);
+  for (size_t j = 0; j < n; ++j) {
+    for (int t = 0; t < MOV_PARAMS; ++t) p[(size_t)t * n + j] = params[MOV_PARAMS * j + t];
+    ki[j] = kind[j];
+    ki[n + j] = radius_cells[j];
+  }
+  h->obs.mv_off.assign(offsets, offsets + (size_t)B + 1);
+  h->obs.mv_B = B;
+  h->obs.mv_n = (int)n;
+  h->obs.mv_step0 = step0;
+  h->obs.mv_gen = h->cor.base_gen;
+  return sync_disc_lists(h, &blk);
+}
+
+int mpmpc_rollout_obstacles(mpmpc_handle h, int32_t B, int32_t* discs_out, int32_t* offsets_out) {
+  if (int rc = enter(h)) return rc;
+  Slot& sl = h->last();
+  if (int rc = h->ro.check(B)) return rc;
+  if (!h->obs.car_rows || !h->obs.discs_live || B != h->obs.obst_B)
+    return fail(MPMPC_E_STATE, "the last rollout step did not build per-car rows for B cars, or the obstacles / movers were set anew "
+                               "since (mpmpc_rollout_set_obstacles / mpmpc_rollout_set_movers)");
+  if (offsets_out) std::memcpy(offsets_out, h->obs.comb_off.data(), sizeof(int32_t) * ((size_t)B + 1));
+  if (discs_out && h->obs.comb_off[B] > 0) {
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(hipMemcpyAsync(discs_out, h->obs.obst_discs, sizeof(int) * 3 * (size_t)h->obs.comb_off[B], hipMemcpyDeviceToHost, sl.stream));
+    HIP_TRY(hipStreamSynchronize(sl.stream));
+  }
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_corridor(mpmpc_handle h, int32_t B, double* ub, double* lb) {
+  if (int rc = enter(h, ub && lb)) return rc;
+  Slot& sl = h->last();
+  if (int rc = h->ro.check(B)) return rc;
+  if (!h->obs.car_rows) return fail(MPMPC_E_STATE, "the last rollout step did not build per-car rows (mpmpc_rollout_set_obstacles)");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t nb = (size_t)B * h->cfg.N;
+  std::vector<int> flag(B);
+  HIP_TRY(hipMemcpyAsync(ub, h->io.ub, sizeof(double) * nb, hipMemcpyDeviceToHost, sl.stream));
+  HIP_TRY(hipMemcpyAsync(lb, h->io.lb, sizeof(double) * nb, hipMemcpyDeviceToHost, sl.stream));
+  HIP_TRY(hipMemcpyAsync(flag.data(), h->obs.ro_flag, sizeof(int) * B, hipMemcpyDeviceToHost, sl.stream));
+  HIP_TRY(hipStreamSynchronize(sl.stream));
+  for (int b = 0; b < B; ++b)
+    if (flag[b] != COR_ROW_OK)
+      for (int n = 0; n < h->cfg.N; ++n) ub[(size_t)b * h->cfg.N + n] = lb[(size_t)b * h->cfg.N + n] = std::nan("");
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_warm_start(mpmpc_handle h, int32_t enable) {
+  if (int rc = enter(h)) return rc;
+  h->ro.warm = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_state(mpmpc_handle h, int32_t B, double* s, double* pose, double* cc, int32_t* wp_id, double* x0,
+                        double* u_last, int32_t* status, int32_t* counter, int32_t* alive) {
+  if (int rc = enter(h)) return rc;
+  Slot& sl = h->last();
+  if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
+                              "call mpmpc_rollout_init again")) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const int N = h->cfg.N;
+#define PULL(dst, src, bytes) if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.stream))
+  PULL(s, h->ro.s, sizeof(double) * B);
+  PULL(pose, h->ro.pose, sizeof(double) * 3 * B);
+  PULL(cc, h->io.cc, sizeof(double) * 2 * N * B);
+  PULL(wp_id, h->io.wp_id, sizeof(int) * B);
+  PULL(x0, h->io.x0, sizeof(double) * 3 * B);
+  PULL(u_last, h->ro.u, sizeof(double) * 2 * B);
+  PULL(status, sl.status, sizeof(int) * B);
+  PULL(counter, h->ro.counter, sizeof(int) * B);
+  PULL(alive, h->ro.alive, sizeof(int) * B);
+#undef PULL
+  HIP_TRY(hipStreamSynchronize(sl.stream));
+  return MPMPC_OK;
+}
+
+}  // extern "C"

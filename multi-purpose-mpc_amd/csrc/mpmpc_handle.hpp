@@ -1,0 +1,232 @@
+// The handle of libmpmpc.so: the error channel, the sub-states a handle is made of - each with its buffers (device_buf.hpp: the
+// handle's destructor frees them), its counts and flags and the views the kernels take - the launch slots, and settle / drain.
+// Part of the one translation unit mpmpc_hip.hip (included there after the solve kernels); host code only.
+// Field names: a field drops the prefix that names its own sub-state (ro.s, rec.cap); every other name is kept.
+#pragma once
+#include "device_buf.hpp"
+
+static thread_local std::string g_err;
+static int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+// (expr: a HIP call, or an allocation of device_buf.hpp, which returns the runtime's code as an int)
+#define HIP_TRY(expr)                                                                              \
+  do {                                                                                             \
+    hipError_t e_ = static_cast<hipError_t>(expr);                                                 \
+    if (e_ != hipSuccess)                                                                          \
+      return fail(MPMPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
+  } while (0)
+
+// path and corridor tables
+struct TabState {
+  Buf<double> kappa, v_ref, ds_next, ub_tab, lb_tab;
+  int n_wp = 0, n_cols = 0;
+  PathTables path_tables() const { return PathTables{kappa, v_ref, ds_next, n_wp, ub_tab, lb_tab, n_cols}; }
+};
+
+// corridor generation on the device: grid, per-waypoint geometry, per-waypoint free segments
+struct CorState {
+  Buf<int8_t> map;
+  int map_h = 0, map_w = 0;
+  double map_ox = 0, map_oy = 0, map_res = 0;
+  Buf<double> gx, gy, gpsi, bub, blb, segs, gtrig;
+  Buf<int> nseg, bad;      // bad[0]: start waypoints without a free segment, bad[1]: K0a overflow code
+  int geom_n = 0;
+  std::vector<double> host_bub, host_blb;   // border points, kept to validate them against the map of the moment
+  // per-car obstacles (K0c): cached border lines of the last build, and what that build was made from
+  Buf<int> line_cells, line_box;      // [n_wp x COR_CELL_CAP], [n_wp x COR_LINE_BOX]
+  unsigned base_gen = 1;        // bumped by mpmpc_set_path / _set_map / _set_path_geometry
+  unsigned built_gen = 0;       // base_gen of the last successful mpmpc_build_corridor (0: none)
+  double built_min_width = 0, built_sm = 0;
+  MapView map_view() const { return MapView{map, map_h, map_w, map_ox, map_oy, map_res}; }
+  PathGeom path_geom(const TabState& tab, int circular) const { return PathGeom{gx, gy, gpsi, tab.ds_next, tab.n_wp, circular, gtrig}; }
+  double* forced_rows(const TabState& tab) const { return segs.get() + (size_t)4 * COR_MAXSEG * tab.n_wp; }      // cor_forced rows behind the segments
+  // the corridor is built for the current map and path
+  bool built(const TabState& tab) const { return built_gen == base_gen && built_gen != 0 && tab.n_cols > 0 && line_cells; }
+};
+
+// per-car discs and movers
+struct ObsState {
+  Buf<int> obst_off, obst_discs, ro_flag;   // CSR lists on the device, per-car row verdicts
+  int obst_B = 0;               // > 0: the rollout's cars carry their own discs (mpmpc_rollout_set_obstacles)
+  unsigned obst_gen = 0;        // base_gen the discs were validated against
+  bool car_rows = false;        // the last rollout step built per-car rows
+  // The two per-car settings, kept on the host: static discs (mpmpc_rollout_set_obstacles; st_B > 0: set; obst_gen) and
+  // movers (mpmpc_rollout_set_movers; mv_B > 0: set; mv_gen).  Whichever setter is called lays out ONE CSR list per car
+  // on the device (obst_off / obst_discs, what K0c reads: the static discs, then a slot per mover that K0m fills every
+  // step) - sync_disc_lists; obst_B is the B of whichever is set.
+  std::vector<int32_t> st_off, st_discs, mv_off, comb_off;
+  int st_B = 0, mv_B = 0, mv_n = 0;      // mv_n: movers of the fleet
+  unsigned mv_gen = 0;          // base_gen the movers were set against
+  long long mv_step0 = 0;
+  Buf<char> mv_block;           // [4][mv_n] doubles (parameters), then [mv_n] ints each: kind, radius, slot; only grows
+  bool discs_live = false;      // obst_discs hold the lists the last rollout step used (mpmpc_rollout_obstacles)
+};
+
+// closed-loop rollout state
+struct RoState {
+  Buf<double> cum, s, pose, u;
+  Buf<int> counter, alive, act, shift;      // act, shift: warm start - certified active sets [B x ld], waypoints advanced [B]
+  int warm = 2;      // 0 off, 1 on, 2 where it pays (see plan_solve)
+  double Ts = 0;
+  int B = 0;
+  bool valid = false;      // the batch blocks still hold the rollout's plans / waypoint ids / states
+  // Does the handle hold the state of a rollout of at least B cars?  `overwritten`: the entry point's own text for a state
+  // that an upload has overwritten (none given: the short form serves for both)
+  int check(int B_, const char* overwritten = "call mpmpc_rollout_init for at least B cars first") const {
+    if (B_ < 1 || B_ > B) return fail(MPMPC_E_STATE, "call mpmpc_rollout_init for at least B cars first");
+    return valid ? MPMPC_OK : fail(MPMPC_E_STATE, overwritten);
+  }
+};
+
+// recorder (mpmpc_rollout_record): the trace has its own memory, [cap] records of lay.bytes each
+struct RecState {
+  Buf<char> buf;
+  Buf<int> ain;             // [B] alive before the step being recorded
+  RoTraceLayout lay{};
+  int cap = 0, B = 0, fields = 0, stride = 1;
+  int count = 0;            // records held
+  long long ro_steps = 0;   // rollout steps since mpmpc_rollout_init
+  // records that steps ro_steps .. ro_steps + n_steps - 1 add (every stride-th step counted from mpmpc_rollout_init)
+  long long records_of(long long n_steps) const { return (ro_steps + n_steps + stride - 1) / stride - (ro_steps + stride - 1) / stride; }
+};
+
+// per-batch inputs and host staging
+struct IoState {
+  // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
+  // of the last upload), and so do the outputs of every launch slot (Slot::out_block: u0, resid, status, iters, z, y): an upload
+  // or a download through the pinned staging buffers is then a single copy instead of five or six - what a single-car call is made of
+  Buf<char> in_block;
+  int* wp_id = nullptr;       // pointers into it (lay_out):
+  double *x0 = nullptr, *cc = nullptr, *lb = nullptr, *ub = nullptr;
+  bool have_rows = false;     // per-instance corridor rows uploaded (else: table)
+  int uploaded = 0, laid_out = 0;
+  Buf<double> qp;      // stage-blocked QP
+  // pinned host staging for mpmpc_upload / mpmpc_download (small copies from pageable memory are
+  // synchronous and slow; empty above STAGE_LIMIT bytes: large batches amortise the direct path)
+  Buf<char, Mem::Pinned> stage_in, stage_out;
+  hipEvent_t ev_in = nullptr;      // the last staged upload has left the pinned buffer
+  bool in_flight = false;
+  // ... above that limit an upload goes through a small page-locked bounce buffer in two halves (allocated by the first such
+  // upload): the device copy of one half runs while the host fills the other, and the call returns when the caller's buffers
+  // have been read - not when the device has them.  (A copy from pageable memory is synchronous: one process feeding several
+  // devices - sharded.py - would otherwise serve them one after the other)
+  Buf<char, Mem::Pinned> bounce;
+  hipEvent_t ev_bounce[2] = {nullptr, nullptr};
+  bool bounce_busy[2] = {false, false};
+  int bounce_turn = 0;
+  // what the solve kernels and K1 read of a batch
+  AssembleIn inputs(const TabState& tab) const { return AssembleIn{tab.path_tables(), wp_id, x0, cc, have_rows ? lb : nullptr, have_rows ? ub : nullptr}; }
+  size_t staged_bytes = 0;  // mpmpc_staged_begin without its mpmpc_staged_end: bytes of the output block on their way back
+  bool staged_async = true; // mpmpc_staged_begin was called as such (not as the first half of mpmpc_solve_staged)
+};
+
+struct mpmpc_handle_s {
+  mpmpc_config cfg;
+  mpmpc_settings st;
+  int ld = 0, n = 0, m = 0;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  TabState tab;
+  CorState cor;
+  ObsState obs;
+  RoState ro;
+  RecState rec;
+  IoState io;
+  // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
+  // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that
+  // never pipelines; slot[1 .. n_slots - 1] are made by the first pipelined resident launch (next_slot).  `cur` is the slot of the
+  // LAST launch, and everything in this library that is not a resident launch - uploads, downloads, the staged calls, corridor build,
+  // rollout, recorder, timed launches - works on last(): its stream, its outputs.  A resident launch first moves `cur` one slot on
+  // (round robin over the `pipeline` slots in use), so that launches k + 1 .. k + pipeline - 1 run beside launch k, each on its
+  // own stream, writing its own outputs.  A function that acts on a slot is handed it; nothing is copied between slots.
+  struct Slot {
+    hipStream_t stream = nullptr;
+    Buf<char> out_block;      // pointers into it (lay_out):
+    double *z = nullptr, *u0 = nullptr, *resid = nullptr, *y = nullptr;
+    int *status = nullptr, *iters = nullptr;
+    bool y_valid = false;     // the slot's last solve launch stored y
+    bool busy = false;        // resident launches in flight on the slot's stream that nothing has waited for yet
+    // instances the early pass of a packed (2 or 4 per wave) launch could not certify: [0] = count, [1..] = ids
+    Buf<int> tail;
+    int tail_flip = 0;          // which of the two lists the next reduced-native launch fills
+    // Deferred tail (batch launches of the reduced-native kernels, not the closed loop).  Launching the tail kernel costs
+    // 4.8 us even when its list is empty - 10 % of a 1 024-instance step - so when the last launch whose outcome the host
+    // has SEEN left no tail, the next launches do not enqueue one: the reduced-native kernel stamps its sequence number into
+    // tail_flag (host memory) if it appends anything, and every entry point through which results or state can be observed
+    // or changed (sync, download, upload, set_*, rollout, timed launches) first drains the stream, looks at the stamp and
+    // runs the tail of the slot's LAST launch if it left one (observe_tail).  A launch that is followed by another launch on
+    // the slot without such a call in between has unobservable results either way (same output buffers).
+    Buf<unsigned, Mem::Pinned> tail_flag;         // page-locked, device-visible
+    unsigned seq = 0;                   // sequence number of the last reduced-native launch
+    bool tail_expect_empty = false;     // the last observed launch left no tail
+    bool tail_ran_late = false;         // the last observe_tail had to run a deferred tail
+    // Second level (reduced_native_tail configurations): the tail goes to the reduced-native tail kernel first, which appends
+    // what IT leaves to a third list (tail + 2 (max_batch + 1)) and stamps tail_flag[1]; the general kernel on that list is
+    // deferred by the same rule.
+    bool tail2_expect_empty = false;
+    // The slot's last solve launch: its plan (mpmpc_launch_plan.hpp), the first stage not yet enqueued, and what the stages
+    // still to come need of the launch they belong to - the batch size, whether y is stored, the solver parameters, the lists
+    // by role (MPMPC_LIST_*).  (The handle's input buffers and path tables are read when a stage is enqueued: every call that
+    // changes them settles first.)
+    SolvePlan plan{};
+    int next_stage = 0;
+    int launch_B = 0;
+    bool want_y = false;
+    SolverParams prm{};
+    int* list[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool deferred() const { return next_stage < plan.n; }      // stages of the last launch were held back
+  };
+  static constexpr int MAX_PIPELINE = 8;
+  Slot slot[MAX_PIPELINE];
+  int n_slots = 0;          // slots allocated: slot[0 .. n_slots - 1]
+  int cur = 0;              // the slot of the last launch
+  Slot& last() { return slot[cur]; }
+  int pipeline = 3;         // launch slots in use = resident launches in flight (1 = one slot only): what mpmpc_set_pipeline asked
+                            // for, three by default, but never more than the process has hardware queues (launch_streams:
+                            // GPU_MAX_HW_QUEUES, 4 if unset) - two streams on one queue take turns.  Measured, config 2, four
+                            // queues: depth 4 = 68.7 M solves/s with the four launch streams on four queues, 39.5 M while a
+                            // synchronous memset of this library had made the null stream hold one of them (two launch streams
+                            // shared a queue: 2.0 instead of 3.85 solve kernels on the chip; profiles/hw_queues/)
+  hipEvent_t ev_order = nullptr;
+  bool order_pending = false;      // asynchronous work other than resident solves is queued on last().stream: the next resident launch
+                                   // goes to ANOTHER stream and has to wait for it (uploads, closed-loop steps: they write what solves read)
+  int force_lanes = 0;      // mpmpc_set_packing: 0 = chosen from the batch size
+  // mpmpc_set_tail_kernel (MPMPC_LEAN_TAIL=0 in the environment: off from the start, for A/B timings of whole programs)
+  bool lean_tail = !(std::getenv("MPMPC_LEAN_TAIL") && std::atoi(std::getenv("MPMPC_LEAN_TAIL")) == 0);
+  bool lean_tail_single = std::getenv("MPMPC_LEAN_TAIL") && std::atoi(std::getenv("MPMPC_LEAN_TAIL")) == 2;      // ONE tail instance per wave
+  bool resident_y = true;   // mpmpc_set_outputs: do resident launches store the multipliers y (46 % of the output bytes)?
+};
+using Slot = mpmpc_handle_s::Slot;
+
+static int observe_tail(mpmpc_handle h, Slot& s);
+// The other slots' launches are drained and their deferred tails, if any, are run (the slot of the last launch is left as it
+// is: what follows on its stream is ordered behind it anyway).
+static int settle_other_slots(mpmpc_handle h) {
+  for (int i = 0; i < h->n_slots; ++i) {
+    Slot& s = h->slot[i];
+    if (i == h->cur || (!s.busy && !s.deferred())) continue;
+    if (int rc = observe_tail(h, s)) return rc;
+  }
+  return MPMPC_OK;
+}
+// ... and then the slot of the last launch: every launch of the handle is done, deferred tails included
+static int drain(mpmpc_handle h) {
+  if (int rc = settle_other_slots(h)) return rc;
+  return observe_tail(h, h->last());
+}
+// first statement of every entry point that reads results or changes what a launch in flight - or a deferred tail launch -
+// works on: `if (int rc = settle(h)) return rc;`
+static int settle(mpmpc_handle h) {
+  if (int rc = mpmpc_staged_end(h)) return rc;      // (of a staged call that was begun, if any)
+  if (int rc = settle_other_slots(h)) return rc;
+  if (h->last().deferred()) {
+    if (int rc = observe_tail(h, h->last())) return rc;
+  }
+  h->order_pending = true;
+  return MPMPC_OK;
+}
+// ... of an entry point whose only pointer is the handle: `if (int rc = enter(h)) return rc;`
+static int enter(mpmpc_handle h) { return h ? settle(h) : fail(MPMPC_E_ARG, "handle is NULL"); }
+// ... and of one with further pointers that must not be null: `if (int rc = enter(h, a && b)) return rc;`
+static int enter(mpmpc_handle h, bool others) { return h && others ? settle(h) : fail(MPMPC_E_ARG, "NULL argument"); }

@@ -1,5 +1,5 @@
 // Moving obstacles of the device rollout ("movers"): where a car's moving discs are at rollout step k.  Scalar
-// per-mover code that compiles for gfx950 (K0m, mpmpc_obstacle_move_kernel in mpmpc_hip.hip) and for the host
+// per-mover code that compiles for gfx950 (K0m, mpmpc_obstacle_move_kernel in mpmpc_closed_loop.hpp) and for the host
 // (tests/emul_movers), like corridor_core.hpp and rollout_core.hpp.
 //
 // A mover is a disc of constant radius r (map cells, Map.add_obstacles' ceil(radius / resolution)) whose centre is a

@@ -1,5 +1,5 @@
 // Closed-loop step around the QP solve, scalar per-instance code that compiles for gfx950 (K3
-// kernels in mpmpc_hip.hip) and for the host (tests/emul).  Replaces, for B cars at once, what
+// kernels in mpmpc_closed_loop.hpp) and for the host (tests/emul).  Replaces, for B cars at once, what
 // src/simulation.py:134-140 does per step on the host:
 //   localise   SpatialBicycleModel.get_current_waypoint   src/spatial_bicycle_models.py:256-279
 //              SpatialBicycleModel.t2s                    src/spatial_bicycle_models.py:183-219

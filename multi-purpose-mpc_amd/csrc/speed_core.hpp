@@ -1,5 +1,5 @@
 // Speed profile of a reference path (K4): per-path code written against an execution policy - one wavefront per
-// path on gfx950 (SpWave in mpmpc_hip.hip: lane-strided loops, shuffle reductions, cyclic reduction for the
+// path on gfx950 (SpWave in mpmpc_speed_profile.hpp: lane-strided loops, shuffle reductions, cyclic reduction for the
 // tridiagonal systems), one thread per path for very long paths and on the host (SpSerial; tests/emul).
 //
 // Replaces ReferencePath.compute_speed_profile (src/reference_path.py:289-354), the reference's second
@@ -66,7 +66,7 @@ MPMPC_HD void sp_tri_factor(const SpWork& W, int n) {
 }
 
 // Execution policy of sp_solve_t.  SpSerial: one thread walks the path (host emulation, and the thread-per-path
-// kernel for very long paths).  The device's SpWave (mpmpc_hip.hip) spreads the elementwise loops over the 64 lanes
+// kernel for very long paths).  The device's SpWave (mpmpc_speed_profile.hpp) spreads the elementwise loops over the 64 lanes
 // of a wavefront, reduces with shuffles and solves the tridiagonal systems by parallel cyclic reduction.
 struct SpSerial {
   MPMPC_HD int first() const { return 0; }

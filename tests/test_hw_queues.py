@@ -66,9 +66,14 @@ def test_the_policy_symbols_are_pure(lib):
 
 
 def test_library_source_never_writes_the_environment_or_uses_the_null_stream():
-    src = open(os.path.join(T.ROOT, "multi-purpose-mpc_amd", "csrc", "mpmpc_hip.hip")).read()
-    for word in ("setenv(", "putenv(", "hipMemset(", "hipMemcpy(", "hipDeviceSynchronize("):
-        assert word not in src, word
+    """the library's translation unit: the .hip and every header beside it (host code lives in headers too)"""
+    csrc = os.path.join(T.ROOT, "multi-purpose-mpc_amd", "csrc")
+    files = ["mpmpc_hip.hip"] + sorted(f for f in os.listdir(csrc) if f.endswith(".hpp"))
+    assert len(files) > 1
+    for name in files:
+        src = open(os.path.join(csrc, name)).read()
+        for word in ("setenv(", "putenv(", "hipMemset(", "hipMemcpy(", "hipDeviceSynchronize("):
+            assert word not in src, (name, word)
 
 
 def _child(mode, limit):
