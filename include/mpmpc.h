@@ -262,7 +262,9 @@ int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, doubl
  *          With per-car obstacles (mpmpc_rollout_set_obstacles) also: -3 the first horizon waypoint of the car's
  *          world has no free segment (the reference raises in update_path_constraints), -4 a border line of the
  *          car's world has more than 8 free segments (COR_MAXSEG, a limit of this library); wp_id and x0 hold
- *          that step's state, the car is not driven, the other cars are unaffected.
+ *          that step's state, the car is not driven, the other cars are unaffected.  The lists K0c reads hold the car's
+ *          static discs, its movers (mpmpc_rollout_set_movers) and its traffic slots (mpmpc_rollout_set_traffic): a row
+ *          blocked by another car's disc ends the car with -3 in the same way.
  * The rollout keeps its plans, waypoint ids and states in the handle's batch blocks: mpmpc_upload / mpmpc_solve /
  * mpmpc_assemble on the SAME handle overwrite them, after which mpmpc_rollout_step / _state / _set_counters return
  * MPMPC_E_STATE until mpmpc_rollout_init is called again.  (mpmpc_download and mpmpc_build_corridor are fine.) */
@@ -324,13 +326,34 @@ int mpmpc_rollout_corridor(mpmpc_handle h, int32_t B, double* ub, double* lb);
  *                           step0 may be negative: a run resumed from a saved state of step k0 (mpmpc_rollout_init
  *                           restarts k at 0) continues its movers with step0 - k0.
  *   mpmpc_rollout_obstacles the disc lists the LAST rollout step used: offsets_out [B+1], discs_out [offsets_out[B]][3]
- *                           (at most 64 B entries; either pointer may be NULL), per car the static discs and then the
- *                           movers, absent ones as (0, 0, 0).  MPMPC_E_STATE if that step built no per-car rows (as
- *                           mpmpc_rollout_corridor), or if either setting was changed since.
+ *                           (at most 64 B entries; either pointer may be NULL), per car the static discs, then the
+ *                           movers, then the traffic slots (mpmpc_rollout_set_traffic), absent ones as (0, 0, 0).
+ *                           MPMPC_E_STATE if that step built no per-car rows (as mpmpc_rollout_corridor), or if any of
+ *                           the three settings was changed since.
  * A rollout without movers launches exactly what it launched before. */
 int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* kind,
                              const int32_t* radius_cells, const double* params, int64_t step0);
 int mpmpc_rollout_obstacles(mpmpc_handle h, int32_t B, int32_t* discs_out, int32_t* offsets_out);
+/* Traffic: the cars of a group see each other as discs, from the fleet's own poses, every step on the device (K0t) - cars
+ * that react to each other without a host round trip per step.  group[B]: cars with the same non-negative value share a
+ * world, a negative value means the car sees nobody and nobody sees it.  radius_cells[B] >= 0: the disc with which car c
+ * appears to the others (radius 0 occupies no cell).  slots S in [1, 64], the same for every car; range_cells: a car sees
+ * no further (negative: no limit).  A step reads pose and alive AS IT FINDS THEM (what mpmpc_rollout_state returns before
+ * the step; what a record holds as pose): car c is present iff alive == 1, group >= 0 and its cell w2m(x, y) lies within
+ * 2^30 cells; a present car is visible iff its disc's square stays in the grid.  A car that has ended or finished is
+ * taken off the track: it is not seen.  Car b, if present, gets the visible cars c != b of its group with
+ * d2 = (cx_c - cx_b)^2 + (cy_c - cy_b)^2 <= range_cells^2, ordered by (d2, car index): the first S as (cx_c, cy_c, r_c), the
+ * other slots (0, 0, 0); a car that is not present gets S absent discs.  The exact statement: csrc/traffic_core.hpp.
+ *   group == NULL: no traffic.  Traffic is a third independent per-car setting beside the static discs and the movers:
+ *   K0c reads, per car, the static discs, then the movers, then the S traffic slots - together at most 64 per car (else
+ *   MPMPC_E_ARG), all settings in force for the same B (else MPMPC_E_STATE); the other two setters check the same against
+ *   the traffic in force.  Also MPMPC_E_ARG: B outside [1, max_batch], a negative radius, slots outside [1, 64], a group
+ *   of more than 1024 cars.  A refused call leaves every setting as it was.  Needs mpmpc_build_corridor like the discs
+ *   (else MPMPC_E_STATE) and is void after a change of map, path or geometry in the same way.  May be called before
+ *   mpmpc_rollout_init or between mpmpc_rollout_step calls: it applies from the next step on and keeps the rollout's
+ *   state.  A rollout without traffic launches exactly what it launched before. */
+int mpmpc_rollout_set_traffic(mpmpc_handle h, int32_t B, const int32_t* group, const int32_t* radius_cells, int32_t slots,
+                              int32_t range_cells);
 
 /* Recorder: while the cars drive, the rollout appends one record per car and recorded step to a device-resident trace
  * (what src/simulation.py:117-157 logs per step on the host: x_log / y_log / v_log and MPC.current_prediction), and

@@ -295,7 +295,7 @@ class BatchMPC:
         poses = np.asarray(poses, float)
         return wp.astype(np.int32), t2s_batch(poses[:, 0], poses[:, 1], poses[:, 2], wx, wy, wpsi)
 
-    def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None):
+    def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -305,6 +305,9 @@ class BatchMPC:
         movers: None or a length-B list of lists of movers.Mover - car b's moving obstacles (a straight line, or along the
         reference path, at a constant speed), advanced on the device every step; combines with `obstacles` (together at
         most 64 per car) and needs corridor='device' as well.  movers.mover_discs gives their discs at any step index.
+        traffic: None or a traffic.Traffic - the cars of a group see each other as discs (the nearest `slots` cars within
+        `range`), from the fleet's own poses, every step on the device; combines with `obstacles` and `movers` (together at
+        most 64 per car) and needs corridor='device' as well.  traffic.traffic_discs gives the discs of any state.
         alive: 1 running, 0 lap finished (s >= length), -1 ended after N - 1 consecutive infeasible steps
         (src/MPC.py:218-220), -2 ended at the end of an open path (wp_id + N >= n_wp, where the reference's
         get_waypoint exits: src/reference_path.py:367-369; wp_id and x0 are that step's, the car is not driven),
@@ -329,17 +332,25 @@ class BatchMPC:
             if len(movers) != np.asarray(s).size:
                 raise ValueError("movers must hold one list of Mover per car")
             rows = [np.array([m.row(self.model.Ts, rp.map.resolution) for m in car], float).reshape(-1, 6) for car in movers]
+        if traffic is not None:
+            if self.corridor_cols is None:
+                raise ValueError("traffic needs corridor='device' (update_corridor_from_map)")
+            if traffic.group.size != np.asarray(s).size:
+                raise ValueError("traffic must hold one group per car")
         if getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
             wps = rp.waypoints
             self.handle.set_path_geometry([w.x for w in wps], [w.y for w in wps], [w.psi for w in wps],
                                           [w.static_border_cells[0] for w in wps],
                                           [w.static_border_cells[1] for w in wps])
-        self.handle.rollout_set_obstacles(None)       # (both off first: the two settings must agree on B while both are on)
+        self.handle.rollout_set_obstacles(None)       # (all off first: the settings must agree on B while they are on)
         self.handle.rollout_set_movers(None)
+        self.handle.rollout_set_traffic(None)
         if obstacles is not None:
             self.handle.rollout_set_obstacles(discs)
         if movers is not None:
             self.handle.rollout_set_movers(rows, step0=0)
+        if traffic is not None:
+            self.handle.rollout_set_traffic(*traffic.cells(rp.map.resolution))
         if record is None or record is False:
             self.handle.rollout_init(self.model.Ts, np.cumsum(rp.segment_lengths), s, poses, cc0)
             self.handle.rollout_step(n_steps)

@@ -1,5 +1,5 @@
 // The closed loop of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind mpmpc_set_corridor):
-// the kernels K0a / K0b (corridor tables from the map), K0c (per-car corridor rows), K0m (movers), K3a / K3b (localise, advance)
+// the kernels K0a / K0b (corridor tables from the map), K0c (per-car corridor rows), K0m (movers), K0t (traffic), K3a / K3b (localise, advance)
 // and the two recorder kernels, and their entry points - mpmpc_set_map, mpmpc_set_path_geometry, mpmpc_build_corridor and every
 // mpmpc_rollout_*.  The state they work on: the sub-states cor, obs, ro, rec of the handle (mpmpc_handle.hpp).
 #pragma once
@@ -218,6 +218,70 @@ __global__ __launch_bounds__(256) void mpmpc_obstacle_move_kernel(int n, long lo
   mov_disc(map, path, kind[j], radius[j], prm[j], prm[(long)n + j], prm[2L * n + j], prm[3L * n + j], k, step0, d);
   int* o = discs + 3L * dst[j];
   o[0] = d[0]; o[1] = d[1]; o[2] = d[2];
+}
+
+// K0t: the traffic of one rollout step (mpmpc_rollout_set_traffic; the law: traffic_core.hpp), launched in front of K3a -
+// it reads pose and alive as the step finds them - when traffic is set.  One WAVEFRONT per car b; the lanes take the
+// members of b's group strided by 64 (the host laid the groups out as a CSR list in ascending car index: tr_layout), each
+// computes its members' cells and stages their keys in LDS: d2 as b sees the member, or -1 when it is no candidate; the
+// position in the list breaks ties, as the car index would.  Then S rounds of "smallest (d2, position) above the last one
+// taken": every lane scans the keys it staged, a 64-lane butterfly takes the minimum of the pairs (unique, so every lane
+// ends with the same winner), lane t keeps the disc of round t.  The rounds end early when no candidate is left.  At the
+// end lanes 0 .. S-1 store the car's S slots - the last S entries of its disc list, where K0c reads them behind the
+// static discs and the movers.  LDS: 16 KB (TR_MAX_GROUP keys and cells); no scratch; trip counts depend on the group's
+// size and S only.
+__global__ __launch_bounds__(64) void mpmpc_traffic_kernel(int B, int S, int range_cells, MapView map,
+                                                           const double* __restrict__ pose, const int* __restrict__ alive,
+                                                           const int* __restrict__ dense, const int* __restrict__ radius,
+                                                           const int* __restrict__ members, const int* __restrict__ goff,
+                                                           const int* __restrict__ off, int* __restrict__ discs) {
+  __shared__ long long key[TR_MAX_GROUP];
+  __shared__ int cell_x[TR_MAX_GROUP], cell_y[TR_MAX_GROUP];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (b >= B) return;
+  int d[3] = {0, 0, 0};                     // lane t: slot t
+  const int g = dense[b];
+  int bx = 0, by = 0;
+  if (alive[b] == 1 && g >= 0 && tr_cell(map, pose[3L * b], pose[3L * b + 1], &bx, &by)) {      // (uniform)
+    const int g0 = goff[g];
+    int n = goff[g + 1] - g0;
+    n = n > TR_MAX_GROUP ? TR_MAX_GROUP : n;      // (the host refuses larger groups)
+    for (int p = lane; p < n; p += 64) {
+      const int c = members[g0 + p];
+      int cx = 0, cy = 0;
+      long long d2 = -1;
+      if (c != b && alive[c] == 1 && tr_cell(map, pose[3L * c], pose[3L * c + 1], &cx, &cy) && tr_visible(map, cx, cy, radius[c]))
+        d2 = tr_d2(bx, by, cx, cy, range_cells);
+      key[p] = d2;
+      cell_x[p] = cx;
+      cell_y[p] = cy;
+    }
+    __syncthreads();
+    long long last_d2 = -1;
+    int last_p = -1;
+    for (int t = 0; t < S; ++t) {
+      long long best = 0x7fffffffffffffffLL;
+      int best_p = 0x7fffffff;
+      for (int p = lane; p < n; p += 64) {
+        const long long k = key[p];
+        if (k >= 0 && tr_less(last_d2, last_p, k, p) && tr_less(k, p, best, best_p)) { best = k; best_p = p; }
+      }
+      for (int m = 32; m >= 1; m >>= 1) {
+        const int lo = __shfl_xor((int)(unsigned)(best & 0xffffffffLL), m, 64), hi = __shfl_xor((int)(best >> 32), m, 64);
+        const int op = __shfl_xor(best_p, m, 64);
+        const long long o = ((long long)hi << 32) | (unsigned)lo;
+        if (tr_less(o, op, best, best_p)) { best = o; best_p = op; }
+      }
+      if (best_p == 0x7fffffff) break;          // (uniform) no candidate left
+      if (lane == t) { d[0] = cell_x[best_p]; d[1] = cell_y[best_p]; d[2] = radius[members[g0 + best_p]]; }
+      last_d2 = best;
+      last_p = best_p;
+    }
+  }
+  if (lane < S) {
+    int* o = discs + 3L * (off[b + 1] - S + lane);
+    o[0] = d[0]; o[1] = d[1]; o[2] = d[2];
+  }
 }
 
 // K3a: where is each car on the path, and what is its path-relative state (one thread per car)
@@ -515,7 +579,8 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   const bool per_car = h->obs.obst_B > 0;
   if (per_car) {
     if (h->obs.obst_B != B) return fail(MPMPC_E_STATE, "the per-car obstacles were set for another number of cars");
-    if ((h->obs.st_B > 0 && h->obs.obst_gen != h->cor.base_gen) || (h->obs.mv_B > 0 && h->obs.mv_gen != h->cor.base_gen) || h->cor.built_gen != h->cor.base_gen)
+    if ((h->obs.st_B > 0 && h->obs.obst_gen != h->cor.base_gen) || (h->obs.mv_B > 0 && h->obs.mv_gen != h->cor.base_gen) ||
+        (h->obs.tr_B > 0 && h->obs.tr_gen != h->cor.base_gen) || h->cor.built_gen != h->cor.base_gen)
       return fail(MPMPC_E_STATE, "map, path or geometry changed since mpmpc_rollout_set_obstacles / mpmpc_build_corridor");
   }
   const bool recording = h->rec.cap > 0;
@@ -536,11 +601,16 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   const MoverPath mp{h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gtrig, h->tab.n_wp, COR_TRIG, h->cfg.circular ? 1 : 0};
   const double* mv_p = (const double*)h->obs.mv_block.get();
   const int* mv_i = (const int*)(mv_p + (size_t)MOV_PARAMS * movers);
+  const bool traffic = per_car && h->obs.tr_B > 0;
+  const int* tr_i = h->obs.tr_block;      // dense group, radius, members [B] each, then the groups' offsets
   for (int t = 0; t < n_steps; ++t) {
     char* rec = recording && h->rec.ro_steps % h->rec.stride == 0 ? h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)h->rec.count : nullptr;
     if (rec)
       hipLaunchKernelGGL(mpmpc_record_snapshot_kernel, dim3((unsigned)(((long)B * RO_REC_BEGIN_ENTRIES + 255) / 256)), dim3(256), 0,
                          sl.stream, B, h->ro.s, h->ro.pose, h->ro.alive, h->rec.ain, rec, h->rec.lay);
+    if (traffic)
+      hipLaunchKernelGGL(mpmpc_traffic_kernel, dim3(B), dim3(64), 0, sl.stream, B, h->obs.tr_S, h->obs.tr_range, mv, h->ro.pose,
+                         h->ro.alive, tr_i, tr_i + B, tr_i + 2 * (size_t)B, tr_i + 3 * (size_t)B, h->obs.obst_off, h->obs.obst_discs);
     hipLaunchKernelGGL(mpmpc_localise_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.N, h->cfg.circular ? 1 : 0,
                        h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, h->ro.s, h->ro.pose, h->ro.alive, h->io.wp_id, h->io.x0, h->ro.shift);
     if (movers > 0)
@@ -568,12 +638,12 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   return MPMPC_OK;
 }
 
-// Lays out the device's per-car disc lists from the two host-side settings (st_* / mv_*): combined offsets, the static
-// discs in place, every mover slot as the absent disc (K0m fills the slots in front of every K0c), and the movers' slot
-// indices.  new_mv: the movers' block as mpmpc_rollout_set_movers assembled it ([4][n] doubles, [2][n] ints kind / radius,
+// Lays out the device's per-car disc lists from the three host-side settings (st_* / mv_* / tr_*): combined offsets, the
+// static discs in place, every mover and traffic slot as the absent disc (K0m and K0t fill the slots in front of every
+// K0c), and the movers' slot indices.  new_mv: the movers' block as mpmpc_rollout_set_movers assembled it ([4][n] doubles, [2][n] ints kind / radius,
 // the slots follow on the device), or NULL when the movers did not change (only their slot indices are written anew).
 static int sync_disc_lists(mpmpc_handle h, std::vector<char>* new_mv) {
-  const int B = h->obs.st_B > 0 ? h->obs.st_B : h->obs.mv_B;
+  const int B = h->obs.st_B > 0 ? h->obs.st_B : (h->obs.mv_B > 0 ? h->obs.mv_B : h->obs.tr_B);
   h->obs.obst_B = B;
   h->obs.discs_live = false;
   if (B == 0) return MPMPC_OK;
@@ -586,7 +656,7 @@ static int sync_disc_lists(mpmpc_handle h, std::vector<char>* new_mv) {
   h->obs.comb_off.assign((size_t)B + 1, 0);
   std::vector<int32_t> dst((size_t)n);
   mov_combine(B, h->obs.st_B > 0 ? h->obs.st_off.data() : nullptr, h->obs.mv_B > 0 ? h->obs.mv_off.data() : nullptr, h->obs.comb_off.data(),
-              dst.data());
+              dst.data(), h->obs.tr_B > 0 ? h->obs.tr_S : 0);
   const size_t total = (size_t)h->obs.comb_off[B];
   std::vector<int32_t> discs(3 * total, 0);
   if (h->obs.st_B > 0)
@@ -610,14 +680,14 @@ static int sync_disc_lists(mpmpc_handle h, std::vector<char>* new_mv) {
 
 int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* discs) {
   if (int rc = enter(h)) return rc;
-  if (!offsets) {      // no static discs: back to the shared table, unless movers are set
+  if (!offsets) {      // no static discs: back to the shared table, unless movers or traffic are set
     h->obs.st_B = 0;
     return sync_disc_lists(h, nullptr);
   }
   const char* why = "";
   if (int rc = cor_check_obstacles(B, h->cfg.max_batch, offsets, discs, h->cor.built(h->tab), h->cor.map_w, h->cor.map_h, &why))
     return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
-  if (int rc = mov_check_combined(B, offsets, h->obs.mv_B, h->obs.mv_off.data(), &why))
+  if (int rc = mov_check_combined(B, offsets, h->obs.mv_B, h->obs.mv_off.data(), &why, h->obs.tr_B, h->obs.tr_S))
     return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
   h->obs.st_off.assign(offsets, offsets + (size_t)B + 1);
   h->obs.st_discs.assign(discs, discs + 3 * (size_t)offsets[B]);
@@ -635,7 +705,8 @@ int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, 
     return sync_disc_lists(h, nullptr);
   }
   const char* why = "";
-  if (int rc = mov_check_movers(B, h->cfg.max_batch, offsets, kind, radius_cells, params, h->cor.built(h->tab), h->obs.st_B, h->obs.st_off.data(), &why))
+  if (int rc = mov_check_movers(B, h->cfg.max_batch, offsets, kind, radius_cells, params, h->cor.built(h->tab), h->obs.st_B, h->obs.st_off.data(), &why,
+                                h->obs.tr_B, h->obs.tr_S))
     return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
   const size_t n = (size_t)offsets[B];
   std::vector<char> blk((sizeof(double) * MOV_PARAMS + 2 * sizeof(int)) * n);
@@ -654,13 +725,39 @@ int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, 
   return sync_disc_lists(h, &blk);
 }
 
+int mpmpc_rollout_set_traffic(mpmpc_handle h, int32_t B, const int32_t* group, const int32_t* radius_cells, int32_t slots,
+                              int32_t range_cells) {
+  if (int rc = enter(h)) return rc;
+  if (!group) {      // no traffic
+    h->obs.tr_B = 0;
+    return sync_disc_lists(h, nullptr);
+  }
+  const char* why = "";
+  if (int rc = tr_check_traffic(B, h->cfg.max_batch, group, radius_cells, slots, h->cor.built(h->tab), h->obs.st_B, h->obs.st_off.data(),
+                                h->obs.mv_B, h->obs.mv_off.data(), &why))
+    return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t nb = (size_t)B;
+  std::vector<int32_t> blk(4 * nb + 1);      // dense group, radius, members, the groups' offsets
+  const int G = tr_layout(B, group, blk.data(), blk.data() + 3 * nb, blk.data() + 2 * nb);
+  std::memcpy(blk.data() + nb, radius_cells, sizeof(int32_t) * nb);
+  if (!h->obs.tr_block) HIP_TRY(h->obs.tr_block.alloc(4 * (size_t)h->cfg.max_batch + 1));
+  HIP_TRY(hipMemcpyAsync(h->obs.tr_block, blk.data(), sizeof(int) * (3 * nb + (size_t)G + 1), hipMemcpyHostToDevice, h->last().stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));      // `blk` leaves scope
+  h->obs.tr_B = B;
+  h->obs.tr_S = slots;
+  h->obs.tr_range = range_cells;
+  h->obs.tr_gen = h->cor.base_gen;
+  return sync_disc_lists(h, nullptr);
+}
+
 int mpmpc_rollout_obstacles(mpmpc_handle h, int32_t B, int32_t* discs_out, int32_t* offsets_out) {
   if (int rc = enter(h)) return rc;
   Slot& sl = h->last();
   if (int rc = h->ro.check(B)) return rc;
   if (!h->obs.car_rows || !h->obs.discs_live || B != h->obs.obst_B)
-    return fail(MPMPC_E_STATE, "the last rollout step did not build per-car rows for B cars, or the obstacles / movers were set anew "
-                               "since (mpmpc_rollout_set_obstacles / mpmpc_rollout_set_movers)");
+    return fail(MPMPC_E_STATE, "the last rollout step did not build per-car rows for B cars, or the obstacles / movers / traffic were set "
+                               "anew since (mpmpc_rollout_set_obstacles / mpmpc_rollout_set_movers / mpmpc_rollout_set_traffic)");
   if (offsets_out) std::memcpy(offsets_out, h->obs.comb_off.data(), sizeof(int32_t) * ((size_t)B + 1));
   if (discs_out && h->obs.comb_off[B] > 0) {
     HIP_TRY(hipSetDevice(h->cfg.device));

@@ -46,21 +46,25 @@ struct CorState {
   bool built(const TabState& tab) const { return built_gen == base_gen && built_gen != 0 && tab.n_cols > 0 && line_cells; }
 };
 
-// per-car discs and movers
+// per-car discs, movers and traffic
 struct ObsState {
   Buf<int> obst_off, obst_discs, ro_flag;   // CSR lists on the device, per-car row verdicts
   int obst_B = 0;               // > 0: the rollout's cars carry their own discs (mpmpc_rollout_set_obstacles)
   unsigned obst_gen = 0;        // base_gen the discs were validated against
   bool car_rows = false;        // the last rollout step built per-car rows
-  // The two per-car settings, kept on the host: static discs (mpmpc_rollout_set_obstacles; st_B > 0: set; obst_gen) and
-  // movers (mpmpc_rollout_set_movers; mv_B > 0: set; mv_gen).  Whichever setter is called lays out ONE CSR list per car
-  // on the device (obst_off / obst_discs, what K0c reads: the static discs, then a slot per mover that K0m fills every
-  // step) - sync_disc_lists; obst_B is the B of whichever is set.
+  // The three per-car settings, kept on the host: static discs (mpmpc_rollout_set_obstacles; st_B > 0: set; obst_gen),
+  // movers (mpmpc_rollout_set_movers; mv_B > 0: set; mv_gen) and traffic (mpmpc_rollout_set_traffic; tr_B > 0: set;
+  // tr_gen).  Whichever setter is called lays out ONE CSR list per car on the device (obst_off / obst_discs, what K0c
+  // reads: the static discs, then a slot per mover that K0m fills every step, then tr_S traffic slots that K0t fills
+  // every step) - sync_disc_lists; obst_B is the B of whichever is set.
   std::vector<int32_t> st_off, st_discs, mv_off, comb_off;
   int st_B = 0, mv_B = 0, mv_n = 0;      // mv_n: movers of the fleet
   unsigned mv_gen = 0;          // base_gen the movers were set against
   long long mv_step0 = 0;
   Buf<char> mv_block;           // [4][mv_n] doubles (parameters), then [mv_n] ints each: kind, radius, slot; only grows
+  int tr_B = 0, tr_S = 0, tr_range = -1;      // traffic: cars, slots per car, range [cells]
+  unsigned tr_gen = 0;          // base_gen the traffic was set against
+  Buf<int> tr_block;            // [4 max_batch + 1]: dense group, radius, members (each [tr_B]), group offsets
   bool discs_live = false;      // obst_discs hold the lists the last rollout step used (mpmpc_rollout_obstacles)
 };
 

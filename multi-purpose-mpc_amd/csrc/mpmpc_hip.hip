@@ -61,6 +61,7 @@ __device__ long long g_phase[4096 * 32];
 #include "corridor_core.hpp"
 #include "rollout_core.hpp"
 #include "obstacle_motion_core.hpp"
+#include "traffic_core.hpp"
 #include "speed_core.hpp"
 
 using namespace mpmpc;

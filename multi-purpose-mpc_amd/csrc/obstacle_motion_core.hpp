@@ -30,6 +30,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <initializer_list>
 
 #include "corridor_core.hpp"
 
@@ -93,24 +94,36 @@ MPMPC_HD void mov_disc(const MapView& m, const MoverPath& p, int kind, int r, do
   d[0] = (int)cx; d[1] = (int)cy; d[2] = r;
 }
 
-// The two per-car settings of a rollout - static discs (mpmpc_rollout_set_obstacles) and movers
-// (mpmpc_rollout_set_movers) - share one CSR list per car: the static discs first, then one slot per mover.  B_x = 0:
+// The three per-car settings of a rollout - static discs (mpmpc_rollout_set_obstacles), movers
+// (mpmpc_rollout_set_movers) and traffic (mpmpc_rollout_set_traffic, traffic_core.hpp) - share one CSR list per car: the
+// static discs first, then one slot per mover, then the car's traffic slots (the same number for every car).  B_x = 0:
 // that setting is off.  Returns 0, -1 (MPMPC_E_ARG) or -3 (MPMPC_E_STATE) and the reason.
 inline int mov_check_combined(int B_static, const int32_t* off_static, int B_movers, const int32_t* off_movers,
-                              const char** why) {
-  if (B_static <= 0 || B_movers <= 0) return 0;
-  if (B_static != B_movers) { *why = "static obstacles and movers were set for different numbers of cars"; return -3; }
-  for (int b = 0; b < B_static; ++b)
-    if (((long)off_static[b + 1] - off_static[b]) + ((long)off_movers[b + 1] - off_movers[b]) > COR_MAX_DISCS) {
-      *why = "more than 64 static discs and movers together for one car (COR_MAX_DISCS)";
+                              const char** why, int B_traffic = 0, int traffic_slots = 0) {
+  int B = 0, on = 0;
+  for (const int v : {B_static, B_movers, B_traffic}) {
+    if (v <= 0) continue;
+    if (on > 0 && v != B) { *why = "static obstacles, movers and traffic were set for different numbers of cars"; return -3; }
+    B = v;
+    ++on;
+  }
+  if (on < 2) return 0;
+  for (int b = 0; b < B; ++b) {
+    const long ns = B_static > 0 ? (long)off_static[b + 1] - off_static[b] : 0;
+    const long nm = B_movers > 0 ? (long)off_movers[b + 1] - off_movers[b] : 0;
+    if (ns + nm + (B_traffic > 0 ? traffic_slots : 0) > COR_MAX_DISCS) {
+      *why = "more than 64 static discs, movers and traffic slots together for one car (COR_MAX_DISCS)";
       return -1;
     }
+  }
   return 0;
 }
 
-// Host-side validation of mpmpc_rollout_set_movers (offsets != NULL); B_static / off_static: the static setting in force.
+// Host-side validation of mpmpc_rollout_set_movers (offsets != NULL); B_static / off_static: the static setting in force,
+// B_traffic / traffic_slots: the traffic in force.
 inline int mov_check_movers(int B, int max_batch, const int32_t* off, const int32_t* kind, const int32_t* radius,
-                            const double* params, bool built, int B_static, const int32_t* off_static, const char** why) {
+                            const double* params, bool built, int B_static, const int32_t* off_static, const char** why,
+                            int B_traffic = 0, int traffic_slots = 0) {
   if (!built) { *why = "needs mpmpc_build_corridor on the current map and path geometry first"; return -3; }
   if (B < 1 || B > max_batch) { *why = "B must be in [1, max_batch]"; return -1; }
   if (off[0] != 0) { *why = "offsets[0] must be 0"; return -1; }
@@ -126,18 +139,20 @@ inline int mov_check_movers(int B, int max_batch, const int32_t* off, const int3
     for (int t = 0; t < MOV_PARAMS; ++t)
       if (!mov_finite(params[MOV_PARAMS * j + t])) { *why = "a mover parameter is not finite"; return -1; }
   }
-  return mov_check_combined(B_static, off_static, B, off, why);
+  return mov_check_combined(B_static, off_static, B, off, why, B_traffic, traffic_slots);
 }
 
 // Combined offsets [B + 1] and, per mover, the index of its slot in the combined disc list.  Either offsets may be
-// NULL (that setting is off).
-inline void mov_combine(int B, const int32_t* off_static, const int32_t* off_movers, int32_t* off, int32_t* dst) {
+// NULL (that setting is off); traffic_slots = 0: no traffic.  Car b's traffic slots are the last traffic_slots entries
+// of its list: off[b + 1] - traffic_slots .. off[b + 1] - 1.
+inline void mov_combine(int B, const int32_t* off_static, const int32_t* off_movers, int32_t* off, int32_t* dst,
+                        int traffic_slots = 0) {
   off[0] = 0;
   for (int b = 0; b < B; ++b) {
     const int ns = off_static ? off_static[b + 1] - off_static[b] : 0;
     const int nm = off_movers ? off_movers[b + 1] - off_movers[b] : 0;
     for (int q = 0; q < nm; ++q) dst[off_movers[b] + q] = off[b] + ns + q;
-    off[b + 1] = off[b] + ns + nm;
+    off[b + 1] = off[b] + ns + nm + traffic_slots;
   }
 }
 

@@ -169,6 +169,7 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_corridor.argtypes = [h, C.c_int32, _dp, _dp]
     lib.mpmpc_rollout_set_movers.argtypes = [h, C.c_int32, _ip, _ip, _ip, _dp, C.c_int64]
     lib.mpmpc_rollout_obstacles.argtypes = [h, C.c_int32, _ip, _ip]
+    lib.mpmpc_rollout_set_traffic.argtypes = [h, C.c_int32, _ip, _ip, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_recorded.argtypes = [h, _ip, _ip]
     lib.mpmpc_rollout_trace.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
@@ -199,7 +200,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_create", "mpmpc_destroy", "mpmpc_set_settings", "mpmpc_set_packing", "mpmpc_set_tail_kernel", "mpmpc_set_path", "mpmpc_set_corridor",
            "mpmpc_set_map", "mpmpc_set_path_geometry", "mpmpc_build_corridor", "mpmpc_rollout_init",
            "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor",
-           "mpmpc_rollout_set_movers", "mpmpc_rollout_obstacles",
+           "mpmpc_rollout_set_movers", "mpmpc_rollout_obstacles", "mpmpc_rollout_set_traffic",
            "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams", "mpmpc_launch_plan",
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_staging",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
@@ -411,9 +412,29 @@ class Handle:
         prm = np.ascontiguousarray(flat[:, 2:], dtype=np.float64)
         self._check(self.lib.mpmpc_rollout_set_movers(self._h, len(lists), _i(off), _i(kind), _i(rad), _d(prm), int(step0)))
 
+    def rollout_set_traffic(self, group, radius_cells=None, slots=1, range_cells=-1):
+        """Traffic: the cars of a group see each other as discs, from the fleet's own poses, every step on the device (K0t).
+        group [B] ints (the same non-negative value: one world; negative: sees nobody, is seen by nobody), radius_cells [B]
+        the disc of each car as the others see it, slots the discs a car gets (the nearest, ties by car index),
+        range_cells how far it sees (negative: no limit); None switches traffic off.  Combines with rollout_set_obstacles
+        and rollout_set_movers (together at most 64 per car, the same number of cars); needs build_corridor on the current
+        map; may be called between rollout_step calls.  traffic.traffic_discs gives the slots of any state."""
+        if group is None:
+            self._check(self.lib.mpmpc_rollout_set_traffic(self._h, 0, None, None, 0, -1))
+            return
+        grp, rad = (np.asarray(a) for a in (group, radius_cells))
+        if grp.ndim != 1 or rad.shape != grp.shape:
+            raise ValueError("group and radius_cells must be [B]")
+        for a in (grp, rad):
+            if a.size and (not np.array_equal(a, np.floor(a)) or np.any(np.abs(a) > 2 ** 30)):
+                raise ValueError("group and radius_cells must be integers")
+        grp, rad = (np.ascontiguousarray(a, dtype=np.int32) for a in (grp, rad))
+        self._check(self.lib.mpmpc_rollout_set_traffic(self._h, grp.size, _i(grp), _i(rad), int(slots), int(range_cells)))
+
     def rollout_obstacles(self):
         """-> one int32 [k_b, 3] array of (cx, cy, r) per car: the discs the last rollout step used - the car's static discs,
-        then its movers where that step had them; an absent mover (off the map, past the end of an open path) is (0, 0, 0)"""
+        then its movers where that step had them, then its traffic slots (rollout_set_traffic); an absent mover (off the
+        map, past the end of an open path) or an empty slot is (0, 0, 0)"""
         B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
         off = np.zeros(B + 1, np.int32)
         self._check(self.lib.mpmpc_rollout_obstacles(self._h, B, None, _i(off)))
