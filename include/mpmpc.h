@@ -542,6 +542,29 @@ int mpmpc_assemble_resident_timed(mpmpc_handle h, int32_t B, int32_t n, float* m
 int mpmpc_speed_profile(int32_t device, int32_t B, int32_t n, const double* li, const double* kappa,
                         const double* limits, double eps, double* v, int32_t* status, int32_t* iters);
 
+/* ---- lidar (K0l): replaces LidarModel.scan, src/lidar_model.py:37-112, for B cars at once, each in a world of its own -
+ * the grid plus the car's discs.  The law, step by step, is csrc/lidar_core.hpp; a cell's beam interval comes from the
+ * DEVICE's atan2 (the first output of this library that a device-libm result decides: two implementations can differ
+ * only where an angle ties with a beam, with -+pi/2 or with the +-pi wrap to within a few ulp).
+ *   mpmpc_lidar_scan    needs no handle.  data [height][width] int8, 1 free / 0 occupied, with its frame (mpmpc_set_map's
+ *                       arguments); pose [B][3] = x, y, psi; offsets [B+1] / discs [offsets[B]][3]: the cars' discs in
+ *                       mpmpc_rollout_set_obstacles' format, offsets == NULL: none; angles [n_beams] finite and ascending;
+ *                       ranges_out [B][n_beams] <- the distance to the nearest occupied cell each beam hits, range_m where
+ *                       it hits none; a row of NaN for a pose that is not finite or further than 2^30 cells from the
+ *                       origin.  MPMPC_E_ARG, before any device call: n_beams outside [1, 2048], angles not finite or
+ *                       not ascending, range_m not positive and finite or above 2048 cells, offsets that decrease, more
+ *                       than 64 discs for a car, a disc whose square leaves the grid.
+ *   mpmpc_rollout_scan  every car of the running rollout from the pose its last step left it at, on the handle's resident
+ *                       map, in the world mpmpc_rollout_obstacles would return (static discs, movers, traffic slots of
+ *                       the last step); without a per-car setting in force: the base map.  Cars are scanned whatever
+ *                       their alive.  Nothing but the result passes through the host, and the call writes nothing the
+ *                       rollout reads.  MPMPC_E_STATE: no rollout of exactly B cars (or one invalidated by an upload),
+ *                       no map, a per-car setting in force that no step has used yet or that was set anew since. */
+int mpmpc_lidar_scan(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                     double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
+                     int32_t n_beams, const double* angles, double range_m, double* ranges_out);
+int mpmpc_rollout_scan(mpmpc_handle h, int32_t B, int32_t n_beams, const double* angles, double range_m, double* ranges_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -368,6 +368,12 @@ class BatchMPC:
             self.handle.rollout_record(0, B=np.asarray(s).size)      # later rollouts are unrecorded again
         return out
 
+    def rollout_scan(self, lidar):
+        """Lidar scans of the cars of the last `rollout`, where it left them and in the worlds of its last step (the map
+        of corridor='device' plus each car's obstacles, movers and traffic discs): lidar is a lidar_model.LidarModel ->
+        ranges [B, lidar.n_measurements].  The rollout's state is untouched."""
+        return self.handle.rollout_scan(lidar.measurements[0], lidar.range)
+
     def staging(self, B):
         """numpy views of the handle's page-locked staging blocks for a batch of B (mpmpc.Handle.staging): a caller that builds
         wp_id / x0 / cc_prev (/ lb / ub) in place and reads u0 / status / z in place skips the host-side copies, which are two

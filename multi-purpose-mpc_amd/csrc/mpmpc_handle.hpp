@@ -96,6 +96,11 @@ struct RecState {
   long long records_of(long long n_steps) const { return (ro_steps + n_steps + stride - 1) / stride - (ro_steps + stride - 1) / stride; }
 };
 
+// lidar of the rollout (mpmpc_rollout_scan): memory of its own - a scan writes nothing the rollout reads
+struct LidState {
+  Buf<double> angles, ranges;      // [LID_MAX_BEAMS], [B x n_beams] of the largest scan so far
+};
+
 // per-batch inputs and host staging
 struct IoState {
   // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
@@ -136,6 +141,7 @@ struct mpmpc_handle_s {
   ObsState obs;
   RoState ro;
   RecState rec;
+  LidState lid;
   IoState io;
   // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
   // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that

@@ -1,0 +1,182 @@
+// The lidar of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind mpmpc_closed_loop.hpp): the
+// kernel K0l and its two entry points - mpmpc_lidar_scan (no handle, like mpmpc_speed_profile) and mpmpc_rollout_scan (the
+// cars of a handle's running rollout in the worlds of its last step).  The law: lidar_core.hpp.
+#pragma once
+
+// K0l: one scan per car, one WORKGROUP of 256 lanes per car.  best[n_beams] (int32 d2, LID_NONE = no hit) and a copy of
+// angles[] live in LDS (8 + 16 KB at LID_MAX_BEAMS) beside the car's discs that meet the window (compacted by an LDS
+// counter; their order does not matter to an OR).  The window is walked in passes of K0L_PASS cells, a row at a time,
+// lane along i, so that a wave reads consecutive bytes of a grid row (the grid is L2-resident: every car of a fleet
+// reads the same few rows), and the rows in the order 0, +1, -1, +2, -2 ... of their distance from the sensor's: along
+// every beam that is near to far.  A pass has two halves with a barrier between them:
+//   sift   per cell the integer work - occupancy, d2, the range test - and then the shortcut: one atan2 gives an enclosure
+//          of the cell's interval (lid_cell_enclosure), and a cell whose enclosure covers no beam that could still take
+//          its d2 is done - behind a wall's front row that is most of the wall.  What is left goes into a queue in LDS.
+//   scan   the queued cells, one per lane and the lanes dense: the nine FP64 atan2 of the cell's interval, its beams
+//          found in the table itself (a binary search for the first angle >= mn, then a walk while angle <= mx:
+//          comparisons against the bits the host passed, never arithmetic on the spacing), LDS atomicMin.
+// The queue is what keeps the nine atan2 off the waves that have one open cell among 64 (without it the shortcut saved
+// a quarter of the time, not most of it).  best[] only ever decreases, so a stale read can only queue a cell in vain; the
+// minimum is order-free (lidar_core.hpp), so no output bit depends on the order of the rows, of the queue, or on the
+// shortcut.  A pose with a NaN or a far-off sensor (lid_sensor_cell) gives a NaN row.
+// off == nullptr: no discs (the base map).  Every index is bounded: the window is clipped to the grid, a car's disc
+// count to COR_MAX_DISCS, the queue to the cells of a pass, n_beams to LID_MAX_BEAMS by the host.
+constexpr int K0L_THREADS = 256;
+constexpr int K0L_PASS = 1024;      // cells per pass = the queue's capacity
+__global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView map, int B, const double* __restrict__ pose,
+                                                                       const int* __restrict__ off,
+                                                                       const int* __restrict__ discs, int n_beams,
+                                                                       const double* __restrict__ angles, double range_m,
+                                                                       double* __restrict__ ranges) {
+  __shared__ double s_ang[LID_MAX_BEAMS];
+  __shared__ int s_best[LID_MAX_BEAMS];
+  __shared__ int s_disc[3 * COR_MAX_DISCS];
+  __shared__ int s_nd;
+  __shared__ int s_queue[K0L_PASS];      // (di + 2048) | (dj + 2048) << 16: |di|, |dj| <= LID_MAX_RANGE_CELLS
+  __shared__ int s_nq;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (b >= B || n_beams > LID_MAX_BEAMS) return;      // (uniform)
+  double* out = ranges + (long)b * n_beams;
+  const double x = pose[3L * b], y = pose[3L * b + 1], psi = pose[3L * b + 2];
+  int cx = 0, cy = 0;
+  if (!lid_sensor_cell(map, x, y, psi, &cx, &cy)) {      // (uniform)
+    for (int k = tid; k < n_beams; k += K0L_THREADS) out[k] = __builtin_nan("");
+    return;
+  }
+  const LidWindow w = lid_window(map, cx, cy, range_m);
+  for (int k = tid; k < n_beams; k += K0L_THREADS) {
+    s_ang[k] = angles[k];
+    s_best[k] = LID_NONE;
+  }
+  if (tid == 0) { s_nd = 0; s_nq = 0; }
+  __syncthreads();
+  if (off) {
+    const int d0 = off[b];
+    int nd = off[b + 1] - d0;
+    nd = nd > COR_MAX_DISCS ? COR_MAX_DISCS : nd;      // (the host refuses more)
+    if (tid < nd) {
+      const int* d = discs + 3L * (d0 + tid);
+      const int box[5] = {0, w.i0, w.j0, w.i1, w.j1};
+      if (d[2] > 0 && cor_disc_meets_box(d, box)) {
+        const int q = atomicAdd(&s_nd, 1);
+        s_disc[3 * q] = d[0]; s_disc[3 * q + 1] = d[1]; s_disc[3 * q + 2] = d[2];
+      }
+    }
+  }
+  __syncthreads();
+  const int nd = s_nd;
+  auto disc = [&](int q) { return (const int*)(s_disc + 3 * q); };
+  const int cols = w.i1 - w.i0 + 1;
+  const int cells = cols > 0 && w.j0 <= w.j1 ? cols * (2 * w.R + 1) : 0;      // at most 4097^2
+  for (int base = 0; base < cells; base += K0L_PASS) {      // (uniform)
+    const int end = base + K0L_PASS < cells ? base + K0L_PASS : cells;
+    for (int t = base + tid; t < end; t += K0L_THREADS) {
+      const int r = t / cols;
+      const int dj = (r & 1) ? (r + 1) / 2 : -(r / 2);
+      const int i = w.i0 + (t - r * cols), j = cy + dj;
+      if (j < w.j0 || j > w.j1) continue;
+      if (!lid_occupied(map, i, j, nd, disc)) continue;
+      int d2;
+      if (!lid_in_range(i - cx, dj, w.lim, &d2)) continue;
+      double lo, hi;
+      if (lid_cell_enclosure(i - cx, dj, d2, psi, &lo, &hi)) {
+        bool open = false;
+        for (int k = lid_first_beam(s_ang, n_beams, lo); k < n_beams && s_ang[k] <= hi; ++k) open = open || d2 < s_best[k];
+        if (!open) continue;
+      }
+      s_queue[atomicAdd(&s_nq, 1)] = (i - cx + LID_MAX_RANGE_CELLS) | ((dj + LID_MAX_RANGE_CELLS) << 16);
+    }
+    __syncthreads();
+    const int nq = s_nq;
+    for (int c = tid; c < nq; c += K0L_THREADS) {
+      const int di = (s_queue[c] & 0xffff) - LID_MAX_RANGE_CELLS, dj = (s_queue[c] >> 16) - LID_MAX_RANGE_CELLS;
+      const int d2 = di * di + dj * dj;
+      double mn, mx;
+      if (!lid_cell_interval(di, dj, psi, &mn, &mx)) continue;
+      for (int k = lid_first_beam(s_ang, n_beams, mn); k < n_beams && s_ang[k] <= mx; ++k)
+        if (d2 < s_best[k]) atomicMin(&s_best[k], d2);
+    }
+    __syncthreads();
+    if (tid == 0) s_nq = 0;      // (every lane has read nq; the barrier below keeps the next sift's appends behind this)
+    __syncthreads();
+  }
+  __syncthreads();
+  for (int k = tid; k < n_beams; k += K0L_THREADS) out[k] = lid_range(s_best[k], map.res, range_m);
+}
+
+// device scratch of mpmpc_lidar_scan, kept between calls like the speed profile's (SpScratch: one per device, each behind
+// its own mutex, never freed)
+static SpScratch g_lid_dev[SP_MAX_DEVICES];
+
+extern "C" {
+
+int mpmpc_lidar_scan(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                     double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
+                     int32_t n_beams, const double* angles, double range_m, double* ranges_out) {
+  const char* why = "";
+  if (lid_check_scan(height, width, data, resolution, B, pose, offsets, discs, n_beams, angles, range_m, ranges_out, &why))
+    return fail(MPMPC_E_ARG, why);
+  if (!mov_finite(origin_x) || !mov_finite(origin_y)) return fail(MPMPC_E_ARG, "the map's origin is not finite");
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
+  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the lidar scratch table");
+  HIP_TRY(hipSetDevice(device));
+  const size_t nb = (size_t)B, n_disc = offsets ? (size_t)offsets[B] : 0;
+  const size_t o_pose = 0, o_ang = o_pose + sizeof(double) * 3 * nb, o_out = o_ang + sizeof(double) * (size_t)n_beams,
+               o_off = o_out + sizeof(double) * nb * (size_t)n_beams, o_disc = o_off + pad8(sizeof(int) * (nb + 1)),
+               o_map = o_disc + pad8(sizeof(int) * 3 * n_disc), need = o_map + pad8((size_t)height * width);
+  SpScratch& g = g_lid_dev[device];
+  std::lock_guard<std::mutex> lock(g.mu);
+  if (g.bytes < need) {
+    if (g.block) (void)device_free(g.block);
+    g.block = nullptr; g.bytes = 0;
+    HIP_TRY(device_alloc((void**)&g.block, need));
+    g.bytes = need;
+  }
+  if (!g.stream) HIP_TRY(hipStreamCreate(&g.stream));
+  hipStream_t stream = g.stream;
+  char* blk = g.block;
+  HIP_TRY(hipMemcpyAsync(blk + o_pose, pose, sizeof(double) * 3 * nb, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(blk + o_ang, angles, sizeof(double) * (size_t)n_beams, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(blk + o_map, data, (size_t)height * width, hipMemcpyHostToDevice, stream));
+  if (offsets) HIP_TRY(hipMemcpyAsync(blk + o_off, offsets, sizeof(int) * (nb + 1), hipMemcpyHostToDevice, stream));
+  if (n_disc > 0) HIP_TRY(hipMemcpyAsync(blk + o_disc, discs, sizeof(int) * 3 * n_disc, hipMemcpyHostToDevice, stream));
+  const MapView mv{(const int8_t*)(blk + o_map), height, width, origin_x, origin_y, resolution};
+  hipLaunchKernelGGL(mpmpc_lidar_scan_kernel, dim3(B), dim3(K0L_THREADS), 0, stream, mv, B, (const double*)(blk + o_pose),
+                     offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), n_beams,
+                     (const double*)(blk + o_ang), range_m, (double*)(blk + o_out));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(ranges_out, blk + o_out, sizeof(double) * nb * (size_t)n_beams, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_scan(mpmpc_handle h, int32_t B, int32_t n_beams, const double* angles, double range_m, double* ranges_out) {
+  if (int rc = enter(h, ranges_out)) return rc;
+  Slot& sl = h->last();
+  if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
+                              "call mpmpc_rollout_init again")) return rc;
+  if (B != h->ro.B) return fail(MPMPC_E_STATE, "the rollout was set up for another number of cars");
+  if (!h->cor.map) return fail(MPMPC_E_STATE, "needs mpmpc_set_map first");
+  const char* why = "";
+  if (lid_check_beams(n_beams, angles, range_m, h->cor.map_res, &why)) return fail(MPMPC_E_ARG, why);
+  const bool per_car = h->obs.obst_B > 0;
+  if (per_car && (!h->obs.car_rows || !h->obs.discs_live || h->obs.obst_B != B))
+    return fail(MPMPC_E_STATE, "per-car obstacles / movers / traffic are set, but no rollout step of B cars has used them yet, or they were "
+                               "set anew since the last step: the cars' worlds are those of a step (mpmpc_rollout_step)");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t n_out = (size_t)B * (size_t)n_beams;
+  if (h->lid.angles.count() < (size_t)n_beams) HIP_TRY(h->lid.angles.alloc((size_t)LID_MAX_BEAMS));
+  if (h->lid.ranges.count() < n_out) HIP_TRY(h->lid.ranges.alloc(n_out));
+  HIP_TRY(hipMemcpyAsync(h->lid.angles, angles, sizeof(double) * (size_t)n_beams, hipMemcpyHostToDevice, sl.stream));
+  hipLaunchKernelGGL(mpmpc_lidar_scan_kernel, dim3(B), dim3(K0L_THREADS), 0, sl.stream, h->cor.map_view(), B, h->ro.pose,
+                     per_car ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), n_beams, h->lid.angles.get(), range_m,
+                     h->lid.ranges.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(ranges_out, h->lid.ranges, sizeof(double) * n_out, hipMemcpyDeviceToHost, sl.stream));
+  HIP_TRY(hipStreamSynchronize(sl.stream));
+  return MPMPC_OK;
+}
+
+}  // extern "C"

@@ -186,6 +186,9 @@ def load_library(path: str | None = None):
     lib.mpmpc_solve_resident_profile.argtypes = [h, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.mpmpc_assemble_resident_timed.argtypes = [h, C.c_int32, C.c_int32, C.POINTER(C.c_float)]
     lib.mpmpc_speed_profile.argtypes = [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, _dp, _ip, _ip]
+    lib.mpmpc_lidar_scan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double,
+                                     C.c_int32, _dp, _ip, _ip, C.c_int32, _dp, C.c_double, _dp]
+    lib.mpmpc_rollout_scan.argtypes = [h, C.c_int32, C.c_int32, _dp, C.c_double, _dp]
     _ipp, _dpp = C.POINTER(_ip), C.POINTER(_dp)
     lib.mpmpc_staging.argtypes = [h, C.c_int32, _ipp, _dpp, _dpp, _dpp, _dpp, _dpp, _dpp, _ipp, _ipp, _dpp, _dpp]
     lib.mpmpc_solve_staged.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -202,7 +205,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor",
            "mpmpc_rollout_set_movers", "mpmpc_rollout_obstacles", "mpmpc_rollout_set_traffic",
            "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams", "mpmpc_launch_plan",
-           "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_staging",
+           "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_lidar_scan", "mpmpc_rollout_scan", "mpmpc_staging",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -442,6 +445,17 @@ class Handle:
         self._check(self.lib.mpmpc_rollout_obstacles(self._h, B, _i(flat) if flat.size else None, None))
         return [flat[off[b]:off[b + 1]] for b in range(B)]
 
+    def rollout_scan(self, angles, range_m):
+        """Lidar scans of every car of the running rollout (K0l), from the pose its last step left it at, in the world that
+        step gave it - the resident map plus the discs rollout_obstacles() returns (the base map when no per-car setting is
+        in force).  angles [n] ascending (lidar_model.LidarModel.measurements[0]), range_m in metres -> ranges [B, n].
+        Changes nothing the rollout reads."""
+        ang = np.ascontiguousarray(angles, dtype=np.float64).ravel()
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        out = np.zeros((B, ang.size))
+        self._check(self.lib.mpmpc_rollout_scan(self._h, B, ang.size, _d(ang), float(range_m), _d(out)))
+        return out
+
     # --- recorder of the rollout: one record per car and recorded step, kept on the device
     TRACE_BASIC = ("s", "pose", "wp_id", "x0", "u", "status", "counter", "alive")
 
@@ -627,3 +641,32 @@ def speed_profile(li, kappa, limits, eps=1e-12, device=0):
     if rc != 0:
         raise MpmpcError("mpmpc_speed_profile: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
     return v, status, iters
+
+
+def lidar_scan(grid, origin, resolution, poses, angles, range_m, discs=None, device=0):
+    """Lidar scans of B cars on the device (K0l, replaces LidarModel.scan's loops, src/lidar_model.py:37-112; the law:
+    csrc/lidar_core.hpp).  grid [H, W] int8 (1 free / 0 occupied) with its origin and resolution, poses [B, 3] = x, y, psi,
+    angles [n] ascending, range_m in metres, discs: one int [k_b, 3] array of (cx, cy, r) map cells per car
+    (Map.obstacle_discs; at most 64) or None.  -> ranges [B, n]."""
+    lib = load_library()
+    grid = np.ascontiguousarray(grid, dtype=np.int8)
+    if grid.ndim != 2:
+        raise ValueError("map grid must be 2-D [height, width]")
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    ang = np.ascontiguousarray(angles, dtype=np.float64).ravel()
+    B = poses.shape[0]
+    off = flat = None
+    if discs is not None:
+        lists = [np.asarray(d, dtype=np.int32).reshape(-1, 3) for d in discs]
+        if len(lists) != B:
+            raise ValueError("discs must hold one list per car")
+        off = np.zeros(B + 1, np.int32)
+        off[1:] = np.cumsum([a.shape[0] for a in lists])
+        flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((0, 3), np.int32), dtype=np.int32)
+    out = np.zeros((B, ang.size))
+    rc = lib.mpmpc_lidar_scan(int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)),
+                              float(origin[0]), float(origin[1]), float(resolution), B, _d(poses), _i(off),
+                              _i(flat) if flat is not None and flat.size else None, ang.size, _d(ang), float(range_m), _d(out))
+    if rc != 0:
+        raise MpmpcError("mpmpc_lidar_scan: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    return out
