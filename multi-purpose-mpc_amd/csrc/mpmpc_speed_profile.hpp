@@ -1,11 +1,11 @@
-// The speed profile of libmpmpc.so, part of the one translation unit mpmpc_hip.hip: the three K4 kernels, the per-device scratch
+// The speed profile of libmpmpc.so, part of the one translation unit mpmpc_hip.hip: the two K4 kernels, the per-device scratch
 // and the entry point mpmpc_speed_profile (speed_core.hpp is the solver they run).  Needs no handle.
 #pragma once
 
-// K4: speed profile.  The kernel of choice is mpmpc_speed_profile_wave_kernel below (one wavefront per path); these
-// two run the same code one thread per path (a serial interior-point / active-set run over a scalar tridiagonal
+// K4: speed profile.  The kernel of choice is mpmpc_speed_profile_wave_kernel below (one wavefront per path); this
+// one runs the same code one thread per path (a serial interior-point / active-set run over a scalar tridiagonal
 // system, speed_core.hpp) for paths too long for the LDS: workspace path-minor in HBM, so that the threads of a
-// wave touch consecutive addresses, or in LDS for a few paths.
+// wave touch consecutive addresses.
 __global__ __launch_bounds__(64) void mpmpc_speed_profile_kernel(int B, int n, const double* __restrict__ li,
                                                                  const double* __restrict__ kappa,
                                                                  const double* __restrict__ limits, double eps,
@@ -20,31 +20,12 @@ __global__ __launch_bounds__(64) void mpmpc_speed_profile_kernel(int B, int n, c
   iters[p] = it;
 }
 
-// Few paths (the usual case is one): one path per block with the workspace in LDS, so that the serial
-// run is bound by LDS latency instead of HBM latency.
-__global__ __launch_bounds__(64) void mpmpc_speed_profile_lds_kernel(int B, int n, const double* __restrict__ li,
-                                                                     const double* __restrict__ kappa,
-                                                                     const double* __restrict__ limits, double eps,
-                                                                     double* __restrict__ v, int* __restrict__ status,
-                                                                     int* __restrict__ iters) {
-  extern __shared__ double sp_lds[];
-  const int p = blockIdx.x;
-  if (threadIdx.x != 0 || p >= B) return;
-  SpWork W{sp_lds, n, 1};
-  SpLimits lim{limits[5 * p], limits[5 * p + 1], limits[5 * p + 2], limits[5 * p + 3], limits[5 * p + 4]};
-  int it = 0;
-  status[p] = sp_solve(n, li + (long)p * n, kappa + (long)p * n, 1, lim, eps, W, v + (long)p * n, 1, &it);
-  iters[p] = it;
-}
-
 // One WAVEFRONT per path: the elementwise loops of sp_solve_t run strided over the 64 lanes, reductions are
-// shuffles, and the tridiagonal systems are solved by parallel cyclic reduction in LDS - "factor" keeps the two
-// multipliers of every row and level (ceil(log2 n) levels) and the final reciprocal diagonal, "solve" applies them to
-// a right-hand side.  Everything (25 work arrays + 25 n doubles of cyclic-reduction state) lives in LDS.
+// shuffles, and the tridiagonal systems are solved by parallel cyclic reduction in LDS (sp_cr_factor / sp_cr_solve of
+// speed_core.hpp, whose rows the lanes share out).  Everything (the SP_ARRAYS work arrays + sp_cr_arrays(n) arrays of
+// cyclic-reduction state, n doubles each) lives in LDS.
 struct SpWave {
-  double* x;          // cyclic-reduction state behind the SP_ARRAYS work arrays
-  int cap;            // row capacity (n of the launch)
-  int levels = 0;
+  SpCyclic cr;        // cyclic-reduction state behind the SP_ARRAYS work arrays
   __device__ int first() const { return threadIdx.x; }
   __device__ int step() const { return 64; }
   __device__ void sync() const { __syncthreads(); }
@@ -57,59 +38,9 @@ struct SpWave {
     return v;
   }
   __device__ bool any(bool b) const { __syncthreads(); return __ballot(b) != 0ull; }
-  // layout of x: A0 B0 C0 A1 B1 C1 (double-buffered rows), D0 D1, BINV, then K1[l], K2[l] per level
-  __device__ double* arr(int a) const { return x + (long)a * cap; }
-  __device__ void tri_factor(const SpWork& W, int n) const {
-    const int lane = threadIdx.x;
-    double *a0 = arr(0), *b0 = arr(1), *c0 = arr(2), *a1 = arr(3), *b1 = arr(4), *c1 = arr(5);
-    for (int i = lane; i < n; i += 64) {
-      a0[i] = i > 0 ? W(SP_ME, i - 1) : 0.0;
-      b0[i] = W(SP_MD, i);
-      c0[i] = i + 1 < n ? W(SP_ME, i) : 0.0;
-    }
-    __syncthreads();
-    int l = 0;
-    for (int s = 1; s < n; s <<= 1, ++l) {
-      double *k1 = arr(9 + 2 * l), *k2 = arr(10 + 2 * l);
-      for (int i = lane; i < n; i += 64) {
-        const bool lo = i - s >= 0, hi = i + s < n;
-        const double m1 = lo ? a0[i] / b0[i - s] : 0.0, m2 = hi ? c0[i] / b0[i + s] : 0.0;
-        k1[i] = m1; k2[i] = m2;
-        a1[i] = lo ? -a0[i - s] * m1 : 0.0;
-        c1[i] = hi ? -c0[i + s] * m2 : 0.0;
-        b1[i] = b0[i] - (lo ? c0[i - s] * m1 : 0.0) - (hi ? a0[i + s] * m2 : 0.0);
-      }
-      __syncthreads();
-      double* t;
-      t = a0; a0 = a1; a1 = t; t = b0; b0 = b1; b1 = t; t = c0; c0 = c1; c1 = t;
-    }
-    double* binv = arr(8);
-    for (int i = lane; i < n; i += 64) binv[i] = 1.0 / b0[i];
-    __syncthreads();
-  }
-  __device__ void tri_solve(const SpWork& W, int n) const {
-    const int lane = threadIdx.x;
-    double *d0 = arr(6), *d1 = arr(7);
-    for (int i = lane; i < n; i += 64) d0[i] = W(SP_RHS, i);
-    __syncthreads();
-    int l = 0;
-    for (int s = 1; s < n; s <<= 1, ++l) {
-      const double *k1 = arr(9 + 2 * l), *k2 = arr(10 + 2 * l);
-      for (int i = lane; i < n; i += 64)
-        d1[i] = d0[i] - (i - s >= 0 ? d0[i - s] * k1[i] : 0.0) - (i + s < n ? d0[i + s] * k2[i] : 0.0);
-      __syncthreads();
-      double* t = d0; d0 = d1; d1 = t;
-    }
-    const double* binv = arr(8);
-    for (int i = lane; i < n; i += 64) W(SP_DX, i) = d0[i] * binv[i];
-    __syncthreads();
-  }
+  __device__ void tri_factor(const SpWork& W, int n) const { sp_cr_factor(*this, cr, W, n); }
+  __device__ void tri_solve(const SpWork& W, int n) const { sp_cr_solve(*this, cr, W, n); }
 };
-__host__ __device__ inline int sp_wave_arrays(int n) {      // doubles of SpWave state per row
-  int levels = 0;
-  for (int s = 1; s < n; s <<= 1) ++levels;
-  return 9 + 2 * levels;
-}
 __global__ __launch_bounds__(64) void mpmpc_speed_profile_wave_kernel(int B, int n, const double* __restrict__ li,
                                                                       const double* __restrict__ kappa,
                                                                       const double* __restrict__ limits, double eps,
@@ -119,7 +50,7 @@ __global__ __launch_bounds__(64) void mpmpc_speed_profile_wave_kernel(int B, int
   const int p = blockIdx.x;
   if (p >= B) return;
   SpWork W{sp_lds, n, 1};
-  SpWave pol{sp_lds + (long)SP_ARRAYS * n, n};
+  SpWave pol{{sp_lds + (long)SP_ARRAYS * n, n}};
   SpLimits lim{limits[5 * p], limits[5 * p + 1], limits[5 * p + 2], limits[5 * p + 3], limits[5 * p + 4]};
   int it = 0;
   const int st = sp_solve_t(pol, n, li + (long)p * n, kappa + (long)p * n, 1, lim, eps, W, v + (long)p * n, 1, &it);
@@ -149,13 +80,15 @@ extern "C" int mpmpc_speed_profile(int32_t device, int32_t B, int32_t n, const d
   if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
   HIP_TRY(hipSetDevice(device));
   const size_t vec = sizeof(double) * (size_t)B * n;
-  const size_t lds = sizeof(double) * SP_ARRAYS * (size_t)n;
-  const size_t lds_wave = sizeof(double) * (SP_ARRAYS + sp_wave_arrays(n)) * (size_t)n;
-  const bool wave = lds_wave <= 156 * 1024, small = !wave && B <= 256 && lds <= 64 * 1024;
+  const size_t lds_wave = sizeof(double) * (SP_ARRAYS + sp_cr_arrays(n)) * (size_t)n;
+  // one wavefront per path while its arrays fit 156 KiB of LDS: n <= 384, where 8 (25 + 9 + 2 * 9) 384 = 159 744 B is
+  // 156 KiB exactly; beyond that one thread per path.  (A kernel that ran one thread per path out of 64 KiB of LDS,
+  // 25 * 8 n <= 65 536: n <= 327, could never be chosen - the wave kernel takes every such n - and is gone.)
+  const bool wave = lds_wave <= 156 * 1024;
   // one block: li, kappa, v, limits, status, iters (+ the HBM workspace of the thread-per-path kernel)
   const size_t o_li = 0, o_kappa = vec, o_v = 2 * vec, o_lim = 3 * vec, o_status = o_lim + pad8(sizeof(double) * 5 * B),
                o_iters = o_status + pad8(sizeof(int) * (size_t)B), o_work = o_iters + pad8(sizeof(int) * (size_t)B),
-               need = o_work + ((wave || small) ? 0 : vec * SP_ARRAYS);
+               need = o_work + (wave ? 0 : vec * SP_ARRAYS);
   if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the speed-profile scratch table");
   SpScratch& g_sp = g_sp_dev[device];
   std::lock_guard<std::mutex> lock(g_sp.mu);
@@ -180,9 +113,6 @@ extern "C" int mpmpc_speed_profile(int32_t device, int32_t B, int32_t n, const d
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wave));
     hipLaunchKernelGGL(mpmpc_speed_profile_wave_kernel, dim3(B), dim3(64), lds_wave, stream, B, n, d_li, d_kappa, d_lim,
                        eps, d_v, d_status, d_iters);
-  } else if (small) {
-    hipLaunchKernelGGL(mpmpc_speed_profile_lds_kernel, dim3(B), dim3(64), lds, stream, B, n, d_li, d_kappa, d_lim, eps,
-                       d_v, d_status, d_iters);
   } else {
     hipLaunchKernelGGL(mpmpc_speed_profile_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, B, n, d_li, d_kappa, d_lim,
                        eps, d_work, d_v, d_status, d_iters);

@@ -65,6 +65,99 @@ MPMPC_HD void sp_tri_factor(const SpWork& W, int n) {
   }
 }
 
+// ---- parallel cyclic reduction of the same tridiagonal systems, written per row: at level l (stride s = 2^l) row i
+// eliminates its neighbours i - s and i + s, so every row of a level is independent of the others and a policy may run
+// the rows of a level in any order - SpWave (mpmpc_speed_profile.hpp) lane-strided on the device, SpCyclicHost below
+// one after the other on the host.  "factor" keeps the two multipliers of every row and level and the final reciprocal
+// diagonal, "solve" applies them to a right-hand side.  Unlike sp_tri_factor it leaves SP_MD / SP_ME as they were.
+// State: sp_cr_arrays(n) arrays of `cap` doubles - A0 B0 C0 A1 B1 C1 (double-buffered rows), D0 D1, BINV, then
+// K1[l], K2[l] per level.
+constexpr int sp_cr_arrays(int n) {
+  int levels = 0;
+  for (int s = 1; s < n; s <<= 1) ++levels;
+  return 9 + 2 * levels;
+}
+struct SpCyclic {
+  double* x;
+  int cap;            // row capacity (n of the launch)
+  MPMPC_HD double* arr(int a) const { return x + (long)a * cap; }
+};
+MPMPC_HD void sp_cr_load_row(const SpWork& W, int n, int i, double* a0, double* b0, double* c0) {
+  a0[i] = i > 0 ? W(SP_ME, i - 1) : 0.0;
+  b0[i] = W(SP_MD, i);
+  c0[i] = i + 1 < n ? W(SP_ME, i) : 0.0;
+}
+MPMPC_HD void sp_cr_factor_row(int n, int s, int i, const double* a0, const double* b0, const double* c0, double* a1,
+                               double* b1, double* c1, double* k1, double* k2) {
+  const bool lo = i - s >= 0, hi = i + s < n;
+  const double m1 = lo ? a0[i] / b0[i - s] : 0.0, m2 = hi ? c0[i] / b0[i + s] : 0.0;
+  k1[i] = m1; k2[i] = m2;
+  a1[i] = lo ? -a0[i - s] * m1 : 0.0;
+  c1[i] = hi ? -c0[i + s] * m2 : 0.0;
+  b1[i] = b0[i] - (lo ? c0[i - s] * m1 : 0.0) - (hi ? a0[i + s] * m2 : 0.0);
+}
+MPMPC_HD void sp_cr_solve_row(int n, int s, int i, const double* d0, double* d1, const double* k1, const double* k2) {
+  d1[i] = d0[i] - (i - s >= 0 ? d0[i - s] * k1[i] : 0.0) - (i + s < n ? d0[i + s] * k2[i] : 0.0);
+}
+template <class P>
+MPMPC_HD void sp_cr_factor(const P& pol, const SpCyclic& cr, const SpWork& W, int n) {
+  const int i0 = pol.first(), di = pol.step();
+  double *a0 = cr.arr(0), *b0 = cr.arr(1), *c0 = cr.arr(2), *a1 = cr.arr(3), *b1 = cr.arr(4), *c1 = cr.arr(5);
+  for (int i = i0; i < n; i += di) sp_cr_load_row(W, n, i, a0, b0, c0);
+  pol.sync();
+  int l = 0;
+  for (int s = 1; s < n; s <<= 1, ++l) {
+    double *k1 = cr.arr(9 + 2 * l), *k2 = cr.arr(10 + 2 * l);
+    for (int i = i0; i < n; i += di) sp_cr_factor_row(n, s, i, a0, b0, c0, a1, b1, c1, k1, k2);
+    pol.sync();
+    double* t;
+    t = a0; a0 = a1; a1 = t; t = b0; b0 = b1; b1 = t; t = c0; c0 = c1; c1 = t;
+  }
+  double* binv = cr.arr(8);
+  for (int i = i0; i < n; i += di) binv[i] = 1.0 / b0[i];
+  pol.sync();
+}
+// d0 (cr.arr(6)) holds the right-hand side -> the array that holds the solution (d0 or d1)
+template <class P>
+MPMPC_HD double* sp_cr_apply(const P& pol, const SpCyclic& cr, int n) {
+  const int i0 = pol.first(), di = pol.step();
+  double *d0 = cr.arr(6), *d1 = cr.arr(7);
+  int l = 0;
+  for (int s = 1; s < n; s <<= 1, ++l) {
+    const double *k1 = cr.arr(9 + 2 * l), *k2 = cr.arr(10 + 2 * l);
+    for (int i = i0; i < n; i += di) sp_cr_solve_row(n, s, i, d0, d1, k1, k2);
+    pol.sync();
+    double* t = d0; d0 = d1; d1 = t;
+  }
+  const double* binv = cr.arr(8);
+  for (int i = i0; i < n; i += di) d0[i] *= binv[i];
+  pol.sync();
+  return d0;
+}
+// RHS -> DX, with one step of iterative refinement against the unfactored matrix (SP_MD / SP_ME): the multipliers of the
+// reduction are rounded level by level, and on long runs of active acceleration rows (diagonal and off-diagonal of the
+// normal equations both ~ z / s, their sum O(1)) the plain solve leaves the interior point a residual floor above its tol.
+template <class P>
+MPMPC_HD void sp_cr_solve(const P& pol, const SpCyclic& cr, const SpWork& W, int n) {
+  const int i0 = pol.first(), di = pol.step();
+  double* d0 = cr.arr(6);
+  for (int i = i0; i < n; i += di) d0[i] = W(SP_RHS, i);
+  pol.sync();
+  const double* y = sp_cr_apply(pol, cr, n);
+  for (int i = i0; i < n; i += di) W(SP_DX, i) = y[i];
+  pol.sync();
+  for (int i = i0; i < n; i += di) {
+    double r = W(SP_RHS, i) - W(SP_MD, i) * W(SP_DX, i);
+    if (i > 0) r -= W(SP_ME, i - 1) * W(SP_DX, i - 1);
+    if (i + 1 < n) r -= W(SP_ME, i) * W(SP_DX, i + 1);
+    d0[i] = r;
+  }
+  pol.sync();
+  y = sp_cr_apply(pol, cr, n);
+  for (int i = i0; i < n; i += di) W(SP_DX, i) += y[i];
+  pol.sync();
+}
+
 // Execution policy of sp_solve_t.  SpSerial: one thread walks the path (host emulation, and the thread-per-path
 // kernel for very long paths).  The device's SpWave (mpmpc_speed_profile.hpp) spreads the elementwise loops over the 64 lanes
 // of a wavefront, reduces with shuffles and solves the tridiagonal systems by parallel cyclic reduction.
@@ -77,6 +170,21 @@ struct SpSerial {
   MPMPC_HD bool any(bool b) const { return b; }
   MPMPC_HD void tri_factor(const SpWork& W, int n) const { sp_tri_factor(W, n); }
   MPMPC_HD void tri_solve(const SpWork& W, int n) const { sp_tri_solve(W, n); }
+};
+
+// The cyclic reduction one row after the other: the host twin of SpWave (tests/emul).  Same per-row arithmetic and the
+// same order of levels as the device; only the sums over the path run serially where the device reduces by butterfly.
+// `x`: sp_cr_arrays(n) * n doubles.
+struct SpCyclicHost {
+  SpCyclic cr;
+  MPMPC_HD int first() const { return 0; }
+  MPMPC_HD int step() const { return 1; }
+  MPMPC_HD void sync() const {}
+  MPMPC_HD double rmax(double x) const { return x; }
+  MPMPC_HD double rsum(double x) const { return x; }
+  MPMPC_HD bool any(bool b) const { return b; }
+  MPMPC_HD void tri_factor(const SpWork& W, int n) const { sp_cr_factor(*this, cr, W, n); }
+  MPMPC_HD void tri_solve(const SpWork& W, int n) const { sp_cr_solve(*this, cr, W, n); }
 };
 
 // v[n] <- optimum; returns SP_SOLVED (KKT certificate <= cert_tol), SP_INACCURATE or SP_BAD_INPUT.
@@ -106,6 +214,7 @@ MPMPC_HD int sp_solve_t(const P& pol, int n, const double* li, const double* kap
   // ---- start: x = 0, unit multipliers, slacks at least 1 (as the host solver this replaces)
   for (int i = i0; i < n; i += di) {
     W(SP_X, i) = 0.0;
+    W(SP_L2, i) = 0.0;                                   // the iterate of the smallest residual so far (see `best`)
     W(SP_SL2, i) = std::fmax(0.0 - lim.v_min, 1.0); W(SP_SU2, i) = std::fmax(W(SP_HI, i) - 0.0, 1.0);
     W(SP_ZL2, i) = 1.0; W(SP_ZU2, i) = 1.0;
     if (i < m1) {
@@ -117,6 +226,7 @@ MPMPC_HD int sp_solve_t(const P& pol, int n, const double* li, const double* kap
   auto ax1 = [&](int a, int k) { return W(SP_C, k) * (W(a, k + 1) - W(a, k)); };
   int it = 0;
   bool converged = false;
+  double best = 1e300;
   for (; it < 60; ++it) {
     // ---- residuals, complementarity, normal-equations matrix
     double res = 0.0, musum = 0.0;
@@ -148,6 +258,11 @@ MPMPC_HD int sp_solve_t(const P& pol, int n, const double* li, const double* kap
     const double mu = pol.rsum(musum) / nb;
     if (res < tol && mu < tol) { converged = true; break; }
     if (!(res < 1e300)) break;
+    // a run that ends without convergence returns its best iterate, not its last (SP_L2 is free until the finish)
+    if (res < best) {
+      best = res;
+      for (int i = i0; i < n; i += di) W(SP_L2, i) = W(SP_X, i);
+    }
     pol.tri_factor(W, n);
     double sigmu = 0.0, alpha = 1.0;
     for (int pass = 0; pass < 2; ++pass) {
@@ -220,10 +335,20 @@ MPMPC_HD int sp_solve_t(const P& pol, int n, const double* li, const double* kap
     }
   }
   if (iters && i0 == 0) *iters = it;
-  // ---- active-set finish: A1 = -1 / 0 / +1 for a difference row at its lower / no / upper bound, A2 for the boxes
-  for (int i = i0; i < n; i += di) {
+  // ---- active-set finish: A1 = -1 / 0 / +1 for a difference row at its lower / no / upper bound, A2 for the boxes.
+  // It starts from the interior-point iterate, multipliers included (L = zu - zl).  Where the active rows are linearly
+  // dependent - a speed peak exactly on a waypoint: rising rows, falling rows and the boxes at both ends of the stretch -
+  // the multipliers are not unique, and the delta-regularised solves below keep the component of their starting point
+  // along the dependency.  From zero that component is the minimum-norm one, with wrong signs on a long stretch of rows
+  // that the update then releases and re-adds one by one; from the interior point it is the central, strictly signed one.
+  for (int i = i0; converged && i < n; i += di) {
     W(SP_A2, i) = W(SP_ZL2, i) > W(SP_SL2, i) ? -1.0 : (W(SP_ZU2, i) > W(SP_SU2, i) ? 1.0 : 0.0);
-    if (i < m1) W(SP_A1, i) = W(SP_ZL1, i) > W(SP_SL1, i) ? -1.0 : (W(SP_ZU1, i) > W(SP_SU1, i) ? 1.0 : 0.0);
+    W(SP_L2, i) = W(SP_ZU2, i) - W(SP_ZL2, i);
+    W(SP_PL2, i) = W(SP_X, i);
+    if (i < m1) {
+      W(SP_A1, i) = W(SP_ZL1, i) > W(SP_SL1, i) ? -1.0 : (W(SP_ZU1, i) > W(SP_SU1, i) ? 1.0 : 0.0);
+      W(SP_L1, i) = W(SP_ZU1, i) - W(SP_ZL1, i);
+    }
   }
   pol.sync();
   bool ok = false;
@@ -232,9 +357,8 @@ MPMPC_HD int sp_solve_t(const P& pol, int n, const double* li, const double* kap
     // the tridiagonal Schur complement S = A1 diag(h) A1' + delta I  (SP_MD / SP_ME, m1 rows)
     for (int i = i0; i < n; i += di) {
       W(SP_RD, i) = 1.0 / (1.0 + delta + (W(SP_A2, i) != 0.0 ? 1.0 / delta : 0.0));       // h
-      W(SP_L2, i) = 0.0;
-      W(SP_PL2, i) = 0.0;                                                                  // x of this round
-      if (i < m1) W(SP_L1, i) = 0.0;
+      if (W(SP_A2, i) == 0.0) W(SP_L2, i) = 0.0;       // (x, lam1, lam2) = (PL2, L1, L2) go on from the round before
+      if (i < m1 && W(SP_A1, i) == 0.0) W(SP_L1, i) = 0.0;
     }
     pol.sync();
     for (int k = i0; k < m1; k += di) {
@@ -328,7 +452,7 @@ MPMPC_HD int sp_solve_t(const P& pol, int n, const double* li, const double* kap
   }
   worst = pol.rmax(worst);
   const bool certified = ok && worst <= cert_tol;
-  for (int i = i0; i < n; i += di) v[i * v_stride] = certified ? W(SP_PL2, i) : W(SP_X, i);
+  for (int i = i0; i < n; i += di) v[i * v_stride] = certified ? W(SP_PL2, i) : (converged ? W(SP_X, i) : W(SP_L2, i));
   return certified ? SP_SOLVED : SP_INACCURATE;
 }
 

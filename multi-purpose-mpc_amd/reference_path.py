@@ -184,7 +184,10 @@ class ReferencePath:
     def compute_speed_profile(self, Constraints, solver=None):
         """Reference velocity per waypoint (src/reference_path.py:289-354).  The QP is solved on the
         device by libmpmpc.so (K4, mpmpc.speed_profile) to a KKT-certified optimum; `solver` is the
-        test hook for the CPU emulation of that kernel (same signature).  No host solver behind it."""
+        test hook for the CPU emulation of that kernel (same signature).  No host solver behind it.
+        A profile the kernel could not certify (status 2) is used with a warning, as the reference uses whatever OSQP
+        returns; inconsistent constraints and a profile that is not finite are errors."""
+        import warnings
         import mpmpc
         n = self.n_waypoints - 1
         li = np.array([self.get_waypoint(i + 1) - self.get_waypoint(i) for i in range(n)], float)
@@ -194,6 +197,10 @@ class ReferencePath:
         if int(status[0]) < 0:
             raise ValueError("speed profile: inconsistent constraints")
         v = v[0]
+        if not np.all(np.isfinite(v)):
+            raise ValueError("speed profile: not finite (status %d)" % int(status[0]))
+        if int(status[0]) != 1:
+            warnings.warn("speed profile: not certified (status %d); using the solver's best iterate" % int(status[0]))
         for i, wp in enumerate(self.waypoints[:-1]):
             wp.v_ref = v[i]
         self.waypoints[-1].v_ref = self.waypoints[-2].v_ref

@@ -376,3 +376,12 @@ extern "C" int emu_speed_profile(int n, const double* li, const double* kappa, c
   SpLimits lim{lim5[0], lim5[1], lim5[2], lim5[3], lim5[4]};
   return sp_solve(n, li, kappa, 1, lim, eps, W, v, 1, iters);
 }
+// ... and of the code mpmpc_speed_profile_wave_kernel executes per wavefront: the same per-row cyclic reduction, row by row
+extern "C" int emu_speed_profile_wave(int n, const double* li, const double* kappa, const double* lim5, double eps,
+                                      double* v, int* iters) {
+  std::vector<double> ws((size_t)(SP_ARRAYS + sp_cr_arrays(n)) * n);
+  SpWork W{ws.data(), n, 1};
+  SpCyclicHost pol{{ws.data() + (size_t)SP_ARRAYS * n, n}};
+  SpLimits lim{lim5[0], lim5[1], lim5[2], lim5[3], lim5[4]};
+  return sp_solve_t(pol, n, li, kappa, 1, lim, eps, W, v, 1, iters);
+}

@@ -246,7 +246,7 @@ def wide_track(track, emu, n_cols):
     return _WIDE_TRACKS[key]
 
 
-def emu_speed_profile(li, kappa, limits, eps=1e-12, device=0):
+def emu_speed_profile(li, kappa, limits, eps=1e-12, device=0, entry="emu_speed_profile"):
     """CPU emulation of mpmpc_speed_profile_kernel (same signature as mpmpc.speed_profile)."""
     lib = Emul().lib
     li = np.atleast_2d(np.ascontiguousarray(li, float))
@@ -256,10 +256,15 @@ def emu_speed_profile(li, kappa, limits, eps=1e-12, device=0):
     v, status, iters = np.zeros((B, n)), np.zeros(B, np.int32), np.zeros(B, np.int32)
     for p in range(B):
         it = C.c_int(0)
-        status[p] = lib.emu_speed_profile(C.c_int(n), _d(li[p]), _d(kappa[p]), _d(limits[p]), C.c_double(eps), _d(v[p]),
+        status[p] = getattr(lib, entry)(C.c_int(n), _d(li[p]), _d(kappa[p]), _d(limits[p]), C.c_double(eps), _d(v[p]),
                                           C.byref(it))
         iters[p] = it.value
     return v, status, iters
+
+
+def emu_speed_profile_wave(li, kappa, limits, eps=1e-12, device=0):
+    """CPU twin of mpmpc_speed_profile_wave_kernel: the cyclic reduction of the device, row by row (same signature)."""
+    return emu_speed_profile(li, kappa, limits, eps, device, entry="emu_speed_profile_wave")
 
 
 # ---- the independent leg (oracle/independent.py, golden G8): nothing below shares code with the device algorithm

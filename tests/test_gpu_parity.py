@@ -744,7 +744,7 @@ def test_speed_profile_on_device():
     assert status[0] == 1 and 3 < iters[0] < 40
     assert np.max(np.abs(v[0] - g2["x"])) < 1e-9
     rng = np.random.default_rng(12)
-    B = 96                                                # LDS variant; the HBM-workspace variant below
+    B = 96                                                # n = 199: one wavefront per path, here and below
     LI = li[None, :] * rng.uniform(0.7, 1.4, (B, n))
     KA = kappa[None, :] * rng.uniform(0.5, 3.0, (B, 1))
     LIM = np.stack([-rng.uniform(0.05, 0.5, B), rng.uniform(0.1, 1.0, B), np.zeros(B), rng.uniform(0.6, 1.5, B),
