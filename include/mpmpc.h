@@ -265,6 +265,7 @@ int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, doubl
  *          that step's state, the car is not driven, the other cars are unaffected.  The lists K0c reads hold the car's
  *          static discs, its movers (mpmpc_rollout_set_movers) and its traffic slots (mpmpc_rollout_set_traffic): a row
  *          blocked by another car's disc ends the car with -3 in the same way.
+ *          With mpmpc_rollout_set_audit in mode 2 also: -5 the car's footprint touched its world at that step's pose.
  * The rollout keeps its plans, waypoint ids and states in the handle's batch blocks: mpmpc_upload / mpmpc_solve /
  * mpmpc_assemble on the SAME handle overwrite them, after which mpmpc_rollout_step / _state / _set_counters return
  * MPMPC_E_STATE until mpmpc_rollout_init is called again.  (mpmpc_download and mpmpc_build_corridor are fine.) */
@@ -564,6 +565,41 @@ int mpmpc_lidar_scan(int32_t device, int32_t height, int32_t width, const int8_t
                      double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
                      int32_t n_beams, const double* angles, double range_m, double* ranges_out);
 int mpmpc_rollout_scan(mpmpc_handle h, int32_t B, int32_t n_beams, const double* angles, double range_m, double* ranges_out);
+
+/* ---- footprint audit (K0f): did a car touch anything, and how close did it get?  For every car its rectangle - length
+ * along the heading, car_width across it, centred at the pose (x, y, psi) - is tested against the car's own world, the grid
+ * plus the car's discs.  The law, step by step, is csrc/footprint_core.hpp: over the occupied cells whose centres lie within
+ * reach_m of the rectangle, contact = a cell centre inside or on the rectangle, clearance = the smallest distance of a cell
+ * centre from the rectangle, reach_m when there is none that near (exact: the window of cells is chosen so that no cell
+ * outside it can matter).  cos(psi) and sin(psi) come from the DEVICE's libm: two implementations can differ in the flag
+ * only where a cell centre lies on the rectangle's boundary to within rounding, and in the clearance by a few ulp.  A
+ * pose that is not finite or lies more than 2^30 cells from the origin gives contact 0, clearance NaN.
+ *   mpmpc_footprint_audit    needs no handle.  data [height][width] int8, 1 free / 0 occupied, with its frame (mpmpc_set_map's
+ *                            arguments); pose [B][3]; offsets [B+1] / discs [offsets[B]][3]: the cars' discs in
+ *                            mpmpc_rollout_set_obstacles' format, offsets == NULL: the base map only; contact_out [B],
+ *                            clearance_out [B].  MPMPC_E_ARG, before any device call: length, car_width or reach_m not
+ *                            positive and finite, reach_m plus half the rectangle's diagonal above 256 cells, offsets
+ *                            that decrease, more than 64 discs for a car, a disc whose square leaves the grid.
+ *   mpmpc_rollout_set_audit  mode 0: off (the default; mpmpc_rollout_step launches nothing new), 1: every step audits every
+ *                            car that is still running after localisation - pose k in world k: the step's static discs,
+ *                            movers and traffic slots, or the base map when no per-car setting is in force -, 2: as 1, and
+ *                            a car in contact ends there with alive = -5: it is not driven, its corridor row is still
+ *                            built and its solve still runs, as for -3 / -4.  The setting persists across
+ *                            mpmpc_rollout_init; the accumulators start over with every mpmpc_rollout_init and every
+ *                            call of this function.  Needs mpmpc_set_map: without it mpmpc_rollout_step fails with
+ *                            MPMPC_E_STATE (and with MPMPC_E_ARG if the window exceeds 256 cells on the map of the moment).
+ *   mpmpc_rollout_audit      the accumulators, [B] each, any pointer may be NULL: contact_steps (audited steps with contact),
+ *                            first_contact (step index of the first, counted from mpmpc_rollout_init; -1: none),
+ *                            min_clearance (the smallest seen; reach_m at the start), min_step (the first step that reached
+ *                            it; -1 while nothing came nearer than reach_m), last_contact / last_clearance (the verdict of
+ *                            the car's last audited step; 0 / NaN before the first).  MPMPC_E_STATE: the audit is off, or
+ *                            its accumulators were set up for another number of cars. */
+int mpmpc_footprint_audit(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                          double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
+                          double length, double car_width, double reach_m, int32_t* contact_out, double* clearance_out);
+int mpmpc_rollout_set_audit(mpmpc_handle h, int32_t mode, double length, double car_width, double reach_m);
+int mpmpc_rollout_audit(mpmpc_handle h, int32_t B, int32_t* contact_steps, int32_t* first_contact, double* min_clearance,
+                        int32_t* min_step, int32_t* last_contact, double* last_clearance);
 
 #ifdef __cplusplus
 }

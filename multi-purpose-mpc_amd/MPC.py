@@ -295,7 +295,7 @@ class BatchMPC:
         poses = np.asarray(poses, float)
         return wp.astype(np.int32), t2s_batch(poses[:, 0], poses[:, 1], poses[:, 2], wx, wy, wpsi)
 
-    def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None):
+    def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -313,7 +313,11 @@ class BatchMPC:
         get_waypoint exits: src/reference_path.py:367-369; wp_id and x0 are that step's, the car is not driven),
         -3 (obstacles) no free segment at the first horizon waypoint of the car's world (the reference raises in
         update_path_constraints), -4 (obstacles) a border line of the car's world has more than 8 free segments (a
-        limit of this library); for -3 / -4 too wp_id and x0 are that step's and the car is not driven.
+        limit of this library); for -3 / -4 too wp_id and x0 are that step's and the car is not driven, -5 (audit with
+        stop=True) the car's footprint touched its world at that step's pose; the car is not driven either.
+        audit: None - no audit; a footprint.Footprint - every step tests the rectangle of every running car, at the pose the
+        step finds it at, against the car's world of that step (the map of corridor='device' plus its obstacles, movers and
+        traffic discs) on the device, and the returned dict also holds "audit": rollout_audit().
         record: None - nothing is recorded; True or a dict of mpmpc.Handle.rollout_record's keyword arguments (capacity,
         plan, prediction, rows, stride; capacity defaults to the records `n_steps` yields) - the run is recorded on the
         device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of the whole run, arrays
@@ -351,10 +355,19 @@ class BatchMPC:
             self.handle.rollout_set_movers(rows, step0=0)
         if traffic is not None:
             self.handle.rollout_set_traffic(*traffic.cells(rp.map.resolution))
+        if audit is None:
+            self.handle.rollout_set_audit(0)          # (off, like the other world settings)
+        else:
+            if self.corridor_cols is None:
+                raise ValueError("the audit needs corridor='device' (update_corridor_from_map): the map lives on the device")
+            self.handle.rollout_set_audit(audit.mode, audit.length, audit.width, audit.reach)
         if record is None or record is False:
             self.handle.rollout_init(self.model.Ts, np.cumsum(rp.segment_lengths), s, poses, cc0)
             self.handle.rollout_step(n_steps)
-            return self.handle.rollout_state()
+            out = self.handle.rollout_state()
+            if audit is not None:
+                out["audit"] = self.handle.rollout_audit()
+            return out
         kw = dict(record) if isinstance(record, dict) else {}
         stride = int(kw.get("stride", 1))
         kw.setdefault("capacity", max(1, -(-int(n_steps) // max(stride, 1))))
@@ -364,6 +377,8 @@ class BatchMPC:
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             out["trace"] = self.handle.rollout_trace()
+            if audit is not None:
+                out["audit"] = self.handle.rollout_audit()
         finally:
             self.handle.rollout_record(0, B=np.asarray(s).size)      # later rollouts are unrecorded again
         return out
@@ -373,6 +388,11 @@ class BatchMPC:
         of corridor='device' plus each car's obstacles, movers and traffic discs): lidar is a lidar_model.LidarModel ->
         ranges [B, lidar.n_measurements].  The rollout's state is untouched."""
         return self.handle.rollout_scan(lidar.measurements[0], lidar.range)
+
+    def rollout_audit(self):
+        """The audit of the last `rollout(..., audit=Footprint)` -> dict of [B] arrays: contact_steps, first_contact,
+        min_clearance, min_step, last_contact, last_clearance (mpmpc.Handle.rollout_audit)."""
+        return self.handle.rollout_audit()
 
     def staging(self, B):
         """numpy views of the handle's page-locked staging blocks for a batch of B (mpmpc.Handle.staging): a caller that builds

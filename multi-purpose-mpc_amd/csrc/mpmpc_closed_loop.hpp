@@ -348,6 +348,12 @@ __global__ __launch_bounds__(256) void mpmpc_record_write_kernel(int B, RoRecSrc
   ro_record_finish(src, rec, lay, i, e);
 }
 
+// the footprint audit inside a rollout (K0f; defined in mpmpc_footprint.hpp, which follows this header): the accumulators
+// start over, may steps of B cars be audited, K0f of step k on the slot's stream
+static int aud_reset(mpmpc_handle h, int B);
+static int aud_check_step(mpmpc_handle h, int B);
+static void aud_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, bool per_car);
+
 extern "C" {
 
 int mpmpc_set_map(mpmpc_handle h, int32_t height, int32_t width, const int8_t* data, double origin_x,
@@ -489,7 +495,7 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   h->io.uploaded = B;
   h->rec.ro_steps = 0;            // the recorder keeps its configuration and starts over
   h->rec.count = 0;
-  return MPMPC_OK;
+  return aud_reset(h, B);         // ... and so does the audit (mpmpc_footprint.hpp)
 }
 
 int mpmpc_rollout_record(mpmpc_handle h, int32_t B, int32_t capacity, int32_t fields, int32_t stride) {
@@ -590,6 +596,8 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
       return fail(MPMPC_E_STATE, "the trace is full: " + std::to_string(h->rec.count) + " of " + std::to_string(h->rec.cap) +
                                      " records held, this call would add " + std::to_string(h->rec.records_of(n_steps)));
   }
+  if (int rc = aud_check_step(h, B)) return rc;
+  const bool auditing = h->aud.mode != FP_MODE_OFF;
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int N = h->cfg.N;
   const size_t car_lds = sizeof(double) * COR_WPC * N + sizeof(int) * (2 * COR_MAXSEG + 3) * N + sizeof(int) * 3 * COR_MAX_DISCS +
@@ -616,6 +624,7 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     if (movers > 0)
       hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
                          h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs);
+    if (auditing) aud_enqueue_step(h, sl, B, h->rec.ro_steps, per_car);      // K0f: pose k in world k
     if (per_car)
       hipLaunchKernelGGL(mpmpc_car_corridor_kernel, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
                          h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells,

@@ -101,6 +101,16 @@ struct LidState {
   Buf<double> angles, ranges;      // [LID_MAX_BEAMS], [B x n_beams] of the largest scan so far
 };
 
+// footprint audit of the rollout (mpmpc_rollout_set_audit): the setting and the per-car accumulators, memory of their own
+struct AudState {
+  int mode = 0;             // FP_MODE_*: 0 off, 1 audit, 2 audit and stop on contact
+  double length = 0, width = 0, reach = 0;
+  int R = 0;                // the window's half-width on the map of the moment (aud_check_step)
+  int B = 0;                // cars the accumulators were reset for (0: not since the setting changed)
+  Buf<int> ints;            // [4][max_batch]: contact_steps, first_contact, min_step, last_contact
+  Buf<double> dbls;         // [2][max_batch]: min_clearance, last_clearance
+};
+
 // per-batch inputs and host staging
 struct IoState {
   // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
@@ -142,6 +152,7 @@ struct mpmpc_handle_s {
   RoState ro;
   RecState rec;
   LidState lid;
+  AudState aud;
   IoState io;
   // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
   // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that

@@ -63,6 +63,7 @@ __device__ long long g_phase[4096 * 32];
 #include "obstacle_motion_core.hpp"
 #include "traffic_core.hpp"
 #include "lidar_core.hpp"
+#include "footprint_core.hpp"
 #include "speed_core.hpp"
 
 using namespace mpmpc;
@@ -908,6 +909,7 @@ int mpmpc_set_corridor(mpmpc_handle h, int32_t n_wp, int32_t n_cols, const doubl
 #include "mpmpc_speed_profile.hpp"
 #include "mpmpc_closed_loop.hpp"
 #include "mpmpc_lidar.hpp"
+#include "mpmpc_footprint.hpp"
 
 extern "C" {
 

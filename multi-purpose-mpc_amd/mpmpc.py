@@ -189,6 +189,10 @@ def load_library(path: str | None = None):
     lib.mpmpc_lidar_scan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double,
                                      C.c_int32, _dp, _ip, _ip, C.c_int32, _dp, C.c_double, _dp]
     lib.mpmpc_rollout_scan.argtypes = [h, C.c_int32, C.c_int32, _dp, C.c_double, _dp]
+    lib.mpmpc_footprint_audit.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double,
+                                          C.c_int32, _dp, _ip, _ip, C.c_double, C.c_double, C.c_double, _ip, _dp]
+    lib.mpmpc_rollout_set_audit.argtypes = [h, C.c_int32, C.c_double, C.c_double, C.c_double]
+    lib.mpmpc_rollout_audit.argtypes = [h, C.c_int32, _ip, _ip, _dp, _ip, _ip, _dp]
     _ipp, _dpp = C.POINTER(_ip), C.POINTER(_dp)
     lib.mpmpc_staging.argtypes = [h, C.c_int32, _ipp, _dpp, _dpp, _dpp, _dpp, _dpp, _dpp, _ipp, _ipp, _dpp, _dpp]
     lib.mpmpc_solve_staged.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -205,7 +209,8 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor",
            "mpmpc_rollout_set_movers", "mpmpc_rollout_obstacles", "mpmpc_rollout_set_traffic",
            "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams", "mpmpc_launch_plan",
-           "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_lidar_scan", "mpmpc_rollout_scan", "mpmpc_staging",
+           "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_lidar_scan", "mpmpc_rollout_scan",
+           "mpmpc_footprint_audit", "mpmpc_rollout_set_audit", "mpmpc_rollout_audit", "mpmpc_staging",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -456,6 +461,29 @@ class Handle:
         self._check(self.lib.mpmpc_rollout_scan(self._h, B, ang.size, _d(ang), float(range_m), _d(out)))
         return out
 
+    # --- footprint audit of the rollout: contact and clearance of every car, every step, accumulated on the device
+    AUDIT_FIELDS = ("contact_steps", "first_contact", "min_clearance", "min_step", "last_contact", "last_clearance")
+
+    def rollout_set_audit(self, mode, length=0.0, width=0.0, reach=0.0):
+        """Audit the cars of the rollouts that follow (K0f; the law: csrc/footprint_core.hpp): every step tests the
+        length x width rectangle of every running car, centred at the pose the step finds it at, against the car's world of
+        that step (the resident map plus its static discs, movers and traffic slots).  mode 0 / None: off, 1: audit,
+        2: audit, and a car in contact ends there with alive = -5.  reach [m]: clearances are exact up to it.  Needs
+        set_map; the setting outlives rollout_init, the accumulators (rollout_audit) start over with it and with this call."""
+        mode = int(mode or 0)
+        self._check(self.lib.mpmpc_rollout_set_audit(self._h, mode, float(length), float(width), float(reach)))
+
+    def rollout_audit(self):
+        """-> dict of [B] arrays: contact_steps (audited steps with contact), first_contact (step index, -1: none),
+        min_clearance (reach at the start), min_step (first step that reached it, -1: none came nearer than reach),
+        last_contact, last_clearance (the verdict of the car's last audited step)"""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        out = {k: np.zeros(B, np.float64 if k.endswith("clearance") else np.int32) for k in self.AUDIT_FIELDS}
+        self._check(self.lib.mpmpc_rollout_audit(self._h, B, _i(out["contact_steps"]), _i(out["first_contact"]),
+                                                 _d(out["min_clearance"]), _i(out["min_step"]), _i(out["last_contact"]),
+                                                 _d(out["last_clearance"])))
+        return out
+
     # --- recorder of the rollout: one record per car and recorded step, kept on the device
     TRACE_BASIC = ("s", "pose", "wp_id", "x0", "u", "status", "counter", "alive")
 
@@ -670,3 +698,33 @@ def lidar_scan(grid, origin, resolution, poses, angles, range_m, discs=None, dev
     if rc != 0:
         raise MpmpcError("mpmpc_lidar_scan: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
     return out
+
+
+def footprint_audit(grid, origin, resolution, poses, length, width, reach, discs=None, device=0):
+    """Contact and clearance of B cars on the device (K0f; the law: csrc/footprint_core.hpp): the length x width rectangle of
+    each car, centred at its pose, against its own world.  grid [H, W] int8 (1 free / 0 occupied) with its origin and
+    resolution, poses [B, 3] = x, y, psi, reach in metres, discs: one int [k_b, 3] array of (cx, cy, r) map cells per car
+    (Map.obstacle_discs; at most 64) or None for the base map.  -> (contact [B] int32, clearance [B]): clearance is the exact
+    distance of the nearest occupied cell centre from the rectangle, capped at reach; NaN for a pose that is not finite."""
+    lib = load_library()
+    grid = np.ascontiguousarray(grid, dtype=np.int8)
+    if grid.ndim != 2:
+        raise ValueError("map grid must be 2-D [height, width]")
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    B = poses.shape[0]
+    off = flat = None
+    if discs is not None:
+        lists = [np.asarray(d, dtype=np.int32).reshape(-1, 3) for d in discs]
+        if len(lists) != B:
+            raise ValueError("discs must hold one list per car")
+        off = np.zeros(B + 1, np.int32)
+        off[1:] = np.cumsum([a.shape[0] for a in lists])
+        flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((0, 3), np.int32), dtype=np.int32)
+    contact, clearance = np.zeros(B, np.int32), np.zeros(B)
+    rc = lib.mpmpc_footprint_audit(int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)),
+                                   float(origin[0]), float(origin[1]), float(resolution), B, _d(poses), _i(off),
+                                   _i(flat) if flat is not None and flat.size else None, float(length), float(width),
+                                   float(reach), _i(contact), _d(clearance))
+    if rc != 0:
+        raise MpmpcError("mpmpc_footprint_audit: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    return contact, clearance
