@@ -355,6 +355,24 @@ int mpmpc_rollout_obstacles(mpmpc_handle h, int32_t B, int32_t* discs_out, int32
  *   state.  A rollout without traffic launches exactly what it launched before. */
 int mpmpc_rollout_set_traffic(mpmpc_handle h, int32_t B, const int32_t* group, const int32_t* radius_cells, int32_t slots,
                               int32_t range_cells);
+/* Walls: the second primitive of a car's world beside the discs - Map.add_boundary of the reference (src/map.py:139-155): a
+ * line between two world points, stamped with skimage's line_aa.  A wall is (x0, y0, x1, y1) in map cells, the w2m of its
+ * two end points, and occupies exactly the cells line_aa(x0, y0, x1, y1) produces (the law: csrc/wall_core.hpp).  A cell
+ * of a car's world is occupied iff it is occupied on the grid, lies in one of the car's discs or on one of its walls.
+ *   offsets [B+1] / walls [offsets[B]][4]: wall q of car b is entry offsets[b] + q.  offsets == NULL: no walls.  Walls are
+ *   a fourth independent per-car setting beside the static discs, the movers and the traffic: K0w rasterises them into a
+ *   table once, when they are set (sized by the sum of the walls' longer extents), and K0c, K0l, K0f and the recorder read
+ *   them from the next step on.  All settings in force must be for the same B (else MPMPC_E_STATE; the other three
+ *   setters check the same against the walls in force).  MPMPC_E_ARG, decided on the host before any device call: B
+ *   outside [1, max_batch], more than 16 walls for one car, offsets that decrease, an end point outside [1, width - 2] x
+ *   [1, height - 2] (the anti-aliased neighbours may step one cell past an end point; the reference raises or wraps
+ *   there).  A wall of one cell is allowed.  A refused call leaves every setting as it was.  Needs mpmpc_build_corridor
+ *   like the discs (else MPMPC_E_STATE) and is void after a change of map, path or geometry in the same way.  May be
+ *   called before mpmpc_rollout_init or between mpmpc_rollout_step calls: it applies from the next step on and keeps the
+ *   rollout's state.  Walls count for every consumer of the world of the last step - mpmpc_rollout_corridor,
+ *   mpmpc_rollout_scan, the audit, recorded rows; mpmpc_rollout_obstacles keeps returning the discs only.  A rollout
+ *   without walls launches exactly what it launched before. */
+int mpmpc_rollout_set_walls(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* walls);
 
 /* Recorder: while the cars drive, the rollout appends one record per car and recorded step to a device-resident trace
  * (what src/simulation.py:117-157 logs per step on the host: x_log / y_log / v_log and MPC.current_prediction), and
@@ -600,6 +618,25 @@ int mpmpc_footprint_audit(int32_t device, int32_t height, int32_t width, const i
 int mpmpc_rollout_set_audit(mpmpc_handle h, int32_t mode, double length, double car_width, double reach_m);
 int mpmpc_rollout_audit(mpmpc_handle h, int32_t B, int32_t* contact_steps, int32_t* first_contact, double* min_clearance,
                         int32_t* min_step, int32_t* last_contact, double* last_clearance);
+
+/* ---- worlds with walls, no handle needed.  wall_offsets [B+1] / walls [wall_offsets[B]][4] as for mpmpc_rollout_set_walls
+ * (NULL: no walls; MPMPC_E_ARG for the same lists it refuses).  K0w rasterises the walls first, on the same stream.
+ *   mpmpc_lidar_scan_world / mpmpc_footprint_audit_world   mpmpc_lidar_scan / mpmpc_footprint_audit in worlds of grid, discs
+ *                       and walls; the two older entry points are calls of these with NULL.
+ *   mpmpc_world_grid    ONE car's world as a grid: grid_out [height][width] int8, 1 free / 0 occupied - data with the
+ *                       n_discs discs ([n_discs][3], at most 64) and the n_walls walls ([n_walls][4], at most 16) stamped
+ *                       in, through the predicate every kernel uses (K-world).  For plots, and the pin of the predicate. */
+int mpmpc_lidar_scan_world(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                           double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
+                           const int32_t* wall_offsets, const int32_t* walls, int32_t n_beams, const double* angles,
+                           double range_m, double* ranges_out);
+int mpmpc_footprint_audit_world(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                                double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
+                                const int32_t* wall_offsets, const int32_t* walls, double length, double car_width, double reach_m,
+                                int32_t* contact_out, double* clearance_out);
+int mpmpc_world_grid(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                     double resolution, int32_t n_discs, const int32_t* discs, int32_t n_walls, const int32_t* walls,
+                     int8_t* grid_out);
 
 #ifdef __cplusplus
 }

@@ -295,7 +295,8 @@ class BatchMPC:
         poses = np.asarray(poses, float)
         return wp.astype(np.int32), t2s_batch(poses[:, 0], poses[:, 1], poses[:, 2], wx, wy, wpsi)
 
-    def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None):
+    def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
+                walls=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -308,6 +309,9 @@ class BatchMPC:
         traffic: None or a traffic.Traffic - the cars of a group see each other as discs (the nearest `slots` cars within
         `range`), from the fleet's own poses, every step on the device; combines with `obstacles` and `movers` (together at
         most 64 per car) and needs corridor='device' as well.  traffic.traffic_discs gives the discs of any state.
+        walls: None or a length-B list of lists of boundaries ((x0, y0), (x1, y1)) in world coordinates - car b drives the
+        path's map with ITS boundaries added (Map.add_boundary); combines with the other three (at most 16 walls per car)
+        and needs corridor='device' as well.
         alive: 1 running, 0 lap finished (s >= length), -1 ended after N - 1 consecutive infeasible steps
         (src/MPC.py:218-220), -2 ended at the end of an open path (wp_id + N >= n_wp, where the reference's
         get_waypoint exits: src/reference_path.py:367-369; wp_id and x0 are that step's, the car is not driven),
@@ -341,6 +345,12 @@ class BatchMPC:
                 raise ValueError("traffic needs corridor='device' (update_corridor_from_map)")
             if traffic.group.size != np.asarray(s).size:
                 raise ValueError("traffic must hold one group per car")
+        if walls is not None:
+            if self.corridor_cols is None:
+                raise ValueError("walls need corridor='device' (update_corridor_from_map)")
+            if len(walls) != np.asarray(s).size:
+                raise ValueError("walls must hold one list of boundaries per car")
+            wall_cells = [rp.map.boundary_walls(w) for w in walls]
         if getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
             wps = rp.waypoints
             self.handle.set_path_geometry([w.x for w in wps], [w.y for w in wps], [w.psi for w in wps],
@@ -349,6 +359,9 @@ class BatchMPC:
         self.handle.rollout_set_obstacles(None)       # (all off first: the settings must agree on B while they are on)
         self.handle.rollout_set_movers(None)
         self.handle.rollout_set_traffic(None)
+        self.handle.rollout_set_walls(None)
+        if walls is not None:
+            self.handle.rollout_set_walls(wall_cells)
         if obstacles is not None:
             self.handle.rollout_set_obstacles(discs)
         if movers is not None:

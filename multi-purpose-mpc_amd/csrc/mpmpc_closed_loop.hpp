@@ -1,7 +1,8 @@
 // The closed loop of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind mpmpc_set_corridor):
 // the kernels K0a / K0b (corridor tables from the map), K0c (per-car corridor rows), K0m (movers), K0t (traffic), K3a / K3b (localise, advance)
 // and the two recorder kernels, and their entry points - mpmpc_set_map, mpmpc_set_path_geometry, mpmpc_build_corridor and every
-// mpmpc_rollout_*.  The state they work on: the sub-states cor, obs, ro, rec of the handle (mpmpc_handle.hpp).
+// mpmpc_rollout_*.  The state they work on: the sub-states cor, obs, ro, rec of the handle (mpmpc_handle.hpp).  The walls of a car's
+// world (mpmpc_rollout_set_walls, below) are rasterised by K0w (mpmpc_walls.hpp, in front of this header).
 #pragma once
 
 // K0a: free segments of every waypoint's border line, one WAVEFRONT per waypoint.  Lane 0 walks Zingl's anti-aliased
@@ -83,7 +84,14 @@ __global__ __launch_bounds__(256) void mpmpc_corridor_select_kernel(PathGeom g, 
 // car still running whose row is blocked / overflowing ends with alive = -3 / -4 (and gets a zero row, so that the
 // solve of a stopped car stays an ordinary QP).  Every car gets its row - the solve runs on stopped cars too, and their
 // status then matches the shared-table rollout's.
-// LDS: 5 KB of staged cells + 0.8 KB of discs + N * (COR_WPC doubles + (2 COR_MAXSEG + 3) ints) = 5.9 KB + 124 B per column.
+// LDS: 5 KB of staged cells + 0.8 KB of discs + N * (COR_WPC doubles + (2 COR_MAXSEG + 3) ints) = 5.9 KB + 124 B per column
+// (+ 384 B of wall headers in the WALLS variant).
+// WALLS (mpmpc_rollout_set_walls): the car's wall headers are staged in LDS next to its discs (at most COR_MAX_WALLS x
+// WALL_HDR ints = 384 B, behind the staged cells), "touched" also means a wall's box meets the line box, and the staged
+// occupancy is !base_free || in a disc || on a wall (wall_core.hpp; one table load per wall whose box holds the cell, through
+// L2).  In that variant off may be nullptr (walls only: no discs).  Nothing else differs; without walls the kernel is the
+// instantiation <false>, the code it always was.
+template <bool WALLS>
 __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, PathGeom g, int N, double min_width,
                                                                 double safety_margin, const double* __restrict__ segs,
                                                                 const int* __restrict__ nseg, const double* __restrict__ wpc,
@@ -92,7 +100,7 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
                                                                 const int* __restrict__ off, const int* __restrict__ discs,
                                                                 const int* __restrict__ wp_id, int* __restrict__ alive,
                                                                 int* __restrict__ flag, double* __restrict__ lb,
-                                                                double* __restrict__ ub) {
+                                                                double* __restrict__ ub, WallView wv) {
   constexpr int PENDING = -1000000;
   extern __shared__ double lds[];
   double* col_o = lds;                                             // [N][COR_WPC]
@@ -105,17 +113,26 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
   unsigned char* stg_free = (unsigned char*)(stg_cell + COR_CELL_CAP);   // [COR_CELL_CAP]
   __shared__ int s_over;
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int d0 = off[b], nd = off[b + 1] - d0;
+  const int d0 = WALLS && !off ? 0 : off[b], nd = WALLS && !off ? 0 : off[b + 1] - d0;
   for (int k = lane; k < 3 * nd; k += 64) dsc[k] = discs[3L * d0 + k];
+  int* whd = (int*)(stg_free + COR_CELL_CAP);                        // [COR_MAX_WALLS][WALL_HDR] (WALLS only)
+  int nw = 0;
+  if (WALLS && wv.off) {
+    const int w0 = wv.off[b];
+    nw = wv.off[b + 1] - w0;
+    nw = nw > COR_MAX_WALLS ? COR_MAX_WALLS : nw;                    // (the host refuses more)
+    for (int k = lane; k < WALL_HDR * nw; k += 64) whd[k] = wv.hdr[(long)WALL_HDR * w0 + k];
+  }
   if (lane == 0) s_over = 0;
   __syncthreads();
   const int wp = wp_id[b] + 1;
   auto disc = [&](int j) { return (const int*)(dsc + 3 * j); };
+  auto whdr = [&](int j) { return (const int*)(whd + WALL_HDR * j); };
   for (int n = lane; n < N; n += 64) {
     const int i = cor_wp(g, wp + n);
     const int* box = line_box + (long)i * COR_LINE_BOX;
     col_off[n] = -1;
-    if (nd > 0 && cor_car_touches(box, nd, disc)) {
+    if (WALLS ? wall_car_touches(box, nd, disc, nw, whdr) : (nd > 0 && cor_car_touches(box, nd, disc))) {
       col_cnt[n] = PENDING;
       col_aux[n] = box[0];
     } else {
@@ -143,7 +160,7 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
       for (int k = lane; k < nc; k += 64) {
         const int cell = cells[k];
         stg_cell[used + k] = cell;
-        stg_free[used + k] = cor_car_cell_free(map, cell, nd, disc) ? 1 : 0;
+        stg_free[used + k] = (WALLS ? wall_car_cell_free(map, cell, nd, disc, nw, whdr, wv.tab) : cor_car_cell_free(map, cell, nd, disc)) ? 1 : 0;
       }
       used += nc;
     }
@@ -353,6 +370,7 @@ __global__ __launch_bounds__(256) void mpmpc_record_write_kernel(int B, RoRecSrc
 static int aud_reset(mpmpc_handle h, int B);
 static int aud_check_step(mpmpc_handle h, int B);
 static void aud_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, bool per_car);
+static const char* const WALLS_OTHER_B = "walls are set for another number of cars (mpmpc_rollout_set_walls)";
 
 extern "C" {
 
@@ -582,11 +600,14 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
                               "call mpmpc_rollout_init again (or use a second handle for single solves)")) return rc;
   if (n_steps < 0) return fail(MPMPC_E_ARG, "n_steps must be >= 0");
-  const bool per_car = h->obs.obst_B > 0;
+  const bool per_car = h->obs.world_B() > 0;
+  const bool discs = h->obs.obst_B > 0, walls = h->obs.wl_B > 0;
   if (per_car) {
-    if (h->obs.obst_B != B) return fail(MPMPC_E_STATE, "the per-car obstacles were set for another number of cars");
+    if (h->obs.world_B() != B || (walls && h->obs.wl_B != B))
+      return fail(MPMPC_E_STATE, "the per-car obstacles were set for another number of cars");
     if ((h->obs.st_B > 0 && h->obs.obst_gen != h->cor.base_gen) || (h->obs.mv_B > 0 && h->obs.mv_gen != h->cor.base_gen) ||
-        (h->obs.tr_B > 0 && h->obs.tr_gen != h->cor.base_gen) || h->cor.built_gen != h->cor.base_gen)
+        (h->obs.tr_B > 0 && h->obs.tr_gen != h->cor.base_gen) || (walls && h->obs.wl_gen != h->cor.base_gen) ||
+        h->cor.built_gen != h->cor.base_gen)
       return fail(MPMPC_E_STATE, "map, path or geometry changed since mpmpc_rollout_set_obstacles / mpmpc_build_corridor");
   }
   const bool recording = h->rec.cap > 0;
@@ -601,15 +622,15 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int N = h->cfg.N;
   const size_t car_lds = sizeof(double) * COR_WPC * N + sizeof(int) * (2 * COR_MAXSEG + 3) * N + sizeof(int) * 3 * COR_MAX_DISCS +
-                         (sizeof(int) + 1) * COR_CELL_CAP;
+                         (sizeof(int) + 1) * COR_CELL_CAP + (walls ? sizeof(int) * WALL_HDR * COR_MAX_WALLS : 0);
   const MapView mv = h->cor.map_view();
   const PathGeom pg = h->cor.path_geom(h->tab, h->cfg.circular);
   h->io.have_rows = per_car;     // K1 / K2 read the per-instance rows K0c writes (else: the table)
-  const int movers = per_car && h->obs.mv_B > 0 ? h->obs.mv_n : 0;
+  const int movers = discs && h->obs.mv_B > 0 ? h->obs.mv_n : 0;
   const MoverPath mp{h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gtrig, h->tab.n_wp, COR_TRIG, h->cfg.circular ? 1 : 0};
   const double* mv_p = (const double*)h->obs.mv_block.get();
   const int* mv_i = (const int*)(mv_p + (size_t)MOV_PARAMS * movers);
-  const bool traffic = per_car && h->obs.tr_B > 0;
+  const bool traffic = discs && h->obs.tr_B > 0;
   const int* tr_i = h->obs.tr_block;      // dense group, radius, members [B] each, then the groups' offsets
   for (int t = 0; t < n_steps; ++t) {
     char* rec = recording && h->rec.ro_steps % h->rec.stride == 0 ? h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)h->rec.count : nullptr;
@@ -625,10 +646,16 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
       hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
                          h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs);
     if (auditing) aud_enqueue_step(h, sl, B, h->rec.ro_steps, per_car);      // K0f: pose k in world k
-    if (per_car)
-      hipLaunchKernelGGL(mpmpc_car_corridor_kernel, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
+    if (walls)
+      hipLaunchKernelGGL(mpmpc_car_corridor_kernel<true>, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
+                         h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
+                         discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), h->io.wp_id, h->ro.alive.get(),
+                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, h->obs.wall_view());
+    else if (per_car)
+      hipLaunchKernelGGL(mpmpc_car_corridor_kernel<false>, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
                          h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells,
-                         h->cor.line_box, h->obs.obst_off, h->obs.obst_discs, h->io.wp_id, h->ro.alive, h->obs.ro_flag, h->io.lb, h->io.ub);
+                         h->cor.line_box, h->obs.obst_off.get(), h->obs.obst_discs.get(), h->io.wp_id, h->ro.alive.get(),
+                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, WallView{nullptr, nullptr, nullptr});
     if (int rc = launch_solve(h, sl, B, true, false)) return rc;  // (the plant step reads z and the status only)
     hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro.Ts,
                        h->tab.kappa, h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter, h->ro.alive, h->ro.pose, h->ro.s, h->ro.u);
@@ -698,6 +725,7 @@ int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offset
     return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
   if (int rc = mov_check_combined(B, offsets, h->obs.mv_B, h->obs.mv_off.data(), &why, h->obs.tr_B, h->obs.tr_S))
     return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  if (h->obs.wl_B > 0 && h->obs.wl_B != B) return fail(MPMPC_E_STATE, WALLS_OTHER_B);
   h->obs.st_off.assign(offsets, offsets + (size_t)B + 1);
   h->obs.st_discs.assign(discs, discs + 3 * (size_t)offsets[B]);
   h->obs.st_B = B;
@@ -717,6 +745,7 @@ int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, 
   if (int rc = mov_check_movers(B, h->cfg.max_batch, offsets, kind, radius_cells, params, h->cor.built(h->tab), h->obs.st_B, h->obs.st_off.data(), &why,
                                 h->obs.tr_B, h->obs.tr_S))
     return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  if (h->obs.wl_B > 0 && h->obs.wl_B != B) return fail(MPMPC_E_STATE, WALLS_OTHER_B);
   const size_t n = (size_t)offsets[B];
   std::vector<char> blk((sizeof(double) * MOV_PARAMS + 2 * sizeof(int)) * n);
   double* p = (double*)blk.data();
@@ -745,6 +774,7 @@ int mpmpc_rollout_set_traffic(mpmpc_handle h, int32_t B, const int32_t* group, c
   if (int rc = tr_check_traffic(B, h->cfg.max_batch, group, radius_cells, slots, h->cor.built(h->tab), h->obs.st_B, h->obs.st_off.data(),
                                 h->obs.mv_B, h->obs.mv_off.data(), &why))
     return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  if (h->obs.wl_B > 0 && h->obs.wl_B != B) return fail(MPMPC_E_STATE, WALLS_OTHER_B);
   HIP_TRY(hipSetDevice(h->cfg.device));
   const size_t nb = (size_t)B;
   std::vector<int32_t> blk(4 * nb + 1);      // dense group, radius, members, the groups' offsets
@@ -760,11 +790,53 @@ int mpmpc_rollout_set_traffic(mpmpc_handle h, int32_t B, const int32_t* group, c
   return sync_disc_lists(h, nullptr);
 }
 
+int mpmpc_rollout_set_walls(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* walls) {
+  if (int rc = enter(h)) return rc;
+  if (!offsets) {      // no walls
+    if (h->obs.wl_B > 0) h->obs.discs_live = false;      // (the worlds change; without walls in force the call changes nothing)
+    h->obs.wl_B = 0;
+    h->obs.wl_n = 0;
+    return MPMPC_OK;
+  }
+  const char* why = "";
+  if (int rc = wall_check_walls(B, h->cfg.max_batch, offsets, walls, h->cor.built(h->tab), h->cor.map_w, h->cor.map_h, h->obs.obst_B, &why))
+    return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  Slot& sl = h->last();
+  const size_t n = (size_t)offsets[B];
+  std::vector<int32_t> hdr(WALL_HDR * n + 1);
+  const size_t total = (size_t)wall_layout((long)n, walls, hdr.data());
+  // a refused call leaves the setting as it was: the new table is built in buffers of its own and swapped in at the end
+  Buf<int> n_off, n_hdr, n_tab, n_raw, n_ok;
+  HIP_TRY(alloc_all(Want{n_off, (size_t)h->cfg.max_batch + 1}, Want{n_hdr, WALL_HDR * n + 1}, Want{n_tab, total + 1}, Want{n_raw, 4 * n + 1},
+                    Want{n_ok, n + 1}));
+  std::vector<int32_t> ok(n, 1);
+  HIP_TRY(hipMemcpyAsync(n_off, offsets, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, sl.stream));
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(n_hdr, hdr.data(), sizeof(int) * WALL_HDR * n, hipMemcpyHostToDevice, sl.stream));
+    HIP_TRY(hipMemcpyAsync(n_raw, walls, sizeof(int) * 4 * n, hipMemcpyHostToDevice, sl.stream));
+    hipLaunchKernelGGL(mpmpc_wall_raster_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, sl.stream, (int)n, n_raw.get(), n_hdr.get(),
+                       n_tab.get(), n_ok.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ok.data(), n_ok, sizeof(int) * n, hipMemcpyDeviceToHost, sl.stream));
+  }
+  HIP_TRY(hipStreamSynchronize(sl.stream));      // the host vectors leave scope
+  for (size_t j = 0; j < n; ++j)
+    if (ok[j] != 1) return fail(MPMPC_E_ARG, "wall " + std::to_string(j) + " does not fit the wall table (csrc/wall_core.hpp, step 3)");
+  h->obs.wl_off = std::move(n_off); h->obs.wl_hdr = std::move(n_hdr); h->obs.wl_tab = std::move(n_tab);
+  h->obs.wl_raw = std::move(n_raw); h->obs.wl_ok = std::move(n_ok);
+  h->obs.wl_B = B;
+  h->obs.wl_n = (int)n;
+  h->obs.wl_gen = h->cor.base_gen;
+  h->obs.discs_live = false;      // the worlds were set anew: those of the last step are gone
+  return MPMPC_OK;
+}
+
 int mpmpc_rollout_obstacles(mpmpc_handle h, int32_t B, int32_t* discs_out, int32_t* offsets_out) {
   if (int rc = enter(h)) return rc;
   Slot& sl = h->last();
   if (int rc = h->ro.check(B)) return rc;
-  if (!h->obs.car_rows || !h->obs.discs_live || B != h->obs.obst_B)
+  if (!h->obs.car_rows || !h->obs.discs_live || B != h->obs.obst_B)      // (a world of walls only has no disc lists)
     return fail(MPMPC_E_STATE, "the last rollout step did not build per-car rows for B cars, or the obstacles / movers / traffic were set "
                                "anew since (mpmpc_rollout_set_obstacles / mpmpc_rollout_set_movers / mpmpc_rollout_set_traffic)");
   if (offsets_out) std::memcpy(offsets_out, h->obs.comb_off.data(), sizeof(int32_t) * ((size_t)B + 1));

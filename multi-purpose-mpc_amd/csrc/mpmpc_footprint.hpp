@@ -20,14 +20,19 @@
 // Every index is bounded: the window is clipped to the grid, R to FP_MAX_REACH_CELLS and a car's disc count to
 // COR_MAX_DISCS (the host refuses more of either); the trip count is at most 513^2 / (64 K0F_ROWS) + 1 passes.
 // LDS: 0.8 KB; no scratch, no atomics.
+// WALLS: the car's walls whose box meets the window are compacted into LDS like the discs (headers, 384 B) and a cell is
+// occupied as wall_core.hpp says (grid, discs, walls); without walls the kernel is the instantiation <false>, the code it
+// always was.
 constexpr int K0F_ROWS = 4;
+template <bool WALLS>
 __global__ __launch_bounds__(64) void mpmpc_footprint_kernel(MapView map, int B, const double* __restrict__ pose,
                                                              const int* __restrict__ off, const int* __restrict__ discs,
                                                              double length, double width, double reach_m, int R, int mode, int k,
                                                              int* __restrict__ alive, int* __restrict__ contact_out,
                                                              double* __restrict__ clearance_out, int* __restrict__ cs,
                                                              int* __restrict__ first, double* __restrict__ min_clr,
-                                                             int* __restrict__ min_step) {
+                                                             int* __restrict__ min_step, WallView wv) {
+  __shared__ int s_whdr[WALLS ? WALL_HDR * COR_MAX_WALLS : 1];
   __shared__ int s_disc[3 * COR_MAX_DISCS];
   const int b = blockIdx.x, lane = threadIdx.x;
   if (b >= B) return;                                   // (uniform)
@@ -62,6 +67,24 @@ __global__ __launch_bounds__(64) void mpmpc_footprint_kernel(MapView map, int B,
       }
       nd = __popcll(m);
     }
+    int nw = 0;
+    if (WALLS && wv.off) {
+      const int w0 = wv.off[b];
+      int n = wv.off[b + 1] - w0;
+      n = n > COR_MAX_WALLS ? COR_MAX_WALLS : n;        // (the host refuses more)
+      bool meets = false;
+      const int* hd = wv.hdr + (long)WALL_HDR * (w0 + (lane < n ? lane : 0));
+      if (lane < n) {
+        const int box[5] = {0, i0, j0, i1, j1};
+        meets = wall_meets_box(hd, box);
+      }
+      const unsigned long long m = __ballot(meets);
+      if (meets) {
+        const int q = __popcll(m & ((1ull << lane) - 1ull));
+        for (int e = 0; e < WALL_HDR; ++e) s_whdr[WALL_HDR * q + e] = hd[e];
+      }
+      nw = __popcll(m);
+    }
     __syncthreads();
     const int cols = i1 - i0 + 1;
     const int cells = cols > 0 && j0 <= j1 ? cols * (2 * R + 1) : 0;      // at most 513^2
@@ -88,6 +111,8 @@ __global__ __launch_bounds__(64) void mpmpc_footprint_kernel(MapView map, int B,
         if (!on[q]) continue;
         bool occ = free_[q] == 0;
         for (int e = 0; e < nd && !occ; ++e) occ = cor_in_disc(ci[q], cj[q], s_disc + 3 * e);
+        if (WALLS)
+          for (int e = 0; e < nw && !occ; ++e) occ = wall_on(ci[q], cj[q], s_whdr + WALL_HDR * e, wv.tab);
         if (!occ) continue;
         const double g = fp_cell_g(map, car, ci[q], cj[q]);
         hit = hit || g == 0.0;
@@ -157,9 +182,17 @@ static int aud_check_step(mpmpc_handle h, int B) {
 static void aud_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, bool per_car) {
   AudState& a = h->aud;
   const size_t mb = (size_t)h->cfg.max_batch;
-  hipLaunchKernelGGL(mpmpc_footprint_kernel, dim3(B), dim3(64), 0, sl.stream, h->cor.map_view(), B, h->ro.pose,
-                     per_car ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), a.length, a.width, a.reach, a.R, a.mode,
-                     (int)k, h->ro.alive.get(), a.ints + 3 * mb, a.dbls + mb, a.ints.get(), a.ints + mb, a.dbls.get(), a.ints + 2 * mb);
+  const bool discs = per_car && h->obs.obst_B > 0;
+  if (per_car && h->obs.wl_B > 0)
+    hipLaunchKernelGGL(mpmpc_footprint_kernel<true>, dim3(B), dim3(64), 0, sl.stream, h->cor.map_view(), B, h->ro.pose.get(),
+                       discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), a.length, a.width, a.reach, a.R, a.mode,
+                       (int)k, h->ro.alive.get(), a.ints + 3 * mb, a.dbls + mb, a.ints.get(), a.ints + mb, a.dbls.get(), a.ints + 2 * mb,
+                       h->obs.wall_view());
+  else
+    hipLaunchKernelGGL(mpmpc_footprint_kernel<false>, dim3(B), dim3(64), 0, sl.stream, h->cor.map_view(), B, h->ro.pose.get(),
+                       discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), a.length, a.width, a.reach, a.R, a.mode,
+                       (int)k, h->ro.alive.get(), a.ints + 3 * mb, a.dbls + mb, a.ints.get(), a.ints + mb, a.dbls.get(), a.ints + 2 * mb,
+                       WallView{nullptr, nullptr, nullptr});
 }
 
 extern "C" {
@@ -167,11 +200,20 @@ extern "C" {
 int mpmpc_footprint_audit(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
                           double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
                           double length, double car_width, double reach_m, int32_t* contact_out, double* clearance_out) {
+  return mpmpc_footprint_audit_world(device, height, width, data, origin_x, origin_y, resolution, B, pose, offsets, discs, nullptr,
+                                     nullptr, length, car_width, reach_m, contact_out, clearance_out);
+}
+
+int mpmpc_footprint_audit_world(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                                double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
+                                const int32_t* wall_offsets, const int32_t* walls, double length, double car_width, double reach_m,
+                                int32_t* contact_out, double* clearance_out) {
   const char* why = "";
   int R = 0;
   if (fp_check_audit(height, width, data, resolution, B, pose, offsets, discs, length, car_width, reach_m, contact_out, clearance_out,
                      &R, &why))
     return fail(MPMPC_E_ARG, why);
+  if (wall_offsets && wall_check_lists(B, wall_offsets, walls, width, height, &why)) return fail(MPMPC_E_ARG, why);
   if (!mov_finite(origin_x) || !mov_finite(origin_y)) return fail(MPMPC_E_ARG, "the map's origin is not finite");
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
@@ -181,7 +223,9 @@ int mpmpc_footprint_audit(int32_t device, int32_t height, int32_t width, const i
   const size_t nb = (size_t)B, n_disc = offsets ? (size_t)offsets[B] : 0;
   const size_t o_pose = 0, o_clr = o_pose + sizeof(double) * 3 * nb, o_con = o_clr + sizeof(double) * nb,
                o_off = o_con + pad8(sizeof(int) * nb), o_disc = o_off + pad8(sizeof(int) * (nb + 1)),
-               o_map = o_disc + pad8(sizeof(int) * 3 * n_disc), need = o_map + pad8((size_t)height * width);
+               o_map = o_disc + pad8(sizeof(int) * 3 * n_disc), o_wall = o_map + pad8((size_t)height * width);
+  WallBlock wb = wall_block(o_wall, B, wall_offsets, walls);
+  const size_t need = wb.end;
   SpScratch& g = g_fp_dev[device];
   std::lock_guard<std::mutex> lock(g.mu);
   if (g.bytes < need) {
@@ -197,16 +241,23 @@ int mpmpc_footprint_audit(int32_t device, int32_t height, int32_t width, const i
   HIP_TRY(hipMemcpyAsync(blk + o_map, data, (size_t)height * width, hipMemcpyHostToDevice, stream));
   if (offsets) HIP_TRY(hipMemcpyAsync(blk + o_off, offsets, sizeof(int) * (nb + 1), hipMemcpyHostToDevice, stream));
   if (n_disc > 0) HIP_TRY(hipMemcpyAsync(blk + o_disc, discs, sizeof(int) * 3 * n_disc, hipMemcpyHostToDevice, stream));
+  if (int rc = wall_block_enqueue(blk, wb, B, wall_offsets, walls, stream)) return rc;      // K0w first, on the same stream
   const MapView mv{(const int8_t*)(blk + o_map), height, width, origin_x, origin_y, resolution};
-  hipLaunchKernelGGL(mpmpc_footprint_kernel, dim3(B), dim3(64), 0, stream, mv, B, (const double*)(blk + o_pose),
-                     offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), length, car_width, reach_m, R,
-                     FP_MODE_AUDIT, 0, (int*)nullptr, (int*)(blk + o_con), (double*)(blk + o_clr), (int*)nullptr, (int*)nullptr,
-                     (double*)nullptr, (int*)nullptr);
+  if (wall_offsets)
+    hipLaunchKernelGGL(mpmpc_footprint_kernel<true>, dim3(B), dim3(64), 0, stream, mv, B, (const double*)(blk + o_pose),
+                       offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), length, car_width, reach_m, R,
+                       FP_MODE_AUDIT, 0, (int*)nullptr, (int*)(blk + o_con), (double*)(blk + o_clr), (int*)nullptr, (int*)nullptr,
+                       (double*)nullptr, (int*)nullptr, wall_block_view(blk, wb, wall_offsets));
+  else
+    hipLaunchKernelGGL(mpmpc_footprint_kernel<false>, dim3(B), dim3(64), 0, stream, mv, B, (const double*)(blk + o_pose),
+                       offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), length, car_width, reach_m, R,
+                       FP_MODE_AUDIT, 0, (int*)nullptr, (int*)(blk + o_con), (double*)(blk + o_clr), (int*)nullptr, (int*)nullptr,
+                       (double*)nullptr, (int*)nullptr, WallView{nullptr, nullptr, nullptr});
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(contact_out, blk + o_con, sizeof(int) * nb, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipMemcpyAsync(clearance_out, blk + o_clr, sizeof(double) * nb, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  return MPMPC_OK;
+  return wall_block_verdict(wb);
 }
 
 int mpmpc_rollout_set_audit(mpmpc_handle h, int32_t mode, double length, double car_width, double reach_m) {

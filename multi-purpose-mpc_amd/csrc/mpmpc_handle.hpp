@@ -66,6 +66,16 @@ struct ObsState {
   unsigned tr_gen = 0;          // base_gen the traffic was set against
   Buf<int> tr_block;            // [4 max_batch + 1]: dense group, radius, members (each [tr_B]), group offsets
   bool discs_live = false;      // obst_discs hold the lists the last rollout step used (mpmpc_rollout_obstacles)
+  // The fourth per-car setting: walls (mpmpc_rollout_set_walls; wl_B > 0: set; wl_gen).  Not discs: a CSR list of its own
+  // (wl_off / wl_hdr, WALL_HDR ints per wall) and the walls' table (wl_tab, sized by the sum of the walls' extents), filled by
+  // K0w when the walls are set.  wl_raw / wl_ok: K0w's input ([n][4]) and its per-wall verdict.  A new setting is built in buffers of its own
+  // and moved in when K0w has accepted every wall (a refused call leaves the old one).
+  Buf<int> wl_off, wl_hdr, wl_tab, wl_raw, wl_ok;
+  int wl_B = 0, wl_n = 0;
+  unsigned wl_gen = 0;          // base_gen the walls were set against
+  // B of the per-car worlds in force (0: none - the shared table), and what the kernels take of the walls
+  int world_B() const { return obst_B > 0 ? obst_B : wl_B; }
+  WallView wall_view() const { return wl_B > 0 ? WallView{wl_off, wl_hdr, wl_tab} : WallView{nullptr, nullptr, nullptr}; }
 };
 
 // closed-loop rollout state

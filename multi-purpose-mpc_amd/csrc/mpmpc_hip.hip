@@ -23,7 +23,8 @@
 //                               mpmpc_reduced_t_pair_block_kernel - horizons 128 .. 255: two stages per lane on a workgroup of two
 //   The twelve solve kernels (K2 ...) are the same steps around their solvers: "the steps of a solve kernel" below.
 //   K0 / K3 / K4                corridor tables from the map and the closed-loop rollout (mpmpc_closed_loop.hpp, with their
-//                               entry points), the speed profile (mpmpc_speed_profile.hpp), the lidar K0l (mpmpc_lidar.hpp).
+//                               entry points), the speed profile (mpmpc_speed_profile.hpp), the lidar K0l (mpmpc_lidar.hpp), the
+//                               footprint audit K0f (mpmpc_footprint.hpp), the walls K0w and K-world (mpmpc_walls.hpp).
 // Host side: the handle and its sub-states are mpmpc_handle.hpp, their buffers device_buf.hpp; this file keeps create / destroy /
 // settings, the path and corridor tables, upload / download / the staged calls, the launch dispatch, the resident and timed launches.
 //
@@ -64,6 +65,7 @@ __device__ long long g_phase[4096 * 32];
 #include "traffic_core.hpp"
 #include "lidar_core.hpp"
 #include "footprint_core.hpp"
+#include "wall_core.hpp"
 #include "speed_core.hpp"
 
 using namespace mpmpc;
@@ -907,6 +909,7 @@ int mpmpc_set_corridor(mpmpc_handle h, int32_t n_wp, int32_t n_cols, const doubl
 
 // (the kernels of the two keep their order in the code object: K4, then K0 / K3 and the recorder)
 #include "mpmpc_speed_profile.hpp"
+#include "mpmpc_walls.hpp"
 #include "mpmpc_closed_loop.hpp"
 #include "mpmpc_lidar.hpp"
 #include "mpmpc_footprint.hpp"

@@ -22,12 +22,18 @@
 // off == nullptr: no discs (the base map).  Every index is bounded: the window is clipped to the grid, a car's disc
 // count to COR_MAX_DISCS, the queue to the cells of a pass, n_beams to LID_MAX_BEAMS by the host.
 constexpr int K0L_THREADS = 256;
+// WALLS: the car's walls whose box meets the window are staged in LDS beside the discs (headers, 384 B) and a cell is
+// occupied as wall_core.hpp says (grid, discs, walls); without walls the kernel is the instantiation <false>, the code it
+// always was.
 constexpr int K0L_PASS = 1024;      // cells per pass = the queue's capacity
+template <bool WALLS>
 __global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView map, int B, const double* __restrict__ pose,
                                                                        const int* __restrict__ off,
                                                                        const int* __restrict__ discs, int n_beams,
                                                                        const double* __restrict__ angles, double range_m,
-                                                                       double* __restrict__ ranges) {
+                                                                       double* __restrict__ ranges, WallView wv) {
+  __shared__ int s_whdr[WALLS ? WALL_HDR * COR_MAX_WALLS : 1];
+  __shared__ int s_nw;
   __shared__ double s_ang[LID_MAX_BEAMS];
   __shared__ int s_best[LID_MAX_BEAMS];
   __shared__ int s_disc[3 * COR_MAX_DISCS];
@@ -48,8 +54,21 @@ __global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView m
     s_ang[k] = angles[k];
     s_best[k] = LID_NONE;
   }
-  if (tid == 0) { s_nd = 0; s_nq = 0; }
+  if (tid == 0) { s_nd = 0; s_nq = 0; s_nw = 0; }
   __syncthreads();
+  if (WALLS && wv.off) {
+    const int w0 = wv.off[b];
+    int n = wv.off[b + 1] - w0;
+    n = n > COR_MAX_WALLS ? COR_MAX_WALLS : n;      // (the host refuses more)
+    if (tid < n) {
+      const int* hd = wv.hdr + (long)WALL_HDR * (w0 + tid);
+      const int box[5] = {0, w.i0, w.j0, w.i1, w.j1};
+      if (wall_meets_box(hd, box)) {
+        const int q = atomicAdd(&s_nw, 1);
+        for (int e = 0; e < WALL_HDR; ++e) s_whdr[WALL_HDR * q + e] = hd[e];
+      }
+    }
+  }
   if (off) {
     const int d0 = off[b];
     int nd = off[b + 1] - d0;
@@ -64,8 +83,9 @@ __global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView m
     }
   }
   __syncthreads();
-  const int nd = s_nd;
+  const int nd = s_nd, nw = WALLS ? s_nw : 0;
   auto disc = [&](int q) { return (const int*)(s_disc + 3 * q); };
+  auto whdr = [&](int q) { return (const int*)(s_whdr + WALL_HDR * q); };
   const int cols = w.i1 - w.i0 + 1;
   const int cells = cols > 0 && w.j0 <= w.j1 ? cols * (2 * w.R + 1) : 0;      // at most 4097^2
   for (int base = 0; base < cells; base += K0L_PASS) {      // (uniform)
@@ -75,7 +95,7 @@ __global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView m
       const int dj = (r & 1) ? (r + 1) / 2 : -(r / 2);
       const int i = w.i0 + (t - r * cols), j = cy + dj;
       if (j < w.j0 || j > w.j1) continue;
-      if (!lid_occupied(map, i, j, nd, disc)) continue;
+      if (!(WALLS ? wall_lid_occupied(map, i, j, nd, disc, nw, whdr, wv.tab) : lid_occupied(map, i, j, nd, disc))) continue;
       int d2;
       if (!lid_in_range(i - cx, dj, w.lim, &d2)) continue;
       double lo, hi;
@@ -113,9 +133,18 @@ extern "C" {
 int mpmpc_lidar_scan(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
                      double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
                      int32_t n_beams, const double* angles, double range_m, double* ranges_out) {
+  return mpmpc_lidar_scan_world(device, height, width, data, origin_x, origin_y, resolution, B, pose, offsets, discs, nullptr, nullptr,
+                                n_beams, angles, range_m, ranges_out);
+}
+
+int mpmpc_lidar_scan_world(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                           double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
+                           const int32_t* wall_offsets, const int32_t* walls, int32_t n_beams, const double* angles,
+                           double range_m, double* ranges_out) {
   const char* why = "";
   if (lid_check_scan(height, width, data, resolution, B, pose, offsets, discs, n_beams, angles, range_m, ranges_out, &why))
     return fail(MPMPC_E_ARG, why);
+  if (wall_offsets && wall_check_lists(B, wall_offsets, walls, width, height, &why)) return fail(MPMPC_E_ARG, why);
   if (!mov_finite(origin_x) || !mov_finite(origin_y)) return fail(MPMPC_E_ARG, "the map's origin is not finite");
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
@@ -125,7 +154,9 @@ int mpmpc_lidar_scan(int32_t device, int32_t height, int32_t width, const int8_t
   const size_t nb = (size_t)B, n_disc = offsets ? (size_t)offsets[B] : 0;
   const size_t o_pose = 0, o_ang = o_pose + sizeof(double) * 3 * nb, o_out = o_ang + sizeof(double) * (size_t)n_beams,
                o_off = o_out + sizeof(double) * nb * (size_t)n_beams, o_disc = o_off + pad8(sizeof(int) * (nb + 1)),
-               o_map = o_disc + pad8(sizeof(int) * 3 * n_disc), need = o_map + pad8((size_t)height * width);
+               o_map = o_disc + pad8(sizeof(int) * 3 * n_disc), o_wall = o_map + pad8((size_t)height * width);
+  WallBlock wb = wall_block(o_wall, B, wall_offsets, walls);
+  const size_t need = wb.end;
   SpScratch& g = g_lid_dev[device];
   std::lock_guard<std::mutex> lock(g.mu);
   if (g.bytes < need) {
@@ -142,14 +173,20 @@ int mpmpc_lidar_scan(int32_t device, int32_t height, int32_t width, const int8_t
   HIP_TRY(hipMemcpyAsync(blk + o_map, data, (size_t)height * width, hipMemcpyHostToDevice, stream));
   if (offsets) HIP_TRY(hipMemcpyAsync(blk + o_off, offsets, sizeof(int) * (nb + 1), hipMemcpyHostToDevice, stream));
   if (n_disc > 0) HIP_TRY(hipMemcpyAsync(blk + o_disc, discs, sizeof(int) * 3 * n_disc, hipMemcpyHostToDevice, stream));
+  if (int rc = wall_block_enqueue(blk, wb, B, wall_offsets, walls, stream)) return rc;      // K0w first, on the same stream
   const MapView mv{(const int8_t*)(blk + o_map), height, width, origin_x, origin_y, resolution};
-  hipLaunchKernelGGL(mpmpc_lidar_scan_kernel, dim3(B), dim3(K0L_THREADS), 0, stream, mv, B, (const double*)(blk + o_pose),
-                     offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), n_beams,
-                     (const double*)(blk + o_ang), range_m, (double*)(blk + o_out));
+  if (wall_offsets)
+    hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<true>, dim3(B), dim3(K0L_THREADS), 0, stream, mv, B, (const double*)(blk + o_pose),
+                       offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), n_beams,
+                       (const double*)(blk + o_ang), range_m, (double*)(blk + o_out), wall_block_view(blk, wb, wall_offsets));
+  else
+    hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<false>, dim3(B), dim3(K0L_THREADS), 0, stream, mv, B, (const double*)(blk + o_pose),
+                       offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), n_beams,
+                       (const double*)(blk + o_ang), range_m, (double*)(blk + o_out), WallView{nullptr, nullptr, nullptr});
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(ranges_out, blk + o_out, sizeof(double) * nb * (size_t)n_beams, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  return MPMPC_OK;
+  return wall_block_verdict(wb);
 }
 
 int mpmpc_rollout_scan(mpmpc_handle h, int32_t B, int32_t n_beams, const double* angles, double range_m, double* ranges_out) {
@@ -161,8 +198,8 @@ int mpmpc_rollout_scan(mpmpc_handle h, int32_t B, int32_t n_beams, const double*
   if (!h->cor.map) return fail(MPMPC_E_STATE, "needs mpmpc_set_map first");
   const char* why = "";
   if (lid_check_beams(n_beams, angles, range_m, h->cor.map_res, &why)) return fail(MPMPC_E_ARG, why);
-  const bool per_car = h->obs.obst_B > 0;
-  if (per_car && (!h->obs.car_rows || !h->obs.discs_live || h->obs.obst_B != B))
+  const bool per_car = h->obs.world_B() > 0, discs = h->obs.obst_B > 0;
+  if (per_car && (!h->obs.car_rows || !h->obs.discs_live || h->obs.world_B() != B))
     return fail(MPMPC_E_STATE, "per-car obstacles / movers / traffic are set, but no rollout step of B cars has used them yet, or they were "
                                "set anew since the last step: the cars' worlds are those of a step (mpmpc_rollout_step)");
   HIP_TRY(hipSetDevice(h->cfg.device));
@@ -170,9 +207,14 @@ int mpmpc_rollout_scan(mpmpc_handle h, int32_t B, int32_t n_beams, const double*
   if (h->lid.angles.count() < (size_t)n_beams) HIP_TRY(h->lid.angles.alloc((size_t)LID_MAX_BEAMS));
   if (h->lid.ranges.count() < n_out) HIP_TRY(h->lid.ranges.alloc(n_out));
   HIP_TRY(hipMemcpyAsync(h->lid.angles, angles, sizeof(double) * (size_t)n_beams, hipMemcpyHostToDevice, sl.stream));
-  hipLaunchKernelGGL(mpmpc_lidar_scan_kernel, dim3(B), dim3(K0L_THREADS), 0, sl.stream, h->cor.map_view(), B, h->ro.pose,
-                     per_car ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), n_beams, h->lid.angles.get(), range_m,
-                     h->lid.ranges.get());
+  if (h->obs.wl_B > 0)
+    hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<true>, dim3(B), dim3(K0L_THREADS), 0, sl.stream, h->cor.map_view(), B, h->ro.pose.get(),
+                       discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), n_beams, h->lid.angles.get(), range_m,
+                       h->lid.ranges.get(), h->obs.wall_view());
+  else
+    hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<false>, dim3(B), dim3(K0L_THREADS), 0, sl.stream, h->cor.map_view(), B, h->ro.pose.get(),
+                       discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), n_beams, h->lid.angles.get(), range_m,
+                       h->lid.ranges.get(), WallView{nullptr, nullptr, nullptr});
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(ranges_out, h->lid.ranges, sizeof(double) * n_out, hipMemcpyDeviceToHost, sl.stream));
   HIP_TRY(hipStreamSynchronize(sl.stream));

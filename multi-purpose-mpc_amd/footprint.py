@@ -31,11 +31,12 @@ class Footprint:
         """mpmpc.Handle.rollout_set_audit's mode: 1 audit, 2 audit and stop on contact"""
         return 2 if self.stop else 1
 
-    def audit_batch(self, poses, map, discs=None):
+    def audit_batch(self, poses, map, discs=None, walls=None):
         """poses [B, 3] = x, y, psi on `map` (map.data, .origin, .resolution); discs: per car an int [k, 3] array of
-        (cx, cy, r) map cells on top of map.data (Map.obstacle_discs), or None -> (contact [B] bool, clearance [B])"""
+        (cx, cy, r) map cells on top of map.data (Map.obstacle_discs), or None; walls: per car an int [k, 4] array of
+        (x0, y0, x1, y1) map cells (Map.boundary_walls), or None -> (contact [B] bool, clearance [B])"""
         contact, clearance = mpmpc.footprint_audit(map.data, map.origin, map.resolution, poses, self.length, self.width,
-                                                   self.reach, discs, device=self.device)
+                                                   self.reach, discs, device=self.device, walls=walls)
         return contact.astype(bool), clearance
 
     def audit(self, car, map):

@@ -35,11 +35,12 @@ class LidarModel:
         ranges = np.ones(self.n_measurements) * self.range
         self.measurements = np.stack((angles, ranges), axis=0)
 
-    def scan_batch(self, poses, map, discs=None):
+    def scan_batch(self, poses, map, discs=None, walls=None):
         """poses [B, 3] = x, y, psi on `map` (map.data, .origin, .resolution); discs: per car an int [k, 3] array of
-        (cx, cy, r) map cells on top of map.data (Map.obstacle_discs), or None -> ranges [B, n_measurements]"""
+        (cx, cy, r) map cells on top of map.data (Map.obstacle_discs), or None; walls: per car an int [k, 4] array of
+        (x0, y0, x1, y1) map cells (Map.boundary_walls), or None -> ranges [B, n_measurements]"""
         return mpmpc.lidar_scan(map.data, map.origin, map.resolution, poses, self.measurements[0], self.range, discs,
-                                device=self.device)
+                                device=self.device, walls=walls)
 
     def scan(self, car, map):
         """updates self.measurements[1] with the scan of one car on map.data"""

@@ -142,6 +142,15 @@ class Map:
             disc = xx ** 2 + yy ** 2 <= rad ** 2
             self.data[cy - rad:cy + rad, cx - rad:cx + rad][disc] = 0
 
+    def boundary_walls(self, boundaries):
+        """-> int32 [k, 4]: (x0, y0, x1, y1) in map cells of each boundary ((x0, y0), (x1, y1)) as add_boundary rasterises it
+        (src/map.py:151-155): the w2m of its two end points; the wall is the cells of line_aa(x0, y0, x1, y1).  What
+        mpmpc.Handle.rollout_set_walls takes per car."""
+        out = np.zeros((len(boundaries), 4), np.int32)
+        for j, (p0, p1) in enumerate(boundaries):
+            out[j] = self.w2m(p0[0], p0[1]) + self.w2m(p1[0], p1[1])
+        return out
+
     def add_boundary(self, boundaries):
         self.boundaries.extend(boundaries)
         for (p0, p1) in boundaries:

@@ -170,6 +170,7 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_set_movers.argtypes = [h, C.c_int32, _ip, _ip, _ip, _dp, C.c_int64]
     lib.mpmpc_rollout_obstacles.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_set_traffic.argtypes = [h, C.c_int32, _ip, _ip, C.c_int32, C.c_int32]
+    lib.mpmpc_rollout_set_walls.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_recorded.argtypes = [h, _ip, _ip]
     lib.mpmpc_rollout_trace.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
@@ -193,6 +194,12 @@ def load_library(path: str | None = None):
                                           C.c_int32, _dp, _ip, _ip, C.c_double, C.c_double, C.c_double, _ip, _dp]
     lib.mpmpc_rollout_set_audit.argtypes = [h, C.c_int32, C.c_double, C.c_double, C.c_double]
     lib.mpmpc_rollout_audit.argtypes = [h, C.c_int32, _ip, _ip, _dp, _ip, _ip, _dp]
+    lib.mpmpc_lidar_scan_world.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double,
+                                           C.c_int32, _dp, _ip, _ip, _ip, _ip, C.c_int32, _dp, C.c_double, _dp]
+    lib.mpmpc_footprint_audit_world.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double,
+                                                C.c_int32, _dp, _ip, _ip, _ip, _ip, C.c_double, C.c_double, C.c_double, _ip, _dp]
+    lib.mpmpc_world_grid.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double,
+                                     C.c_int32, _ip, C.c_int32, _ip, C.POINTER(C.c_int8)]
     _ipp, _dpp = C.POINTER(_ip), C.POINTER(_dp)
     lib.mpmpc_staging.argtypes = [h, C.c_int32, _ipp, _dpp, _dpp, _dpp, _dpp, _dpp, _dpp, _ipp, _ipp, _dpp, _dpp]
     lib.mpmpc_solve_staged.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -210,7 +217,8 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_rollout_set_movers", "mpmpc_rollout_obstacles", "mpmpc_rollout_set_traffic",
            "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams", "mpmpc_launch_plan",
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_lidar_scan", "mpmpc_rollout_scan",
-           "mpmpc_footprint_audit", "mpmpc_rollout_set_audit", "mpmpc_rollout_audit", "mpmpc_staging",
+           "mpmpc_footprint_audit", "mpmpc_rollout_set_audit", "mpmpc_rollout_audit", "mpmpc_rollout_set_walls",
+           "mpmpc_lidar_scan_world", "mpmpc_footprint_audit_world", "mpmpc_world_grid", "mpmpc_staging",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -438,6 +446,18 @@ class Handle:
                 raise ValueError("group and radius_cells must be integers")
         grp, rad = (np.ascontiguousarray(a, dtype=np.int32) for a in (grp, rad))
         self._check(self.lib.mpmpc_rollout_set_traffic(self._h, grp.size, _i(grp), _i(rad), int(slots), int(range_cells)))
+
+    def rollout_set_walls(self, walls):
+        """Per-car boundary walls (Map.add_boundary on the device; the law: csrc/wall_core.hpp): walls = one int [k_b, 4]
+        array of (x0, y0, x1, y1) map cells per car (Map.boundary_walls; k_b may be 0, at most 16), or None for no walls.
+        A fourth setting beside rollout_set_obstacles / _movers / _traffic (the same number of cars); needs build_corridor
+        on the current map; may be called between rollout_step calls (applies from the next step, keeps the rollout's
+        state).  rollout_corridor, rollout_scan, the audit and recorded rows see the walls; rollout_obstacles returns discs."""
+        if walls is None:
+            self._check(self.lib.mpmpc_rollout_set_walls(self._h, 0, None, None))
+            return
+        off, flat = _wall_csr(walls)
+        self._check(self.lib.mpmpc_rollout_set_walls(self._h, off.size - 1, _i(off), _i(flat) if flat.size else None))
 
     def rollout_obstacles(self):
         """-> one int32 [k_b, 3] array of (cx, cy, r) per car: the discs the last rollout step used - the car's static discs,
@@ -671,7 +691,37 @@ def speed_profile(li, kappa, limits, eps=1e-12, device=0):
     return v, status, iters
 
 
-def lidar_scan(grid, origin, resolution, poses, angles, range_m, discs=None, device=0):
+def _wall_csr(walls, B=None):
+    """one int [k_b, 4] array per car -> (offsets [B + 1], walls [n, 4]) as the C ABI takes them"""
+    lists = [np.asarray(w, dtype=np.int32).reshape(-1, 4) for w in walls]
+    if B is not None and len(lists) != B:
+        raise ValueError("walls must hold one list per car")
+    off = np.zeros(len(lists) + 1, np.int32)
+    off[1:] = np.cumsum([a.shape[0] for a in lists])
+    flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((0, 4), np.int32), dtype=np.int32)
+    return off, flat
+
+
+def world_grid(grid, origin, resolution, discs=None, walls=None, device=0):
+    """ONE car's world as a grid (K-world): grid [H, W] int8 (1 free / 0 occupied) with discs [k, 3] (Map.obstacle_discs) and
+    walls [k, 4] (Map.boundary_walls) stamped in by the predicate every kernel uses -> int8 [H, W]; what Map.add_obstacles
+    and Map.add_boundary leave in Map.data."""
+    lib = load_library()
+    grid = np.ascontiguousarray(grid, dtype=np.int8)
+    if grid.ndim != 2:
+        raise ValueError("map grid must be 2-D [height, width]")
+    d = np.ascontiguousarray(np.asarray(discs if discs is not None else [], dtype=np.int32).reshape(-1, 3))
+    w = np.ascontiguousarray(np.asarray(walls if walls is not None else [], dtype=np.int32).reshape(-1, 4))
+    out = np.zeros_like(grid)
+    rc = lib.mpmpc_world_grid(int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)), float(origin[0]),
+                              float(origin[1]), float(resolution), d.shape[0], _i(d) if d.size else None, w.shape[0],
+                              _i(w) if w.size else None, out.ctypes.data_as(C.POINTER(C.c_int8)))
+    if rc != 0:
+        raise MpmpcError("mpmpc_world_grid: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    return out
+
+
+def lidar_scan(grid, origin, resolution, poses, angles, range_m, discs=None, device=0, walls=None):
     """Lidar scans of B cars on the device (K0l, replaces LidarModel.scan's loops, src/lidar_model.py:37-112; the law:
     csrc/lidar_core.hpp).  grid [H, W] int8 (1 free / 0 occupied) with its origin and resolution, poses [B, 3] = x, y, psi,
     angles [n] ascending, range_m in metres, discs: one int [k_b, 3] array of (cx, cy, r) map cells per car
@@ -692,6 +742,15 @@ def lidar_scan(grid, origin, resolution, poses, angles, range_m, discs=None, dev
         off[1:] = np.cumsum([a.shape[0] for a in lists])
         flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((0, 3), np.int32), dtype=np.int32)
     out = np.zeros((B, ang.size))
+    if walls is not None:
+        woff, wflat = _wall_csr(walls, B)
+        rc = lib.mpmpc_lidar_scan_world(int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)),
+                                        float(origin[0]), float(origin[1]), float(resolution), B, _d(poses), _i(off),
+                                        _i(flat) if flat is not None and flat.size else None, _i(woff),
+                                        _i(wflat) if wflat.size else None, ang.size, _d(ang), float(range_m), _d(out))
+        if rc != 0:
+            raise MpmpcError("mpmpc_lidar_scan_world: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+        return out
     rc = lib.mpmpc_lidar_scan(int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)),
                               float(origin[0]), float(origin[1]), float(resolution), B, _d(poses), _i(off),
                               _i(flat) if flat is not None and flat.size else None, ang.size, _d(ang), float(range_m), _d(out))
@@ -700,7 +759,7 @@ def lidar_scan(grid, origin, resolution, poses, angles, range_m, discs=None, dev
     return out
 
 
-def footprint_audit(grid, origin, resolution, poses, length, width, reach, discs=None, device=0):
+def footprint_audit(grid, origin, resolution, poses, length, width, reach, discs=None, device=0, walls=None):
     """Contact and clearance of B cars on the device (K0f; the law: csrc/footprint_core.hpp): the length x width rectangle of
     each car, centred at its pose, against its own world.  grid [H, W] int8 (1 free / 0 occupied) with its origin and
     resolution, poses [B, 3] = x, y, psi, reach in metres, discs: one int [k_b, 3] array of (cx, cy, r) map cells per car
@@ -721,6 +780,16 @@ def footprint_audit(grid, origin, resolution, poses, length, width, reach, discs
         off[1:] = np.cumsum([a.shape[0] for a in lists])
         flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((0, 3), np.int32), dtype=np.int32)
     contact, clearance = np.zeros(B, np.int32), np.zeros(B)
+    if walls is not None:
+        woff, wflat = _wall_csr(walls, B)
+        rc = lib.mpmpc_footprint_audit_world(int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)),
+                                             float(origin[0]), float(origin[1]), float(resolution), B, _d(poses), _i(off),
+                                             _i(flat) if flat is not None and flat.size else None, _i(woff),
+                                             _i(wflat) if wflat.size else None, float(length), float(width), float(reach),
+                                             _i(contact), _d(clearance))
+        if rc != 0:
+            raise MpmpcError("mpmpc_footprint_audit_world: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+        return contact, clearance
     rc = lib.mpmpc_footprint_audit(int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)),
                                    float(origin[0]), float(origin[1]), float(resolution), B, _d(poses), _i(off),
                                    _i(flat) if flat is not None and flat.size else None, float(length), float(width),
