@@ -638,6 +638,38 @@ int mpmpc_world_grid(int32_t device, int32_t height, int32_t width, const int8_t
                      double resolution, int32_t n_discs, const int32_t* discs, int32_t n_walls, const int32_t* walls,
                      int8_t* grid_out);
 
+/* ---- perception: plan on what the lidar saw (K0s; the law: csrc/perception_core.hpp).  A car has up to 64 disc slots - its
+ * combined list in the order mpmpc_rollout_obstacles returns it: static discs, movers, traffic slots - and up to 16 wall slots.
+ * A slot is SEEN by a scan iff it occupies a nearest hit cell of some beam.
+ *   mpmpc_perception_scan         no handle; arguments, checks (MPMPC_E_ARG before any device call), scratch and stream as for
+ *                                 mpmpc_lidar_scan_world.  ranges_out [B][n_beams] may be NULL and is bit-equal to
+ *                                 mpmpc_lidar_scan_world's; disc_seen_out [B] uint64, bit q = disc slot q; wall_seen_out [B]
+ *                                 uint32, bit q = wall slot q (neither may be NULL).
+ *   mpmpc_rollout_set_perception  angles == NULL: off (the default; mpmpc_rollout_step launches what it always did).  Else every
+ *                                 step, every car with alive == 1 as the step finds it scans its TRUE world of that step from
+ *                                 its pose; seen slots get last_seen = k (steps count from mpmpc_rollout_init) and first_seen
+ *                                 = k if it was -1.  The step's corridor rows (K0c) are then built in the PERCEIVED world: the
+ *                                 base map plus the KNOWN slots - a static disc or a wall once seen, a mover for `hold` further
+ *                                 steps after it was last seen (at its true disc of the step), a traffic slot in the step it is
+ *                                 seen.  mpmpc_rollout_corridor, recorded rows and the verdicts -3 / -4 report that world; the
+ *                                 audit, mpmpc_rollout_scan, mpmpc_rollout_obstacles and traffic stay in the true one.
+ *                                 MPMPC_E_ARG: what mpmpc_lidar_scan refuses of n_beams, angles and range_m; hold < 0.  The
+ *                                 setting persists across mpmpc_rollout_init and may be changed between steps; this call,
+ *                                 mpmpc_rollout_init and each of the four per-car setters reset every slot of every car to
+ *                                 "never seen".  A step with perception on needs mpmpc_set_map (else MPMPC_E_STATE); while no
+ *                                 per-car setting is in force there is nothing to perceive and the step launches nothing new.
+ *   mpmpc_rollout_perception      what the cars know: disc_first / disc_last [B][64], wall_first / wall_last [B][16] (step
+ *                                 indices, -1: never seen, and for unused slots), disc_known [B] uint64 / wall_known [B]
+ *                                 uint32: the masks the last step planned with.  Any pointer may be NULL.  MPMPC_E_STATE:
+ *                                 perception is off, no step has perceived since a reset, or B is not the rollout's. */
+int mpmpc_perception_scan(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                          double resolution, int32_t B, const double* pose, const int32_t* offsets, const int32_t* discs,
+                          const int32_t* wall_offsets, const int32_t* walls, int32_t n_beams, const double* angles, double range_m,
+                          double* ranges_out, uint64_t* disc_seen_out, uint32_t* wall_seen_out);
+int mpmpc_rollout_set_perception(mpmpc_handle h, int32_t n_beams, const double* angles, double range_m, int32_t hold);
+int mpmpc_rollout_perception(mpmpc_handle h, int32_t B, int32_t* disc_first, int32_t* disc_last, int32_t* wall_first,
+                             int32_t* wall_last, uint64_t* disc_known, uint32_t* wall_known);
+
 #ifdef __cplusplus
 }
 #endif

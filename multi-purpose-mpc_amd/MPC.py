@@ -296,7 +296,7 @@ class BatchMPC:
         return wp.astype(np.int32), t2s_batch(poses[:, 0], poses[:, 1], poses[:, 2], wx, wy, wpsi)
 
     def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
-                walls=None):
+                walls=None, perception=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -322,6 +322,11 @@ class BatchMPC:
         audit: None - no audit; a footprint.Footprint - every step tests the rectangle of every running car, at the pose the
         step finds it at, against the car's world of that step (the map of corridor='device' plus its obstacles, movers and
         traffic discs) on the device, and the returned dict also holds "audit": rollout_audit().
+        perception: None - every car knows its whole world from step 0; a perception.Perception - every step every running
+        car scans its true world with the lidar (K0s) and its corridor is built from the base map plus what it has seen so
+        far (static obstacles and walls once seen, a mover for `hold` steps after it was last seen, traffic while seen);
+        the audit and rollout_scan keep judging the true world.  Needs corridor='device'; the returned dict also holds
+        "perception": rollout_perception() (None when no step perceived: no per-car world, or n_steps = 0).
         record: None - nothing is recorded; True or a dict of mpmpc.Handle.rollout_record's keyword arguments (capacity,
         plan, prediction, rows, stride; capacity defaults to the records `n_steps` yields) - the run is recorded on the
         device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of the whole run, arrays
@@ -351,11 +356,14 @@ class BatchMPC:
             if len(walls) != np.asarray(s).size:
                 raise ValueError("walls must hold one list of boundaries per car")
             wall_cells = [rp.map.boundary_walls(w) for w in walls]
+        if perception is not None and self.corridor_cols is None:
+            raise ValueError("perception needs corridor='device' (update_corridor_from_map): the map lives on the device")
         if getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
             wps = rp.waypoints
             self.handle.set_path_geometry([w.x for w in wps], [w.y for w in wps], [w.psi for w in wps],
                                           [w.static_border_cells[0] for w in wps],
                                           [w.static_border_cells[1] for w in wps])
+        self.handle.rollout_set_perception(None)      # (off first, like the other settings)
         self.handle.rollout_set_obstacles(None)       # (all off first: the settings must agree on B while they are on)
         self.handle.rollout_set_movers(None)
         self.handle.rollout_set_traffic(None)
@@ -374,12 +382,18 @@ class BatchMPC:
             if self.corridor_cols is None:
                 raise ValueError("the audit needs corridor='device' (update_corridor_from_map): the map lives on the device")
             self.handle.rollout_set_audit(audit.mode, audit.length, audit.width, audit.reach)
+        if perception is not None:
+            self.handle.rollout_set_perception(perception.angles, perception.range, perception.hold)
+        perceived = perception is not None and int(n_steps) > 0 and any(
+            v is not None for v in (obstacles, movers, traffic, walls))
         if record is None or record is False:
             self.handle.rollout_init(self.model.Ts, np.cumsum(rp.segment_lengths), s, poses, cc0)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             if audit is not None:
                 out["audit"] = self.handle.rollout_audit()
+            if perception is not None:
+                out["perception"] = self.handle.rollout_perception() if perceived else None
             return out
         kw = dict(record) if isinstance(record, dict) else {}
         stride = int(kw.get("stride", 1))
@@ -392,6 +406,8 @@ class BatchMPC:
             out["trace"] = self.handle.rollout_trace()
             if audit is not None:
                 out["audit"] = self.handle.rollout_audit()
+            if perception is not None:
+                out["perception"] = self.handle.rollout_perception() if perceived else None
         finally:
             self.handle.rollout_record(0, B=np.asarray(s).size)      # later rollouts are unrecorded again
         return out
@@ -401,6 +417,10 @@ class BatchMPC:
         of corridor='device' plus each car's obstacles, movers and traffic discs): lidar is a lidar_model.LidarModel ->
         ranges [B, lidar.n_measurements].  The rollout's state is untouched."""
         return self.handle.rollout_scan(lidar.measurements[0], lidar.range)
+
+    def rollout_perception(self):
+        """What the cars of the last `rollout(..., perception=Perception)` know (mpmpc.Handle.rollout_perception)."""
+        return self.handle.rollout_perception()
 
     def rollout_audit(self):
         """The audit of the last `rollout(..., audit=Footprint)` -> dict of [B] arrays: contact_steps, first_contact,

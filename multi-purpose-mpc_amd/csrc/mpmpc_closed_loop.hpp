@@ -370,6 +370,12 @@ __global__ __launch_bounds__(256) void mpmpc_record_write_kernel(int B, RoRecSrc
 static int aud_reset(mpmpc_handle h, int B);
 static int aud_check_step(mpmpc_handle h, int B);
 static void aud_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, bool per_car);
+// perception inside a rollout (K0s; defined in mpmpc_perception.hpp, behind the lidar): may steps of B cars perceive - and do
+// they (perception on and a per-car setting in force) -, K0s of step k on the slot's stream
+static int per_check_step(mpmpc_handle h, int B, bool per_car, bool* active);
+static void per_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k);
+static const int* per_plan_discs(mpmpc_handle h);      // the perceived lists
+static const int* per_plan_whdr(mpmpc_handle h);
 static const char* const WALLS_OTHER_B = "walls are set for another number of cars (mpmpc_rollout_set_walls)";
 
 extern "C" {
@@ -513,6 +519,7 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   h->io.uploaded = B;
   h->rec.ro_steps = 0;            // the recorder keeps its configuration and starts over
   h->rec.count = 0;
+  h->per.forget();                // what the cars know starts over; the setting stays
   return aud_reset(h, B);         // ... and so does the audit (mpmpc_footprint.hpp)
 }
 
@@ -620,6 +627,14 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   if (int rc = aud_check_step(h, B)) return rc;
   const bool auditing = h->aud.mode != FP_MODE_OFF;
   HIP_TRY(hipSetDevice(h->cfg.device));
+  bool perceiving = false;
+  if (h->per.n_beams > 0) {
+    if (int rc = per_check_step(h, B, per_car, &perceiving)) return rc;
+  }
+  // the world K0c plans in: the true lists, or - perceiving - the lists K0s writes in front of it
+  const int* plan_discs = perceiving ? per_plan_discs(h) : h->obs.obst_discs.get();
+  WallView plan_walls = h->obs.wall_view();
+  if (perceiving && walls) plan_walls.hdr = per_plan_whdr(h);
   const int N = h->cfg.N;
   const size_t car_lds = sizeof(double) * COR_WPC * N + sizeof(int) * (2 * COR_MAXSEG + 3) * N + sizeof(int) * 3 * COR_MAX_DISCS +
                          (sizeof(int) + 1) * COR_CELL_CAP + (walls ? sizeof(int) * WALL_HDR * COR_MAX_WALLS : 0);
@@ -640,21 +655,27 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     if (traffic)
       hipLaunchKernelGGL(mpmpc_traffic_kernel, dim3(B), dim3(64), 0, sl.stream, B, h->obs.tr_S, h->obs.tr_range, mv, h->ro.pose,
                          h->ro.alive, tr_i, tr_i + B, tr_i + 2 * (size_t)B, tr_i + 3 * (size_t)B, h->obs.obst_off, h->obs.obst_discs);
+    if (perceiving) {      // K0m and K0s in front of K3a: K0s reads alive as the step finds it, K0m reads nothing K3a writes
+      if (movers > 0)
+        hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
+                           h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs);
+      per_enqueue_step(h, sl, B, h->rec.ro_steps);
+    }
     hipLaunchKernelGGL(mpmpc_localise_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.N, h->cfg.circular ? 1 : 0,
                        h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, h->ro.s, h->ro.pose, h->ro.alive, h->io.wp_id, h->io.x0, h->ro.shift);
-    if (movers > 0)
+    if (movers > 0 && !perceiving)
       hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
                          h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs);
     if (auditing) aud_enqueue_step(h, sl, B, h->rec.ro_steps, per_car);      // K0f: pose k in world k
     if (walls)
       hipLaunchKernelGGL(mpmpc_car_corridor_kernel<true>, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
                          h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
-                         discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), h->io.wp_id, h->ro.alive.get(),
-                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, h->obs.wall_view());
+                         discs ? h->obs.obst_off.get() : nullptr, plan_discs, h->io.wp_id, h->ro.alive.get(),
+                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, plan_walls);
     else if (per_car)
       hipLaunchKernelGGL(mpmpc_car_corridor_kernel<false>, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
                          h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells,
-                         h->cor.line_box, h->obs.obst_off.get(), h->obs.obst_discs.get(), h->io.wp_id, h->ro.alive.get(),
+                         h->cor.line_box, h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(),
                          h->obs.ro_flag.get(), h->io.lb, h->io.ub, WallView{nullptr, nullptr, nullptr});
     if (int rc = launch_solve(h, sl, B, true, false)) return rc;  // (the plant step reads z and the status only)
     hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro.Ts,
@@ -671,6 +692,7 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   }
   HIP_TRY(hipGetLastError());
   if (n_steps > 0) h->obs.car_rows = h->obs.discs_live = per_car;
+  if (n_steps > 0 && perceiving) h->per.B = B;
   return MPMPC_OK;
 }
 
@@ -716,6 +738,7 @@ static int sync_disc_lists(mpmpc_handle h, std::vector<char>* new_mv) {
 
 int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* discs) {
   if (int rc = enter(h)) return rc;
+  h->per.forget();      // the worlds change: what the cars know of them starts over
   if (!offsets) {      // no static discs: back to the shared table, unless movers or traffic are set
     h->obs.st_B = 0;
     return sync_disc_lists(h, nullptr);
@@ -736,6 +759,7 @@ int mpmpc_rollout_set_obstacles(mpmpc_handle h, int32_t B, const int32_t* offset
 int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* kind,
                              const int32_t* radius_cells, const double* params, int64_t step0) {
   if (int rc = enter(h)) return rc;
+  h->per.forget();      // the worlds change: what the cars know of them starts over
   if (!offsets) {      // no movers
     h->obs.mv_B = 0;
     h->obs.mv_n = 0;
@@ -766,6 +790,7 @@ int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, 
 int mpmpc_rollout_set_traffic(mpmpc_handle h, int32_t B, const int32_t* group, const int32_t* radius_cells, int32_t slots,
                               int32_t range_cells) {
   if (int rc = enter(h)) return rc;
+  h->per.forget();      // the worlds change: what the cars know of them starts over
   if (!group) {      // no traffic
     h->obs.tr_B = 0;
     return sync_disc_lists(h, nullptr);
@@ -792,6 +817,7 @@ int mpmpc_rollout_set_traffic(mpmpc_handle h, int32_t B, const int32_t* group, c
 
 int mpmpc_rollout_set_walls(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* walls) {
   if (int rc = enter(h)) return rc;
+  h->per.forget();      // the worlds change: what the cars know of them starts over
   if (!offsets) {      // no walls
     if (h->obs.wl_B > 0) h->obs.discs_live = false;      // (the worlds change; without walls in force the call changes nothing)
     h->obs.wl_B = 0;

@@ -121,6 +121,22 @@ struct AudState {
   Buf<double> dbls;         // [2][max_batch]: min_clearance, last_clearance
 };
 
+// perception of the rollout (mpmpc_rollout_set_perception; the law: perception_core.hpp): the setting, what every car knows of
+// its world and the perceived lists K0c reads, memory of their own, sized by max_batch on first use
+struct PerState {
+  int n_beams = 0;          // 0: off
+  double range = 0;
+  int hold = 0;
+  std::vector<double> host_angles;      // kept to check the range against the map of the moment
+  Buf<double> angles;       // [LID_MAX_BEAMS]
+  Buf<int> mem;             // K0s's block, max_batch cars wide (K0S_* in mpmpc_lidar.hpp): first_seen / last_seen of every slot, the masks
+                            // the last step planned with, static discs and movers per car, and the perceived lists K0c reads (the
+                            // layouts of obs.obst_discs and obs.wl_hdr)
+  bool fresh = true;        // every slot is to be reset to -1 in front of the next perceiving step
+  int B = 0;                // cars of the perceiving steps since the last reset (0: none yet)
+  void forget() { fresh = true; B = 0; }
+};
+
 // per-batch inputs and host staging
 struct IoState {
   // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
@@ -163,6 +179,7 @@ struct mpmpc_handle_s {
   RecState rec;
   LidState lid;
   AudState aud;
+  PerState per;
   IoState io;
   // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
   // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that

@@ -66,6 +66,7 @@ __device__ long long g_phase[4096 * 32];
 #include "lidar_core.hpp"
 #include "footprint_core.hpp"
 #include "wall_core.hpp"
+#include "perception_core.hpp"
 #include "speed_core.hpp"
 
 using namespace mpmpc;
@@ -912,6 +913,7 @@ int mpmpc_set_corridor(mpmpc_handle h, int32_t n_wp, int32_t n_cols, const doubl
 #include "mpmpc_walls.hpp"
 #include "mpmpc_closed_loop.hpp"
 #include "mpmpc_lidar.hpp"
+#include "mpmpc_perception.hpp"
 #include "mpmpc_footprint.hpp"
 
 extern "C" {

@@ -26,12 +26,37 @@ constexpr int K0L_THREADS = 256;
 // occupied as wall_core.hpp says (grid, discs, walls); without walls the kernel is the instantiation <false>, the code it
 // always was.
 constexpr int K0L_PASS = 1024;      // cells per pass = the queue's capacity
-template <bool WALLS>
-__global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView map, int B, const double* __restrict__ pose,
-                                                                       const int* __restrict__ off,
-                                                                       const int* __restrict__ discs, int n_beams,
-                                                                       const double* __restrict__ angles, double range_m,
-                                                                       double* __restrict__ ranges, WallView wv) {
+// ONE BODY for K0l and for K0s (mpmpc_perception.hpp), which marks what the scan saw: PER 0 is K0l - the code it always was,
+// `pa` unused -, PER 1 a scan that also returns the seen masks, PER 2 the perception of a rollout step.  The law of the
+// marking: perception_core.hpp.  K0s's two further phases:
+//   mark   behind the scan's last barrier best[] is final.  The staged discs and walls keep their SLOT INDEX (s_dslot / s_wslot:
+//          the compaction drops the order); for each, the lanes stride over the cells of its box clipped to the window: the
+//          integer tests first (cor_in_disc / wall_on, the range), then the enclosure as a filter (no beam in it with best == d2:
+//          done), then the exact interval; a cell that owns a beam sets the slot's bit by an LDS atomicOr (two words of discs,
+//          one of walls).  A slot whose bit is set is left at once - the OR is order-free.
+//   know   (PER 2) lanes 0 .. 63 take the car's disc slots, lanes 64 .. 79 its wall slots: first_seen / last_seen, KNOWN, and
+//          the car's perceived discs and wall headers, which K0c reads in place of the true ones.
+// A car that does not scan (PER 2: alive != 1 as the step finds it; any PER: a NaN row) sees nothing and still runs `know`.
+// K0s's memory is ONE block of ints, `cars` cars wide, its arrays back to back (two pointers in the kernel's arguments where
+// eleven made the compiler reserve a stack): PER 1 the seen masks - discs [cars][2] (bit q of the 64: slot q), walls [cars] -,
+// PER 2 the arrays below, K0S_* = the array's offset in ints per car.
+constexpr int K0S_DISC_FIRST = 0, K0S_DISC_LAST = K0S_DISC_FIRST + COR_MAX_DISCS;       // [cars][COR_MAX_DISCS] each
+constexpr int K0S_WALL_FIRST = K0S_DISC_LAST + COR_MAX_DISCS, K0S_WALL_LAST = K0S_WALL_FIRST + COR_MAX_WALLS;      // [cars][COR_MAX_WALLS] each
+constexpr int K0S_DISC_KNOWN = K0S_WALL_LAST + COR_MAX_WALLS, K0S_WALL_KNOWN = K0S_DISC_KNOWN + 2;      // [cars][2], [cars]
+constexpr int K0S_COUNTS = K0S_WALL_KNOWN + 1;      // [cars][2]: static discs, movers of the car (the slots behind them are traffic)
+constexpr int K0S_DISCS = K0S_COUNTS + 2;           // the perceived discs: the layout of `discs` (at most [cars][COR_MAX_DISCS][3])
+constexpr int K0S_WHDR = K0S_DISCS + 3 * COR_MAX_DISCS;      // the perceived wall headers: the layout of wv.hdr
+constexpr int K0S_INTS = K0S_WHDR + WALL_HDR * COR_MAX_WALLS;
+struct K0sArgs {
+  const int* alive;      // PER 2
+  int* mem;
+  int cars;
+  int k, hold;           // PER 2
+};
+template <bool WALLS, int PER>
+__device__ __forceinline__ void k0l_scan_car(const MapView& map, int B, const double* __restrict__ pose, const int* __restrict__ off,
+                                             const int* __restrict__ discs, int n_beams, const double* __restrict__ angles,
+                                             double range_m, double* __restrict__ ranges, const WallView& wv, const K0sArgs& pa) {
   __shared__ int s_whdr[WALLS ? WALL_HDR * COR_MAX_WALLS : 1];
   __shared__ int s_nw;
   __shared__ double s_ang[LID_MAX_BEAMS];
@@ -40,15 +65,22 @@ __global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView m
   __shared__ int s_nd;
   __shared__ int s_queue[K0L_PASS];      // (di + 2048) | (dj + 2048) << 16: |di|, |dj| <= LID_MAX_RANGE_CELLS
   __shared__ int s_nq;
+  __shared__ int s_dslot[PER ? COR_MAX_DISCS : 1], s_wslot[PER ? COR_MAX_WALLS : 1];      // K0s: the staged primitives' slots
+  __shared__ unsigned s_seen[3], s_known[3];      // K0s: discs 0 .. 31, discs 32 .. 63, walls
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= B || n_beams > LID_MAX_BEAMS) return;      // (uniform)
   double* out = ranges + (long)b * n_beams;
   const double x = pose[3L * b], y = pose[3L * b + 1], psi = pose[3L * b + 2];
   int cx = 0, cy = 0;
-  if (!lid_sensor_cell(map, x, y, psi, &cx, &cy)) {      // (uniform)
-    for (int k = tid; k < n_beams; k += K0L_THREADS) out[k] = __builtin_nan("");
-    return;
+  bool scans = PER != 2 || pa.alive[b] == 1;      // (uniform)
+  if (PER && tid < 3) { s_seen[tid] = 0u; s_known[tid] = 0u; }      // (the scan's first barrier, or `know`'s, orders these)
+  if (scans && !lid_sensor_cell(map, x, y, psi, &cx, &cy)) {      // (uniform)
+    if (PER == 0 || ranges)
+      for (int k = tid; k < n_beams; k += K0L_THREADS) out[k] = __builtin_nan("");
+    if (PER == 0) return;
+    scans = false;
   }
+  if (PER == 0 || scans) {
   const LidWindow w = lid_window(map, cx, cy, range_m);
   for (int k = tid; k < n_beams; k += K0L_THREADS) {
     s_ang[k] = angles[k];
@@ -66,6 +98,7 @@ __global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView m
       if (wall_meets_box(hd, box)) {
         const int q = atomicAdd(&s_nw, 1);
         for (int e = 0; e < WALL_HDR; ++e) s_whdr[WALL_HDR * q + e] = hd[e];
+        if (PER) s_wslot[q] = tid;
       }
     }
   }
@@ -79,6 +112,7 @@ __global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView m
       if (d[2] > 0 && cor_disc_meets_box(d, box)) {
         const int q = atomicAdd(&s_nd, 1);
         s_disc[3 * q] = d[0]; s_disc[3 * q + 1] = d[1]; s_disc[3 * q + 2] = d[2];
+        if (PER) s_dslot[q] = tid;
       }
     }
   }
@@ -121,7 +155,91 @@ __global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView m
     __syncthreads();
   }
   __syncthreads();
-  for (int k = tid; k < n_beams; k += K0L_THREADS) out[k] = lid_range(s_best[k], map.res, range_m);
+  if (PER == 0 || ranges)
+    for (int k = tid; k < n_beams; k += K0L_THREADS) out[k] = lid_range(s_best[k], map.res, range_m);
+  if (PER) {      // mark: best[] is final, nothing below writes it
+    for (int q = 0; q < nd; ++q) {      // (uniform)
+      const int* d = disc(q);
+      const int slot = s_dslot[q] & (COR_MAX_DISCS - 1);
+      const int x0 = d[0] - d[2] < w.i0 ? w.i0 : d[0] - d[2], x1 = d[0] + d[2] - 1 > w.i1 ? w.i1 : d[0] + d[2] - 1;
+      const int y0 = d[1] - d[2] < w.j0 ? w.j0 : d[1] - d[2], y1 = d[1] + d[2] - 1 > w.j1 ? w.j1 : d[1] + d[2] - 1;
+      const int bc = x1 - x0 + 1, n = bc > 0 && y1 >= y0 ? bc * (y1 - y0 + 1) : 0;      // (at most 4097^2)
+      for (int t = tid; t < n; t += K0L_THREADS) {
+        if ((s_seen[slot >> 5] >> (slot & 31)) & 1u) break;
+        const int r = t / bc, i = x0 + (t - r * bc), j = y0 + r;
+        int d2;
+        if (!cor_in_disc(i, j, d) || !lid_in_range(i - cx, j - cy, w.lim, &d2)) continue;
+        if (!per_cell_may_own(i - cx, j - cy, d2, psi, s_ang, n_beams, s_best)) continue;
+        if (per_cell_owns_beam(i - cx, j - cy, d2, psi, s_ang, n_beams, s_best)) atomicOr(&s_seen[slot >> 5], 1u << (slot & 31));
+      }
+    }
+    for (int q = 0; q < nw; ++q) {      // (uniform)
+      const int* hd = whdr(q);
+      const int slot = s_wslot[q] & (COR_MAX_WALLS - 1);
+      const int x0 = hd[0] < w.i0 ? w.i0 : hd[0], x1 = hd[2] > w.i1 ? w.i1 : hd[2];
+      const int y0 = hd[1] < w.j0 ? w.j0 : hd[1], y1 = hd[3] > w.j1 ? w.j1 : hd[3];
+      const int bc = x1 - x0 + 1, n = bc > 0 && y1 >= y0 ? bc * (y1 - y0 + 1) : 0;
+      for (int t = tid; t < n; t += K0L_THREADS) {
+        if ((s_seen[2] >> slot) & 1u) break;
+        const int r = t / bc, i = x0 + (t - r * bc), j = y0 + r;
+        int d2;
+        if (!wall_on(i, j, hd, wv.tab) || !lid_in_range(i - cx, j - cy, w.lim, &d2)) continue;
+        if (!per_cell_may_own(i - cx, j - cy, d2, psi, s_ang, n_beams, s_best)) continue;
+        if (per_cell_owns_beam(i - cx, j - cy, d2, psi, s_ang, n_beams, s_best)) atomicOr(&s_seen[2], 1u << slot);
+      }
+    }
+  }
+  }
+  if (PER == 0) return;
+  __syncthreads();
+  if (PER == 1 && tid == 0) {
+    pa.mem[2L * b] = (int)s_seen[0]; pa.mem[2L * b + 1] = (int)s_seen[1];
+    pa.mem[2L * pa.cars + b] = (int)s_seen[2];
+  }
+  if (PER == 2) {      // know
+    auto arr = [&](int a) { return pa.mem + (long)a * pa.cars; };
+    if (tid < COR_MAX_DISCS) {
+      const int d0 = off ? off[b] : 0;
+      int n = off ? off[b + 1] - d0 : 0;
+      n = n > COR_MAX_DISCS ? COR_MAX_DISCS : n;
+      if (tid < n) {
+        const long e = (long)COR_MAX_DISCS * b + tid;
+        int first = arr(K0S_DISC_FIRST)[e], last = arr(K0S_DISC_LAST)[e];
+        per_mark(((s_seen[tid >> 5] >> (tid & 31)) & 1u) != 0, pa.k, &first, &last);
+        arr(K0S_DISC_FIRST)[e] = first; arr(K0S_DISC_LAST)[e] = last;
+        const bool known = per_known(per_disc_kind(tid, arr(K0S_COUNTS)[2L * b], arr(K0S_COUNTS)[2L * b + 1]), last, pa.k, pa.hold);
+        per_disc(known, discs + 3L * (d0 + tid), arr(K0S_DISCS) + 3L * (d0 + tid));
+        if (known) atomicOr(&s_known[tid >> 5], 1u << (tid & 31));
+      }
+    } else if (WALLS && tid < COR_MAX_DISCS + COR_MAX_WALLS && wv.off) {
+      const int q = tid - COR_MAX_DISCS, w0 = wv.off[b];
+      int n = wv.off[b + 1] - w0;
+      n = n > COR_MAX_WALLS ? COR_MAX_WALLS : n;
+      if (q < n) {
+        const long e = (long)COR_MAX_WALLS * b + q;
+        int first = arr(K0S_WALL_FIRST)[e], last = arr(K0S_WALL_LAST)[e];
+        per_mark(((s_seen[2] >> q) & 1u) != 0, pa.k, &first, &last);
+        arr(K0S_WALL_FIRST)[e] = first; arr(K0S_WALL_LAST)[e] = last;
+        const bool known = per_known(PER_WALL, last, pa.k, pa.hold);
+        per_wall(known, wv.hdr + (long)WALL_HDR * (w0 + q), arr(K0S_WHDR) + (long)WALL_HDR * (w0 + q));
+        if (known) atomicOr(&s_known[2], 1u << q);
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      arr(K0S_DISC_KNOWN)[2L * b] = (int)s_known[0]; arr(K0S_DISC_KNOWN)[2L * b + 1] = (int)s_known[1];
+      arr(K0S_WALL_KNOWN)[b] = (int)s_known[2];
+    }
+  }
+}
+
+template <bool WALLS>
+__global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView map, int B, const double* __restrict__ pose,
+                                                                       const int* __restrict__ off,
+                                                                       const int* __restrict__ discs, int n_beams,
+                                                                       const double* __restrict__ angles, double range_m,
+                                                                       double* __restrict__ ranges, WallView wv) {
+  k0l_scan_car<WALLS, 0>(map, B, pose, off, discs, n_beams, angles, range_m, ranges, wv, K0sArgs{});
 }
 
 // device scratch of mpmpc_lidar_scan, kept between calls like the speed profile's (SpScratch: one per device, each behind

@@ -200,6 +200,11 @@ def load_library(path: str | None = None):
                                                 C.c_int32, _dp, _ip, _ip, _ip, _ip, C.c_double, C.c_double, C.c_double, _ip, _dp]
     lib.mpmpc_world_grid.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double,
                                      C.c_int32, _ip, C.c_int32, _ip, C.POINTER(C.c_int8)]
+    lib.mpmpc_perception_scan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double,
+                                          C.c_int32, _dp, _ip, _ip, _ip, _ip, C.c_int32, _dp, C.c_double, _dp,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    lib.mpmpc_rollout_set_perception.argtypes = [h, C.c_int32, _dp, C.c_double, C.c_int32]
+    lib.mpmpc_rollout_perception.argtypes = [h, C.c_int32, _ip, _ip, _ip, _ip, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     _ipp, _dpp = C.POINTER(_ip), C.POINTER(_dp)
     lib.mpmpc_staging.argtypes = [h, C.c_int32, _ipp, _dpp, _dpp, _dpp, _dpp, _dpp, _dpp, _ipp, _ipp, _dpp, _dpp]
     lib.mpmpc_solve_staged.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -219,6 +224,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_lidar_scan", "mpmpc_rollout_scan",
            "mpmpc_footprint_audit", "mpmpc_rollout_set_audit", "mpmpc_rollout_audit", "mpmpc_rollout_set_walls",
            "mpmpc_lidar_scan_world", "mpmpc_footprint_audit_world", "mpmpc_world_grid", "mpmpc_staging",
+           "mpmpc_perception_scan", "mpmpc_rollout_set_perception", "mpmpc_rollout_perception",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -479,6 +485,33 @@ class Handle:
         B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
         out = np.zeros((B, ang.size))
         self._check(self.lib.mpmpc_rollout_scan(self._h, B, ang.size, _d(ang), float(range_m), _d(out)))
+        return out
+
+    # --- perception of the rollout: plan on what the lidar saw (K0s; the law: csrc/perception_core.hpp)
+    def rollout_set_perception(self, angles, range_m=0.0, hold=0):
+        """Every step of the rollouts that follow, every running car scans its TRUE world (angles [n] ascending,
+        lidar_model.LidarModel.measurements[0]; range_m in metres) and its corridor is built from what it KNOWS: the base map,
+        static discs and walls once seen, a mover for `hold` further steps after it was last seen, a traffic slot while
+        seen.  None switches perception off (the default).  Needs set_map; the setting outlives rollout_init, the
+        knowledge starts over with it, with this call and with every per-car setter.  The audit, rollout_scan and
+        rollout_obstacles stay in the true world; rollout_corridor and recorded rows are the perceived world's."""
+        if angles is None:
+            self._check(self.lib.mpmpc_rollout_set_perception(self._h, 0, None, 0.0, 0))
+            return
+        ang = np.ascontiguousarray(angles, dtype=np.float64).ravel()
+        self._check(self.lib.mpmpc_rollout_set_perception(self._h, ang.size, _d(ang), float(range_m), int(hold)))
+
+    def rollout_perception(self):
+        """-> dict: disc_first, disc_last [B, 64], wall_first, wall_last [B, 16] (the step a slot was first / last seen at, -1:
+        never, and for unused slots; disc slots in rollout_obstacles' order), disc_known [B] uint64, wall_known [B] uint32
+        (bit q = slot q: the masks the last step planned with)"""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        out = dict(disc_first=np.zeros((B, 64), np.int32), disc_last=np.zeros((B, 64), np.int32),
+                   wall_first=np.zeros((B, 16), np.int32), wall_last=np.zeros((B, 16), np.int32),
+                   disc_known=np.zeros(B, np.uint64), wall_known=np.zeros(B, np.uint32))
+        self._check(self.lib.mpmpc_rollout_perception(self._h, B, _i(out["disc_first"]), _i(out["disc_last"]), _i(out["wall_first"]),
+                                                      _i(out["wall_last"]), out["disc_known"].ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                      out["wall_known"].ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
 
     # --- footprint audit of the rollout: contact and clearance of every car, every step, accumulated on the device
@@ -757,6 +790,38 @@ def lidar_scan(grid, origin, resolution, poses, angles, range_m, discs=None, dev
     if rc != 0:
         raise MpmpcError("mpmpc_lidar_scan: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
     return out
+
+
+def perception_scan(grid, origin, resolution, poses, angles, range_m, discs=None, walls=None, device=0):
+    """Lidar scans of B cars and WHAT THEY SAW (K0s; the law: csrc/perception_core.hpp): the arguments of lidar_scan ->
+    (ranges [B, n] - lidar_scan's bit for bit -, disc_seen [B] uint64, wall_seen [B] uint32): bit q is set iff disc / wall q of
+    the car's list occupies a nearest hit cell of some beam."""
+    lib = load_library()
+    grid = np.ascontiguousarray(grid, dtype=np.int8)
+    if grid.ndim != 2:
+        raise ValueError("map grid must be 2-D [height, width]")
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    ang = np.ascontiguousarray(angles, dtype=np.float64).ravel()
+    B = poses.shape[0]
+    off = flat = woff = wflat = None
+    if discs is not None:
+        lists = [np.asarray(d, dtype=np.int32).reshape(-1, 3) for d in discs]
+        if len(lists) != B:
+            raise ValueError("discs must hold one list per car")
+        off = np.zeros(B + 1, np.int32)
+        off[1:] = np.cumsum([a.shape[0] for a in lists])
+        flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((0, 3), np.int32), dtype=np.int32)
+    if walls is not None:
+        woff, wflat = _wall_csr(walls, B)
+    out, dseen, wseen = np.zeros((B, ang.size)), np.zeros(B, np.uint64), np.zeros(B, np.uint32)
+    rc = lib.mpmpc_perception_scan(int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)),
+                                   float(origin[0]), float(origin[1]), float(resolution), B, _d(poses), _i(off),
+                                   _i(flat) if flat is not None and flat.size else None, _i(woff),
+                                   _i(wflat) if wflat is not None and wflat.size else None, ang.size, _d(ang), float(range_m),
+                                   _d(out), dseen.ctypes.data_as(C.POINTER(C.c_uint64)), wseen.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc != 0:
+        raise MpmpcError("mpmpc_perception_scan: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    return out, dseen, wseen
 
 
 def footprint_audit(grid, origin, resolution, poses, length, width, reach, discs=None, device=0, walls=None):
