@@ -670,6 +670,47 @@ int mpmpc_rollout_set_perception(mpmpc_handle h, int32_t n_beams, const double* 
 int mpmpc_rollout_perception(mpmpc_handle h, int32_t B, int32_t* disc_first, int32_t* disc_last, int32_t* wall_first,
                              int32_t* wall_last, uint64_t* disc_known, uint32_t* wall_known);
 
+/* ---- reference paths (K0p): replaces ReferencePath.__init__, src/reference_path.py:110-287, for P paths at once, each in a
+ * world of its own - from corner points to the per-waypoint tables and the static width.  The law, step by step, is
+ * csrc/path_core.hpp.  Counts, smoothing, waypoints and the normals' target cells are host code inside the call - every libm
+ * result of a path (atan2, cos, sin) is the HOST's, as for mpmpc_set_path_geometry -; the width, 18 anti-aliased lines per
+ * waypoint through the world's predicate, is the kernel.  No handle is needed.
+ *   mpmpc_path_count   host only: the number of waypoints a path of these corner points ([n_corners][2]) will have; 1 or less:
+ *                      there is no path.  Callers size `cap` with it.  MPMPC_E_ARG (a negative value): fewer than 2 corners, a
+ *                      corner or a resolution that is not finite (and positive), smoothing outside [0, 63].
+ *   mpmpc_path_build   data [height][width] int8, 1 free / 0 occupied, with its frame (mpmpc_set_map's arguments);
+ *                      corner_offsets [P+1] / corners [corner_offsets[P]][2]: the paths' corner points; spec [P][2] =
+ *                      path_resolution, max_width; ispec [P][2] = smoothing, circular; disc_offsets / discs and wall_offsets /
+ *                      walls: the paths' worlds in the formats of mpmpc_rollout_set_obstacles / mpmpc_rollout_set_walls
+ *                      (Map.obstacle_discs, Map.boundary_walls), NULL offsets: the base map; K0w rasterises the walls first,
+ *                      on the same stream.  n_wp [P], status [P], length [P]; x, y, psi, kappa, ds_next, ub, lb [P][cap];
+ *                      border [P][cap][4] = ub_x, ub_y, lb_x, lb_y, the static border cells mpmpc_set_path_geometry takes.
+ *                      Rows from n_wp[p] on, and every row (and the length) of a path with a negative status, are NaN.
+ *                      status[p]   0  built
+ *                                  1  built, and some probed cell lay outside the grid: it counted as occupied (the reference
+ *                                     would have raised there, or wrapped around)
+ *                                 -1  fewer than 2 waypoints
+ *                                 -2  n_wp[p] > cap (n_wp[p] still says how many)
+ *                      A path with a negative status does not disturb the others.  MPMPC_E_ARG, decided on the host before any
+ *                      device call and with every output untouched: P < 1, cap < 1, offsets that do not start at 0 or that
+ *                      decrease, a path with fewer than 2 corners, a corner, resolution or max_width that is not finite (and
+ *                      positive), a corner further than 2^30 cells from the origin, smoothing outside [0, 63], max_width /
+ *                      resolution above 512 cells, a map side above 65534, and what mpmpc_lidar_scan_world refuses of disc
+ *                      and wall lists (64 discs and 16 walls per path, squares or walls leaving the grid).
+ *   mpmpc_path_build_timed   the same call, and ms [3] <- the host part (steps 1 - 4, host clock), the wall rasterisation and
+ *                      the width kernel (device events), in milliseconds. */
+int32_t mpmpc_path_count(int32_t n_corners, const double* corners, double path_resolution, int32_t smoothing);
+int mpmpc_path_build(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                     double resolution, int32_t P, const int32_t* corner_offsets, const double* corners, const double* spec,
+                     const int32_t* ispec, const int32_t* disc_offsets, const int32_t* discs, const int32_t* wall_offsets,
+                     const int32_t* walls, int32_t cap, int32_t* n_wp, int32_t* status, double* x, double* y, double* psi,
+                     double* kappa, double* ds_next, double* ub, double* lb, double* border, double* length);
+int mpmpc_path_build_timed(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y,
+                           double resolution, int32_t P, const int32_t* corner_offsets, const double* corners, const double* spec,
+                           const int32_t* ispec, const int32_t* disc_offsets, const int32_t* discs, const int32_t* wall_offsets,
+                           const int32_t* walls, int32_t cap, int32_t* n_wp, int32_t* status, double* x, double* y, double* psi,
+                           double* kappa, double* ds_next, double* ub, double* lb, double* border, double* length, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

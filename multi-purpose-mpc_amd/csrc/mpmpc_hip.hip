@@ -24,7 +24,8 @@
 //   The twelve solve kernels (K2 ...) are the same steps around their solvers: "the steps of a solve kernel" below.
 //   K0 / K3 / K4                corridor tables from the map and the closed-loop rollout (mpmpc_closed_loop.hpp, with their
 //                               entry points), the speed profile (mpmpc_speed_profile.hpp), the lidar K0l (mpmpc_lidar.hpp), the
-//                               footprint audit K0f (mpmpc_footprint.hpp), the walls K0w and K-world (mpmpc_walls.hpp).
+//                               footprint audit K0f (mpmpc_footprint.hpp), the walls K0w and K-world (mpmpc_walls.hpp), the
+//                               reference paths' static width K0p (mpmpc_path.hpp).
 // Host side: the handle and its sub-states are mpmpc_handle.hpp, their buffers device_buf.hpp; this file keeps create / destroy /
 // settings, the path and corridor tables, upload / download / the staged calls, the launch dispatch, the resident and timed launches.
 //
@@ -33,6 +34,7 @@
 
 #include <atomic>
 #include <cerrno>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -68,6 +70,7 @@ __device__ long long g_phase[4096 * 32];
 #include "wall_core.hpp"
 #include "perception_core.hpp"
 #include "speed_core.hpp"
+#include "path_core.hpp"
 
 using namespace mpmpc;
 
@@ -913,6 +916,7 @@ int mpmpc_set_corridor(mpmpc_handle h, int32_t n_wp, int32_t n_cols, const doubl
 #include "mpmpc_walls.hpp"
 #include "mpmpc_closed_loop.hpp"
 #include "mpmpc_lidar.hpp"
+#include "mpmpc_path.hpp"
 #include "mpmpc_perception.hpp"
 #include "mpmpc_footprint.hpp"
 

@@ -205,6 +205,11 @@ def load_library(path: str | None = None):
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     lib.mpmpc_rollout_set_perception.argtypes = [h, C.c_int32, _dp, C.c_double, C.c_int32]
     lib.mpmpc_rollout_perception.argtypes = [h, C.c_int32, _ip, _ip, _ip, _ip, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    lib.mpmpc_path_count.argtypes = [C.c_int32, _dp, C.c_double, C.c_int32]
+    lib.mpmpc_path_count.restype = C.c_int32
+    lib.mpmpc_path_build.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double,
+                                     C.c_int32, _ip, _dp, _dp, _ip, _ip, _ip, _ip, _ip, C.c_int32, _ip, _ip] + [_dp] * 9
+    lib.mpmpc_path_build_timed.argtypes = lib.mpmpc_path_build.argtypes + [C.POINTER(C.c_float)]
     _ipp, _dpp = C.POINTER(_ip), C.POINTER(_dp)
     lib.mpmpc_staging.argtypes = [h, C.c_int32, _ipp, _dpp, _dpp, _dpp, _dpp, _dpp, _dpp, _ipp, _ipp, _dpp, _dpp]
     lib.mpmpc_solve_staged.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -225,6 +230,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_footprint_audit", "mpmpc_rollout_set_audit", "mpmpc_rollout_audit", "mpmpc_rollout_set_walls",
            "mpmpc_lidar_scan_world", "mpmpc_footprint_audit_world", "mpmpc_world_grid", "mpmpc_staging",
            "mpmpc_perception_scan", "mpmpc_rollout_set_perception", "mpmpc_rollout_perception",
+           "mpmpc_path_count", "mpmpc_path_build", "mpmpc_path_build_timed",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -789,6 +795,83 @@ def lidar_scan(grid, origin, resolution, poses, angles, range_m, discs=None, dev
                               _i(flat) if flat is not None and flat.size else None, ang.size, _d(ang), float(range_m), _d(out))
     if rc != 0:
         raise MpmpcError("mpmpc_lidar_scan: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    return out
+
+
+def path_count(route, path_resolution, smoothing_distance):
+    """The number of waypoints ReferencePath would give a route of corner points [k, 2] (host only, mpmpc_path_count);
+    1 or less: there is no path."""
+    lib = load_library()
+    c = np.ascontiguousarray(route, dtype=np.float64).reshape(-1, 2)
+    n = lib.mpmpc_path_count(c.shape[0], _d(c), float(path_resolution), int(smoothing_distance))
+    if n < 0:
+        raise MpmpcError("mpmpc_path_count: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), n))
+    return n
+
+
+def path_build(grid, origin, resolution, routes, path_resolution, smoothing_distance, max_width, circular=True, discs=None,
+               walls=None, device=0, timings=None):
+    """Reference paths of P routes on the device (K0p, replaces ReferencePath.__init__, src/reference_path.py:110-287; the
+    law: csrc/path_core.hpp).  grid [H, W] int8 (1 free / 0 occupied) with its origin and resolution; routes: a list of [k, 2]
+    arrays of corner points; path_resolution, smoothing_distance, max_width, circular: scalars or one value per route;
+    discs / walls: one int [k_p, 3] / [k_p, 4] array per route (Map.obstacle_discs / Map.boundary_walls) or None for the
+    base map.  The rows per path are sized by mpmpc_path_count.  timings: a list that receives the call's (host, wall
+    rasterisation, width kernel) milliseconds.
+    -> one dict per route: n_wp, status (0 built, 1 built but probed outside the grid, -1 fewer than 2 waypoints), x, y, psi,
+    kappa, ds_next, ub, lb [n_wp], border_ub, border_lb [n_wp, 2], length (empty / NaN for status < 0)."""
+    lib = load_library()
+    grid = np.ascontiguousarray(grid, dtype=np.int8)
+    if grid.ndim != 2:
+        raise ValueError("map grid must be 2-D [height, width]")
+    lists = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 2) for r in routes]
+    P = len(lists)
+    if P < 1:
+        raise ValueError("routes must hold at least one route")
+    coff = np.zeros(P + 1, np.int32)
+    coff[1:] = np.cumsum([a.shape[0] for a in lists])
+    corners = np.ascontiguousarray(np.concatenate(lists))
+    spec = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(path_resolution, float), (P,)),
+                                          np.broadcast_to(np.asarray(max_width, float), (P,))], 1))
+    ispec = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(smoothing_distance), (P,)),
+                                           np.broadcast_to(np.asarray(circular), (P,))], 1).astype(np.int32))
+    cap = 1
+    for p in range(P):
+        n = lib.mpmpc_path_count(lists[p].shape[0], _d(lists[p]), float(spec[p, 0]), int(ispec[p, 0]))
+        if n < 0:
+            raise MpmpcError("mpmpc_path_count: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), n))
+        cap = max(cap, int(n))
+    doff = dflat = woff = wflat = None
+    if discs is not None:
+        dl = [np.asarray(d, dtype=np.int32).reshape(-1, 3) for d in discs]
+        if len(dl) != P:
+            raise ValueError("discs must hold one list per route")
+        doff = np.zeros(P + 1, np.int32)
+        doff[1:] = np.cumsum([a.shape[0] for a in dl])
+        dflat = np.ascontiguousarray(np.concatenate(dl) if doff[-1] else np.zeros((0, 3), np.int32), dtype=np.int32)
+    if walls is not None:
+        woff, wflat = _wall_csr(walls, P)
+    n_wp, status = np.zeros(P, np.int32), np.zeros(P, np.int32)
+    tab = {k: np.zeros((P, cap)) for k in ("x", "y", "psi", "kappa", "ds_next", "ub", "lb")}
+    border, length = np.zeros((P, cap, 4)), np.zeros(P)
+    args = [int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)), float(origin[0]), float(origin[1]),
+            float(resolution), P, _i(coff), _d(corners), _d(spec), _i(ispec), _i(doff),
+            _i(dflat) if dflat is not None and dflat.size else None, _i(woff), _i(wflat) if wflat is not None and wflat.size else None,
+            cap, _i(n_wp), _i(status)] + [_d(tab[k]) for k in ("x", "y", "psi", "kappa", "ds_next", "ub", "lb")] + [_d(border), _d(length)]
+    if timings is None:
+        rc = lib.mpmpc_path_build(*args)
+    else:
+        ms = (C.c_float * 3)()
+        rc = lib.mpmpc_path_build_timed(*args, ms)
+        timings[:] = [float(v) for v in ms]
+    if rc != 0:
+        raise MpmpcError("mpmpc_path_build: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    out = []
+    for p in range(P):
+        n = int(n_wp[p]) if status[p] >= 0 else 0
+        rec = {k: v[p, :n].copy() for k, v in tab.items()}
+        rec.update(n_wp=int(n_wp[p]), status=int(status[p]), border_ub=border[p, :n, :2].copy(), border_lb=border[p, :n, 2:].copy(),
+                   length=float(length[p]))
+        out.append(rec)
     return out
 
 

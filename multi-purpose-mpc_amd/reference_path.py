@@ -15,7 +15,8 @@ order and return types, so src/simulation.py's body runs against it unchanged):
 Additions used by the batched GPU path: `tables()` (per-waypoint kappa / v_ref / ds_next arrays for
 `mpmpc_set_path`) and `corridor_table(n_cols, ...)` (update_path_constraints for every start
 waypoint of a static map, for `mpmpc_set_corridor`); `ReferencePath.from_tables` rebuilds a path
-from stored per-waypoint data (the committed fixtures) without the map image.
+from stored per-waypoint data (the committed fixtures) without the map image; `ReferencePath.on_device`
+has the device build what the constructor computes (K0p, `mpmpc.path_build`) and returns the same object.
 
 Faithfulness notes: curvature of waypoint 0 is the integer 0 (src/reference_path.py:182); the
 forward projection of the previous corridor borders uses cos for both coordinates of the upper and
@@ -89,6 +90,25 @@ class ReferencePath:
             if ub_static is not None:
                 w.ub, w.lb = float(ub_static[i]), float(lb_static[i])
         return self
+
+    @classmethod
+    def on_device(cls, map, wp_x, wp_y, resolution, smoothing_distance, max_width, circular, device=0):
+        """The object the constructor would have made, built by the device (K0p, mpmpc.path_build; the law:
+        csrc/path_core.hpp) on the map as it stands - obstacles and boundaries already stamped into map.data included.
+        Raises ValueError for a route that gives fewer than 2 waypoints; warns when a width probe left the grid (the
+        cell outside counted as occupied; the constructor would have raised or wrapped around there)."""
+        import warnings
+        import mpmpc
+        route = np.stack([np.asarray(wp_x, float), np.asarray(wp_y, float)], 1)
+        rec = mpmpc.path_build(map.data, map.origin, map.resolution, [route], resolution, smoothing_distance, max_width,
+                               circular=bool(circular), device=device)[0]
+        if rec["status"] < 0:
+            raise ValueError("reference path: the route gives %d waypoints (status %d)" % (rec["n_wp"], rec["status"]))
+        if rec["status"] == 1:
+            warnings.warn("reference path: a width probe left the grid; the cell outside counted as occupied")
+        return cls.from_tables(map, rec["x"], rec["y"], rec["psi"], rec["kappa"], circular=circular, border_ub=rec["border_ub"],
+                               border_lb=rec["border_lb"], ub_static=rec["ub"], lb_static=rec["lb"], resolution=resolution,
+                               smoothing_distance=smoothing_distance)
 
     # ------------------------------------------------------------------ construction
     def _construct_path(self, wp_x, wp_y):
