@@ -229,6 +229,43 @@ int mpmpc_set_path(mpmpc_handle h, int32_t n_wp, const double* kappa, const doub
 int mpmpc_set_corridor(mpmpc_handle h, int32_t n_wp, int32_t n_cols, const double* ub,
                        const double* lb);
 
+/* Route fleets: every instance of a batch follows its own reference path.  The tables of mpmpc_set_path (and of
+ * mpmpc_set_corridor, mpmpc_set_path_geometry, mpmpc_build_corridor, which keep their signatures) are then the
+ * CONCATENATION of P routes: route p is rows first[p] .. first[p + 1] - 1 of every per-waypoint table and has its own
+ * circular[p]; the handle-wide mpmpc_config.circular is ignored while routes are set.
+ * The law.  For an instance on route p, n = first[p + 1] - first[p]: every waypoint index of the single-path code is
+ * formed with n_wp := n and circular := circular[p] on LOCAL waypoint ids 0 .. n - 1 - stage k reads rows wp + k and
+ * max(wp + k - 1, 0), wrapped on a circular route (one subtraction when n > N, modulo otherwise), clamped to n - 1 on an
+ * open one - and first[p] is added last, at the load.  wp_id is local to the route wherever it crosses this interface:
+ * mpmpc_upload / _assemble / _solve / the staged calls take local ids (0 <= wp_id < n, and wp_id + N < n on an open
+ * route, per instance), and the corridor-table row an instance reads is global row first[p] + wp_id.
+ *   mpmpc_set_routes      after mpmpc_set_path: first [P + 1] with first[0] = 0, strictly increasing, first[P] = n_wp of
+ *                         the path set; every route has at least 2 waypoints; circular [P].  P = 0 returns the handle to
+ *                         one path.  A new mpmpc_set_path clears the routes.  MPMPC_E_STATE without a path.  When the
+ *                         routes change, the corridor table of a handle on which mpmpc_build_corridor has run is void (its
+ *                         horizons were walked under the old ones): build it again; a table given by mpmpc_set_corridor
+ *                         on a handle that never built one stays.
+ *   mpmpc_set_car_routes  route [B]: the route of instance i in every later call with this B, until set again; ids outside
+ *                         [0, P) are MPMPC_E_ARG.  With routes set, a call on another number of instances than the last
+ *                         mpmpc_set_car_routes returns MPMPC_E_STATE.
+ *   Both calls invalidate the batch on the device - its local wp_id were checked against the old routes: upload again before
+ *   mpmpc_solve_resident, which returns MPMPC_E_STATE until then.
+ *   mpmpc_check_routes    the argument checks of mpmpc_set_routes on their own (no handle, no device).
+ * What works with routes: mpmpc_set_corridor, mpmpc_set_path_geometry, mpmpc_build_corridor (the horizon walk of a start
+ * waypoint wraps or clamps inside its route; the table comes out concatenated), mpmpc_assemble, mpmpc_upload, mpmpc_solve, the
+ * resident and staged solves, at every packing - and the closed loop: mpmpc_rollout_init after mpmpc_set_car_routes for its B,
+ * with cum_lengths [n_wp] the routes' own cumulative lengths laid end to end (each route's starts at 0; s is the arc length
+ * along the car's route), then mpmpc_rollout_step with every setting: per-car obstacles, walls, movers (an along-the-path
+ * mover follows the route of the car that owns it), traffic (a group may span routes: cars of different routes meet),
+ * perception, audit, recorder (wp_id local; the predicted path and the corridor row are the route's), scan.  alive = 0 (s past
+ * the route's length) and -2 (the horizon passes the end of an OPEN route) are decided per route.  Two differences from one
+ * path: the closed-loop warm start is off while routes are set (mpmpc_rollout_warm_start is kept for when they are cleared),
+ * and setting routes or car routes ends a rollout in progress (mpmpc_rollout_init again).  Without routes a handle computes
+ * what it computed before. */
+int mpmpc_check_routes(int32_t n_wp, int32_t P, const int32_t* first, const int32_t* circular);
+int mpmpc_set_routes(mpmpc_handle h, int32_t P, const int32_t* first, const int32_t* circular);
+int mpmpc_set_car_routes(mpmpc_handle h, int32_t B, const int32_t* route);
+
 /* Device-side corridor generation: the three calls below replace, for a map that
  * changes between steps, the host loop of ReferencePath.update_path_constraints + _compute_free_segments
  * + skimage.draw.line_aa + Map.w2m/m2w (src/reference_path.py:466-648, src/map.py:77-101).

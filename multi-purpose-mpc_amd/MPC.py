@@ -188,9 +188,20 @@ class MPC:
             plt.scatter(self.current_prediction[0], self.current_prediction[1], c=PREDICTION, s=30)
 
 
+def _spatial_states(rp, s, poses):
+    """(wp_id[B], x0[B,3]) of cars at arc lengths s and world poses on the reference path rp"""
+    wp = current_waypoint_batch(rp.segment_lengths, s)
+    wx = np.array([w.x for w in rp.waypoints])[wp]
+    wy = np.array([w.y for w in rp.waypoints])[wp]
+    wpsi = np.array([w.psi for w in rp.waypoints])[wp]
+    poses = np.asarray(poses, float)
+    return wp.astype(np.int32), t2s_batch(poses[:, 0], poses[:, 1], poses[:, 2], wx, wy, wpsi)
+
+
 class BatchMPC:
     """B independent controllers sharing one path, weights and limits; one launch per call.  The map is shared too, except
-    in rollout(..., obstacles=...), where every car adds its own obstacles to it."""
+    in rollout(..., obstacles=...), where every car adds its own obstacles to it.  set_routes gives the controller several
+    paths, one per car: get_control_batch(..., routes=...) and rollout(..., routes=...)."""
 
     def __init__(self, model, N, Q, R, QN, StateConstraints, InputConstraints, ay_max, max_batch,
                  settings=None, device=0, corridor=None):
@@ -203,6 +214,7 @@ class BatchMPC:
             raise RuntimeError("reference path has no speed profile (call compute_speed_profile first)")
         self.handle.set_path(kappa, v_ref, ds)
         self._path = model.reference_path
+        self._routes = None               # set_routes: the ReferencePath of every route, else None - the one path
         self.corridor_cols = None
         self._corridor_tables = None      # host copies of a static corridor table (for the further handles of get_control_stream)
         self._stream = None
@@ -219,10 +231,14 @@ class BatchMPC:
 
     def _corridor_from_map(self, h, n_cols):
         rp, m = self._path, self._path.map
-        wps = rp.waypoints
         h.set_map(m.data, m.origin, m.resolution)
-        h.set_path_geometry([w.x for w in wps], [w.y for w in wps], [w.psi for w in wps],
-                            [w.static_border_cells[0] for w in wps], [w.static_border_cells[1] for w in wps])
+        if self._routes is not None:      # the concatenated geometry of the routes (set_routes)
+            g = self._route_geometry
+            h.set_path_geometry(g["x"], g["y"], g["psi"], g["border_ub"], g["border_lb"])
+        else:
+            wps = rp.waypoints
+            h.set_path_geometry([w.x for w in wps], [w.y for w in wps], [w.psi for w in wps],
+                                [w.static_border_cells[0] for w in wps], [w.static_border_cells[1] for w in wps])
         sm = self.model.safety_margin
         return h.build_corridor(n_cols, 2 * sm, sm, want_tables=False)[2]
 
@@ -285,18 +301,57 @@ class BatchMPC:
         self._corridor_tables = None
         return bad
 
-    def spatial_states(self, s, poses):
-        """(wp_id[B], x0[B,3]) from arc lengths and world poses, as get_control does per car."""
-        rp = self._path
-        wp = current_waypoint_batch(rp.segment_lengths, s)
-        wx = np.array([w.x for w in rp.waypoints])[wp]
-        wy = np.array([w.y for w in rp.waypoints])[wp]
-        wpsi = np.array([w.psi for w in rp.waypoints])[wp]
-        poses = np.asarray(poses, float)
-        return wp.astype(np.int32), t2s_batch(poses[:, 0], poses[:, 1], poses[:, 2], wx, wy, wpsi)
+    # --- route fleets: every car of a batch follows its own reference path (mpmpc.Handle.set_routes)
+    def set_routes(self, paths, n_cols=None):
+        """paths: a list of ReferencePath objects on this controller's map, each with its speed profile - the handle's path
+        tables become their concatenation, and get_control_batch(..., routes=route_of_car) solves every car on its own route
+        (wp_id local to it).  With corridor='device' the table is rebuilt from the map for all routes at once (a start
+        waypoint's horizon stays inside its route); otherwise give set_corridor the concatenated table.  None or an empty
+        list returns the controller to the one path it was made with.  rollout(..., routes=route_of_car) drives the fleet in closed
+        loop, every car on its route (s is the arc length along it, wp_id comes back local to it; the warm start is off).
+        get_control_stream stays single-path: it raises while routes are set."""
+        self._close_ring()
+        had_device_table = self.corridor_cols is not None
+        if not paths:
+            self._routes = None
+            self.handle.set_path(*self._path.tables())          # (clears the routes)
+            if had_device_table:
+                self.update_corridor_from_map(n_cols or self.corridor_cols)
+            return None
+        tabs = []
+        for rp in paths:
+            kappa, v_ref, ds = rp.tables()
+            if np.any(np.isnan(v_ref)):
+                raise RuntimeError("a route has no speed profile (call compute_speed_profile first)")
+            wps = rp.waypoints
+            tabs.append(dict(kappa=kappa, v_ref=v_ref, ds_next=ds, x=[w.x for w in wps], y=[w.y for w in wps], psi=[w.psi for w in wps],
+                             border_ub=[w.static_border_cells[0] for w in wps], border_lb=[w.static_border_cells[1] for w in wps]))
+        cat, first = mpmpc.concat_routes(tabs)
+        h = self.handle
+        h.set_path(cat["kappa"], cat["v_ref"], cat["ds_next"])
+        h.set_routes(first, [1 if rp.circular else 0 for rp in paths])
+        self._routes, self._route_geometry, self._corridor_tables = list(paths), cat, None
+        if had_device_table:
+            return self.update_corridor_from_map(n_cols or self.corridor_cols)
+        h.set_path_geometry(cat["x"], cat["y"], cat["psi"], cat["border_ub"], cat["border_lb"])      # (the closed loop localises on it)
+        return None
+
+    def spatial_states(self, s, poses, routes=None):
+        """(wp_id[B], x0[B,3]) from arc lengths and world poses, as get_control does per car.  routes (with set_routes): the
+        route of every car - s is the arc length along it, wp_id comes out local to it."""
+        if routes is not None:
+            if self._routes is None:
+                raise ValueError("routes need set_routes first")
+            routes, s, poses = np.asarray(routes), np.asarray(s, float), np.asarray(poses, float)
+            wp, x0 = np.zeros(s.size, np.int32), np.zeros((s.size, 3))
+            for p in np.unique(routes):
+                idx = np.flatnonzero(routes == p)
+                wp[idx], x0[idx] = _spatial_states(self._routes[int(p)], s[idx], poses[idx])
+            return wp, x0
+        return _spatial_states(self._path, s, poses)
 
     def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
-                walls=None, perception=None):
+                walls=None, perception=None, routes=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -333,6 +388,15 @@ class BatchMPC:
         [records, B, ...] with the state every recorded step started from, its control, status, ... (what
         src/simulation.py:117-157 logs per step)."""
         rp = self._path
+        fleet = getattr(self, "_routes", None)      # (getattr: tests call rollout on stand-ins without __init__)
+        if (fleet is None) != (routes is None):
+            raise ValueError("rollout(routes=...) goes with set_routes: both or neither")
+        if fleet is not None:
+            if len(routes) != np.asarray(s).size:
+                raise ValueError("routes must hold one route id per car")
+            cum = np.concatenate([np.cumsum(p.segment_lengths) for p in fleet])      # each route's own, from 0, laid end to end
+        else:
+            cum = None      # (the one path's, taken where the rollout starts: the argument checks below come first)
         if obstacles is not None:
             if self.corridor_cols is None:
                 raise ValueError("per-car obstacles need corridor='device' (update_corridor_from_map)")
@@ -358,7 +422,9 @@ class BatchMPC:
             wall_cells = [rp.map.boundary_walls(w) for w in walls]
         if perception is not None and self.corridor_cols is None:
             raise ValueError("perception needs corridor='device' (update_corridor_from_map): the map lives on the device")
-        if getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
+        if fleet is not None:
+            self.handle.set_car_routes(routes)      # (the routes' geometry went up with set_routes)
+        elif getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
             wps = rp.waypoints
             self.handle.set_path_geometry([w.x for w in wps], [w.y for w in wps], [w.psi for w in wps],
                                           [w.static_border_cells[0] for w in wps],
@@ -384,10 +450,12 @@ class BatchMPC:
             self.handle.rollout_set_audit(audit.mode, audit.length, audit.width, audit.reach)
         if perception is not None:
             self.handle.rollout_set_perception(perception.angles, perception.range, perception.hold)
+        if cum is None:
+            cum = np.cumsum(rp.segment_lengths)
         perceived = perception is not None and int(n_steps) > 0 and any(
             v is not None for v in (obstacles, movers, traffic, walls))
         if record is None or record is False:
-            self.handle.rollout_init(self.model.Ts, np.cumsum(rp.segment_lengths), s, poses, cc0)
+            self.handle.rollout_init(self.model.Ts, cum, s, poses, cc0)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             if audit is not None:
@@ -400,7 +468,7 @@ class BatchMPC:
         kw.setdefault("capacity", max(1, -(-int(n_steps) // max(stride, 1))))
         self.handle.rollout_record(B=np.asarray(s).size, **kw)
         try:
-            self.handle.rollout_init(self.model.Ts, np.cumsum(rp.segment_lengths), s, poses, cc0)
+            self.handle.rollout_init(self.model.Ts, cum, s, poses, cc0)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             out["trace"] = self.handle.rollout_trace()
@@ -448,6 +516,8 @@ class BatchMPC:
         (corridor=(ub, lb), corridor="device" / update_corridor_from_map: every handle of the ring holds it).  Settings,
         packing and tail kernel follow this controller's set_settings / set_packing / set_tail_kernel."""
         import streamed
+        if self._routes is not None:
+            raise NotImplementedError("get_control_stream follows one path: routes are set (set_routes(None) returns to it)")
         if depth < 1:
             raise ValueError("depth must be >= 1")
         if self._stream is None or self._stream.depth != depth:
@@ -475,8 +545,11 @@ class BatchMPC:
                 plan[:, 1::2] = np.arctan(plan[:, 1::2] * self.model.length)
             yield sol.u0, plan, sol.status
 
-    def get_control_batch(self, wp_id, x0, cc_prev, lb=None, ub=None):
-        """-> (u [B,2] = (v, delta), plan [B,2N] with delta entries, status [B], Solution)."""
+    def get_control_batch(self, wp_id, x0, cc_prev, lb=None, ub=None, routes=None):
+        """-> (u [B,2] = (v, delta), plan [B,2N] with delta entries, status [B], Solution).  routes (with set_routes): the route
+        of every car, wp_id local to it; None keeps the routes of the last call."""
+        if routes is not None:
+            self.handle.set_car_routes(routes)
         sol = self.handle.solve(wp_id, x0, cc_prev, lb, ub)
         plan = sol.z[:, -2 * self.N:].copy()
         plan[:, 1::2] = np.arctan(plan[:, 1::2] * self.model.length)

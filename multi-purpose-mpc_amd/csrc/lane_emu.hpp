@@ -95,6 +95,12 @@ inline VI modi(const VI& a, int m) { VI r; for (int i = 0; i < EMU_W; ++i) r.v[i
 inline VI mini(const VI& a, int b) { VI r; for (int i = 0; i < EMU_W; ++i) r.v[i] = a.v[i] < b ? a.v[i] : b; return r; }
 inline VI maxi(const VI& a, int b) { VI r; for (int i = 0; i < EMU_W; ++i) r.v[i] = a.v[i] > b ? a.v[i] : b; return r; }
 inline VI operator*(const VI& a, int b) { VI r; for (int i = 0; i < EMU_W; ++i) r.v[i] = a.v[i] * b; return r; }
+// ... with a per-lane right-hand side (route fleets: every lane has its own route length, mpmpc_assemble.hpp)
+inline VB operator>(const VI& a, const VI& b) { VB r; for (int i = 0; i < EMU_W; ++i) r.v[i] = a.v[i] > b.v[i]; return r; }
+inline VB operator>=(const VI& a, const VI& b) { VB r; for (int i = 0; i < EMU_W; ++i) r.v[i] = a.v[i] >= b.v[i]; return r; }
+inline VI operator-(const VI& a, const VI& b) { VI r; for (int i = 0; i < EMU_W; ++i) r.v[i] = a.v[i] - b.v[i]; return r; }
+inline VI modi(const VI& a, const VI& m) { VI r; for (int i = 0; i < EMU_W; ++i) r.v[i] = a.v[i] % m.v[i]; return r; }
+inline VI mini(const VI& a, const VI& b) { VI r; for (int i = 0; i < EMU_W; ++i) r.v[i] = a.v[i] < b.v[i] ? a.v[i] : b.v[i]; return r; }
 
 inline VD fma_(const VD& a, const VD& b, const VD& c) { MPMPC_OP(fma); VD r; for (int i = 0; i < EMU_W; ++i) r.v[i] = std::fma(a.v[i], b.v[i], c.v[i]); return r; }
 inline VD sqrt_(const VD& a) { MPMPC_OP(sqrt); VD r; for (int i = 0; i < EMU_W; ++i) r.v[i] = std::sqrt(a.v[i]); return r; }

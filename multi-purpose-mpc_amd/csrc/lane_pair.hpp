@@ -74,6 +74,12 @@ MPMPC_HD I2 operator*(const I2& a, int b) { return I2(a.v[0] * b, a.v[1] * b); }
 MPMPC_HD I2 modi(const I2& a, int m) { return I2(modi(a.v[0], m), modi(a.v[1], m)); }
 MPMPC_HD I2 mini(const I2& a, int b) { return I2(mini(a.v[0], b), mini(a.v[1], b)); }
 MPMPC_HD I2 maxi(const I2& a, int b) { return I2(maxi(a.v[0], b), maxi(a.v[1], b)); }
+// ... with a per-lane right-hand side (route fleets: every lane has its own route length, mpmpc_assemble.hpp)
+MPMPC_HD B2 operator>(const I2& a, const I2& b) { return B2(a.v[0] > b.v[0], a.v[1] > b.v[1]); }
+MPMPC_HD B2 operator>=(const I2& a, const I2& b) { return B2(a.v[0] >= b.v[0], a.v[1] >= b.v[1]); }
+MPMPC_HD I2 operator-(const I2& a, const I2& b) { return I2(a.v[0] - b.v[0], a.v[1] - b.v[1]); }
+MPMPC_HD I2 modi(const I2& a, const I2& m) { return I2(modi(a.v[0], m.v[0]), modi(a.v[1], m.v[1])); }
+MPMPC_HD I2 mini(const I2& a, const I2& b) { return I2(mini(a.v[0], b.v[0]), mini(a.v[1], b.v[1])); }
 
 MPMPC_HD D2 fma_(const D2& a, const D2& b, const D2& c) { return D2(fma_(a.v[0], b.v[0], c.v[0]), fma_(a.v[1], b.v[1], c.v[1])); }
 #define MPMPC_P2_UN(f) MPMPC_HD D2 f(const D2& a) { return D2(f(a.v[0]), f(a.v[1])); }

@@ -125,12 +125,32 @@ struct PathTables {
   const double* ub_tab;   // [n_wp x n_cols] or null
   const double* lb_tab;
   int n_cols;
+  // Route fleets (mpmpc_set_routes / mpmpc_set_car_routes): the tables are the concatenation of several routes and every
+  // instance is on one of them.  route[2 i], route[2 i + 1] = the first row of instance i's route and its length n,
+  // NEGATED on an open route (n >= 2, so the sign is free).  Null: one path, n_wp and cfg.circular as ever.
+  const int* route = nullptr;
 };
+// The rows of stage k of an instance at LOCAL waypoint wp of a route of n waypoints: ik = wp + k and ip = max(wp + k - 1, 0)
+// wrapped (circular) or clamped (open) inside the route - the single-path law of gather_stage with n_wp := n and
+// circular := the route's, every operand per lane (a packed wave holds instances of different routes).  The caller adds the
+// route's first row at the load.
+template <class L>
+MPMPC_HD void route_rows(int N, const typename L::ival& nn, typename L::ival& ik, typename L::ival& ip) {
+  using Mk = typename L::mask;
+  using I = typename L::ival;
+  const Mk circ = nn > 0;
+  const I n = seli(circ, nn, nn * (-1));
+  const Mk one_wrap = n > I(N);      // 0 <= wp < n and k <= N < n: one wrap at most
+  const I last = n - 1;
+  ik = seli(circ, seli(one_wrap, seli(ik >= n, ik - n, ik), modi(ik, n)), mini(ik, last));
+  ip = seli(circ, seli(one_wrap, seli(ip >= n, ip - n, ip), modi(ip, n)), mini(ip, last));
+}
 
 // One (instance, stage) of K1: gather the waypoint data, build the fields, store them
 // stage-blocked as qp[(field * B + inst) * ld + k] (consecutive lanes -> consecutive addresses).
 // (assemble_fields: the 27 fields in registers - what the solve kernel goes on with; assemble_lane: K1, stores them)
-template <class L>
+// ROUTES = false: compiled without the route view (the closed loop's warm-started kernels, which routes do not reach)
+template <class L, bool ROUTES = true>
 MPMPC_HD void gather_stage(const mpmpc_config& c, const PathTables& t, int B, const typename L::ival& inst,
                            const typename L::ival& k, const int* wp_id, const double* x0, const double* cc,
                            const double* lb, const double* ub, StageIn<L>& in, bool with_cc = true) {
@@ -143,7 +163,12 @@ MPMPC_HD void gather_stage(const mpmpc_config& c, const PathTables& t, int B, co
   in.terminal = (k == N);
   I wp = L::gatheri(wp_id, inst, ok, 0);
   I ik = wp + k, ip = maxi(wp + k - 1, 0);
-  if (c.circular) {
+  I row = wp;      // the corridor table's row of the instance
+  if (ROUTES && t.route != nullptr) {      // (uniform: a kernel argument) wp_id is local to the instance's route
+    const I first = L::gatheri(t.route, inst * 2, ok, 0);
+    route_rows<L>(N, L::gatheri(t.route, inst * 2 + 1, ok, 1), ik, ip);
+    ik = ik + first; ip = ip + first; row = wp + first;
+  } else if (c.circular) {
     if (t.n_wp > N) {        // 0 <= wp < n_wp (checked at upload) and k <= N < n_wp: one wrap at most - no integer division
       ik = seli(ik >= t.n_wp, ik - t.n_wp, ik);
       ip = seli(ip >= t.n_wp, ip - t.n_wp, ip);
@@ -170,16 +195,16 @@ MPMPC_HD void gather_stage(const mpmpc_config& c, const PathTables& t, int B, co
     in.lbk = L::gather(lb, inst * N + k - 1, inner, 0.0);
     in.ubk = L::gather(ub, inst * N + k - 1, inner, 0.0);
   } else {
-    in.lbk = L::gather(t.lb_tab, wp * t.n_cols + k - 1, inner, 0.0);
-    in.ubk = L::gather(t.ub_tab, wp * t.n_cols + k - 1, inner, 0.0);
+    in.lbk = L::gather(t.lb_tab, row * t.n_cols + k - 1, inner, 0.0);
+    in.ubk = L::gather(t.ub_tab, row * t.n_cols + k - 1, inner, 0.0);
   }
 }
-template <class L>
+template <class L, bool ROUTES = true>
 MPMPC_HD void assemble_fields(const mpmpc_config& c, const PathTables& t, int B, const typename L::ival& inst,
                               const typename L::ival& k, const int* wp_id, const double* x0, const double* cc,
                               const double* lb, const double* ub, typename L::real* out) {
   StageIn<L> in;
-  gather_stage<L>(c, t, B, inst, k, wp_id, x0, cc, lb, ub, in);
+  gather_stage<L, ROUTES>(c, t, B, inst, k, wp_id, x0, cc, lb, ub, in);
   assemble_stage<L>(c, in, out);
 }
 template <class L>

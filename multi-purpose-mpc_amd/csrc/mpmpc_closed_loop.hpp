@@ -100,8 +100,18 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
                                                                 const int* __restrict__ off, const int* __restrict__ discs,
                                                                 const int* __restrict__ wp_id, int* __restrict__ alive,
                                                                 int* __restrict__ flag, double* __restrict__ lb,
-                                                                double* __restrict__ ub, WallView wv) {
+                                                                double* __restrict__ ub, WallView wv,
+                                                                const int* __restrict__ route) {
   constexpr int PENDING = -1000000;
+  // Route fleets: the car's view of the path - the geometry's base pointers and K0a's caches (indexed by GLOBAL row) moved to the
+  // first row of its route, n_wp and circular the route's (route[2 b], route[2 b + 1]: PathTables::route); wp_id is local.
+  // Everything below, and corridor_core.hpp, works on the view.  (uniform per block; null: one path, nothing moves)
+  if (route) {
+    const long f = route[2 * blockIdx.x];
+    const int nn = route[2 * blockIdx.x + 1];
+    g = PathGeom{g.x + f, g.y + f, g.psi + f, g.ds_next + f, nn > 0 ? nn : -nn, nn > 0 ? 1 : 0, g.trig + f * COR_TRIG};
+    segs += f * 4 * COR_MAXSEG; nseg += f; wpc += f * COR_WPC; line_cells += f * COR_CELL_CAP; line_box += f * COR_LINE_BOX;
+  }
   extern __shared__ double lds[];
   double* col_o = lds;                                             // [N][COR_WPC]
   int* col_seg = (int*)(col_o + (long)N * COR_WPC);                // [N][2 * COR_MAXSEG] packed end cells
@@ -228,9 +238,21 @@ __global__ __launch_bounds__(256) void mpmpc_obstacle_move_kernel(int n, long lo
                                                                   MoverPath path, const int* __restrict__ kind,
                                                                   const int* __restrict__ radius,
                                                                   const double* __restrict__ prm,
-                                                                  const int* __restrict__ dst, int* __restrict__ discs) {
+                                                                  const int* __restrict__ dst, int* __restrict__ discs,
+                                                                  const int* __restrict__ off, int B,
+                                                                  const int* __restrict__ route) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
+  if (route) {      // route fleets: an along-the-path mover follows the route of the car that owns its slot (off: the cars' CSR offsets)
+    int lo = 0, hi = B;      // the car b with off[b] <= dst[j] < off[b + 1]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) / 2;
+      if (off[mid] <= dst[j]) lo = mid; else hi = mid;
+    }
+    const long f = route[2 * lo];
+    const int nn = route[2 * lo + 1];
+    path = MoverPath{path.cum + f, path.x + f, path.y + f, path.trig + f * path.trig_ld, nn > 0 ? nn : -nn, path.trig_ld, nn > 0 ? 1 : 0};
+  }
   int d[3];
   mov_disc(map, path, kind[j], radius[j], prm[j], prm[(long)n + j], prm[2L * n + j], prm[3L * n + j], k, step0, d);
   int* o = discs + 3L * dst[j];
@@ -309,9 +331,16 @@ __global__ __launch_bounds__(256) void mpmpc_localise_kernel(int B, int n_wp, in
                                                              const double* __restrict__ gpsi, const double* __restrict__ s,
                                                              const double* __restrict__ pose, int* __restrict__ alive,
                                                              int* __restrict__ wp_id, double* __restrict__ x0,
-                                                             int* __restrict__ shift) {
+                                                             int* __restrict__ shift, const int* __restrict__ route) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= B || alive[i] != 1) return;
+  if (route) {      // route fleets: the car's slice of cum and of the geometry, its route's length and flag; wp_id stays local
+    const long f = route[2 * i];
+    const int nn = route[2 * i + 1];
+    cum += f; gx += f; gy += f; gpsi += f;
+    n_wp = nn > 0 ? nn : -nn;
+    circular = nn > 0 ? 1 : 0;
+  }
   const int wp = ro_current_waypoint(cum, n_wp, s[i]);
   if (wp < 0) { alive[i] = 0; return; }              // lap finished
   if (shift) {                                        // waypoints advanced since the last step (warm start)
@@ -330,7 +359,8 @@ __global__ __launch_bounds__(256) void mpmpc_advance_kernel(int B, int N, double
                                                             const int* __restrict__ status, const double* __restrict__ z,
                                                             double* __restrict__ cc, int* __restrict__ counter,
                                                             int* __restrict__ alive, double* __restrict__ pose,
-                                                            double* __restrict__ s, double* __restrict__ u_last) {
+                                                            double* __restrict__ s, double* __restrict__ u_last,
+                                                            const int* __restrict__ route) {
   // one thread per (car, plan entry): the N arctangents of a car's new plan are independent; the thread of entry 0
   // then drives the car (it reads only plan entries it wrote itself, or - fallback - entries nobody writes)
   const int g = blockIdx.x * 256 + threadIdx.x;
@@ -339,7 +369,7 @@ __global__ __launch_bounds__(256) void mpmpc_advance_kernel(int B, int N, double
   const int n = 5 * N + 3;
   const int st = status[i];
   if (ro_usable(st)) ro_plan_entry(N, L, z + (long)i * n, cc + (long)i * 2 * N, k);
-  if (k == 0 && !ro_drive(N, L, Ts, st, cc + (long)i * 2 * N, counter + i, x0 + 3 * i, kappa[wp_id[i]], pose + 3 * i,
+  if (k == 0 && !ro_drive(N, L, Ts, st, cc + (long)i * 2 * N, counter + i, x0 + 3 * i, kappa[wp_id[i] + (route ? route[2 * i] : 0)], pose + 3 * i,
                           s + i, u_last + 2 * i))
     alive[i] = -1;
 }
@@ -453,10 +483,23 @@ int mpmpc_build_corridor(mpmpc_handle h, int32_t n_cols, double min_width, doubl
   }
   HIP_TRY(hipMemsetAsync(h->cor.bad, 0, 2 * sizeof(int), sl.stream));
   double* wpc = h->cor.forced_rows(h->tab);
-  hipLaunchKernelGGL(mpmpc_free_segments_kernel, dim3(n), dim3(64), 0, sl.stream, mv, pg, h->cor.bub, h->cor.blb, min_width,
-                     safety_margin, h->cor.segs, h->cor.nseg, wpc, h->cor.bad + 1, h->cor.line_cells, h->cor.line_box);
-  hipLaunchKernelGGL(mpmpc_corridor_select_kernel, dim3((n * n_cols + 255) / 256), dim3(256), 0, sl.stream, pg, h->cor.segs,
-                     h->cor.nseg, n_cols, safety_margin, h->tab.ub_tab, h->tab.lb_tab, h->cor.bad, wpc);
+  // One pair of launches per route (one path: one pair).  A route's view is its rows of every per-waypoint array - the geometry,
+  // the border cells, K0a's caches, the table - with its own length and circular flag: the horizon walk of a start waypoint
+  // wraps or clamps inside its route, and nothing in the kernels or in corridor_core.hpp knows of routes.
+  const int P = h->tab.routes.n_routes ? h->tab.routes.n_routes : 1;
+  for (int p = 0; p < P; ++p) {
+    const size_t f = h->tab.routes.n_routes ? (size_t)h->tab.routes.first[p] : 0;
+    const int np = h->tab.routes.n_routes ? h->tab.routes.first[p + 1] - h->tab.routes.first[p] : n;
+    const PathGeom g{pg.x + f, pg.y + f, pg.psi + f, pg.ds_next + f, np, h->tab.routes.n_routes ? (h->tab.routes.circ[p] ? 1 : 0) : pg.circular,
+                     pg.trig + f * COR_TRIG};
+    double* const segs = h->cor.segs + f * 4 * COR_MAXSEG;
+    hipLaunchKernelGGL(mpmpc_free_segments_kernel, dim3(np), dim3(64), 0, sl.stream, mv, g, h->cor.bub + 2 * f, h->cor.blb + 2 * f, min_width,
+                       safety_margin, segs, h->cor.nseg + f, wpc + f * COR_WPC, h->cor.bad + 1, h->cor.line_cells + f * COR_CELL_CAP,
+                       h->cor.line_box + f * COR_LINE_BOX);
+    hipLaunchKernelGGL(mpmpc_corridor_select_kernel, dim3((np * n_cols + 255) / 256), dim3(256), 0, sl.stream, g, segs,
+                       h->cor.nseg + f, n_cols, safety_margin, h->tab.ub_tab + f * n_cols, h->tab.lb_tab + f * n_cols, h->cor.bad,
+                       wpc + f * COR_WPC);
+  }
   HIP_TRY(hipGetLastError());
   int bad2[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(bad2, h->cor.bad, 2 * sizeof(int), hipMemcpyDeviceToHost, sl.stream));
@@ -487,6 +530,7 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   if (h->tab.n_wp == 0 || h->cor.geom_n != h->tab.n_wp) return fail(MPMPC_E_STATE, "needs mpmpc_set_path and mpmpc_set_path_geometry");
   if (h->tab.n_cols == 0) return fail(MPMPC_E_STATE, "needs a corridor table (mpmpc_set_corridor / mpmpc_build_corridor)");
   if (h->rec.cap > 0 && h->rec.B != B) return fail(MPMPC_E_STATE, "mpmpc_rollout_record was set up for another number of cars");
+  if (int rc = check_car_routes(h, B)) return rc;      // (routes: cum_lengths is the routes' own, each from 0, laid end to end)
   HIP_TRY(hipSetDevice(h->cfg.device));
   const size_t mb = (size_t)h->cfg.max_batch;
   if (!h->ro.s)      // (all seven or none)
@@ -647,6 +691,8 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   const int* mv_i = (const int*)(mv_p + (size_t)MOV_PARAMS * movers);
   const bool traffic = discs && h->obs.tr_B > 0;
   const int* tr_i = h->obs.tr_block;      // dense group, radius, members [B] each, then the groups' offsets
+  if (int rc = check_car_routes(h, B)) return rc;
+  const int* route = h->tab.path_tables().route;      // route fleets: the cars' {first row, length} headers (null: one path)
   for (int t = 0; t < n_steps; ++t) {
     char* rec = recording && h->rec.ro_steps % h->rec.stride == 0 ? h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)h->rec.count : nullptr;
     if (rec)
@@ -658,32 +704,34 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     if (perceiving) {      // K0m and K0s in front of K3a: K0s reads alive as the step finds it, K0m reads nothing K3a writes
       if (movers > 0)
         hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
-                           h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs);
+                           h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs.get(),
+                           h->obs.obst_off.get(), B, route);
       per_enqueue_step(h, sl, B, h->rec.ro_steps);
     }
     hipLaunchKernelGGL(mpmpc_localise_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.N, h->cfg.circular ? 1 : 0,
-                       h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, h->ro.s, h->ro.pose, h->ro.alive, h->io.wp_id, h->io.x0, h->ro.shift);
+                       h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, h->ro.s, h->ro.pose, h->ro.alive, h->io.wp_id, h->io.x0, h->ro.shift, route);
     if (movers > 0 && !perceiving)
       hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
-                         h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs);
+                         h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs.get(),
+                           h->obs.obst_off.get(), B, route);
     if (auditing) aud_enqueue_step(h, sl, B, h->rec.ro_steps, per_car);      // K0f: pose k in world k
     if (walls)
       hipLaunchKernelGGL(mpmpc_car_corridor_kernel<true>, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
                          h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
                          discs ? h->obs.obst_off.get() : nullptr, plan_discs, h->io.wp_id, h->ro.alive.get(),
-                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, plan_walls);
+                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, plan_walls, route);
     else if (per_car)
       hipLaunchKernelGGL(mpmpc_car_corridor_kernel<false>, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
                          h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells,
                          h->cor.line_box, h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(),
-                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, WallView{nullptr, nullptr, nullptr});
+                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, WallView{nullptr, nullptr, nullptr}, route);
     if (int rc = launch_solve(h, sl, B, true, false)) return rc;  // (the plant step reads z and the status only)
     hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro.Ts,
-                       h->tab.kappa, h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter, h->ro.alive, h->ro.pose, h->ro.s, h->ro.u);
+                       h->tab.kappa, h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter, h->ro.alive, h->ro.pose, h->ro.s, h->ro.u, route);
     if (rec) {
       const RoRecSrc src{h->ro.alive, h->rec.ain, h->io.wp_id, sl.status, h->ro.counter, h->io.x0, h->ro.u, h->io.cc, sl.z,
                          h->cor.gx, h->cor.gy, h->cor.gtrig, per_car ? h->io.ub : h->tab.ub_tab, per_car ? h->io.lb : h->tab.lb_tab,
-                         per_car ? (long long)N : (long long)h->tab.n_cols, per_car ? 1 : 0, COR_TRIG, N, h->tab.n_wp, h->cfg.circular ? 1 : 0};
+                         per_car ? (long long)N : (long long)h->tab.n_cols, per_car ? 1 : 0, COR_TRIG, N, h->tab.n_wp, h->cfg.circular ? 1 : 0, route};
       hipLaunchKernelGGL(mpmpc_record_write_kernel, dim3((unsigned)(((long)B * h->rec.lay.entries + 255) / 256)), dim3(256), 0,
                          sl.stream, B, src, rec, h->rec.lay);
       ++h->rec.count;

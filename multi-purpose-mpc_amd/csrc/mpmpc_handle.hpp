@@ -4,6 +4,7 @@
 // Field names: a field drops the prefix that names its own sub-state (ro.s, rec.cap); every other name is kept.
 #pragma once
 #include "device_buf.hpp"
+#include "route_state.hpp"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) {
@@ -22,7 +23,16 @@ static int fail(int code, const std::string& msg) {
 struct TabState {
   Buf<double> kappa, v_ref, ds_next, ub_tab, lb_tab;
   int n_wp = 0, n_cols = 0;
-  PathTables path_tables() const { return PathTables{kappa, v_ref, ds_next, n_wp, ub_tab, lb_tab, n_cols}; }
+  // Route fleets (mpmpc_set_routes / mpmpc_set_car_routes): what the routes are and which one every instance is on
+  // (route_state.hpp: host only), and the device form of the latter, max_batch wide - the {first row, length, negated when
+  // open} pairs that gather_stage reads (PathTables::route).
+  RouteState routes;
+  Buf<int> car_hdr;
+  PathTables path_tables() const {
+    PathTables t{kappa, v_ref, ds_next, n_wp, ub_tab, lb_tab, n_cols};
+    if (routes.n_routes) t.route = car_hdr;
+    return t;
+  }
 };
 
 // corridor generation on the device: grid, per-waypoint geometry, per-waypoint free segments

@@ -190,10 +190,11 @@ MPMPC_HD int inst_in_packed_list_again(const int* list, int B) {
 }
 // (the workgroup kernels keep the values of step 2 through the solve: LaneBlock's *_again are the same threadIdx.x)
 
-template <class L>
+// (ROUTES = false: without the route view of gather_stage - the warm-started kernels of the closed loop, which refuses routes)
+template <class L, bool ROUTES = true>
 MPMPC_HD void assemble_in(const mpmpc_config& cfg, const AssembleIn& ain, int B, const typename L::ival& inst,
                           const typename L::ival& k, typename L::real* fields) {
-  assemble_fields<L>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
+  assemble_fields<L, ROUTES>(cfg, ain.tab, B, inst, k, ain.wp_id, ain.x0, ain.cc, ain.lb, ain.ub, fields);
 }
 
 // Has this lane stage 0 of an instance of the batch that the solver left MPMPC_UNSOLVED?  For an `if`, on the scalars of the
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(64) void mpmpc_solve_kernel(mpmpc_config cfg, Solve
   }
   MPMPC_TICK_BEGIN(8);
   double fields[MPMPC_NUM_FIELDS];
-  assemble_in<L>(cfg, ain, B, inst, k, fields);
+  assemble_in<L, !WARM>(cfg, ain, B, inst, k, fields);
   Solver<L, VAR == 1, VAR == 2, VAR == 3, VAR == 2> s;   // (the reduced variant factors its 16-lane chains by cyclic reduction, like the reduced-native kernels)
   // (second launch of a packed batch: the interior-point iterations the first launch spent on this instance)
   const int base_ipm = (mode == 2 && iters) ? iters[inst * 2 + 1] : 0;
@@ -336,7 +337,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   }
   MPMPC_TICK_BEGIN(8);
   double fields[MPMPC_NUM_FIELDS];
-  assemble_in<L>(cfg, ain, B, inst, k, fields);
+  assemble_in<L, !WARM>(cfg, ain, B, inst, k, fields);
   ReducedSolver<L> s;
   s.template run<WARM>(fields, B, inst, k, cfg.N, st, guess);
   MPMPC_TICK_BEGIN(7);
@@ -887,6 +888,7 @@ int mpmpc_set_path(mpmpc_handle h, int32_t n_wp, const double* kappa, const doub
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int cols = h->tab.n_wp == n_wp ? h->tab.n_cols : 0;   // a corridor table of another path is void
   h->tab.n_wp = h->tab.n_cols = 0;      // a failure below leaves "no path set", not tables of mixed lengths
+  h->tab.routes.clear();                // routes belong to the path they were set on
   if (int rc = upload_table(h, h->tab.kappa, kappa, n_wp)) return rc;
   if (int rc = upload_table(h, h->tab.v_ref, v_ref, n_wp)) return rc;
   if (int rc = upload_table(h, h->tab.ds_next, ds_next, n_wp)) return rc;
@@ -909,8 +911,68 @@ int mpmpc_set_corridor(mpmpc_handle h, int32_t n_wp, int32_t n_cols, const doubl
   return MPMPC_OK;
 }
 
+// The routes change.  A corridor table that mpmpc_build_corridor made walked its horizons under the old ones (or the one path):
+// it is void - the solves then ask for a table instead of reading rows that cross a route's end.  (built_gen != 0: a build has
+// succeeded on this handle, whatever mpmpc_set_map / _set_path_geometry did to the generation since; a table that
+// mpmpc_set_corridor gave AFTER a build goes too - the safe side: the caller gives it again.)  And the batch on the device was
+// checked against the old routes: its local wp_id may lie outside the new ones, so it has to be uploaded again.
+static void routes_change(mpmpc_handle h) {
+  if (h->cor.built_gen != 0) h->tab.n_cols = 0;
+  ++h->cor.base_gen;
+  h->io.uploaded = 0;
+  h->ro.valid = false;
+}
+
+// ---- Route fleets: the path table as the concatenation of P routes, every instance on one of them (the law: include/mpmpc.h;
+// the state and every check on it: route_state.hpp - host only, tests/emul_routes drives it without a device).
+int mpmpc_check_routes(int32_t n_wp, int32_t P, const int32_t* first, const int32_t* circular) {
+  const char* why = "";
+  if (int rc = RouteState::check(n_wp, P, first, circular, &why)) return fail(rc, why);
+  return MPMPC_OK;
+}
+
+int mpmpc_set_routes(mpmpc_handle h, int32_t P, const int32_t* first, const int32_t* circular) {
+  if (int rc = enter(h)) return rc;
+  const char* why = "";
+  bool changed = false;
+  const int rc = h->tab.routes.set_routes(h->tab.n_wp, P, first, circular, &changed, &why);
+  if (changed) routes_change(h);
+  return rc ? fail(rc, why) : MPMPC_OK;
+}
+
+int mpmpc_set_car_routes(mpmpc_handle h, int32_t B, const int32_t* route) {
+  if (int rc = enter(h, route)) return rc;
+  TabState& t = h->tab;
+  const char* why = "";
+  std::vector<int32_t> hdr;
+  if (int rc = t.routes.car_headers(h->cfg.max_batch, B, route, &hdr, &why)) return fail(rc, why);
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  t.routes.car_B = 0;      // a failure below leaves "not given"
+  // The batch on the device was checked against the routes its cars had (check_wp_ids): re-dealt, a local wp_id may lie past
+  // its new route's end - the corridor row first + wp would be read out of bounds - so it is to be uploaded again.
+  h->io.uploaded = 0;
+  h->ro.valid = false;
+  // (the one header array is safe to overwrite here: `enter` has drained every other slot with launches in flight, and what the
+  //  last slot's stream still has queued is ordered in front of this copy)
+  if (!t.car_hdr) HIP_TRY(t.car_hdr.alloc(2 * (size_t)h->cfg.max_batch));
+  HIP_TRY(hipMemcpyAsync(t.car_hdr, hdr.data(), hdr.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->last().stream));
+  HIP_TRY(hipStreamSynchronize(h->last().stream));      // `hdr` leaves scope
+  t.routes.keep_car_routes(B, route);
+  return MPMPC_OK;
+}
+
 }  // extern "C"
 
+static int check_car_routes(mpmpc_handle h, int B) {
+  const char* why = "";
+  if (int rc = h->tab.routes.check_batch(B, &why)) return fail(rc, why);
+  return MPMPC_OK;
+}
+static int check_wp_ids(mpmpc_handle h, int B, const int32_t* wp_id) {
+  const char* why = "";
+  if (int rc = h->tab.routes.check_wp_ids(B, wp_id, h->cfg.N, h->tab.n_wp, h->cfg.circular != 0, &why)) return fail(rc, why);
+  return MPMPC_OK;
+}
 // (the kernels of the two keep their order in the code object: K4, then K0 / K3 and the recorder)
 #include "mpmpc_speed_profile.hpp"
 #include "mpmpc_walls.hpp"
@@ -930,11 +992,7 @@ int mpmpc_upload(mpmpc_handle h, int32_t B, const int32_t* wp_id, const double* 
   if ((lb == nullptr) != (ub == nullptr)) return fail(MPMPC_E_ARG, "lb and ub must both be given or both NULL");
   if (!lb && h->tab.n_cols == 0) return fail(MPMPC_E_STATE, "no corridor rows given and no corridor table set");
   const int N = h->cfg.N;
-  for (int i = 0; i < B; ++i) {
-    if (wp_id[i] < 0 || wp_id[i] >= h->tab.n_wp) return fail(MPMPC_E_ARG, "wp_id out of range");
-    // an open path ends the run when the horizon passes its last waypoint (src/reference_path.py:367-369)
-    if (!h->cfg.circular && wp_id[i] + N >= h->tab.n_wp) return fail(MPMPC_E_ARG, "Reached end of path!");
-  }
+  if (int rc = check_wp_ids(h, B, wp_id)) return rc;
   HIP_TRY(hipSetDevice(h->cfg.device));
   h->ro.valid = false;        // the batch blocks are about to be re-laid out and overwritten
   if (B != h->io.laid_out) lay_out(h, B);
@@ -992,6 +1050,7 @@ static int upload_through_bounce(mpmpc_handle h, void* dst, const void* src, siz
 }
 
 static int launch_assemble(mpmpc_handle h, int B) {
+  if (int rc = check_car_routes(h, B)) return rc;
   const AssembleIn in = h->io.inputs(h->tab);
   const int total = B * h->ld;
   const int blocks = (total + K1_THREADS - 1) / K1_THREADS;
@@ -1173,10 +1232,13 @@ static int run_stages(mpmpc_handle h, Slot& sl, bool late) {
 
 // A solve launch on slot `sl`: plan it, bind the slot's lists to their roles, run the stages.
 static int launch_solve(mpmpc_handle h, Slot& sl, int B, bool closed_loop, bool want_y, LaunchKind kind) {
+  if (int rc = check_car_routes(h, B)) return rc;
+  // (route fleets start every closed-loop solve cold: the warm-started instantiations are compiled without the route view -
+  //  gather_stage<L, ROUTES = false> - so that they keep the registers they had)
   sl.y_valid = sl.want_y = want_y;
   sl.launch_B = B;
   sl.prm = make_params(h->st);
-  sl.plan = plan_solve(h->cfg, h->st, LaunchKnobs{h->force_lanes, h->lean_tail, h->lean_tail_single, h->pipeline, h->ro.warm}, B, closed_loop, kind);
+  sl.plan = plan_solve(h->cfg, h->st, LaunchKnobs{h->force_lanes, h->lean_tail, h->lean_tail_single, h->pipeline, h->tab.routes.n_routes ? 0 : h->ro.warm}, B, closed_loop, kind);
   sl.next_stage = 0;
   // tail lists ([0] = count, [1..] = instance ids), two of them used in turn: the tail launch of this step empties the
   // list of the next one, so that no memset has to sit between the launches of consecutive steps; the third is what the
@@ -1480,10 +1542,7 @@ int mpmpc_staged_begin(mpmpc_handle h, int32_t B, int32_t with_rows, int32_t wan
   const int N = h->cfg.N;
   const BlockLayout L = block_layout(N, B);
   const int32_t* wp = reinterpret_cast<const int32_t*>(h->io.stage_in + L.wp_id);
-  for (int i = 0; i < B; ++i) {
-    if (wp[i] < 0 || wp[i] >= h->tab.n_wp) return fail(MPMPC_E_ARG, "wp_id out of range");
-    if (!h->cfg.circular && wp[i] + N >= h->tab.n_wp) return fail(MPMPC_E_ARG, "Reached end of path!");
-  }
+  if (int rc = check_wp_ids(h, B, wp)) return rc;
   HIP_TRY(hipSetDevice(h->cfg.device));
   if (h->io.in_flight) { HIP_TRY(hipEventSynchronize(h->io.ev_in)); h->io.in_flight = false; }
   h->ro.valid = false;

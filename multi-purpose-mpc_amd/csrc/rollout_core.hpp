@@ -157,6 +157,7 @@ struct RoRecSrc {
   const double *row_ub, *row_lb;            // corridor rows: row `wp_id` of the table, or row `car` of the per-car rows
   long long row_ld;
   int per_car, trig_ld, N, n_wp, circular;
+  const int* route = nullptr;               // route fleets: {first row, length - negated when open} per car (PathTables::route)
 };
 
 // entry e of car i, in the order x0[3], u[2], wp_id, status, counter, alive, then plan / pred_x / pred_y / ub / lb as recorded
@@ -182,8 +183,12 @@ MPMPC_HD void ro_record_finish(const RoRecSrc& r, char* rec, const RoTraceLayout
       const int k = (is_y ? e - (N - 2) : e) + 2;      // stage 2 .. N-1
       double v = nan;
       if (ro_rec_pred(a_in, a, r.status[i])) {
+        const int nn = r.route ? r.route[2 * i + 1] : 0;      // the car's route: wrap / clamp inside it, its first row added last
+        const int n = r.route ? (nn > 0 ? nn : -nn) : r.n_wp;
+        const bool circular = r.route ? nn > 0 : r.circular != 0;
         int w = r.wp_id[i] + k;
-        if (w >= r.n_wp) w = r.circular ? w % r.n_wp : r.n_wp - 1;
+        if (w >= n) w = circular ? w % n : n - 1;
+        if (r.route) w += r.route[2 * i];
         double px, py;
         ro_pred_point(r.gx[w], r.gy[w], r.trig[(long long)w * r.trig_ld], r.trig[(long long)w * r.trig_ld + 1],
                       r.z[(5LL * N + 3) * i + 3 * k], &px, &py);
@@ -197,7 +202,7 @@ MPMPC_HD void ro_record_finish(const RoRecSrc& r, char* rec, const RoTraceLayout
   if (l.ub >= 0 && e < 2 * N) {
     const bool is_lb = e >= N;
     const int k = is_lb ? e - N : e;
-    const long long row = r.per_car ? i : (solved ? r.wp_id[i] : 0);
+    const long long row = r.per_car ? i : (solved ? r.wp_id[i] + (r.route ? r.route[2 * i] : 0) : 0);
     const double* src = is_lb ? r.row_lb : r.row_ub;
     ((double*)(rec + (is_lb ? l.lb : l.ub)))[(long long)N * i + k] = solved ? src[row * r.row_ld + k] : nan;
   }

@@ -157,6 +157,9 @@ def load_library(path: str | None = None):
     lib.mpmpc_launch_plan.restype = C.c_int32
     lib.mpmpc_set_path.argtypes = [h, C.c_int32, _dp, _dp, _dp]
     lib.mpmpc_set_corridor.argtypes = [h, C.c_int32, C.c_int32, _dp, _dp]
+    lib.mpmpc_check_routes.argtypes = [C.c_int32, C.c_int32, _ip, _ip]
+    lib.mpmpc_set_routes.argtypes = [h, C.c_int32, _ip, _ip]
+    lib.mpmpc_set_car_routes.argtypes = [h, C.c_int32, _ip]
     lib.mpmpc_set_map.argtypes = [h, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double]
     lib.mpmpc_set_path_geometry.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp, _dp]
     lib.mpmpc_build_corridor.argtypes = [h, C.c_int32, C.c_double, C.c_double, _dp, _dp, _ip]
@@ -231,6 +234,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_lidar_scan_world", "mpmpc_footprint_audit_world", "mpmpc_world_grid", "mpmpc_staging",
            "mpmpc_perception_scan", "mpmpc_rollout_set_perception", "mpmpc_rollout_perception",
            "mpmpc_path_count", "mpmpc_path_build", "mpmpc_path_build_timed",
+           "mpmpc_check_routes", "mpmpc_set_routes", "mpmpc_set_car_routes",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -333,6 +337,22 @@ class Handle:
             raise ValueError("corridor tables must be equal-shape [n_wp x n_cols]")
         self._check(self.lib.mpmpc_set_corridor(self._h, ub.shape[0], ub.shape[1], _d(ub), _d(lb)))
         self._have_table = True
+
+    # --- route fleets: the path tables are the concatenation of several routes, every instance is on one of them
+    def set_routes(self, first, circular):
+        """After set_path: route p is rows first[p] .. first[p + 1] - 1 of every per-waypoint table (first[0] = 0, first[-1] =
+        the path's length; concat_routes returns it) with its own circular[p].  wp_id is then local to an instance's route in
+        every call.  An empty `circular` (P = 0) returns the handle to one path; a new set_path clears the routes."""
+        f = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+        c = np.ascontiguousarray(circular, dtype=np.int32).reshape(-1)
+        if c.size and f.size != c.size + 1:
+            raise ValueError("first needs one entry more than circular")
+        self._check(self.lib.mpmpc_set_routes(self._h, c.size, _i(f) if c.size else None, _i(c) if c.size else None))
+
+    def set_car_routes(self, route):
+        """route[i]: the route of instance i in every later call on len(route) instances, until set again."""
+        r = np.ascontiguousarray(route, dtype=np.int32).reshape(-1)
+        self._check(self.lib.mpmpc_set_car_routes(self._h, r.size, _i(r)))
 
     # --- corridor generation on the device (dynamic maps)
     def set_map(self, data, origin, resolution):
@@ -873,6 +893,41 @@ def path_build(grid, origin, resolution, routes, path_resolution, smoothing_dist
                    length=float(length[p]))
         out.append(rec)
     return out
+
+
+def concat_routes(routes):
+    """The tables of several routes laid end to end, for a handle with routes (Handle.set_routes).  routes: one dict of
+    per-waypoint arrays per route - what path_build returns, or any dict with at least kappa - or the
+    (kappa, v_ref, ds_next) tuple of ReferencePath.tables().  -> (tables, first): every key that all routes hold as
+    an array with one row per waypoint, concatenated in route order, and first [P + 1], the row each route starts at.
+    `cum_lengths` is re-based so that each route's starts at 0; everything else is copied as it is."""
+    routes = [dict(zip(("kappa", "v_ref", "ds_next"), r)) if isinstance(r, (tuple, list)) else r for r in routes]
+    if not routes:
+        raise ValueError("concat_routes needs at least one route")
+    n = [int(np.asarray(r["kappa"]).shape[0]) for r in routes]
+    first = np.zeros(len(routes) + 1, np.int32)
+    first[1:] = np.cumsum(n)
+    tables = {}
+    for key in routes[0]:
+        parts = [np.asarray(r[key]) if key in r else None for r in routes]
+        if any(a is None or a.ndim < 1 or a.shape[0] != k for a, k in zip(parts, n)):
+            continue
+        if key == "cum_lengths":
+            parts = [np.asarray(a, float) - float(a[0]) for a in parts]
+        tables[key] = np.ascontiguousarray(np.concatenate(parts))
+    return tables, first
+
+
+def check_routes(n_wp, first, circular):
+    """The argument checks of Handle.set_routes on their own (no handle, no device): raises MpmpcError as it would."""
+    lib = load_library()
+    f = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+    c = np.ascontiguousarray(circular, dtype=np.int32).reshape(-1)
+    if f.size != c.size + 1:
+        raise ValueError("first needs one entry more than circular")
+    rc = lib.mpmpc_check_routes(int(n_wp), c.size, _i(f), _i(c) if c.size else None)
+    if rc != 0:
+        raise MpmpcError("mpmpc error %d: %s" % (rc, lib.mpmpc_last_error().decode()))
 
 
 def perception_scan(grid, origin, resolution, poses, angles, range_m, discs=None, walls=None, device=0):
