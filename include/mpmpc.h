@@ -260,11 +260,46 @@ int mpmpc_set_corridor(mpmpc_handle h, int32_t n_wp, int32_t n_cols, const doubl
  * perception, audit, recorder (wp_id local; the predicted path and the corridor row are the route's), scan.  alive = 0 (s past
  * the route's length) and -2 (the horizon passes the end of an OPEN route) are decided per route.  Two differences from one
  * path: the closed-loop warm start is off while routes are set (mpmpc_rollout_warm_start is kept for when they are cleared),
- * and setting routes or car routes ends a rollout in progress (mpmpc_rollout_init again).  Without routes a handle computes
- * what it computed before. */
+ * and setting routes or car routes ends a rollout in progress (mpmpc_rollout_init again; mpmpc_rollout_reroute below changes
+ * the routes of running cars and does not).  Without routes a handle computes what it computed before. */
 int mpmpc_check_routes(int32_t n_wp, int32_t P, const int32_t* first, const int32_t* circular);
 int mpmpc_set_routes(mpmpc_handle h, int32_t P, const int32_t* first, const int32_t* circular);
 int mpmpc_set_car_routes(mpmpc_handle h, int32_t B, const int32_t* route);
+
+/* Where is a pose on a route, and re-routing the cars of a running rollout.
+ * The law (csrc/project_core.hpp).  A route is rows first .. first + n - 1 of x, y, psi, cum; cum is the route's own cumulative
+ * length starting at 0, what mpmpc_rollout_init takes.  For a pose (px, py, ppsi) and every local waypoint j:
+ * d2[j] = dx dx + dy dy with dx = px - x[j], dy = py - y[j] (every operation rounded on its own); e_psi[j] is the heading error
+ * of the rollout's localisation, fmod(ppsi - psi[j] + pi, 2 pi), + 2 pi if negative, - pi; j is eligible when
+ * |e_psi[j]| <= max_heading (max_heading >= pi: every waypoint - the gate keeps a car on the right branch where routes cross
+ * or run back beside themselves).  wp is the eligible j of the smallest d2, ties to the lowest j; -1 when none is eligible or a
+ * pose component is not finite.  dist = sqrt(d2[wp]); x0 = (e_y, e_psi, 0) of the pose at waypoint wp, as the rollout forms
+ * it; s = cum[wp].  With wp = -1: dist = +inf, x0 and s NaN.  s = cum[wp] on purpose: the rollout's localisation then finds
+ * wp again for every wp < n - 1, and "finished" at wp = n - 1.
+ *   mpmpc_project          no handle.  The tables are [n_wp]; P = 0 or first = NULL: one route of n_wp rows, else first [P + 1]
+ *                          by the rules of mpmpc_check_routes.  pose [B*3].  cand [B*K]: the K candidate routes of every pose
+ *                          (ids may repeat); NULL with K = P (K = 1 for one route): every route.  An id outside [0, P),
+ *                          max_heading negative or NaN: MPMPC_E_ARG.  Outputs [B*K] (x0_out [B*K*3]), any may be NULL.
+ *   mpmpc_rollout_reroute  needs routes, and a rollout in progress on exactly B cars (else MPMPC_E_STATE).  route [B]: the
+ *                          route car i is to take, -1: keep; an id outside [-1, P), max_dist or max_heading negative or NaN:
+ *                          MPMPC_E_ARG, nothing changes (max_dist may be +inf).  On the device, every RUNNING car (alive = 1)
+ *                          with route[i] >= 0 is projected from its current pose onto that route; if wp >= 0 and
+ *                          dist <= max_dist the car is on that route from now on with s = cum[wp] of it and accepted = 1, else
+ *                          it keeps its route and s and accepted = 0 (as for a car that is not running, or kept).  A car sent
+ *                          to the route it is on is treated like any other: s snaps to the nearest waypoint.  Pose, plan,
+ *                          u_last, infeasibility counter, alive, audit accumulators, perception memory, recorder and every
+ *                          per-car world setting stay as they are; wp_id and x0 of an accepted car become the projection's
+ *                          (local to the new route) until the next step localises anew.  The rollout goes on: the call does
+ *                          not end it and voids neither the batch nor the corridor table.  The next step localises on the new
+ *                          route, an along-the-path mover of the car follows it, and a car put within N waypoints of an open
+ *                          route's end gets alive = -2 at its next step.  accepted_out [B] may be NULL.
+ *   mpmpc_rollout_routes   route_out [B]: the route every car is on now.  MPMPC_E_STATE without routes or car routes for B. */
+int mpmpc_project(int32_t device, int32_t n_wp, const double* x, const double* y, const double* psi, const double* cum,
+                  int32_t P, const int32_t* first, int32_t B, const double* pose, int32_t K, const int32_t* cand,
+                  double max_heading, int32_t* wp_out, double* dist_out, double* x0_out, double* s_out);
+int mpmpc_rollout_reroute(mpmpc_handle h, int32_t B, const int32_t* route, double max_dist, double max_heading,
+                          int32_t* accepted_out);
+int mpmpc_rollout_routes(mpmpc_handle h, int32_t B, int32_t* route_out);
 
 /* Device-side corridor generation: the three calls below replace, for a map that
  * changes between steps, the host loop of ReferencePath.update_path_constraints + _compute_free_segments

@@ -331,6 +331,7 @@ class BatchMPC:
         h.set_path(cat["kappa"], cat["v_ref"], cat["ds_next"])
         h.set_routes(first, [1 if rp.circular else 0 for rp in paths])
         self._routes, self._route_geometry, self._corridor_tables = list(paths), cat, None
+        self._route_first = first
         if had_device_table:
             return self.update_corridor_from_map(n_cols or self.corridor_cols)
         h.set_path_geometry(cat["x"], cat["y"], cat["psi"], cat["border_ub"], cat["border_lb"])      # (the closed loop localises on it)
@@ -350,11 +351,42 @@ class BatchMPC:
             return wp, x0
         return _spatial_states(self._path, s, poses)
 
+    # --- where poses are on the routes, and re-routing the cars of a rollout (mpmpc.project / mpmpc.Handle.rollout_reroute)
+    def project(self, poses, routes=None, max_heading=np.pi / 2):
+        """Project world poses [B, 3] onto the routes of set_routes, or onto the one path: the nearest waypoint whose heading
+        differs from the pose's by at most max_heading, on the device.  routes: None - every route; [B] or [B, K] - the
+        candidate route(s) of every pose.  -> mpmpc.project's dict: wp (local to the route, -1: none), dist, x0, s, each
+        [B, K, ...]; s is the arc length rollout takes."""
+        if self._routes is not None:
+            g = self._route_geometry
+            x, y, psi, first = g["x"], g["y"], g["psi"], self._route_first
+            cum = np.concatenate([np.cumsum(p.segment_lengths) for p in self._routes])
+        else:
+            if routes is not None:
+                raise ValueError("routes need set_routes first")
+            wps = self._path.waypoints
+            x, y, psi, first = [w.x for w in wps], [w.y for w in wps], [w.psi for w in wps], None
+            cum = np.cumsum(self._path.segment_lengths)
+        poses = np.asarray(poses, float).reshape(-1, 3)
+        cand = None if routes is None else np.asarray(routes, np.int32).reshape(poses.shape[0], -1)
+        return mpmpc.project(x, y, psi, cum, poses, first=first, cand=cand, max_heading=max_heading, device=self._cfg.device)
+
+    def reroute(self, routes, max_dist=np.inf, max_heading=np.pi / 2):
+        """Re-route the cars of the rollout the handle holds (after rollout(..., routes=...), before further
+        handle.rollout_step calls): routes[i] >= 0 puts running car i on that route of set_routes, at the waypoint its pose
+        projects on, if that lies within max_dist and max_heading; -1 keeps its route.  The rollout's state stays on the
+        device and the rollout goes on.  -> accepted, bool [B]."""
+        if self._routes is None:
+            raise ValueError("reroute needs set_routes first")
+        return self.handle.rollout_reroute(routes, max_dist, max_heading)
+
     def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
                 walls=None, perception=None, routes=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
+        s: the cars' arc lengths, or None - every car starts where its pose projects on its route (project with
+        max_heading = pi / 2: s is the arc length of that waypoint); a car that projects on no waypoint raises ValueError.
         obstacles: None (every car drives the path's map) or a length-B list of lists of Obstacle - car b drives the
         path's map with ITS obstacles added (Map.add_obstacles), its corridor rebuilt on the device every step; needs
         corridor='device' (the last update_corridor_from_map's map is the base every car's obstacles are added to).
@@ -392,11 +424,17 @@ class BatchMPC:
         if (fleet is None) != (routes is None):
             raise ValueError("rollout(routes=...) goes with set_routes: both or neither")
         if fleet is not None:
-            if len(routes) != np.asarray(s).size:
+            if len(routes) != (np.asarray(s).size if s is not None else np.asarray(poses).size // 3):
                 raise ValueError("routes must hold one route id per car")
             cum = np.concatenate([np.cumsum(p.segment_lengths) for p in fleet])      # each route's own, from 0, laid end to end
         else:
             cum = None      # (the one path's, taken where the rollout starts: the argument checks below come first)
+        if s is None:
+            on = self.project(poses, routes=None if fleet is None else np.asarray(routes).reshape(-1, 1))
+            lost = np.flatnonzero(on["wp"][:, 0] < 0)
+            if lost.size:
+                raise ValueError("rollout(s=None): cars %s project on no waypoint of their routes" % lost[:8].tolist())
+            s = on["s"][:, 0]
         if obstacles is not None:
             if self.corridor_cols is None:
                 raise ValueError("per-car obstacles need corridor='device' (update_corridor_from_map)")

@@ -92,6 +92,7 @@ struct ObsState {
 struct RoState {
   Buf<double> cum, s, pose, u;
   Buf<int> counter, alive, act, shift;      // act, shift: warm start - certified active sets [B x ld], waypoints advanced [B]
+  Buf<char> reroute;      // mpmpc_rollout_reroute's block (mpmpc_project.hpp): the request, the projection, the verdicts
   int warm = 2;      // 0 off, 1 on, 2 where it pays (see plan_solve)
   double Ts = 0;
   int B = 0;

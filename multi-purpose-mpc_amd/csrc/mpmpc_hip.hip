@@ -25,7 +25,8 @@
 //   K0 / K3 / K4                corridor tables from the map and the closed-loop rollout (mpmpc_closed_loop.hpp, with their
 //                               entry points), the speed profile (mpmpc_speed_profile.hpp), the lidar K0l (mpmpc_lidar.hpp), the
 //                               footprint audit K0f (mpmpc_footprint.hpp), the walls K0w and K-world (mpmpc_walls.hpp), the
-//                               reference paths' static width K0p (mpmpc_path.hpp).
+//                               reference paths' static width K0p (mpmpc_path.hpp), the pose projection and the re-route of a
+//                               running rollout (mpmpc_project.hpp).
 // Host side: the handle and its sub-states are mpmpc_handle.hpp, their buffers device_buf.hpp; this file keeps create / destroy /
 // settings, the path and corridor tables, upload / download / the staged calls, the launch dispatch, the resident and timed launches.
 //
@@ -71,6 +72,7 @@ __device__ long long g_phase[4096 * 32];
 #include "perception_core.hpp"
 #include "speed_core.hpp"
 #include "path_core.hpp"
+#include "project_core.hpp"
 
 using namespace mpmpc;
 
@@ -981,6 +983,7 @@ static int check_wp_ids(mpmpc_handle h, int B, const int32_t* wp_id) {
 #include "mpmpc_path.hpp"
 #include "mpmpc_perception.hpp"
 #include "mpmpc_footprint.hpp"
+#include "mpmpc_project.hpp"
 
 extern "C" {
 

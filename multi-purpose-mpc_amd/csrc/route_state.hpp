@@ -19,6 +19,10 @@ struct RouteState {
   // the arguments of set_routes on their own
   static int check(int n_wp, int P, const int32_t* f, const int32_t* c, const char** why) {
     if (P < 1 || !f || !c) return *why = "routes: need P >= 1, first and circular", MPMPC_E_ARG;
+    return check_first(n_wp, P, f, why);
+  }
+  // ... of `first` alone (mpmpc_project takes routes without their flags)
+  static int check_first(int n_wp, int P, const int32_t* f, const char** why) {
     if (f[0] != 0) return *why = "routes: first[0] must be 0", MPMPC_E_ARG;
     for (int p = 0; p < P; ++p) {
       if (f[p + 1] <= f[p]) return *why = "routes: first must be strictly increasing", MPMPC_E_ARG;
@@ -63,6 +67,39 @@ struct RouteState {
     return MPMPC_OK;
   }
   void keep_car_routes(int B, const int32_t* route) { car_route.assign(route, route + B); car_B = B; }
+  // Re-route (mpmpc_rollout_reroute): may the cars of a rollout of `rollout_B` cars (0: none in progress) be projected onto
+  // route [B] (-1: keep)?  Nothing changes here: the device decides car by car, and `rerouted` then takes its verdicts.
+  int check_reroute(int B, const int32_t* route, int rollout_B, const char** why) const {
+    if (!route) return *why = "NULL argument", MPMPC_E_ARG;
+    if (n_routes == 0) return *why = "no routes set (mpmpc_set_routes)", MPMPC_E_STATE;
+    if (B < 1 || car_B != B) return *why = "no car routes for this number of instances (mpmpc_set_car_routes)", MPMPC_E_STATE;
+    if (rollout_B != B) return *why = "no rollout in progress on this number of cars (mpmpc_rollout_init)", MPMPC_E_STATE;
+    for (int i = 0; i < B; ++i)
+      if (route[i] < -1 || route[i] >= n_routes) return *why = "route id out of range (-1 keeps the car's route)", MPMPC_E_ARG;
+    return MPMPC_OK;
+  }
+  // {first row, length - negated on an open route} of every route: what the device writes into an accepted car's header
+  void route_headers(std::vector<int32_t>* hdr) const {
+    hdr->resize(2 * (size_t)n_routes);
+    for (int p = 0; p < n_routes; ++p) {
+      const int n = first[p + 1] - first[p];
+      (*hdr)[2 * p] = first[p];
+      (*hdr)[2 * p + 1] = circ[p] ? n : -n;
+    }
+  }
+  // the cars the device accepted are on their new routes: check_wp_ids and every later call see them
+  void rerouted(int B, const int32_t* route, const int32_t* accepted) {
+    for (int i = 0; i < B; ++i)
+      if (accepted[i]) car_route[i] = route[i];
+  }
+  // the route every car is on now
+  int car_routes(int B, int32_t* route_out, const char** why) const {
+    if (!route_out) return *why = "NULL argument", MPMPC_E_ARG;
+    if (n_routes == 0) return *why = "no routes set (mpmpc_set_routes)", MPMPC_E_STATE;
+    if (B < 1 || car_B != B) return *why = "no car routes for this number of instances (mpmpc_set_car_routes)", MPMPC_E_STATE;
+    for (int i = 0; i < B; ++i) route_out[i] = car_route[i];
+    return MPMPC_OK;
+  }
   // With routes set, a call on B instances needs their routes.  (Without routes: nothing to check.)
   int check_batch(int B, const char** why) const {
     if (n_routes && car_B != B) return *why = "routes are set: call mpmpc_set_car_routes for this number of instances first", MPMPC_E_STATE;

@@ -160,6 +160,10 @@ def load_library(path: str | None = None):
     lib.mpmpc_check_routes.argtypes = [C.c_int32, C.c_int32, _ip, _ip]
     lib.mpmpc_set_routes.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_set_car_routes.argtypes = [h, C.c_int32, _ip]
+    lib.mpmpc_project.argtypes = [C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_int32, _ip, C.c_int32, _dp, C.c_int32, _ip,
+                                  C.c_double, _ip, _dp, _dp, _dp]
+    lib.mpmpc_rollout_reroute.argtypes = [h, C.c_int32, _ip, C.c_double, C.c_double, _ip]
+    lib.mpmpc_rollout_routes.argtypes = [h, C.c_int32, _ip]
     lib.mpmpc_set_map.argtypes = [h, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double]
     lib.mpmpc_set_path_geometry.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp, _dp]
     lib.mpmpc_build_corridor.argtypes = [h, C.c_int32, C.c_double, C.c_double, _dp, _dp, _ip]
@@ -235,6 +239,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_perception_scan", "mpmpc_rollout_set_perception", "mpmpc_rollout_perception",
            "mpmpc_path_count", "mpmpc_path_build", "mpmpc_path_build_timed",
            "mpmpc_check_routes", "mpmpc_set_routes", "mpmpc_set_car_routes",
+           "mpmpc_project", "mpmpc_rollout_reroute", "mpmpc_rollout_routes",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -353,6 +358,7 @@ class Handle:
         """route[i]: the route of instance i in every later call on len(route) instances, until set again."""
         r = np.ascontiguousarray(route, dtype=np.int32).reshape(-1)
         self._check(self.lib.mpmpc_set_car_routes(self._h, r.size, _i(r)))
+        self._route_B = r.size
 
     # --- corridor generation on the device (dynamic maps)
     def set_map(self, data, origin, resolution):
@@ -398,6 +404,22 @@ class Handle:
         """MPC.infeasibility_counter of every car (to resume a recorded run)"""
         c = np.ascontiguousarray(counters, dtype=np.int32).ravel()
         self._check(self.lib.mpmpc_rollout_set_counters(self._h, c.size, _i(c)))
+
+    def rollout_reroute(self, route, max_dist=np.inf, max_heading=np.pi / 2):
+        """Route fleets, between rollout_step calls: route[i] >= 0 projects running car i from its current pose onto that route
+        (nearest waypoint whose heading differs by at most max_heading) and, if it lies within max_dist, puts the car on it with
+        s at that waypoint; -1 keeps the car's route.  Everything else of the rollout stays, on the device (include/mpmpc.h).
+        -> accepted, bool [B]."""
+        r = np.ascontiguousarray(route, dtype=np.int32).reshape(-1)
+        acc = np.zeros(r.size, np.int32)
+        self._check(self.lib.mpmpc_rollout_reroute(self._h, r.size, _i(r), float(max_dist), float(max_heading), _i(acc)))
+        return acc != 0
+
+    def rollout_routes(self):
+        """-> the route every car of the last set_car_routes is on now (rollout_reroute moves cars), int32 [B]."""
+        out = np.zeros(getattr(self, "_route_B", 0), np.int32)
+        self._check(self.lib.mpmpc_rollout_routes(self._h, out.size, _i(np.zeros(1, np.int32)) if out.size == 0 else _i(out)))
+        return out
 
     def rollout_warm_start(self, enable=True):
         """closed loop: try the previous step's shifted active set first.  True / False force it on / off, "auto"
@@ -928,6 +950,33 @@ def check_routes(n_wp, first, circular):
     rc = lib.mpmpc_check_routes(int(n_wp), c.size, _i(f), _i(c) if c.size else None)
     if rc != 0:
         raise MpmpcError("mpmpc error %d: %s" % (rc, lib.mpmpc_last_error().decode()))
+
+
+def project(x, y, psi, cum, poses, first=None, cand=None, max_heading=np.pi, device=0):
+    """Where are B world poses on routes (mpmpc_project_kernel; the law: csrc/project_core.hpp, include/mpmpc.h)?  x, y, psi,
+    cum: the waypoints' tables, cum every route's own cumulative length from 0 (concat_routes re-bases it); first [P + 1]: the
+    routes' first rows (None: one route); poses [B, 3]; cand [B, K]: the candidate routes of every pose (None: every route);
+    a waypoint counts when the pose's heading differs from its by at most max_heading.
+    -> dict(wp [B, K] local to the route, -1: none; dist [B, K]; x0 [B, K, 3] = (e_y, e_psi, 0); s [B, K] = cum at wp)."""
+    lib = load_library()
+    x, y, psi, cum = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (x, y, psi, cum))
+    if not (x.size == y.size == psi.size == cum.size):
+        raise ValueError("x, y, psi and cum must have equal length")
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    B = poses.shape[0]
+    f = None if first is None else np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+    P = 0 if f is None else f.size - 1
+    if cand is None:
+        c, K = None, max(P, 1)
+    else:
+        c = np.ascontiguousarray(cand, dtype=np.int32).reshape(B, -1)
+        K = c.shape[1]
+    out = dict(wp=np.zeros((B, K), np.int32), dist=np.zeros((B, K)), x0=np.zeros((B, K, 3)), s=np.zeros((B, K)))
+    rc = lib.mpmpc_project(int(device), x.size, _d(x), _d(y), _d(psi), _d(cum), P, _i(f), B, _d(poses), K, _i(c), float(max_heading),
+                           _i(out["wp"]), _d(out["dist"]), _d(out["x0"]), _d(out["s"]))
+    if rc != 0:
+        raise MpmpcError("mpmpc error %d: %s" % (rc, lib.mpmpc_last_error().decode()))
+    return out
 
 
 def perception_scan(grid, origin, resolution, poses, angles, range_m, discs=None, walls=None, device=0):
