@@ -407,6 +407,39 @@ int mpmpc_rollout_corridor(mpmpc_handle h, int32_t B, double* ub, double* lb);
 int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* kind,
                              const int32_t* radius_cells, const double* params, int64_t step0);
 int mpmpc_rollout_obstacles(mpmpc_handle h, int32_t B, int32_t* discs_out, int32_t* offsets_out);
+/* Lookahead: every column of a car's horizon sees the car's movers where they will be when the car gets there.  Without it
+ * K0c builds all N columns against the movers' discs of the current step k: a car reserves room where a crossing mover is
+ * now for its whole horizon, and none where the mover will be.  The setting is fleet-wide and off by default:
+ *   seg_time[n_wp]   entry i = the seconds a car is expected to need from waypoint i to i + 1, indexed by the global row of
+ *                    the path table (route fleets lay it end to end like the path); ds_next / v_ref is the time model the
+ *                    MPC's own time state is linearised around
+ *   max_lead         in steps, 1 .. 1048576
+ * For car b at step k with local wp_id, column c is waypoint cor_wp(wp_id + 1 + c) of the car's route (K0c's own index:
+ * circular wrap, open-route clamping), and its lead is
+ *     t_-1 = 0;   t_c = t_(c-1) + seg_time[row of cor_wp(wp_id + c)]     c = 0 .. N-1
+ *     q = floor(t_c / Ts)        lead_c = (q < max_lead) ? (int)q : max_lead
+ * (a strictly sequential sum, every add and the division rounded on their own; an infinite t_c saturates to max_lead; Ts is
+ * mpmpc_rollout_init's).  Column c is built in this world: static discs, walls and traffic slots as at step k; mover slot q
+ * as its disc of step k + lead_c (K0h evaluates the movers' closed form once per (mover, column), in front of K0c).  One
+ * gate: a mover whose slot in the list K0c plans from is absent at step k - off the grid, or, under
+ * mpmpc_rollout_set_perception, not known - is absent in every column.  Under perception a car thus anticipates exactly the
+ * movers it currently knows: knowing a mover means knowing its motion law (a simplification).  The exact statement:
+ * csrc/lookahead_core.hpp.  Everything else of a step is unchanged: the verdicts -3 / -4 are taken at column 0 of the
+ * anticipated row, the audit keeps judging the true world of step k, recorded rows and mpmpc_rollout_corridor are the
+ * anticipated rows, mpmpc_rollout_obstacles keeps returning the discs of step k.  Traffic slots are not anticipated.
+ *   mpmpc_rollout_set_lookahead   seg_time == NULL: off.  MPMPC_E_ARG: n_wp differs from the path table's, an entry is
+ *                           negative or NaN (+inf is allowed), max_lead < 1 or above the cap, N > 255, or the movers in
+ *                           force times N times 12 bytes exceed 256 MiB (mpmpc_rollout_set_movers then checks the same
+ *                           against the lookahead in force).  May be called before mpmpc_rollout_init or between
+ *                           mpmpc_rollout_step calls: it applies from the next step on and keeps the rollout's state.
+ *                           After a change of map, path, routes or geometry the next step returns MPMPC_E_STATE until it
+ *                           is set again, like the per-car settings.
+ *   mpmpc_rollout_lookahead what the LAST step's K0h wrote: lead_out [B x N], discs_out [movers of the fleet x N x 3]
+ *                           (mover-major, in mpmpc_rollout_set_movers' order; may be NULL), ungated.  MPMPC_E_STATE if that
+ *                           step did not look ahead for B cars (lookahead off, no movers), or a setting changed since.
+ * A rollout without lookahead, or without movers, launches exactly what it launched before. */
+int mpmpc_rollout_set_lookahead(mpmpc_handle h, int32_t n_wp, const double* seg_time, int32_t max_lead);
+int mpmpc_rollout_lookahead(mpmpc_handle h, int32_t B, int32_t* lead_out, int32_t* discs_out);
 /* Traffic: the cars of a group see each other as discs, from the fleet's own poses, every step on the device (K0t) - cars
  * that react to each other without a host round trip per step.  group[B]: cars with the same non-negative value share a
  * world, a negative value means the car sees nobody and nobody sees it.  radius_cells[B] >= 0: the disc with which car c

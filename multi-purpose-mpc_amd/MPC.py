@@ -381,7 +381,7 @@ class BatchMPC:
         return self.handle.rollout_reroute(routes, max_dist, max_heading)
 
     def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
-                walls=None, perception=None, routes=None):
+                walls=None, perception=None, routes=None, lookahead=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -414,6 +414,12 @@ class BatchMPC:
         far (static obstacles and walls once seen, a mover for `hold` steps after it was last seen, traffic while seen);
         the audit and rollout_scan keep judging the true world.  Needs corridor='device'; the returned dict also holds
         "perception": rollout_perception() (None when no step perceived: no per-car world, or n_steps = 0).
+        lookahead: None - every column of a car's horizon is built against its movers' discs of the current step; a
+        lookahead.Lookahead - column c sees them at step k + lead_c, lead_c = min(floor(t_c / Ts), max_lead) with t_c the
+        expected arrival time summed over the waypoints in between (default table: ds_next / v_ref of the path or routes in
+        force), K0h on the device every step.  Static obstacles, walls and traffic are not anticipated; under perception a
+        car anticipates the movers it currently knows.  Needs corridor='device'; handle.rollout_lookahead() returns the
+        last step's leads and discs.
         record: None - nothing is recorded; True or a dict of mpmpc.Handle.rollout_record's keyword arguments (capacity,
         plan, prediction, rows, stride; capacity defaults to the records `n_steps` yields) - the run is recorded on the
         device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of the whole run, arrays
@@ -460,6 +466,8 @@ class BatchMPC:
             wall_cells = [rp.map.boundary_walls(w) for w in walls]
         if perception is not None and self.corridor_cols is None:
             raise ValueError("perception needs corridor='device' (update_corridor_from_map): the map lives on the device")
+        if lookahead is not None and self.corridor_cols is None:
+            raise ValueError("lookahead needs corridor='device' (update_corridor_from_map): it anticipates movers")
         if fleet is not None:
             self.handle.set_car_routes(routes)      # (the routes' geometry went up with set_routes)
         elif getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
@@ -488,6 +496,13 @@ class BatchMPC:
             self.handle.rollout_set_audit(audit.mode, audit.length, audit.width, audit.reach)
         if perception is not None:
             self.handle.rollout_set_perception(perception.angles, perception.range, perception.hold)
+        if lookahead is not None:
+            _, v_ref, ds = (self._route_geometry[k] for k in ("kappa", "v_ref", "ds_next")) if fleet is not None else rp.tables()
+            self.handle.rollout_set_lookahead(lookahead.table(ds, v_ref), lookahead.max_lead)
+            self._lookahead_set = True
+        elif getattr(self, "_lookahead_set", False):      # (off again; a controller that never looked ahead calls nothing new)
+            self.handle.rollout_set_lookahead(None)
+            self._lookahead_set = False
         if cum is None:
             cum = np.cumsum(rp.segment_lengths)
         perceived = perception is not None and int(n_steps) > 0 and any(

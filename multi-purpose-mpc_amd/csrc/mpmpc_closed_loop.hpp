@@ -1,5 +1,5 @@
 // The closed loop of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind mpmpc_set_corridor):
-// the kernels K0a / K0b (corridor tables from the map), K0c (per-car corridor rows), K0m (movers), K0t (traffic), K3a / K3b (localise, advance)
+// the kernels K0a / K0b (corridor tables from the map), K0c (per-car corridor rows), K0m (movers), K0h (the movers over the horizon), K0t (traffic), K3a / K3b (localise, advance)
 // and the two recorder kernels, and their entry points - mpmpc_set_map, mpmpc_set_path_geometry, mpmpc_build_corridor and every
 // mpmpc_rollout_*.  The state they work on: the sub-states cor, obs, ro, rec of the handle (mpmpc_handle.hpp).  The walls of a car's
 // world (mpmpc_rollout_set_walls, below) are rasterised by K0w (mpmpc_walls.hpp, in front of this header).
@@ -90,8 +90,17 @@ __global__ __launch_bounds__(256) void mpmpc_corridor_select_kernel(PathGeom g, 
 // WALL_HDR ints = 384 B, behind the staged cells), "touched" also means a wall's box meets the line box, and the staged
 // occupancy is !base_free || in a disc || on a wall (wall_core.hpp; one table load per wall whose box holds the cell, through
 // L2).  In that variant off may be nullptr (walls only: no discs).  Nothing else differs; without walls the kernel is the
-// instantiation <false>, the code it always was.
-template <bool WALLS>
+// instantiation <false, false>, the code it always was.
+// LEAD (mpmpc_rollout_set_lookahead with movers in the fleet; the law: lookahead_core.hpp): the disc accessor depends on the
+// column - for a mover slot whose disc of step k has r > 0 it returns K0h's table entry of (slot, column), else the staged
+// entry as without LEAD (look_col_disc) - in the touched test (lane = column) and in the staged occupancy of a column's cells.
+// Nothing else differs; <., false> takes an empty LookNone and is instruction for instruction what it was.
+struct LookNone {};
+struct LookView {
+  const int* car;      // [B + 1][2]: first mover of the car in the fleet's list, first mover slot in the car's own list
+  const int* tab;      // [movers][N][3]: K0h's horizon discs (read through L2: staging a car's rows in LDS bought nothing)
+};
+template <bool WALLS, bool LEAD = false>
 __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, PathGeom g, int N, double min_width,
                                                                 double safety_margin, const double* __restrict__ segs,
                                                                 const int* __restrict__ nseg, const double* __restrict__ wpc,
@@ -101,7 +110,8 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
                                                                 const int* __restrict__ wp_id, int* __restrict__ alive,
                                                                 int* __restrict__ flag, double* __restrict__ lb,
                                                                 double* __restrict__ ub, WallView wv,
-                                                                const int* __restrict__ route) {
+                                                                const int* __restrict__ route,
+                                                                std::conditional_t<LEAD, LookView, LookNone> lk) {
   constexpr int PENDING = -1000000;
   // Route fleets: the car's view of the path - the geometry's base pointers and K0a's caches (indexed by GLOBAL row) moved to the
   // first row of its route, n_wp and circular the route's (route[2 b], route[2 b + 1]: PathTables::route); wp_id is local.
@@ -133,16 +143,40 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
     nw = nw > COR_MAX_WALLS ? COR_MAX_WALLS : nw;                    // (the host refuses more)
     for (int k = lane; k < WALL_HDR * nw; k += 64) whd[k] = wv.hdr[(long)WALL_HDR * w0 + k];
   }
+  int ns = 0, nm = 0;               // LEAD: the car's mover slots ns .. ns + nm - 1 and their rows of K0h's table
+  const int* hz = nullptr;
+  if constexpr (LEAD) {
+    const int m0 = lk.car[2 * b];
+    ns = lk.car[2 * b + 1];
+    nm = lk.car[2 * b + 2] - m0;
+    hz = lk.tab + (long)m0 * N * 3;
+  }
   if (lane == 0) s_over = 0;
   __syncthreads();
   const int wp = wp_id[b] + 1;
   auto disc = [&](int j) { return (const int*)(dsc + 3 * j); };
   auto whdr = [&](int j) { return (const int*)(whd + WALL_HDR * j); };
+  auto touches = [&](const int* box, int c) {
+    if constexpr (LEAD) {
+      auto dcol = [&](int j) { return look_col_disc(dsc, j, ns, nm, hz, N, c); };
+      return WALLS ? wall_car_touches(box, nd, dcol, nw, whdr) : (nd > 0 && cor_car_touches(box, nd, dcol));
+    } else {
+      return WALLS ? wall_car_touches(box, nd, disc, nw, whdr) : (nd > 0 && cor_car_touches(box, nd, disc));
+    }
+  };
+  auto cell_free = [&](int cell, int c) {
+    if constexpr (LEAD) {
+      auto dcol = [&](int j) { return look_col_disc(dsc, j, ns, nm, hz, N, c); };
+      return WALLS ? wall_car_cell_free(map, cell, nd, dcol, nw, whdr, wv.tab) : cor_car_cell_free(map, cell, nd, dcol);
+    } else {
+      return WALLS ? wall_car_cell_free(map, cell, nd, disc, nw, whdr, wv.tab) : cor_car_cell_free(map, cell, nd, disc);
+    }
+  };
   for (int n = lane; n < N; n += 64) {
     const int i = cor_wp(g, wp + n);
     const int* box = line_box + (long)i * COR_LINE_BOX;
     col_off[n] = -1;
-    if (WALLS ? wall_car_touches(box, nd, disc, nw, whdr) : (nd > 0 && cor_car_touches(box, nd, disc))) {
+    if (touches(box, n)) {
       col_cnt[n] = PENDING;
       col_aux[n] = box[0];
     } else {
@@ -170,7 +204,7 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
       for (int k = lane; k < nc; k += 64) {
         const int cell = cells[k];
         stg_cell[used + k] = cell;
-        stg_free[used + k] = (WALLS ? wall_car_cell_free(map, cell, nd, disc, nw, whdr, wv.tab) : cor_car_cell_free(map, cell, nd, disc)) ? 1 : 0;
+        stg_free[used + k] = cell_free(cell, c) ? 1 : 0;
       }
       used += nc;
     }
@@ -257,6 +291,48 @@ __global__ __launch_bounds__(256) void mpmpc_obstacle_move_kernel(int n, long lo
   mov_disc(map, path, kind[j], radius[j], prm[j], prm[(long)n + j], prm[2L * n + j], prm[3L * n + j], k, step0, d);
   int* o = discs + 3L * dst[j];
   o[0] = d[0]; o[1] = d[1]; o[2] = d[2];
+}
+
+// K0h: the movers' discs over every car's horizon (mpmpc_rollout_set_lookahead; the law: lookahead_core.hpp), launched behind
+// K3a - it reads wp_id - when lookahead is set and the fleet has movers.  One 64-lane block per car: the lanes fetch the car's
+// N seg_time entries side by side, lane 0 runs the N dependent adds of the lead law over them in LDS (no scan: the rounding
+// order is the law's), then the lanes stride over the car's (mover, column) pairs, each one mov_disc at step k + lead_c on the
+// route view of the car as K0m forms it.  lead [B][N], tab [movers][N][3]: what the LEAD instantiations of K0c read.
+// LDS: 3 KB; no scratch; no device-libm result in any cell (mov_centre's trigonometry is K0's host table).
+__global__ __launch_bounds__(64) void mpmpc_mover_horizon_kernel(int N, long long k, long long step0, double Ts, int max_lead,
+                                                                 MapView map, PathGeom g, MoverPath path,
+                                                                 const double* __restrict__ seg_time,
+                                                                 const int* __restrict__ wp_id, int n,
+                                                                 const int* __restrict__ kind, const int* __restrict__ radius,
+                                                                 const double* __restrict__ prm, const int* __restrict__ car,
+                                                                 int* __restrict__ lead, int* __restrict__ tab,
+                                                                 const int* __restrict__ route) {
+  __shared__ double s_seg[256];      // (N <= 255)
+  __shared__ int s_lead[256];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (route) {      // route fleets: the car's view of the path, of seg_time and of what an along-the-path mover follows
+    const long f = route[2 * b];
+    const int nn = route[2 * b + 1];
+    g.n_wp = nn > 0 ? nn : -nn;
+    g.circular = nn > 0 ? 1 : 0;
+    seg_time += f;
+    path = MoverPath{path.cum + f, path.x + f, path.y + f, path.trig + f * path.trig_ld, g.n_wp, path.trig_ld, g.circular};
+  }
+  const int wp = wp_id[b];
+  for (int c = lane; c < N; c += 64) s_seg[c] = seg_time[look_seg_row(g, wp, c)];
+  __syncthreads();
+  if (lane == 0) look_leads(N, Ts, max_lead, [&](int c) { return s_seg[c]; }, s_lead);
+  __syncthreads();
+  for (int c = lane; c < N; c += 64) lead[(long)b * N + c] = s_lead[c];
+  const int m0 = car[2 * b], pairs = (car[2 * b + 2] - m0) * N;
+  for (int p = lane; p < pairs; p += 64) {
+    const int q = p / N, c = p - q * N;
+    const long j = m0 + q;
+    int d[3];
+    mov_disc(map, path, kind[j], radius[j], prm[j], prm[(long)n + j], prm[2L * n + j], prm[3L * n + j], k + s_lead[c], step0, d);
+    int* o = tab + (j * N + c) * 3;
+    o[0] = d[0]; o[1] = d[1]; o[2] = d[2];
+  }
 }
 
 // K0t: the traffic of one rollout step (mpmpc_rollout_set_traffic; the law: traffic_core.hpp), launched in front of K3a -
@@ -406,6 +482,12 @@ static int per_check_step(mpmpc_handle h, int B, bool per_car, bool* active);
 static void per_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k);
 static const int* per_plan_discs(mpmpc_handle h);      // the perceived lists
 static const int* per_plan_whdr(mpmpc_handle h);
+// lookahead inside a rollout (K0h; defined in mpmpc_lookahead.hpp, behind this header): may steps of B cars run - and do they
+// look ahead (the setting on and `movers` > 0; the tables are laid out then) -, K0h of step k on the slot's stream
+static int look_check_step(mpmpc_handle h, int B, int movers, bool* active);
+static void look_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, int movers, const MapView& mv, const PathGeom& pg,
+                              const MoverPath& mp, const int* route);
+static const char* const LOOK_OVER_BUDGET = "the lookahead's disc table (movers x N x 12 bytes) would exceed 256 MiB (LOOK_TABLE_BUDGET)";
 static const char* const WALLS_OTHER_B = "walls are set for another number of cars (mpmpc_rollout_set_walls)";
 
 extern "C" {
@@ -564,6 +646,7 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   h->rec.ro_steps = 0;            // the recorder keeps its configuration and starts over
   h->rec.count = 0;
   h->per.forget();                // what the cars know starts over; the setting stays
+  h->look.ran_B = 0;              // (lookahead: the setting stays too, the last step's table is no step's of this rollout)
   return aud_reset(h, B);         // ... and so does the audit (mpmpc_footprint.hpp)
 }
 
@@ -693,6 +776,11 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   const int* tr_i = h->obs.tr_block;      // dense group, radius, members [B] each, then the groups' offsets
   if (int rc = check_car_routes(h, B)) return rc;
   const int* route = h->tab.path_tables().route;      // route fleets: the cars' {first row, length} headers (null: one path)
+  bool looking = false;
+  if (h->look.max_lead > 0) {
+    if (int rc = look_check_step(h, B, movers, &looking)) return rc;
+  }
+  const LookView lk{h->look.car.get(), h->look.tab.get()};
   for (int t = 0; t < n_steps; ++t) {
     char* rec = recording && h->rec.ro_steps % h->rec.stride == 0 ? h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)h->rec.count : nullptr;
     if (rec)
@@ -715,16 +803,28 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
                          h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs.get(),
                            h->obs.obst_off.get(), B, route);
     if (auditing) aud_enqueue_step(h, sl, B, h->rec.ro_steps, per_car);      // K0f: pose k in world k
-    if (walls)
+    if (looking) {      // K0h, then K0c<., true> on its table
+      look_enqueue_step(h, sl, B, h->rec.ro_steps, movers, mv, pg, mp, route);
+      if (walls)
+        hipLaunchKernelGGL((mpmpc_car_corridor_kernel<true, true>), dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
+                           h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
+                           h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(), h->obs.ro_flag.get(), h->io.lb, h->io.ub,
+                           plan_walls, route, lk);
+      else
+        hipLaunchKernelGGL((mpmpc_car_corridor_kernel<false, true>), dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
+                           h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
+                           h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(), h->obs.ro_flag.get(), h->io.lb, h->io.ub,
+                           WallView{nullptr, nullptr, nullptr}, route, lk);
+    } else if (walls)
       hipLaunchKernelGGL(mpmpc_car_corridor_kernel<true>, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
                          h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
                          discs ? h->obs.obst_off.get() : nullptr, plan_discs, h->io.wp_id, h->ro.alive.get(),
-                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, plan_walls, route);
+                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, plan_walls, route, LookNone{});
     else if (per_car)
       hipLaunchKernelGGL(mpmpc_car_corridor_kernel<false>, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
                          h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells,
                          h->cor.line_box, h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(),
-                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, WallView{nullptr, nullptr, nullptr}, route);
+                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, WallView{nullptr, nullptr, nullptr}, route, LookNone{});
     if (int rc = launch_solve(h, sl, B, true, false)) return rc;  // (the plant step reads z and the status only)
     hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro.Ts,
                        h->tab.kappa, h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter, h->ro.alive, h->ro.pose, h->ro.s, h->ro.u, route);
@@ -741,6 +841,7 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   HIP_TRY(hipGetLastError());
   if (n_steps > 0) h->obs.car_rows = h->obs.discs_live = per_car;
   if (n_steps > 0 && perceiving) h->per.B = B;
+  if (n_steps > 0) { h->look.ran_B = looking ? B : 0; h->look.ran_n = looking ? movers : 0; }
   return MPMPC_OK;
 }
 
@@ -752,6 +853,8 @@ static int sync_disc_lists(mpmpc_handle h, std::vector<char>* new_mv) {
   const int B = h->obs.st_B > 0 ? h->obs.st_B : (h->obs.mv_B > 0 ? h->obs.mv_B : h->obs.tr_B);
   h->obs.obst_B = B;
   h->obs.discs_live = false;
+  h->look.laid = false;      // (the lookahead's tables follow the lists: look_check_step lays them out anew)
+  h->look.ran_B = 0;
   if (B == 0) return MPMPC_OK;
   HIP_TRY(hipSetDevice(h->cfg.device));
   Slot& sl = h->last();
@@ -818,6 +921,7 @@ int mpmpc_rollout_set_movers(mpmpc_handle h, int32_t B, const int32_t* offsets, 
                                 h->obs.tr_B, h->obs.tr_S))
     return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
   if (h->obs.wl_B > 0 && h->obs.wl_B != B) return fail(MPMPC_E_STATE, WALLS_OTHER_B);
+  if (h->look.max_lead > 0 && look_table_bytes(offsets[B], h->cfg.N) > LOOK_TABLE_BUDGET) return fail(MPMPC_E_ARG, LOOK_OVER_BUDGET);
   const size_t n = (size_t)offsets[B];
   std::vector<char> blk((sizeof(double) * MOV_PARAMS + 2 * sizeof(int)) * n);
   double* p = (double*)blk.data();

@@ -148,6 +148,21 @@ struct PerState {
   void forget() { fresh = true; B = 0; }
 };
 
+// lookahead of the rollout (mpmpc_rollout_set_lookahead; the law: lookahead_core.hpp): the setting, and what K0h writes every
+// step for the LEAD instantiations of K0c - memory of its own, laid out for the movers in force in front of the first step that
+// needs it (mpmpc_lookahead.hpp)
+struct LookState {
+  int max_lead = 0;         // 0: off
+  unsigned gen = 0;         // base_gen the setting was made against
+  Buf<double> seg;          // seg_time [n_wp]
+  Buf<int> lead;            // [max_batch x N] the leads of the last step
+  Buf<int> car;             // [B + 1][2]: a car's first mover in the fleet's list, its first mover slot in its own disc list
+  Buf<int> tab;             // [movers of the fleet][N][3] the horizon discs of the last step; only grows
+  std::vector<int32_t> host_car;
+  bool laid = false;        // car and tab fit the per-car settings in force
+  int ran_B = 0, ran_n = 0; // cars and movers K0h ran for in the last step (0: it did not run)
+};
+
 // per-batch inputs and host staging
 struct IoState {
   // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
@@ -191,6 +206,7 @@ struct mpmpc_handle_s {
   LidState lid;
   AudState aud;
   PerState per;
+  LookState look;
   IoState io;
   // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
   // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that

@@ -65,6 +65,7 @@ __device__ long long g_phase[4096 * 32];
 #include "corridor_core.hpp"
 #include "rollout_core.hpp"
 #include "obstacle_motion_core.hpp"
+#include "lookahead_core.hpp"
 #include "traffic_core.hpp"
 #include "lidar_core.hpp"
 #include "footprint_core.hpp"
@@ -979,6 +980,7 @@ static int check_wp_ids(mpmpc_handle h, int B, const int32_t* wp_id) {
 #include "mpmpc_speed_profile.hpp"
 #include "mpmpc_walls.hpp"
 #include "mpmpc_closed_loop.hpp"
+#include "mpmpc_lookahead.hpp"
 #include "mpmpc_lidar.hpp"
 #include "mpmpc_path.hpp"
 #include "mpmpc_perception.hpp"

@@ -176,6 +176,8 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_corridor.argtypes = [h, C.c_int32, _dp, _dp]
     lib.mpmpc_rollout_set_movers.argtypes = [h, C.c_int32, _ip, _ip, _ip, _dp, C.c_int64]
     lib.mpmpc_rollout_obstacles.argtypes = [h, C.c_int32, _ip, _ip]
+    lib.mpmpc_rollout_set_lookahead.argtypes = [h, C.c_int32, _dp, C.c_int32]
+    lib.mpmpc_rollout_lookahead.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_set_traffic.argtypes = [h, C.c_int32, _ip, _ip, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_set_walls.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -232,6 +234,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_set_map", "mpmpc_set_path_geometry", "mpmpc_build_corridor", "mpmpc_rollout_init",
            "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor",
            "mpmpc_rollout_set_movers", "mpmpc_rollout_obstacles", "mpmpc_rollout_set_traffic",
+           "mpmpc_rollout_set_lookahead", "mpmpc_rollout_lookahead",
            "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams", "mpmpc_launch_plan",
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_lidar_scan", "mpmpc_rollout_scan",
            "mpmpc_footprint_audit", "mpmpc_rollout_set_audit", "mpmpc_rollout_audit", "mpmpc_rollout_set_walls",
@@ -481,6 +484,29 @@ class Handle:
         kind, rad = (np.ascontiguousarray(flat[:, c], dtype=np.int32) for c in (0, 1))
         prm = np.ascontiguousarray(flat[:, 2:], dtype=np.float64)
         self._check(self.lib.mpmpc_rollout_set_movers(self._h, len(lists), _i(off), _i(kind), _i(rad), _d(prm), int(step0)))
+        self._n_movers = int(off[-1])      # (rollout_lookahead sizes its disc table by it)
+
+    def rollout_set_lookahead(self, seg_time, max_lead=1):
+        """Lookahead (K0h; the law: csrc/lookahead_core.hpp): column c of every car's horizon sees the car's movers at step
+        k + lead_c, lead_c = min(floor(t_c / Ts), max_lead) with t_c the running sum of seg_time [n_wp] (seconds from
+        waypoint i to i + 1, by global row of the path table; lookahead.Lookahead.seg_time_of gives ds_next / v_ref) from the
+        car's waypoint on.  None switches it off (the default).  May be called between rollout_step calls; void after a
+        change of map, path, routes or geometry like the per-car settings."""
+        if seg_time is None:
+            self._check(self.lib.mpmpc_rollout_set_lookahead(self._h, 0, None, 0))
+            return
+        t = np.ascontiguousarray(seg_time, dtype=np.float64).ravel()
+        self._check(self.lib.mpmpc_rollout_set_lookahead(self._h, t.size, _d(t), int(max_lead)))
+
+    def rollout_lookahead(self):
+        """-> (lead int32 [B, N], discs int32 [movers, N, 3]): what the last step's K0h wrote - every column's lead and
+        every mover's disc at every column of its car (mover-major, rollout_set_movers' order; ungated: K0c drops the
+        columns of a mover whose slot is absent at the step itself)."""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        lead = np.zeros((max(B, 1), self.N), np.int32)
+        discs = np.zeros((int(getattr(self, "_n_movers", 0)), self.N, 3), np.int32)
+        self._check(self.lib.mpmpc_rollout_lookahead(self._h, B, _i(lead), _i(discs) if discs.size else None))
+        return lead[:B], discs
 
     def rollout_set_traffic(self, group, radius_cells=None, slots=1, range_cells=-1):
         """Traffic: the cars of a group see each other as discs, from the fleet's own poses, every step on the device (K0t).
