@@ -426,7 +426,8 @@ int mpmpc_rollout_obstacles(mpmpc_handle h, int32_t B, int32_t* discs_out, int32
  * movers it currently knows: knowing a mover means knowing its motion law (a simplification).  The exact statement:
  * csrc/lookahead_core.hpp.  Everything else of a step is unchanged: the verdicts -3 / -4 are taken at column 0 of the
  * anticipated row, the audit keeps judging the true world of step k, recorded rows and mpmpc_rollout_corridor are the
- * anticipated rows, mpmpc_rollout_obstacles keeps returning the discs of step k.  Traffic slots are not anticipated.
+ * anticipated rows, mpmpc_rollout_obstacles keeps returning the discs of step k.  Traffic slots are anticipated only with
+ * mpmpc_rollout_set_lookahead_traffic (below).
  *   mpmpc_rollout_set_lookahead   seg_time == NULL: off.  MPMPC_E_ARG: n_wp differs from the path table's, an entry is
  *                           negative or NaN (+inf is allowed), max_lead < 1 or above the cap, N > 255, or the movers in
  *                           force times N times 12 bytes exceed 256 MiB (mpmpc_rollout_set_movers then checks the same
@@ -460,6 +461,42 @@ int mpmpc_rollout_lookahead(mpmpc_handle h, int32_t B, int32_t* lead_out, int32_
  *   state.  A rollout without traffic launches exactly what it launched before. */
 int mpmpc_rollout_set_traffic(mpmpc_handle h, int32_t B, const int32_t* group, const int32_t* radius_cells, int32_t slots,
                               int32_t range_cells);
+/* Lookahead for traffic: every column of a car's horizon sees the cars in its traffic slots where their own plans put them
+ * when the car gets there.  Without it K0c plans all N columns against the neighbours' discs of the current step: a car
+ * reserves room where a neighbour is now for its whole horizon, and none where it will be.  A fleet-wide flag, off by default,
+ * independent of the order in which it, mpmpc_rollout_set_lookahead and mpmpc_rollout_set_traffic are called: a step
+ * anticipates traffic iff lookahead is set, traffic is set and the flag is on - and then looks ahead with or without movers
+ * (mpmpc_rollout_lookahead then returns the leads of such a step, and no discs when there are no movers).
+ *   Tracks (K3t, at the end of such a step): stage j = 0 .. N of car n's solved plan lies at waypoint wp_id + j of its route
+ *   (wrapped or clamped like the recorded predicted path) with lateral offset e_y_j = z[3 j] and arrival time t_j = z[3 j + 2]:
+ *       valid[n]    = alive[n] == 1 after the step, and its status usable (1, 2, -2)
+ *       cells[n][j] = the map cell of the predicted point (the recorder's pred_x / pred_y), or (INT32_MIN, 0) when it is not
+ *                     finite or beyond 2^30 cells
+ *       tm[n][0] = 0;  tm[n][j] = max(tm[n][j-1], t_j)  (a NaN is never taken)
+ *   Who (K0t): who[b][t] = the car in traffic slot t of car b at the step, -1: empty.
+ *   Horizon (K0ht, in front of K0c): with n = who[b][t], d the slot's TRUE disc of step k, L = lead[b][c]
+ *       discs[b][t][c] = d   if n < 0 or L == 0 or !valid[n]   (valid, cells, tm: the tracks step k - 1 left)
+ *       else  j* = the largest j with tm[n][j] <= (L + 1) * Ts;  (cx, cy) = cells[n][j*];
+ *             discs[b][t][c] = (0, 0, 0) if that stage has no cell or the square of radius d.r around it leaves the grid,
+ *                              else (cx, cy, d.r)
+ *   K0c: for a traffic slot whose entry in the list it plans from (under perception: the perceived list) has r > 0, column
+ *   c is built against discs[b][t][c]; else against that entry.  A neighbour is held at its plan's end beyond tm[n][N]; the
+ *   slots are chosen by current distance (anticipation moves them, it does not re-select); knowing a neighbour means knowing
+ *   its plan (a simplification).  mpmpc_rollout_init, mpmpc_rollout_reroute, switching the flag on and every per-car setter
+ *   make every track invalid: the first step after them plans against the discs of the step itself.  The exact statement:
+ *   csrc/traffic_lookahead_core.hpp.  The audit, mpmpc_rollout_obstacles and mpmpc_rollout_scan keep the true world of step k.
+ *   mpmpc_rollout_set_lookahead_traffic   enable != 0: on.  MPMPC_E_ARG: N > 255, or B x slots x N x 12 bytes of the traffic in
+ *                           force exceed 256 MiB while lookahead is set - whichever of the three setters comes last refuses,
+ *                           and the setting that was in force stays.
+ *   mpmpc_rollout_tracks    what the LAST step's K3t left: valid_out [B], cells_out [B x (N + 1) x 2], tm_out [B x (N + 1)]
+ *                           (the last two may be NULL).
+ *   mpmpc_rollout_lookahead_traffic   what the LAST step's K0t and K0ht wrote: who_out [B x slots], discs_out
+ *                           [B x slots x N x 3] (may be NULL), ungated.
+ *   Both getters: MPMPC_E_STATE if that step did not anticipate traffic for B cars, or a setting changed since (as
+ *   mpmpc_rollout_lookahead).  A rollout with the flag off launches exactly what it launched before. */
+int mpmpc_rollout_set_lookahead_traffic(mpmpc_handle h, int32_t enable);
+int mpmpc_rollout_tracks(mpmpc_handle h, int32_t B, int32_t* valid_out, int32_t* cells_out, double* tm_out);
+int mpmpc_rollout_lookahead_traffic(mpmpc_handle h, int32_t B, int32_t* who_out, int32_t* discs_out);
 /* Walls: the second primitive of a car's world beside the discs - Map.add_boundary of the reference (src/map.py:139-155): a
  * line between two world points, stamped with skimage's line_aa.  A wall is (x0, y0, x1, y1) in map cells, the w2m of its
  * two end points, and occupies exactly the cells line_aa(x0, y0, x1, y1) produces (the law: csrc/wall_core.hpp).  A cell

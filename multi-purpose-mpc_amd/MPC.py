@@ -417,9 +417,12 @@ class BatchMPC:
         lookahead: None - every column of a car's horizon is built against its movers' discs of the current step; a
         lookahead.Lookahead - column c sees them at step k + lead_c, lead_c = min(floor(t_c / Ts), max_lead) with t_c the
         expected arrival time summed over the waypoints in between (default table: ds_next / v_ref of the path or routes in
-        force), K0h on the device every step.  Static obstacles, walls and traffic are not anticipated; under perception a
+        force), K0h on the device every step.  Static obstacles and walls are not anticipated; under perception a
         car anticipates the movers it currently knows.  Needs corridor='device'; handle.rollout_lookahead() returns the
-        last step's leads and discs.
+        last step's leads and discs.  Lookahead(..., traffic=True) together with `traffic`: column c also sees the cars in the
+        car's traffic slots where their own plans of the step before put them at step k + lead_c (K3t, K0ht;
+        csrc/traffic_lookahead_core.hpp); handle.rollout_tracks() and handle.rollout_lookahead_traffic() return the plan
+        tracks and the slots' horizon discs of the last step.
         record: None - nothing is recorded; True or a dict of mpmpc.Handle.rollout_record's keyword arguments (capacity,
         plan, prediction, rows, stride; capacity defaults to the records `n_steps` yields) - the run is recorded on the
         device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of the whole run, arrays
@@ -503,6 +506,10 @@ class BatchMPC:
         elif getattr(self, "_lookahead_set", False):      # (off again; a controller that never looked ahead calls nothing new)
             self.handle.rollout_set_lookahead(None)
             self._lookahead_set = False
+        ahead_traffic = lookahead is not None and getattr(lookahead, "traffic", False)
+        if ahead_traffic or getattr(self, "_lookahead_traffic_set", False):      # (the same rule for the flag)
+            self.handle.rollout_set_lookahead_traffic(ahead_traffic)
+            self._lookahead_traffic_set = ahead_traffic
         if cum is None:
             cum = np.cumsum(rp.segment_lengths)
         perceived = perception is not None and int(n_steps) > 0 and any(

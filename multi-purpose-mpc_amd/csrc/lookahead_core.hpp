@@ -18,7 +18,8 @@
 // negative or NaN: look_check_setting).  Ts is the rollout's.
 //
 // Column c is then built in this world:
-//   static discs, walls and traffic slots as at step k (lead 0: unchanged);
+//   static discs, walls and traffic slots as at step k (lead 0: unchanged; the traffic slots follow their occupants' plans
+//   instead when mpmpc_rollout_set_lookahead_traffic is on: traffic_lookahead_core.hpp);
 //   mover slot q as mov_disc(..., k + lead_c, step0) on the route view of the owning car, as K0m forms it;
 //   ONE gate: a mover whose slot in the list K0c plans from is absent at step k (r == 0: off the grid, or - under
 //   perception - not known) is absent in every column.  Under perception a car thus anticipates exactly the movers it

@@ -95,12 +95,22 @@ __global__ __launch_bounds__(256) void mpmpc_corridor_select_kernel(PathGeom g, 
 // column - for a mover slot whose disc of step k has r > 0 it returns K0h's table entry of (slot, column), else the staged
 // entry as without LEAD (look_col_disc) - in the touched test (lane = column) and in the staged occupancy of a column's cells.
 // Nothing else differs; <., false> takes an empty LookNone and is instruction for instruction what it was.
+// TRAF (mpmpc_rollout_set_lookahead_traffic active; the law: traffic_lookahead_core.hpp): the accessor of the LEAD variant gets a
+// second per-column source - for one of the car's last S slots, its traffic slots, whose entry of the list K0c plans from has
+// r > 0 it returns K0ht's table entry of (slot, column) (tlk_col_disc) - in the same two places.  A third template parameter
+// rather than a null view: the instantiations <., false, false> and the mover-only <., true, false> keep their instructions.
 struct LookNone {};
 struct LookView {
   const int* car;      // [B + 1][2]: first mover of the car in the fleet's list, first mover slot in the car's own list
   const int* tab;      // [movers][N][3]: K0h's horizon discs (read through L2: staging a car's rows in LDS bought nothing)
 };
-template <bool WALLS, bool LEAD = false>
+struct LookTrafficView {
+  const int* car;      // as LookView's
+  const int* tab;
+  const int* tz;       // [B][S][N][3]: K0ht's horizon discs of the cars' traffic slots (through L2, like tab)
+  int S;               // traffic slots per car
+};
+template <bool WALLS, bool LEAD = false, bool TRAF = false>
 __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, PathGeom g, int N, double min_width,
                                                                 double safety_margin, const double* __restrict__ segs,
                                                                 const int* __restrict__ nseg, const double* __restrict__ wpc,
@@ -111,7 +121,8 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
                                                                 int* __restrict__ flag, double* __restrict__ lb,
                                                                 double* __restrict__ ub, WallView wv,
                                                                 const int* __restrict__ route,
-                                                                std::conditional_t<LEAD, LookView, LookNone> lk) {
+                                                                std::conditional_t<TRAF, LookTrafficView, std::conditional_t<LEAD, LookView, LookNone>> lk) {
+  static_assert(LEAD || !TRAF, "the traffic horizon needs the leads");
   constexpr int PENDING = -1000000;
   // Route fleets: the car's view of the path - the geometry's base pointers and K0a's caches (indexed by GLOBAL row) moved to the
   // first row of its route, n_wp and circular the route's (route[2 b], route[2 b + 1]: PathTables::route); wp_id is local.
@@ -151,13 +162,22 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
     nm = lk.car[2 * b + 2] - m0;
     hz = lk.tab + (long)m0 * N * 3;
   }
+  int ts = 0;                       // TRAF: the car's traffic slots nd - ts .. nd - 1 and its rows of K0ht's table
+  const int* tzb = nullptr;
+  if constexpr (TRAF) {
+    ts = lk.S < nd ? lk.S : nd;     // (the layout gives every car S slots)
+    tzb = lk.tz + (long)b * lk.S * N * 3;
+  }
   if (lane == 0) s_over = 0;
   __syncthreads();
   const int wp = wp_id[b] + 1;
   auto disc = [&](int j) { return (const int*)(dsc + 3 * j); };
   auto whdr = [&](int j) { return (const int*)(whd + WALL_HDR * j); };
   auto touches = [&](const int* box, int c) {
-    if constexpr (LEAD) {
+    if constexpr (TRAF) {
+      auto dcol = [&](int j) { return tlk_col_disc(dsc, j, ns, nm, hz, nd, ts, tzb, N, c); };
+      return WALLS ? wall_car_touches(box, nd, dcol, nw, whdr) : (nd > 0 && cor_car_touches(box, nd, dcol));
+    } else if constexpr (LEAD) {
       auto dcol = [&](int j) { return look_col_disc(dsc, j, ns, nm, hz, N, c); };
       return WALLS ? wall_car_touches(box, nd, dcol, nw, whdr) : (nd > 0 && cor_car_touches(box, nd, dcol));
     } else {
@@ -165,7 +185,10 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
     }
   };
   auto cell_free = [&](int cell, int c) {
-    if constexpr (LEAD) {
+    if constexpr (TRAF) {
+      auto dcol = [&](int j) { return tlk_col_disc(dsc, j, ns, nm, hz, nd, ts, tzb, N, c); };
+      return WALLS ? wall_car_cell_free(map, cell, nd, dcol, nw, whdr, wv.tab) : cor_car_cell_free(map, cell, nd, dcol);
+    } else if constexpr (LEAD) {
       auto dcol = [&](int j) { return look_col_disc(dsc, j, ns, nm, hz, N, c); };
       return WALLS ? wall_car_cell_free(map, cell, nd, dcol, nw, whdr, wv.tab) : cor_car_cell_free(map, cell, nd, dcol);
     } else {
@@ -345,16 +368,21 @@ __global__ __launch_bounds__(64) void mpmpc_mover_horizon_kernel(int N, long lon
 // end lanes 0 .. S-1 store the car's S slots - the last S entries of its disc list, where K0c reads them behind the
 // static discs and the movers.  LDS: 16 KB (TR_MAX_GROUP keys and cells); no scratch; trip counts depend on the group's
 // size and S only.
+// WHO (mpmpc_rollout_set_lookahead_traffic active): lane t also keeps the car index of slot t's occupant and stores it in
+// who[b][t], -1 for an empty slot - what K0ht reads.  <false> takes an empty LookNone and is the code the kernel always was.
+template <bool WHO = false>
 __global__ __launch_bounds__(64) void mpmpc_traffic_kernel(int B, int S, int range_cells, MapView map,
                                                            const double* __restrict__ pose, const int* __restrict__ alive,
                                                            const int* __restrict__ dense, const int* __restrict__ radius,
                                                            const int* __restrict__ members, const int* __restrict__ goff,
-                                                           const int* __restrict__ off, int* __restrict__ discs) {
+                                                           const int* __restrict__ off, int* __restrict__ discs,
+                                                           std::conditional_t<WHO, int*, LookNone> who) {
   __shared__ long long key[TR_MAX_GROUP];
   __shared__ int cell_x[TR_MAX_GROUP], cell_y[TR_MAX_GROUP];
   const int b = blockIdx.x, lane = threadIdx.x;
   if (b >= B) return;
   int d[3] = {0, 0, 0};                     // lane t: slot t
+  [[maybe_unused]] int occupant = -1;       // (WHO) lane t: the car in slot t
   const int g = dense[b];
   int bx = 0, by = 0;
   if (alive[b] == 1 && g >= 0 && tr_cell(map, pose[3L * b], pose[3L * b + 1], &bx, &by)) {      // (uniform)
@@ -389,6 +417,9 @@ __global__ __launch_bounds__(64) void mpmpc_traffic_kernel(int B, int S, int ran
       }
       if (best_p == 0x7fffffff) break;          // (uniform) no candidate left
       if (lane == t) { d[0] = cell_x[best_p]; d[1] = cell_y[best_p]; d[2] = radius[members[g0 + best_p]]; }
+      if constexpr (WHO) {
+        if (lane == t) occupant = members[g0 + best_p];
+      }
       last_d2 = best;
       last_p = best_p;
     }
@@ -396,6 +427,75 @@ __global__ __launch_bounds__(64) void mpmpc_traffic_kernel(int B, int S, int ran
   if (lane < S) {
     int* o = discs + 3L * (off[b + 1] - S + lane);
     o[0] = d[0]; o[1] = d[1]; o[2] = d[2];
+    if constexpr (WHO) who[(long)b * S + lane] = occupant;
+  }
+}
+
+// K0ht: the cars' traffic slots over their horizons (mpmpc_rollout_set_lookahead_traffic; the law: traffic_lookahead_core.hpp),
+// launched behind K0h - it reads the leads of the step - and in front of K0c.  One 64-lane block per car b; the lanes stride over
+// the car's S x N (slot, column) pairs, each one tlk_disc: the slot's disc of step k from the TRUE list, its occupant from
+// K0t's who, and - where the column has a lead and the occupant a valid track - a binary search of at most 8 probes in the
+// occupant's tm (through L2) for the stage its plan has reached by then.  tz [B][S][N][3].  No LDS, no scratch.
+__global__ __launch_bounds__(64) void mpmpc_traffic_horizon_kernel(int N, int S, double Ts, MapView map,
+                                                                   const int* __restrict__ off, const int* __restrict__ discs,
+                                                                   const int* __restrict__ who, const int* __restrict__ lead,
+                                                                   const int* __restrict__ valid, const int* __restrict__ cells,
+                                                                   const double* __restrict__ tm, int* __restrict__ tz) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int* slots = discs + 3L * (off[b + 1] - S);
+  for (int p = lane; p < S * N; p += 64) {
+    const int t = p / N, c = p - t * N;
+    int d[3];
+    tlk_disc(map, slots + 3 * t, who[(long)b * S + t], lead[(long)b * N + c], Ts, N, valid, cells, tm, d);
+    int* o = tz + ((long)b * S * N + p) * 3;
+    o[0] = d[0]; o[1] = d[1]; o[2] = d[2];
+  }
+}
+
+// K3t: the plan tracks a step leaves (mpmpc_rollout_set_lookahead_traffic; the law: traffic_lookahead_core.hpp), launched behind
+// K3b while the setting is active.  One WAVEFRONT per car n; the lanes take the N + 1 <= 256 stages of its plan in up to four
+// chunks of 64: lane j's cell from z's e_y at the stage's waypoint (K0's host trig table: no device libm), and the running
+// maximum of the times as an inclusive max-scan over the chunk (six shuffle steps; a maximum is exact, so the grouping does
+// not matter: tlk_time_key / tlk_time_max) with the last lane's value carried into the next chunk.  No LDS, no scratch.
+__global__ __launch_bounds__(64) void mpmpc_plan_track_kernel(int B, int N, MapView map, const double* __restrict__ gx,
+                                                              const double* __restrict__ gy, const double* __restrict__ trig,
+                                                              int n_wp, int circular, const int* __restrict__ wp_id,
+                                                              const int* __restrict__ alive, const int* __restrict__ status,
+                                                              const double* __restrict__ z, const int* __restrict__ route,
+                                                              int* __restrict__ valid, int* __restrict__ cells,
+                                                              double* __restrict__ tm) {
+  const int n = blockIdx.x, lane = threadIdx.x;
+  if (n >= B) return;
+  long long first = 0;
+  if (route) {      // route fleets: the car's route
+    first = route[2 * n];
+    const int nn = route[2 * n + 1];
+    n_wp = nn > 0 ? nn : -nn;
+    circular = nn > 0 ? 1 : 0;
+  }
+  if (lane == 0) valid[n] = tlk_valid(alive[n], status[n]) ? 1 : 0;
+  const double* zn = z + (long long)(5 * N + 3) * n;
+  const int wp = wp_id[n];
+  double carry = 0.0;      // tm of the last stage of the chunk before (chunk 0: stage 0's own key)
+  for (int j0 = 0; j0 <= N; j0 += 64) {      // (uniform)
+    const int j = j0 + lane;
+    const bool have = j <= N;
+    double v = -HUGE_VAL;      // (past the plan's end: never taken)
+    if (have) {
+      const long long w = tlk_stage_row(wp, j, n_wp, circular != 0, first);
+      int cell[2];
+      tlk_stage_cell(map, gx[w], gy[w], trig[w * COR_TRIG], trig[w * COR_TRIG + 1], zn[3 * j], cell);
+      int* o = cells + ((long long)n * (N + 1) + j) * 2;
+      o[0] = cell[0]; o[1] = cell[1];
+      v = tlk_time_key(j, zn[3 * j + 2]);
+    }
+    for (int m = 1; m < 64; m <<= 1) {      // inclusive scan: lane l ends with the leftmost maximum of lanes 0 .. l
+      const double before = __shfl_up(v, m, 64);
+      if (lane >= m) v = tlk_time_max(before, v);
+    }
+    v = tlk_time_max(carry, v);
+    if (have) tm[(long long)n * (N + 1) + j] = v;
+    carry = __shfl(v, 63, 64);
   }
 }
 
@@ -484,10 +584,17 @@ static const int* per_plan_discs(mpmpc_handle h);      // the perceived lists
 static const int* per_plan_whdr(mpmpc_handle h);
 // lookahead inside a rollout (K0h; defined in mpmpc_lookahead.hpp, behind this header): may steps of B cars run - and do they
 // look ahead (the setting on and `movers` > 0; the tables are laid out then) -, K0h of step k on the slot's stream
-static int look_check_step(mpmpc_handle h, int B, int movers, bool* active);
+// `traffic`: traffic is set for the step's cars; *ahead_traffic: the step also anticipates traffic (the flag of
+// mpmpc_rollout_set_lookahead_traffic on; it then looks ahead with or without movers, and the tracks and tables of
+// traffic_lookahead_core.hpp are laid out)
+static int look_check_step(mpmpc_handle h, int B, int movers, bool traffic, bool* active, bool* ahead_traffic);
 static void look_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, int movers, const MapView& mv, const PathGeom& pg,
                               const MoverPath& mp, const int* route);
+// ... K0ht of the step behind K0h, K3t of the step behind K3b
+static void tlk_enqueue_horizon(mpmpc_handle h, Slot& sl, int B, const MapView& mv);
+static void tlk_enqueue_tracks(mpmpc_handle h, Slot& sl, int B, const MapView& mv, const int* route);
 static const char* const LOOK_OVER_BUDGET = "the lookahead's disc table (movers x N x 12 bytes) would exceed 256 MiB (LOOK_TABLE_BUDGET)";
+static const char* const TLK_OVER_BUDGET = "the traffic lookahead's disc table (B x slots x N x 12 bytes) would exceed 256 MiB (LOOK_TABLE_BUDGET)";
 static const char* const WALLS_OTHER_B = "walls are set for another number of cars (mpmpc_rollout_set_walls)";
 
 extern "C" {
@@ -647,6 +754,7 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   h->rec.count = 0;
   h->per.forget();                // what the cars know starts over; the setting stays
   h->look.ran_B = 0;              // (lookahead: the setting stays too, the last step's table is no step's of this rollout)
+  h->tlk.forget();                // (... and no plan track is: every car is a frozen disc in the first step)
   return aud_reset(h, B);         // ... and so does the audit (mpmpc_footprint.hpp)
 }
 
@@ -776,19 +884,26 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   const int* tr_i = h->obs.tr_block;      // dense group, radius, members [B] each, then the groups' offsets
   if (int rc = check_car_routes(h, B)) return rc;
   const int* route = h->tab.path_tables().route;      // route fleets: the cars' {first row, length} headers (null: one path)
-  bool looking = false;
+  bool looking = false, ahead_traffic = false;
   if (h->look.max_lead > 0) {
-    if (int rc = look_check_step(h, B, movers, &looking)) return rc;
+    if (int rc = look_check_step(h, B, movers, traffic, &looking, &ahead_traffic)) return rc;
   }
   const LookView lk{h->look.car.get(), h->look.tab.get()};
+  const LookTrafficView lkt{h->look.car.get(), h->look.tab.get(), h->tlk.tz.get(), h->obs.tr_S};
+  if (ahead_traffic && !h->tlk.tracks_live && n_steps > 0)      // no track is the last step's: every car is a frozen disc for one step
+    HIP_TRY(hipMemsetAsync(h->tlk.valid, 0, sizeof(int) * (size_t)h->cfg.max_batch, sl.stream));
   for (int t = 0; t < n_steps; ++t) {
     char* rec = recording && h->rec.ro_steps % h->rec.stride == 0 ? h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)h->rec.count : nullptr;
     if (rec)
       hipLaunchKernelGGL(mpmpc_record_snapshot_kernel, dim3((unsigned)(((long)B * RO_REC_BEGIN_ENTRIES + 255) / 256)), dim3(256), 0,
                          sl.stream, B, h->ro.s, h->ro.pose, h->ro.alive, h->rec.ain, rec, h->rec.lay);
-    if (traffic)
-      hipLaunchKernelGGL(mpmpc_traffic_kernel, dim3(B), dim3(64), 0, sl.stream, B, h->obs.tr_S, h->obs.tr_range, mv, h->ro.pose,
-                         h->ro.alive, tr_i, tr_i + B, tr_i + 2 * (size_t)B, tr_i + 3 * (size_t)B, h->obs.obst_off, h->obs.obst_discs);
+    if (ahead_traffic)      // K0t with the slots' occupants (K0ht reads them)
+      hipLaunchKernelGGL(mpmpc_traffic_kernel<true>, dim3(B), dim3(64), 0, sl.stream, B, h->obs.tr_S, h->obs.tr_range, mv, h->ro.pose.get(),
+                         h->ro.alive.get(), tr_i, tr_i + B, tr_i + 2 * (size_t)B, tr_i + 3 * (size_t)B, h->obs.obst_off.get(),
+                         h->obs.obst_discs.get(), h->tlk.who.get());
+    else if (traffic)
+      hipLaunchKernelGGL(mpmpc_traffic_kernel<false>, dim3(B), dim3(64), 0, sl.stream, B, h->obs.tr_S, h->obs.tr_range, mv, h->ro.pose,
+                         h->ro.alive, tr_i, tr_i + B, tr_i + 2 * (size_t)B, tr_i + 3 * (size_t)B, h->obs.obst_off, h->obs.obst_discs, LookNone{});
     if (perceiving) {      // K0m and K0s in front of K3a: K0s reads alive as the step finds it, K0m reads nothing K3a writes
       if (movers > 0)
         hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
@@ -803,7 +918,20 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
                          h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs.get(),
                            h->obs.obst_off.get(), B, route);
     if (auditing) aud_enqueue_step(h, sl, B, h->rec.ro_steps, per_car);      // K0f: pose k in world k
-    if (looking) {      // K0h, then K0c<., true> on its table
+    if (ahead_traffic) {      // K0h, K0ht, then K0c's traffic instantiation on both tables
+      look_enqueue_step(h, sl, B, h->rec.ro_steps, movers, mv, pg, mp, route);
+      tlk_enqueue_horizon(h, sl, B, mv);
+      if (walls)
+        hipLaunchKernelGGL((mpmpc_car_corridor_kernel<true, true, true>), dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
+                           h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
+                           h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(), h->obs.ro_flag.get(), h->io.lb, h->io.ub,
+                           plan_walls, route, lkt);
+      else
+        hipLaunchKernelGGL((mpmpc_car_corridor_kernel<false, true, true>), dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
+                           h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
+                           h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(), h->obs.ro_flag.get(), h->io.lb, h->io.ub,
+                           WallView{nullptr, nullptr, nullptr}, route, lkt);
+    } else if (looking) {      // K0h, then K0c<., true> on its table
       look_enqueue_step(h, sl, B, h->rec.ro_steps, movers, mv, pg, mp, route);
       if (walls)
         hipLaunchKernelGGL((mpmpc_car_corridor_kernel<true, true>), dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
@@ -828,6 +956,7 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     if (int rc = launch_solve(h, sl, B, true, false)) return rc;  // (the plant step reads z and the status only)
     hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro.Ts,
                        h->tab.kappa, h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter, h->ro.alive, h->ro.pose, h->ro.s, h->ro.u, route);
+    if (ahead_traffic) tlk_enqueue_tracks(h, sl, B, mv, route);      // K3t: the plans of this step, for the next one's K0ht
     if (rec) {
       const RoRecSrc src{h->ro.alive, h->rec.ain, h->io.wp_id, sl.status, h->ro.counter, h->io.x0, h->ro.u, h->io.cc, sl.z,
                          h->cor.gx, h->cor.gy, h->cor.gtrig, per_car ? h->io.ub : h->tab.ub_tab, per_car ? h->io.lb : h->tab.lb_tab,
@@ -842,6 +971,7 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   if (n_steps > 0) h->obs.car_rows = h->obs.discs_live = per_car;
   if (n_steps > 0 && perceiving) h->per.B = B;
   if (n_steps > 0) { h->look.ran_B = looking ? B : 0; h->look.ran_n = looking ? movers : 0; }
+  if (n_steps > 0) { h->tlk.ran_B = ahead_traffic ? B : 0; h->tlk.ran_S = ahead_traffic ? h->obs.tr_S : 0; h->tlk.tracks_live = ahead_traffic; }
   return MPMPC_OK;
 }
 
@@ -855,6 +985,7 @@ static int sync_disc_lists(mpmpc_handle h, std::vector<char>* new_mv) {
   h->obs.discs_live = false;
   h->look.laid = false;      // (the lookahead's tables follow the lists: look_check_step lays them out anew)
   h->look.ran_B = 0;
+  h->tlk.forget();
   if (B == 0) return MPMPC_OK;
   HIP_TRY(hipSetDevice(h->cfg.device));
   Slot& sl = h->last();
@@ -952,6 +1083,7 @@ int mpmpc_rollout_set_traffic(mpmpc_handle h, int32_t B, const int32_t* group, c
                                 h->obs.mv_B, h->obs.mv_off.data(), &why))
     return fail(rc == -3 ? MPMPC_E_STATE : MPMPC_E_ARG, why);
   if (h->obs.wl_B > 0 && h->obs.wl_B != B) return fail(MPMPC_E_STATE, WALLS_OTHER_B);
+  if (h->tlk.on && h->look.max_lead > 0 && tlk_table_bytes(B, slots, h->cfg.N) > LOOK_TABLE_BUDGET) return fail(MPMPC_E_ARG, TLK_OVER_BUDGET);
   HIP_TRY(hipSetDevice(h->cfg.device));
   const size_t nb = (size_t)B;
   std::vector<int32_t> blk(4 * nb + 1);      // dense group, radius, members, the groups' offsets

@@ -163,6 +163,21 @@ struct LookState {
   int ran_B = 0, ran_n = 0; // cars and movers K0h ran for in the last step (0: it did not run)
 };
 
+// lookahead for traffic (mpmpc_rollout_set_lookahead_traffic; the law: traffic_lookahead_core.hpp): the flag, the plan tracks
+// K3t leaves at the end of every step that anticipates traffic, and what K0t and K0ht write in front of K0c - memory of its
+// own, sized in front of the first step that needs it (mpmpc_lookahead.hpp)
+struct TlkState {
+  bool on = false;          // the flag; a step anticipates traffic iff it is on, lookahead is set and traffic is set
+  Buf<int> valid;           // [max_batch]: may the car's track be read
+  Buf<int> cells;           // [max_batch][N + 1][2]: the cell of every stage of the car's plan (TLK_OFF: none)
+  Buf<double> tm;           // [max_batch][N + 1]: the running maximum of the plan's times
+  Buf<int> who;             // [B][S] the occupants of the traffic slots of the last step; only grows
+  Buf<int> tz;              // [B][S][N][3] the horizon discs of the traffic slots of the last step; only grows
+  bool tracks_live = false; // the tracks are those of the rollout's last step (else valid is cleared in front of the next reader)
+  int ran_B = 0, ran_S = 0; // cars and slots K0ht ran for in the last step (0: it did not run)
+  void forget() { tracks_live = false; ran_B = 0; }
+};
+
 // per-batch inputs and host staging
 struct IoState {
   // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
@@ -207,6 +222,7 @@ struct mpmpc_handle_s {
   AudState aud;
   PerState per;
   LookState look;
+  TlkState tlk;
   IoState io;
   // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
   // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that

@@ -67,6 +67,7 @@ __device__ long long g_phase[4096 * 32];
 #include "obstacle_motion_core.hpp"
 #include "lookahead_core.hpp"
 #include "traffic_core.hpp"
+#include "traffic_lookahead_core.hpp"
 #include "lidar_core.hpp"
 #include "footprint_core.hpp"
 #include "wall_core.hpp"

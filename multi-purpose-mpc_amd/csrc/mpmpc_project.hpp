@@ -155,6 +155,7 @@ int mpmpc_rollout_reroute(mpmpc_handle h, int32_t B, const int32_t* route, doubl
   HIP_TRY(hipMemcpyAsync(acc.data(), blk + o_acc, sizeof(int) * B, hipMemcpyDeviceToHost, sl.stream));
   HIP_TRY(hipStreamSynchronize(sl.stream));      // `rhdr` and `acc` leave scope; the mirror needs the verdicts
   t.routes.rerouted(B, route, acc.data());
+  h->tlk.forget();      // (traffic lookahead: a plan track lies on the route it was made on - the whole fleet's start over)
   if (accepted_out) std::memcpy(accepted_out, acc.data(), sizeof(int32_t) * (size_t)B);
   return MPMPC_OK;
 }

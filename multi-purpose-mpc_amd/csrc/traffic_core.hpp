@@ -112,11 +112,13 @@ inline int tr_check_traffic(int B, int max_batch, const int32_t* group, const in
 }
 
 // The S slots of car b, one car after the other (the host twin; K0t does the same selection with a wavefront).
-// out [S][3].
+// out [S][3]; who [S] (optional): the car index of every slot's occupant, -1 for an empty slot (what K0t writes for the
+// traffic lookahead, traffic_lookahead_core.hpp).
 inline void tr_slots_car(const MapView& m, const double* pose, const int32_t* alive, const int32_t* dense,
                          const int32_t* radius, const int32_t* goff, const int32_t* members, int S, int range_cells, int b,
-                         int32_t* out) {
+                         int32_t* out, int32_t* who = nullptr) {
   for (int k = 0; k < 3 * S; ++k) out[k] = 0;
+  for (int t = 0; who && t < S; ++t) who[t] = -1;
   int bx, by;
   if (alive[b] != 1 || dense[b] < 0 || !tr_cell(m, pose[3L * b], pose[3L * b + 1], &bx, &by)) return;
   const int g0 = goff[dense[b]], n = goff[dense[b] + 1] - g0;
@@ -133,6 +135,7 @@ inline void tr_slots_car(const MapView& m, const double* pose, const int32_t* al
   std::sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& c) { return tr_less(a.d2, a.pos, c.d2, c.pos); });
   for (int t = 0; t < S && t < (int)cand.size(); ++t) {
     out[3 * t] = cand[t].cx; out[3 * t + 1] = cand[t].cy; out[3 * t + 2] = radius[members[g0 + cand[t].pos]];
+    if (who) who[t] = members[g0 + cand[t].pos];
   }
 }
 

@@ -178,6 +178,9 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_obstacles.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_set_lookahead.argtypes = [h, C.c_int32, _dp, C.c_int32]
     lib.mpmpc_rollout_lookahead.argtypes = [h, C.c_int32, _ip, _ip]
+    lib.mpmpc_rollout_set_lookahead_traffic.argtypes = [h, C.c_int32]
+    lib.mpmpc_rollout_tracks.argtypes = [h, C.c_int32, _ip, _ip, _dp]
+    lib.mpmpc_rollout_lookahead_traffic.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_set_traffic.argtypes = [h, C.c_int32, _ip, _ip, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_set_walls.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -235,6 +238,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_rollout_step", "mpmpc_rollout_set_counters", "mpmpc_rollout_warm_start", "mpmpc_rollout_state", "mpmpc_rollout_set_obstacles", "mpmpc_rollout_corridor",
            "mpmpc_rollout_set_movers", "mpmpc_rollout_obstacles", "mpmpc_rollout_set_traffic",
            "mpmpc_rollout_set_lookahead", "mpmpc_rollout_lookahead",
+           "mpmpc_rollout_set_lookahead_traffic", "mpmpc_rollout_tracks", "mpmpc_rollout_lookahead_traffic",
            "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams", "mpmpc_launch_plan",
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_lidar_scan", "mpmpc_rollout_scan",
            "mpmpc_footprint_audit", "mpmpc_rollout_set_audit", "mpmpc_rollout_audit", "mpmpc_rollout_set_walls",
@@ -474,6 +478,7 @@ class Handle:
         the same number of cars); needs build_corridor on the current map; may be called between rollout_step calls."""
         if movers is None:
             self._check(self.lib.mpmpc_rollout_set_movers(self._h, 0, None, None, None, None, 0))
+            self._n_movers = 0
             return
         lists = [np.asarray(m, dtype=np.float64).reshape(-1, 6) for m in movers]
         off = np.zeros(len(lists) + 1, np.int32)
@@ -508,6 +513,34 @@ class Handle:
         self._check(self.lib.mpmpc_rollout_lookahead(self._h, B, _i(lead), _i(discs) if discs.size else None))
         return lead[:B], discs
 
+    def rollout_set_lookahead_traffic(self, enable=True):
+        """Lookahead for traffic (K3t, K0ht; the law: csrc/traffic_lookahead_core.hpp): while rollout_set_lookahead and
+        rollout_set_traffic are both in force, column c of a car's horizon sees the cars in its traffic slots where their own
+        plans of the step before put them at step k + lead_c (a neighbour without a valid plan, or a column with lead 0: where
+        it is now).  A fleet-wide flag, off by default, independent of the order of the three calls; such a step looks ahead
+        with or without movers.  rollout_init, rollout_reroute and switching it on make every plan invalid for one step."""
+        self._check(self.lib.mpmpc_rollout_set_lookahead_traffic(self._h, 1 if enable else 0))
+
+    def rollout_tracks(self):
+        """-> dict(valid bool [B], cells int32 [B, N + 1, 2], tm [B, N + 1]): the plan tracks the last step left - the map cell
+        of every stage of every car's plan ((INT32_MIN, 0): none) and the running maximum of its arrival times; valid: the
+        next step may read the car's track (the car is running and its solve was usable).  lookahead.plan_tracks restates it."""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        n = max(B, 1)
+        valid, cells, tm = np.zeros(n, np.int32), np.zeros((n, self.N + 1, 2), np.int32), np.zeros((n, self.N + 1))
+        self._check(self.lib.mpmpc_rollout_tracks(self._h, B, _i(valid), _i(cells), _d(tm)))
+        return dict(valid=valid[:B] != 0, cells=cells[:B], tm=tm[:B])
+
+    def rollout_lookahead_traffic(self):
+        """-> (who int32 [B, S], discs int32 [B, S, N, 3]): what the last step's K0t and K0ht wrote - the car in every traffic
+        slot (-1: empty) and the slot's disc at every column of its car (ungated: K0c keeps the staged entry of a slot that is
+        absent in the list it plans from).  lookahead.traffic_discs restates it."""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        S = int(getattr(self, "_tr_S", 0))
+        who, discs = np.zeros((max(B, 1), max(S, 1)), np.int32), np.zeros((max(B, 1), max(S, 1), self.N, 3), np.int32)
+        self._check(self.lib.mpmpc_rollout_lookahead_traffic(self._h, B, _i(who), _i(discs)))
+        return who[:B, :S], discs[:B, :S]
+
     def rollout_set_traffic(self, group, radius_cells=None, slots=1, range_cells=-1):
         """Traffic: the cars of a group see each other as discs, from the fleet's own poses, every step on the device (K0t).
         group [B] ints (the same non-negative value: one world; negative: sees nobody, is seen by nobody), radius_cells [B]
@@ -517,6 +550,7 @@ class Handle:
         map; may be called between rollout_step calls.  traffic.traffic_discs gives the slots of any state."""
         if group is None:
             self._check(self.lib.mpmpc_rollout_set_traffic(self._h, 0, None, None, 0, -1))
+            self._tr_S = 0
             return
         grp, rad = (np.asarray(a) for a in (group, radius_cells))
         if grp.ndim != 1 or rad.shape != grp.shape:
@@ -526,6 +560,7 @@ class Handle:
                 raise ValueError("group and radius_cells must be integers")
         grp, rad = (np.ascontiguousarray(a, dtype=np.int32) for a in (grp, rad))
         self._check(self.lib.mpmpc_rollout_set_traffic(self._h, grp.size, _i(grp), _i(rad), int(slots), int(range_cells)))
+        self._tr_S = int(slots)      # (rollout_lookahead_traffic sizes its arrays by it)
 
     def rollout_set_walls(self, walls):
         """Per-car boundary walls (Map.add_boundary on the device; the law: csrc/wall_core.hpp): walls = one int [k_b, 4]
