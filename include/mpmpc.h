@@ -515,6 +515,53 @@ int mpmpc_rollout_lookahead_traffic(mpmpc_handle h, int32_t B, int32_t* who_out,
  *   mpmpc_rollout_scan, the audit, recorded rows; mpmpc_rollout_obstacles keeps returning the discs only.  A rollout
  *   without walls launches exactly what it launched before. */
 int mpmpc_rollout_set_walls(mpmpc_handle h, int32_t B, const int32_t* offsets, const int32_t* walls);
+/* Plant: the vehicle that differs from the controller's model, per car and off by default - the sim-to-real question (does
+ * this tuning still clear the obstacle with 5 % wheelbase error, a steering bias, a lagging servo, noisy localisation?)
+ * without a host round trip per step.  With a plant in force the true vehicle and the controller's knowledge of its pose
+ * separate: the TRUE pose stays what mpmpc_rollout_state returns, and K3a localises on a MEASURED pose kept in a buffer of
+ * its own (K3n writes it in front of K3a); K3p drives the car in place of K3b.  params [B][11] per car, in this order
+ * (identity: 1, 1, 0, 1, 1, 1, +inf, 0, 0, 0, 0):
+ *    0 speed_gain       finite              4 speed_lag   in (0, 1]                   7 speed_noise    [m/s]
+ *    1 steer_gain       finite              5 steer_lag   in (0, 1]                   8 steer_noise    [rad]
+ *    2 steer_offset     finite [rad]        6 steer_rate  > 0 [rad / step], +inf ok   9 position_noise [m]
+ *    3 wheelbase_scale  finite, > 0                                                  10 heading_noise  [rad]   (7 .. 10 finite, >= 0)
+ * Per step k (0-based, counted from mpmpc_rollout_init - the movers' index), j = k - step0, (n_v, n_d, n_x, n_y, n_psi) the
+ * car's five variates of the step:
+ *    measure   meas = (x + position_noise n_x, y + position_noise n_y, psi + heading_noise n_psi)      cars with alive == 1
+ *    drive     (v_cmd, d_cmd), the infeasibility counter, u (the COMMANDED control) and the N - 1 ending as without a plant;
+ *              v_t = speed_gain v_cmd + speed_noise n_v;   d_t = steer_gain d_cmd + steer_offset + steer_noise n_d;
+ *              v_act += speed_lag (v_t - v_act);  d_new = d_act + steer_lag (d_t - d_act), its change from d_act limited to
+ *              +-steer_rate;  the bicycle step with (v_act, d_act) and the wheelbase L wheelbase_scale;  s advances by the
+ *              model's s_dot on v_act and the x0 of the MEASURED pose (wheel odometry: s drifts from the true arc length;
+ *              mpmpc_rollout_reroute onto the car's own route relocalises it)
+ * The variates are triangular on (-1, 1) (standard deviation 1 / sqrt 6), one 32-bit word of Philox4x32-10 each, key = the
+ * seed, counter = (car0 + car, j, block): a draw depends on (seed, car0 + car, j, channel) only - not on B, on the steps per
+ * call or on other cars - so the noise of any step can be recomputed from its index (mpmpc_plant_noise), as the movers'
+ * positions can.  Gaussian noise is not offered.  The exact operation order, the generator and the variate are stated in
+ * csrc/plant_core.hpp; an identity plant reproduces the rollout without one bit for bit.
+ * The audit, mpmpc_rollout_scan, perception (K0s), traffic (K0t), the plan tracks, the recorder and mpmpc_rollout_reroute
+ * keep reading the true pose: they judge or sense the true car.  x0 (state, recorder) is the measured pose's.
+ *   mpmpc_rollout_set_plant  params == NULL: no plant.  act0 [B][2]: the executed (v, delta) the actuators start from, or
+ *                           NULL for zeros; the call sets them and zeroes the accumulators.  car0: the index of car 0 in a
+ *                           larger fleet.  step0 may be negative: a run resumed from a saved state of step k0 continues its
+ *                           noise with step0 = -k0 and act0 = the saved act.  May be called before mpmpc_rollout_init or
+ *                           between mpmpc_rollout_step calls: it applies from the next step on and keeps the rollout's
+ *                           state.  MPMPC_E_ARG: a parameter outside the table, act0 not finite, B outside [1, max_batch];
+ *                           a refused call leaves the previous setting in force.  A step whose B differs returns
+ *                           MPMPC_E_STATE.  mpmpc_rollout_init with a plant in force keeps the parameters and zeroes the
+ *                           actuator states and the accumulators.
+ *   mpmpc_rollout_plant     any pointer may be NULL.  act [B][2]: the executed (v, delta) of the last driven step; meas
+ *                           [B][3]: the pose K3a saw in the last step (cars that were running); ey_max / ey_sq / steps [B]:
+ *                           max |e|, sum of e^2 and the number of steps over the steps the car was driven, e = the lateral
+ *                           offset of the TRUE pose the step found the car at from the step's waypoint (cos / sin from K0's
+ *                           host table: no device-libm result).  MPMPC_E_STATE if no step ran under the setting in force.
+ *   mpmpc_plant_noise       out [n_steps][B][5] = (n_v, n_d, n_x, n_y, n_psi) of cars car0 .. car0 + B - 1 at j = j0 ..
+ *                           j0 + n_steps - 1, computed on the device with plant_core.hpp's code; no handle needed.
+ * A rollout without a plant launches exactly what it launched before. */
+int mpmpc_rollout_set_plant(mpmpc_handle h, int32_t B, const double* params, uint64_t seed, int32_t car0, int64_t step0,
+                            const double* act0);
+int mpmpc_rollout_plant(mpmpc_handle h, int32_t B, double* act, double* meas, double* ey_max, double* ey_sq, int32_t* steps);
+int mpmpc_plant_noise(int32_t device, uint64_t seed, int32_t car0, int32_t B, int64_t j0, int32_t n_steps, double* out);
 
 /* Recorder: while the cars drive, the rollout appends one record per car and recorded step to a device-resident trace
  * (what src/simulation.py:117-157 logs per step on the host: x_log / y_log / v_log and MPC.current_prediction), and

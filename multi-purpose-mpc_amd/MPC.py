@@ -381,7 +381,7 @@ class BatchMPC:
         return self.handle.rollout_reroute(routes, max_dist, max_heading)
 
     def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
-                walls=None, perception=None, routes=None, lookahead=None):
+                walls=None, perception=None, routes=None, lookahead=None, plant=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -423,6 +423,14 @@ class BatchMPC:
         car's traffic slots where their own plans of the step before put them at step k + lead_c (K3t, K0ht;
         csrc/traffic_lookahead_core.hpp); handle.rollout_tracks() and handle.rollout_lookahead_traffic() return the plan
         tracks and the slots' horizon discs of the last step.
+        plant: None - every car drives the controller's own model, exactly; a plant.Plant - the true vehicle of every car
+        (gains, steering offset, wheelbase scale, actuator lags, steering rate limit, noise on the commands and on the pose
+        the controller localises on; per car, K3n / K3p on the device, csrc/plant_core.hpp).  Needs no corridor='device'.  The
+        controllers see the MEASURED pose: wp_id / x0, and through them the plan and s (wheel odometry on the measured
+        spatial state - s drifts from the true arc length; `reroute` onto a car's own route relocalises it).  Everything
+        else keeps the TRUE pose, "pose" of the returned dict: the audit, rollout_scan, perception, traffic and its plan
+        tracks, the recorder's pose and `reroute`.  The returned dict also holds "plant": handle.rollout_plant() - act, meas,
+        ey_max, ey_sq, steps (None when n_steps = 0).
         record: None - nothing is recorded; True or a dict of mpmpc.Handle.rollout_record's keyword arguments (capacity,
         plan, prediction, rows, stride; capacity defaults to the records `n_steps` yields) - the run is recorded on the
         device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of the whole run, arrays
@@ -510,6 +518,12 @@ class BatchMPC:
         if ahead_traffic or getattr(self, "_lookahead_traffic_set", False):      # (the same rule for the flag)
             self.handle.rollout_set_lookahead_traffic(ahead_traffic)
             self._lookahead_traffic_set = ahead_traffic
+        if plant is not None:
+            self.handle.rollout_set_plant(plant.params(np.asarray(s).size), plant.seed, plant.car0, plant.step0)
+            self._plant_set = True
+        elif getattr(self, "_plant_set", False):      # (off again; a controller that never had a plant calls nothing new)
+            self.handle.rollout_set_plant(None)
+            self._plant_set = False
         if cum is None:
             cum = np.cumsum(rp.segment_lengths)
         perceived = perception is not None and int(n_steps) > 0 and any(
@@ -522,6 +536,8 @@ class BatchMPC:
                 out["audit"] = self.handle.rollout_audit()
             if perception is not None:
                 out["perception"] = self.handle.rollout_perception() if perceived else None
+            if plant is not None:
+                out["plant"] = self.handle.rollout_plant() if int(n_steps) > 0 else None
             return out
         kw = dict(record) if isinstance(record, dict) else {}
         stride = int(kw.get("stride", 1))
@@ -536,6 +552,8 @@ class BatchMPC:
                 out["audit"] = self.handle.rollout_audit()
             if perception is not None:
                 out["perception"] = self.handle.rollout_perception() if perceived else None
+            if plant is not None:
+                out["plant"] = self.handle.rollout_plant() if int(n_steps) > 0 else None
         finally:
             self.handle.rollout_record(0, B=np.asarray(s).size)      # later rollouts are unrecorded again
         return out

@@ -1,6 +1,6 @@
 // The closed loop of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind mpmpc_set_corridor):
 // the kernels K0a / K0b (corridor tables from the map), K0c (per-car corridor rows), K0m (movers), K0h (the movers over the horizon), K0t (traffic), K3a / K3b (localise, advance)
-// and the two recorder kernels, and their entry points - mpmpc_set_map, mpmpc_set_path_geometry, mpmpc_build_corridor and every
+// and the two recorder kernels (K3n / K3p, the plant models a step launches around K3a and in place of K3b: mpmpc_plant.hpp, in front of this header), and their entry points - mpmpc_set_map, mpmpc_set_path_geometry, mpmpc_build_corridor and every
 // mpmpc_rollout_*.  The state they work on: the sub-states cor, obs, ro, rec of the handle (mpmpc_handle.hpp).  The walls of a car's
 // world (mpmpc_rollout_set_walls, below) are rasterised by K0w (mpmpc_walls.hpp, in front of this header).
 #pragma once
@@ -755,6 +755,9 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   h->per.forget();                // what the cars know starts over; the setting stays
   h->look.ran_B = 0;              // (lookahead: the setting stays too, the last step's table is no step's of this rollout)
   h->tlk.forget();                // (... and no plan track is: every car is a frozen disc in the first step)
+  if (h->pl.B > 0) {              // a plant in force keeps its parameters; its actuators and accumulators start over
+    if (int rc = plant_reset(h, sl, h->pl.B, nullptr)) return rc;
+  }
   return aud_reset(h, B);         // ... and so does the audit (mpmpc_footprint.hpp)
 }
 
@@ -859,6 +862,8 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
       return fail(MPMPC_E_STATE, "the trace is full: " + std::to_string(h->rec.count) + " of " + std::to_string(h->rec.cap) +
                                      " records held, this call would add " + std::to_string(h->rec.records_of(n_steps)));
   }
+  const bool plant = h->pl.B > 0;
+  if (plant && h->pl.B != B) return fail(MPMPC_E_STATE, "the plant was set for another number of cars (mpmpc_rollout_set_plant)");
   if (int rc = aud_check_step(h, B)) return rc;
   const bool auditing = h->aud.mode != FP_MODE_OFF;
   HIP_TRY(hipSetDevice(h->cfg.device));
@@ -911,8 +916,10 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
                            h->obs.obst_off.get(), B, route);
       per_enqueue_step(h, sl, B, h->rec.ro_steps);
     }
+    if (plant) plant_enqueue_measure(h, sl, B, h->rec.ro_steps);      // K3n: K3a localises on the measured poses
     hipLaunchKernelGGL(mpmpc_localise_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.N, h->cfg.circular ? 1 : 0,
-                       h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, h->ro.s, h->ro.pose, h->ro.alive, h->io.wp_id, h->io.x0, h->ro.shift, route);
+                       h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, h->ro.s, plant ? h->pl.meas.get() : h->ro.pose.get(), h->ro.alive, h->io.wp_id,
+                       h->io.x0, h->ro.shift, route);
     if (movers > 0 && !perceiving)
       hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
                          h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs.get(),
@@ -954,8 +961,13 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
                          h->cor.line_box, h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(),
                          h->obs.ro_flag.get(), h->io.lb, h->io.ub, WallView{nullptr, nullptr, nullptr}, route, LookNone{});
     if (int rc = launch_solve(h, sl, B, true, false)) return rc;  // (the plant step reads z and the status only)
-    hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro.Ts,
-                       h->tab.kappa, h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter, h->ro.alive, h->ro.pose, h->ro.s, h->ro.u, route);
+    if (plant)      // K3p: the plant in place of ro_drive
+      hipLaunchKernelGGL(mpmpc_advance_plant_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase,
+                         h->ro.Ts, h->tab.kappa.get(), h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter.get(), h->ro.alive.get(),
+                         h->ro.pose.get(), h->ro.s.get(), h->ro.u.get(), route, plant_view(h, h->rec.ro_steps));
+    else
+      hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro.Ts,
+                         h->tab.kappa, h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter, h->ro.alive, h->ro.pose, h->ro.s, h->ro.u, route);
     if (ahead_traffic) tlk_enqueue_tracks(h, sl, B, mv, route);      // K3t: the plans of this step, for the next one's K0ht
     if (rec) {
       const RoRecSrc src{h->ro.alive, h->rec.ain, h->io.wp_id, sl.status, h->ro.counter, h->io.x0, h->ro.u, h->io.cc, sl.z,
@@ -970,6 +982,7 @@ int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
   HIP_TRY(hipGetLastError());
   if (n_steps > 0) h->obs.car_rows = h->obs.discs_live = per_car;
   if (n_steps > 0 && perceiving) h->per.B = B;
+  if (n_steps > 0 && plant) h->pl.ran = true;
   if (n_steps > 0) { h->look.ran_B = looking ? B : 0; h->look.ran_n = looking ? movers : 0; }
   if (n_steps > 0) { h->tlk.ran_B = ahead_traffic ? B : 0; h->tlk.ran_S = ahead_traffic ? h->obs.tr_S : 0; h->tlk.tracks_live = ahead_traffic; }
   return MPMPC_OK;

@@ -178,6 +178,21 @@ struct TlkState {
   void forget() { tracks_live = false; ran_B = 0; }
 };
 
+// plant models of the rollout (mpmpc_rollout_set_plant; the law: plant_core.hpp): the setting, the cars' actuator states, the
+// measured poses K3a localises on and the tracking accumulators - memory of its own, sized by max_batch when first set
+struct PlantState {
+  int B = 0;                // > 0: a plant is in force for B cars
+  unsigned long long seed = 0;
+  int car0 = 0;
+  long long step0 = 0;
+  Buf<double> prm;          // [max_batch][PL_PARAMS]
+  Buf<double> act;          // [max_batch][2]: the executed (v, delta) of the last driven step
+  Buf<double> meas;         // [max_batch][3]: the pose K3a saw in the last step
+  Buf<double> ey;           // [2][max_batch]: ey_max, ey_sq
+  Buf<int> steps;           // [max_batch]
+  bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_plant)
+};
+
 // per-batch inputs and host staging
 struct IoState {
   // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
@@ -223,6 +238,7 @@ struct mpmpc_handle_s {
   PerState per;
   LookState look;
   TlkState tlk;
+  PlantState pl;
   IoState io;
   // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
   // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that

@@ -75,6 +75,7 @@ __device__ long long g_phase[4096 * 32];
 #include "speed_core.hpp"
 #include "path_core.hpp"
 #include "project_core.hpp"
+#include "plant_core.hpp"
 
 using namespace mpmpc;
 
@@ -980,6 +981,7 @@ static int check_wp_ids(mpmpc_handle h, int B, const int32_t* wp_id) {
 // (the kernels of the two keep their order in the code object: K4, then K0 / K3 and the recorder)
 #include "mpmpc_speed_profile.hpp"
 #include "mpmpc_walls.hpp"
+#include "mpmpc_plant.hpp"
 #include "mpmpc_closed_loop.hpp"
 #include "mpmpc_lookahead.hpp"
 #include "mpmpc_lidar.hpp"

@@ -183,6 +183,9 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_lookahead_traffic.argtypes = [h, C.c_int32, _ip, _ip]
     lib.mpmpc_rollout_set_traffic.argtypes = [h, C.c_int32, _ip, _ip, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_set_walls.argtypes = [h, C.c_int32, _ip, _ip]
+    lib.mpmpc_rollout_set_plant.argtypes = [h, C.c_int32, _dp, C.c_uint64, C.c_int32, C.c_int64, _dp]
+    lib.mpmpc_rollout_plant.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp, _ip]
+    lib.mpmpc_plant_noise.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _dp]
     lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_recorded.argtypes = [h, _ip, _ip]
     lib.mpmpc_rollout_trace.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
@@ -247,6 +250,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_path_count", "mpmpc_path_build", "mpmpc_path_build_timed",
            "mpmpc_check_routes", "mpmpc_set_routes", "mpmpc_set_car_routes",
            "mpmpc_project", "mpmpc_rollout_reroute", "mpmpc_rollout_routes",
+           "mpmpc_rollout_set_plant", "mpmpc_rollout_plant", "mpmpc_plant_noise",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -623,6 +627,37 @@ class Handle:
                                                       out["wall_known"].ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
 
+    # --- plant models of the rollout: the vehicle that differs from the controller's model, per car
+    PLANT_FIELDS = ("act", "meas", "ey_max", "ey_sq", "steps")
+
+    def rollout_set_plant(self, params, seed=0, car0=0, step0=0, act0=None):
+        """The true vehicle of the rollouts that follow (K3n / K3p; the law: csrc/plant_core.hpp): params [B, 11] per car -
+        plant.Plant.params(B): speed_gain, steer_gain, steer_offset, wheelbase_scale, speed_lag, steer_lag, steer_rate,
+        speed_noise, steer_noise, position_noise, heading_noise - or None for no plant (the default: every car drives the
+        controller's own model).  A draw of the noise depends on (seed, car0 + car, k - step0, channel) only.  act0 [B, 2]: the
+        executed (v, delta) the actuators start from (None: zeros).  The true pose stays rollout_state()["pose"] - what the
+        audit, rollout_scan, perception, traffic, the recorder and rollout_reroute read; the controllers localise on the
+        measured pose (rollout_plant()["meas"]).  May be called before rollout_init or between rollout_step calls."""
+        if params is None:
+            self._check(self.lib.mpmpc_rollout_set_plant(self._h, 0, None, 0, 0, 0, None))
+            return
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 11:
+            raise ValueError("plant parameters must be [B, 11] (plant.Plant.params)")
+        a = None if act0 is None else np.ascontiguousarray(act0, dtype=np.float64).reshape(p.shape[0], 2)
+        self._check(self.lib.mpmpc_rollout_set_plant(self._h, p.shape[0], _d(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(car0), int(step0),
+                                                     _d(a)))
+
+    def rollout_plant(self):
+        """-> dict of the plant's per-car state: act [B, 2] the executed (v, delta) of the last driven step, meas [B, 3] the
+        pose the controller saw in the last step, ey_max / ey_sq / steps [B]: max |e|, sum of e^2 and the number of steps over
+        the steps the car was driven - e the lateral offset of the TRUE pose from the step's waypoint."""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        out = dict(act=np.zeros((B, 2)), meas=np.zeros((B, 3)), ey_max=np.zeros(B), ey_sq=np.zeros(B), steps=np.zeros(B, np.int32))
+        self._check(self.lib.mpmpc_rollout_plant(self._h, B, _d(out["act"]), _d(out["meas"]), _d(out["ey_max"]), _d(out["ey_sq"]),
+                                                 _i(out["steps"])))
+        return out
+
     # --- footprint audit of the rollout: contact and clearance of every car, every step, accumulated on the device
     AUDIT_FIELDS = ("contact_steps", "first_contact", "min_clearance", "min_step", "last_contact", "last_clearance")
 
@@ -831,6 +866,18 @@ def speed_profile(li, kappa, limits, eps=1e-12, device=0):
     if rc != 0:
         raise MpmpcError("mpmpc_speed_profile: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
     return v, status, iters
+
+
+def plant_noise(seed, car0, B, j0, n_steps, device=0):
+    """The plant's draws (csrc/plant_core.hpp) of cars car0 .. car0 + B - 1 at j = j0 .. j0 + n_steps - 1, computed on the
+    device -> float64 [n_steps, B, 5] = (n_v, n_delta, n_x, n_y, n_psi).  plant.Plant.noise is the numpy evaluation."""
+    lib = load_library()
+    out = np.zeros((int(n_steps), int(B), 5))
+    rc = lib.mpmpc_plant_noise(device, int(seed) & 0xFFFFFFFFFFFFFFFF, int(car0), int(B), int(j0), int(n_steps),
+                               _d(out) if out.size else _d(np.zeros(1)))
+    if rc != 0:
+        raise MpmpcError("mpmpc_plant_noise: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    return out
 
 
 def _wall_csr(walls, B=None):

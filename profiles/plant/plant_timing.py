@@ -1,0 +1,116 @@
+"""Per-step time of the device rollout with a plant (K3n / K3p), with an identity plant and without one, the method of profiles/rollout_warm.py: N = 30,
+Sim_Track's free corridor, the default warm start, 5 warm-up steps, then 60 timed steps between two synchronisations; every
+variant is repeated, the variants alternating, and the median and the spread over the repeats are printed.
+
+    python profiles/plant/plant_timing.py [--parent OTHER/libmpmpc.so] [--repeats 7] [--B 1024 8192]
+    python profiles/plant/plant_timing.py --trace --B 1024      # plant on only, for a kernel trace around it (rocprofv3)
+
+--parent: a build of another commit's library, loaded into the same process and timed as a third variant (the parent has no
+plant: it is "plant off" on the older code).  (GPU box)"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+for d in ("multi-purpose-mpc_amd", "tests", "oracle"):
+    sys.path.insert(0, os.path.join(ROOT, d))
+import mpc_np as M          # noqa: E402
+import mpmpc                # noqa: E402
+import mpmpc_testlib as T   # noqa: E402
+import scenarios            # noqa: E402
+from plant import Plant     # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--parent", default=None)
+ap.add_argument("--repeats", type=int, default=7)
+ap.add_argument("--B", type=int, nargs="+", default=[1024, 8192])
+ap.add_argument("--trace", action="store_true")
+args = ap.parse_args()
+
+NOISY = Plant(speed_gain=0.97, steer_gain=1.03, steer_offset=0.01, wheelbase_scale=1.03, speed_lag=0.8, steer_lag=0.8, steer_rate=0.3,
+              speed_noise=0.02, steer_noise=0.01, position_noise=0.002, heading_noise=0.005, seed=12345)
+g1 = np.load(M.GOLDEN + "/g1_path_sim_track.npz")
+g3 = np.load(M.GOLDEN + "/g3_corridor.npz")
+N, warmup, steps = 30, 5, 60
+tr = scenarios.sim_track()
+cum = np.cumsum(g1["segment_lengths"])
+this_lib = mpmpc.load_library()
+
+
+def load_other(path):
+    """another build of the library: every entry point it shares with this one, declared as this one's"""
+    import ctypes
+    lib = ctypes.CDLL(path)
+    for name in mpmpc.EXPORTS:
+        if hasattr(lib, name):
+            getattr(lib, name).argtypes = getattr(this_lib, name).argtypes
+            getattr(lib, name).restype = getattr(this_lib, name).restype
+    return lib
+
+
+parent_lib = load_other(args.parent) if args.parent else None
+
+
+def handle(lib, B):
+    mpmpc._lib = lib      # (Handle binds the library it is made with)
+    try:
+        h = mpmpc.Handle(T.stock_config(N, max_batch=B))
+    finally:
+        mpmpc._lib = this_lib
+    h.set_path(tr.kappa, tr.v_ref, tr.ds_next)
+    h.set_corridor(g3["ub_free"], g3["lb_free"])
+    h.set_path_geometry(g1["x"], g1["y"], g1["psi"], g1["border_ub"], g1["border_lb"])
+    return h
+
+
+def timed(h, s0, poses):
+    h.rollout_init(0.05, cum, s0, poses)
+    h.rollout_step(warmup)
+    h.sync()
+    t = time.perf_counter()
+    h.rollout_step(steps)
+    h.sync()
+    return (time.perf_counter() - t) / steps * 1e3
+
+
+for B in args.B:
+    starts = np.random.default_rng(7).integers(0, 200, B)
+    s0, poses = cum[starts], np.stack([g1["x"][starts], g1["y"][starts], g1["psi"][starts]], axis=1)
+    variants = {}
+    if not args.trace:
+        if parent_lib is not None:
+            variants["parent"] = handle(parent_lib, B)
+        variants["plant off"] = handle(this_lib, B)
+        variants["identity"] = handle(this_lib, B)      # K3n and K3p launched, the trajectories those of plant off
+        variants["identity"].rollout_set_plant(Plant().params(B), NOISY.seed)
+    variants["plant on"] = handle(this_lib, B)
+    variants["plant on"].rollout_set_plant(NOISY.params(B), NOISY.seed)
+    ms = {k: [] for k in variants}
+    for _ in range(1 if args.trace else args.repeats):
+        for k, h in variants.items():
+            ms[k].append(timed(h, s0, poses))
+    for k, v in ms.items():
+        v = np.sort(v)
+        print("B=%5d %-9s  median %.4f ms/step   min %.4f  max %.4f   (%d repeats of %d steps)" % (B, k, np.median(v), v[0], v[-1], v.size, steps))
+    if "parent" in variants:      # plant off computes what the parent computed
+        a, b = variants["parent"].rollout_state(), variants["plant off"].rollout_state()
+        print("B=%5d plant off against the parent, max |ds| %.1e, max |dpose| %.1e, statuses equal: %s" %
+              (B, np.max(np.abs(a["s"] - b["s"])), np.max(np.abs(a["pose"] - b["pose"])), np.array_equal(a["status"], b["status"])))
+    if "identity" in variants:
+        a, b = variants["plant off"].rollout_state(), variants["identity"].rollout_state()
+        print("B=%5d identity plant against plant off: all of the state bit-equal: %s" %
+              (B, all(np.array_equal(a[k], b[k]) for k in a)))
+    pl, st = variants["plant on"].rollout_plant(), variants["plant on"].rollout_state()
+    ref = variants["plant off"].rollout_state() if "plant off" in variants else None
+    for name, q in (("plant on", st), ("plant off", ref)):
+        if q is not None:
+            print("B=%5d %-9s  alive == 1: %d of %d; statuses of the last step: %s; infeasibility counters > 0: %d" %
+                  (B, name, int((q["alive"] == 1).sum()), B, dict(zip(*(v.tolist() for v in np.unique(q["status"], return_counts=True)))),
+                   int((q["counter"] > 0).sum())))
+    print("B=%5d plant on: rms e_y %.4f m, max |e_y| %.4f m over the driven steps" %
+          (B, float(np.sqrt(pl["ey_sq"].sum() / max(int(pl["steps"].sum()), 1))), float(pl["ey_max"].max())))
+    for h in variants.values():
+        h.close()
