@@ -198,6 +198,31 @@ struct PathGeom {
   const double* trig;                    // [n_wp x COR_TRIG], cor_trig_row of every waypoint (host libm)
 };
 
+// Route fleets: a car's view of the path tables.  Its header is the pair {first row, length - negated when the route is open}
+// (PathTables::route; mpmpc_project.hpp writes it); a null `route` is the one path (n_wp, circular), nothing moves.  This is the
+// one place that decodes a header: the kernels of the rollout and their CPU twins take their view from here.  wp_id is local
+// to the view; per-waypoint arrays are indexed by `first` + the local row.
+struct RouteView {
+  long first;      // first row
+  int len;         // the header's second word: the length, negated when the route is open
+  // (decoded where they are used, not when the view is formed, and both in one body: a kernel's instructions keep their order)
+  MPMPC_HD void lengths(int& n, int& circular) const { n = len > 0 ? len : -len; circular = len > 0 ? 1 : 0; }
+  MPMPC_HD int n() const { return len > 0 ? len : -len; }
+  MPMPC_HD int circular() const { return len > 0 ? 1 : 0; }
+};
+template <class Index>
+MPMPC_HD RouteView route_header(const int* route, Index car) { return RouteView{route[2 * car], route[2 * car + 1]}; }      // (route != null)
+MPMPC_HD RouteView route_view(const int* route, int car, int n_wp, int circular) {
+  return route ? route_header(route, car) : RouteView{0, circular ? n_wp : -n_wp};
+}
+// the geometry moved onto a view
+MPMPC_HD PathGeom route_geom(PathGeom g, RouteView v) {
+  g.x += v.first; g.y += v.first; g.psi += v.first; g.ds_next += v.first;
+  v.lengths(g.n_wp, g.circular);
+  g.trig += v.first * COR_TRIG;
+  return g;
+}
+
 // sign(wrap(atan2(py - wy, px - wx) - psi)) without an arctangent: the wrapped angle between the heading and the
 // direction to the point is positive iff the point lies to the left of the heading, i.e. iff the cross product
 // cos(psi) dy - sin(psi) dx is positive; on the heading line itself the angle is 0 (ahead: sign 0) or pi, which

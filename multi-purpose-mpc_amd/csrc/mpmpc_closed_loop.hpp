@@ -1,8 +1,12 @@
 // The closed loop of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind mpmpc_set_corridor):
-// the kernels K0a / K0b (corridor tables from the map), K0c (per-car corridor rows), K0m (movers), K0h (the movers over the horizon), K0t (traffic), K3a / K3b (localise, advance)
-// and the two recorder kernels (K3n / K3p, the plant models a step launches around K3a and in place of K3b: mpmpc_plant.hpp, in front of this header), and their entry points - mpmpc_set_map, mpmpc_set_path_geometry, mpmpc_build_corridor and every
-// mpmpc_rollout_*.  The state they work on: the sub-states cor, obs, ro, rec of the handle (mpmpc_handle.hpp).  The walls of a car's
-// world (mpmpc_rollout_set_walls, below) are rasterised by K0w (mpmpc_walls.hpp, in front of this header).
+// the kernels K0a / K0b (corridor tables from the map), K0c (per-car corridor rows), K0m (movers), K0h (the movers over the
+// horizon), K0t / K0ht / K3t (traffic, its horizon, the plan tracks), K3a / K3b (localise, advance) and the two recorder kernels
+// K3r, and the entry points that set a rollout up and read it back - mpmpc_set_map, mpmpc_set_path_geometry,
+// mpmpc_build_corridor and every mpmpc_rollout_* but the step.  mpmpc_rollout_step itself - its plan, one enqueue function per
+// kernel, the loop - is mpmpc_rollout_step.hpp, behind the features a step drives (mpmpc_plant.hpp in front of this header,
+// mpmpc_lookahead.hpp, mpmpc_perception.hpp and mpmpc_footprint.hpp behind it).  The state they work on: the sub-states cor,
+// obs, ro, rec of the handle (mpmpc_handle.hpp).  The walls of a car's world (mpmpc_rollout_set_walls, below) are rasterised by
+// K0w (mpmpc_walls.hpp, in front of this header).
 #pragma once
 
 // K0a: free segments of every waypoint's border line, one WAVEFRONT per waypoint.  Lane 0 walks Zingl's anti-aliased
@@ -125,12 +129,12 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
   static_assert(LEAD || !TRAF, "the traffic horizon needs the leads");
   constexpr int PENDING = -1000000;
   // Route fleets: the car's view of the path - the geometry's base pointers and K0a's caches (indexed by GLOBAL row) moved to the
-  // first row of its route, n_wp and circular the route's (route[2 b], route[2 b + 1]: PathTables::route); wp_id is local.
+  // first row of its route, n_wp and circular the route's (route_view: corridor_core.hpp); wp_id is local.
   // Everything below, and corridor_core.hpp, works on the view.  (uniform per block; null: one path, nothing moves)
   if (route) {
-    const long f = route[2 * blockIdx.x];
-    const int nn = route[2 * blockIdx.x + 1];
-    g = PathGeom{g.x + f, g.y + f, g.psi + f, g.ds_next + f, nn > 0 ? nn : -nn, nn > 0 ? 1 : 0, g.trig + f * COR_TRIG};
+    const RouteView v = route_header(route, blockIdx.x);
+    const long f = v.first;
+    g = route_geom(g, v);
     segs += f * 4 * COR_MAXSEG; nseg += f; wpc += f * COR_WPC; line_cells += f * COR_CELL_CAP; line_box += f * COR_LINE_BOX;
   }
   extern __shared__ double lds[];
@@ -173,28 +177,26 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
   const int wp = wp_id[b] + 1;
   auto disc = [&](int j) { return (const int*)(dsc + 3 * j); };
   auto whdr = [&](int j) { return (const int*)(whd + WALL_HDR * j); };
+  // the disc accessor `d` of column c - the one choice between the three sources - and what is returned with it (a macro, not a
+  // function that returns the closure: every such form moved the LEAD instantiations, docs/HISTORY.md)
+#define K0C_WITH_COL_DISC(c, EXPR)                                                                                  \
+  if constexpr (TRAF) {                                                                                             \
+    auto d = [&](int j) { return tlk_col_disc(dsc, j, ns, nm, hz, nd, ts, tzb, N, c); };                            \
+    return EXPR;                                                                                                    \
+  } else if constexpr (LEAD) {                                                                                      \
+    auto d = [&](int j) { return look_col_disc(dsc, j, ns, nm, hz, N, c); };                                        \
+    return EXPR;                                                                                                    \
+  } else {                                                                                                          \
+    auto& d = disc;                                                                                                 \
+    return EXPR;                                                                                                    \
+  }
   auto touches = [&](const int* box, int c) {
-    if constexpr (TRAF) {
-      auto dcol = [&](int j) { return tlk_col_disc(dsc, j, ns, nm, hz, nd, ts, tzb, N, c); };
-      return WALLS ? wall_car_touches(box, nd, dcol, nw, whdr) : (nd > 0 && cor_car_touches(box, nd, dcol));
-    } else if constexpr (LEAD) {
-      auto dcol = [&](int j) { return look_col_disc(dsc, j, ns, nm, hz, N, c); };
-      return WALLS ? wall_car_touches(box, nd, dcol, nw, whdr) : (nd > 0 && cor_car_touches(box, nd, dcol));
-    } else {
-      return WALLS ? wall_car_touches(box, nd, disc, nw, whdr) : (nd > 0 && cor_car_touches(box, nd, disc));
-    }
+    K0C_WITH_COL_DISC(c, WALLS ? wall_car_touches(box, nd, d, nw, whdr) : (nd > 0 && cor_car_touches(box, nd, d)))
   };
   auto cell_free = [&](int cell, int c) {
-    if constexpr (TRAF) {
-      auto dcol = [&](int j) { return tlk_col_disc(dsc, j, ns, nm, hz, nd, ts, tzb, N, c); };
-      return WALLS ? wall_car_cell_free(map, cell, nd, dcol, nw, whdr, wv.tab) : cor_car_cell_free(map, cell, nd, dcol);
-    } else if constexpr (LEAD) {
-      auto dcol = [&](int j) { return look_col_disc(dsc, j, ns, nm, hz, N, c); };
-      return WALLS ? wall_car_cell_free(map, cell, nd, dcol, nw, whdr, wv.tab) : cor_car_cell_free(map, cell, nd, dcol);
-    } else {
-      return WALLS ? wall_car_cell_free(map, cell, nd, disc, nw, whdr, wv.tab) : cor_car_cell_free(map, cell, nd, disc);
-    }
+    K0C_WITH_COL_DISC(c, WALLS ? wall_car_cell_free(map, cell, nd, d, nw, whdr, wv.tab) : cor_car_cell_free(map, cell, nd, d))
   };
+#undef K0C_WITH_COL_DISC
   for (int n = lane; n < N; n += 64) {
     const int i = cor_wp(g, wp + n);
     const int* box = line_box + (long)i * COR_LINE_BOX;
@@ -306,9 +308,7 @@ __global__ __launch_bounds__(256) void mpmpc_obstacle_move_kernel(int n, long lo
       const int mid = (lo + hi) / 2;
       if (off[mid] <= dst[j]) lo = mid; else hi = mid;
     }
-    const long f = route[2 * lo];
-    const int nn = route[2 * lo + 1];
-    path = MoverPath{path.cum + f, path.x + f, path.y + f, path.trig + f * path.trig_ld, nn > 0 ? nn : -nn, path.trig_ld, nn > 0 ? 1 : 0};
+    path = route_path(path, route_header(route, lo));
   }
   int d[3];
   mov_disc(map, path, kind[j], radius[j], prm[j], prm[(long)n + j], prm[2L * n + j], prm[3L * n + j], k, step0, d);
@@ -334,6 +334,7 @@ __global__ __launch_bounds__(64) void mpmpc_mover_horizon_kernel(int N, long lon
   __shared__ int s_lead[256];
   const int b = blockIdx.x, lane = threadIdx.x;
   if (route) {      // route fleets: the car's view of the path, of seg_time and of what an along-the-path mover follows
+    // (written out, not route_view / route_path: every form of them moved this kernel's registers - docs/HISTORY.md)
     const long f = route[2 * b];
     const int nn = route[2 * b + 1];
     g.n_wp = nn > 0 ? nn : -nn;
@@ -468,10 +469,9 @@ __global__ __launch_bounds__(64) void mpmpc_plan_track_kernel(int B, int N, MapV
   if (n >= B) return;
   long long first = 0;
   if (route) {      // route fleets: the car's route
-    first = route[2 * n];
-    const int nn = route[2 * n + 1];
-    n_wp = nn > 0 ? nn : -nn;
-    circular = nn > 0 ? 1 : 0;
+    const RouteView v = route_header(route, n);
+    first = v.first;
+    v.lengths(n_wp, circular);
   }
   if (lane == 0) valid[n] = tlk_valid(alive[n], status[n]) ? 1 : 0;
   const double* zn = z + (long long)(5 * N + 3) * n;
@@ -511,11 +511,9 @@ __global__ __launch_bounds__(256) void mpmpc_localise_kernel(int B, int n_wp, in
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= B || alive[i] != 1) return;
   if (route) {      // route fleets: the car's slice of cum and of the geometry, its route's length and flag; wp_id stays local
-    const long f = route[2 * i];
-    const int nn = route[2 * i + 1];
-    cum += f; gx += f; gy += f; gpsi += f;
-    n_wp = nn > 0 ? nn : -nn;
-    circular = nn > 0 ? 1 : 0;
+    const RouteView v = route_header(route, i);
+    cum += v.first; gx += v.first; gy += v.first; gpsi += v.first;
+    v.lengths(n_wp, circular);
   }
   const int wp = ro_current_waypoint(cum, n_wp, s[i]);
   if (wp < 0) { alive[i] = 0; return; }              // lap finished
@@ -545,7 +543,7 @@ __global__ __launch_bounds__(256) void mpmpc_advance_kernel(int B, int N, double
   const int n = 5 * N + 3;
   const int st = status[i];
   if (ro_usable(st)) ro_plan_entry(N, L, z + (long)i * n, cc + (long)i * 2 * N, k);
-  if (k == 0 && !ro_drive(N, L, Ts, st, cc + (long)i * 2 * N, counter + i, x0 + 3 * i, kappa[wp_id[i] + (route ? route[2 * i] : 0)], pose + 3 * i,
+  if (k == 0 && !ro_drive(N, L, Ts, st, cc + (long)i * 2 * N, counter + i, x0 + 3 * i, kappa[wp_id[i] + (int)route_view(route, i, 0, 0).first], pose + 3 * i,
                           s + i, u_last + 2 * i))
     alive[i] = -1;
 }
@@ -571,28 +569,9 @@ __global__ __launch_bounds__(256) void mpmpc_record_write_kernel(int B, RoRecSrc
   ro_record_finish(src, rec, lay, i, e);
 }
 
-// the footprint audit inside a rollout (K0f; defined in mpmpc_footprint.hpp, which follows this header): the accumulators
-// start over, may steps of B cars be audited, K0f of step k on the slot's stream
+// the footprint audit (mpmpc_footprint.hpp, which follows this header): its accumulators start over with a rollout
 static int aud_reset(mpmpc_handle h, int B);
-static int aud_check_step(mpmpc_handle h, int B);
-static void aud_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, bool per_car);
-// perception inside a rollout (K0s; defined in mpmpc_perception.hpp, behind the lidar): may steps of B cars perceive - and do
-// they (perception on and a per-car setting in force) -, K0s of step k on the slot's stream
-static int per_check_step(mpmpc_handle h, int B, bool per_car, bool* active);
-static void per_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k);
-static const int* per_plan_discs(mpmpc_handle h);      // the perceived lists
-static const int* per_plan_whdr(mpmpc_handle h);
-// lookahead inside a rollout (K0h; defined in mpmpc_lookahead.hpp, behind this header): may steps of B cars run - and do they
-// look ahead (the setting on and `movers` > 0; the tables are laid out then) -, K0h of step k on the slot's stream
-// `traffic`: traffic is set for the step's cars; *ahead_traffic: the step also anticipates traffic (the flag of
-// mpmpc_rollout_set_lookahead_traffic on; it then looks ahead with or without movers, and the tracks and tables of
-// traffic_lookahead_core.hpp are laid out)
-static int look_check_step(mpmpc_handle h, int B, int movers, bool traffic, bool* active, bool* ahead_traffic);
-static void look_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, int movers, const MapView& mv, const PathGeom& pg,
-                              const MoverPath& mp, const int* route);
-// ... K0ht of the step behind K0h, K3t of the step behind K3b
-static void tlk_enqueue_horizon(mpmpc_handle h, Slot& sl, int B, const MapView& mv);
-static void tlk_enqueue_tracks(mpmpc_handle h, Slot& sl, int B, const MapView& mv, const int* route);
+// refusals of the setters below; mpmpc_lookahead.hpp raises the first two as well
 static const char* const LOOK_OVER_BUDGET = "the lookahead's disc table (movers x N x 12 bytes) would exceed 256 MiB (LOOK_TABLE_BUDGET)";
 static const char* const TLK_OVER_BUDGET = "the traffic lookahead's disc table (B x slots x N x 12 bytes) would exceed 256 MiB (LOOK_TABLE_BUDGET)";
 static const char* const WALLS_OTHER_B = "walls are set for another number of cars (mpmpc_rollout_set_walls)";
@@ -836,155 +815,6 @@ int mpmpc_rollout_set_counters(mpmpc_handle h, int32_t B, const int32_t* counter
   HIP_TRY(hipSetDevice(h->cfg.device));
   HIP_TRY(hipMemcpyAsync(h->ro.counter, counter, sizeof(int) * B, hipMemcpyHostToDevice, h->last().stream));
   HIP_TRY(hipStreamSynchronize(h->last().stream));
-  return MPMPC_OK;
-}
-
-int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
-  if (int rc = enter(h)) return rc;
-  Slot& sl = h->last();
-  if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
-                              "call mpmpc_rollout_init again (or use a second handle for single solves)")) return rc;
-  if (n_steps < 0) return fail(MPMPC_E_ARG, "n_steps must be >= 0");
-  const bool per_car = h->obs.world_B() > 0;
-  const bool discs = h->obs.obst_B > 0, walls = h->obs.wl_B > 0;
-  if (per_car) {
-    if (h->obs.world_B() != B || (walls && h->obs.wl_B != B))
-      return fail(MPMPC_E_STATE, "the per-car obstacles were set for another number of cars");
-    if ((h->obs.st_B > 0 && h->obs.obst_gen != h->cor.base_gen) || (h->obs.mv_B > 0 && h->obs.mv_gen != h->cor.base_gen) ||
-        (h->obs.tr_B > 0 && h->obs.tr_gen != h->cor.base_gen) || (walls && h->obs.wl_gen != h->cor.base_gen) ||
-        h->cor.built_gen != h->cor.base_gen)
-      return fail(MPMPC_E_STATE, "map, path or geometry changed since mpmpc_rollout_set_obstacles / mpmpc_build_corridor");
-  }
-  const bool recording = h->rec.cap > 0;
-  if (recording) {
-    if (h->rec.B != B) return fail(MPMPC_E_STATE, "mpmpc_rollout_record was set up for another number of cars");
-    if (h->rec.count + h->rec.records_of(n_steps) > h->rec.cap)
-      return fail(MPMPC_E_STATE, "the trace is full: " + std::to_string(h->rec.count) + " of " + std::to_string(h->rec.cap) +
-                                     " records held, this call would add " + std::to_string(h->rec.records_of(n_steps)));
-  }
-  const bool plant = h->pl.B > 0;
-  if (plant && h->pl.B != B) return fail(MPMPC_E_STATE, "the plant was set for another number of cars (mpmpc_rollout_set_plant)");
-  if (int rc = aud_check_step(h, B)) return rc;
-  const bool auditing = h->aud.mode != FP_MODE_OFF;
-  HIP_TRY(hipSetDevice(h->cfg.device));
-  bool perceiving = false;
-  if (h->per.n_beams > 0) {
-    if (int rc = per_check_step(h, B, per_car, &perceiving)) return rc;
-  }
-  // the world K0c plans in: the true lists, or - perceiving - the lists K0s writes in front of it
-  const int* plan_discs = perceiving ? per_plan_discs(h) : h->obs.obst_discs.get();
-  WallView plan_walls = h->obs.wall_view();
-  if (perceiving && walls) plan_walls.hdr = per_plan_whdr(h);
-  const int N = h->cfg.N;
-  const size_t car_lds = sizeof(double) * COR_WPC * N + sizeof(int) * (2 * COR_MAXSEG + 3) * N + sizeof(int) * 3 * COR_MAX_DISCS +
-                         (sizeof(int) + 1) * COR_CELL_CAP + (walls ? sizeof(int) * WALL_HDR * COR_MAX_WALLS : 0);
-  const MapView mv = h->cor.map_view();
-  const PathGeom pg = h->cor.path_geom(h->tab, h->cfg.circular);
-  h->io.have_rows = per_car;     // K1 / K2 read the per-instance rows K0c writes (else: the table)
-  const int movers = discs && h->obs.mv_B > 0 ? h->obs.mv_n : 0;
-  const MoverPath mp{h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gtrig, h->tab.n_wp, COR_TRIG, h->cfg.circular ? 1 : 0};
-  const double* mv_p = (const double*)h->obs.mv_block.get();
-  const int* mv_i = (const int*)(mv_p + (size_t)MOV_PARAMS * movers);
-  const bool traffic = discs && h->obs.tr_B > 0;
-  const int* tr_i = h->obs.tr_block;      // dense group, radius, members [B] each, then the groups' offsets
-  if (int rc = check_car_routes(h, B)) return rc;
-  const int* route = h->tab.path_tables().route;      // route fleets: the cars' {first row, length} headers (null: one path)
-  bool looking = false, ahead_traffic = false;
-  if (h->look.max_lead > 0) {
-    if (int rc = look_check_step(h, B, movers, traffic, &looking, &ahead_traffic)) return rc;
-  }
-  const LookView lk{h->look.car.get(), h->look.tab.get()};
-  const LookTrafficView lkt{h->look.car.get(), h->look.tab.get(), h->tlk.tz.get(), h->obs.tr_S};
-  if (ahead_traffic && !h->tlk.tracks_live && n_steps > 0)      // no track is the last step's: every car is a frozen disc for one step
-    HIP_TRY(hipMemsetAsync(h->tlk.valid, 0, sizeof(int) * (size_t)h->cfg.max_batch, sl.stream));
-  for (int t = 0; t < n_steps; ++t) {
-    char* rec = recording && h->rec.ro_steps % h->rec.stride == 0 ? h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)h->rec.count : nullptr;
-    if (rec)
-      hipLaunchKernelGGL(mpmpc_record_snapshot_kernel, dim3((unsigned)(((long)B * RO_REC_BEGIN_ENTRIES + 255) / 256)), dim3(256), 0,
-                         sl.stream, B, h->ro.s, h->ro.pose, h->ro.alive, h->rec.ain, rec, h->rec.lay);
-    if (ahead_traffic)      // K0t with the slots' occupants (K0ht reads them)
-      hipLaunchKernelGGL(mpmpc_traffic_kernel<true>, dim3(B), dim3(64), 0, sl.stream, B, h->obs.tr_S, h->obs.tr_range, mv, h->ro.pose.get(),
-                         h->ro.alive.get(), tr_i, tr_i + B, tr_i + 2 * (size_t)B, tr_i + 3 * (size_t)B, h->obs.obst_off.get(),
-                         h->obs.obst_discs.get(), h->tlk.who.get());
-    else if (traffic)
-      hipLaunchKernelGGL(mpmpc_traffic_kernel<false>, dim3(B), dim3(64), 0, sl.stream, B, h->obs.tr_S, h->obs.tr_range, mv, h->ro.pose,
-                         h->ro.alive, tr_i, tr_i + B, tr_i + 2 * (size_t)B, tr_i + 3 * (size_t)B, h->obs.obst_off, h->obs.obst_discs, LookNone{});
-    if (perceiving) {      // K0m and K0s in front of K3a: K0s reads alive as the step finds it, K0m reads nothing K3a writes
-      if (movers > 0)
-        hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
-                           h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs.get(),
-                           h->obs.obst_off.get(), B, route);
-      per_enqueue_step(h, sl, B, h->rec.ro_steps);
-    }
-    if (plant) plant_enqueue_measure(h, sl, B, h->rec.ro_steps);      // K3n: K3a localises on the measured poses
-    hipLaunchKernelGGL(mpmpc_localise_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.N, h->cfg.circular ? 1 : 0,
-                       h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, h->ro.s, plant ? h->pl.meas.get() : h->ro.pose.get(), h->ro.alive, h->io.wp_id,
-                       h->io.x0, h->ro.shift, route);
-    if (movers > 0 && !perceiving)
-      hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((movers + 255) / 256), dim3(256), 0, sl.stream, movers, h->rec.ro_steps,
-                         h->obs.mv_step0, mv, mp, mv_i, mv_i + movers, mv_p, mv_i + 2 * (size_t)movers, h->obs.obst_discs.get(),
-                           h->obs.obst_off.get(), B, route);
-    if (auditing) aud_enqueue_step(h, sl, B, h->rec.ro_steps, per_car);      // K0f: pose k in world k
-    if (ahead_traffic) {      // K0h, K0ht, then K0c's traffic instantiation on both tables
-      look_enqueue_step(h, sl, B, h->rec.ro_steps, movers, mv, pg, mp, route);
-      tlk_enqueue_horizon(h, sl, B, mv);
-      if (walls)
-        hipLaunchKernelGGL((mpmpc_car_corridor_kernel<true, true, true>), dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
-                           h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
-                           h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(), h->obs.ro_flag.get(), h->io.lb, h->io.ub,
-                           plan_walls, route, lkt);
-      else
-        hipLaunchKernelGGL((mpmpc_car_corridor_kernel<false, true, true>), dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
-                           h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
-                           h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(), h->obs.ro_flag.get(), h->io.lb, h->io.ub,
-                           WallView{nullptr, nullptr, nullptr}, route, lkt);
-    } else if (looking) {      // K0h, then K0c<., true> on its table
-      look_enqueue_step(h, sl, B, h->rec.ro_steps, movers, mv, pg, mp, route);
-      if (walls)
-        hipLaunchKernelGGL((mpmpc_car_corridor_kernel<true, true>), dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
-                           h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
-                           h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(), h->obs.ro_flag.get(), h->io.lb, h->io.ub,
-                           plan_walls, route, lk);
-      else
-        hipLaunchKernelGGL((mpmpc_car_corridor_kernel<false, true>), dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
-                           h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
-                           h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(), h->obs.ro_flag.get(), h->io.lb, h->io.ub,
-                           WallView{nullptr, nullptr, nullptr}, route, lk);
-    } else if (walls)
-      hipLaunchKernelGGL(mpmpc_car_corridor_kernel<true>, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
-                         h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells, h->cor.line_box,
-                         discs ? h->obs.obst_off.get() : nullptr, plan_discs, h->io.wp_id, h->ro.alive.get(),
-                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, plan_walls, route, LookNone{});
-    else if (per_car)
-      hipLaunchKernelGGL(mpmpc_car_corridor_kernel<false>, dim3(B), dim3(64), car_lds, sl.stream, mv, pg, N, h->cor.built_min_width,
-                         h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells,
-                         h->cor.line_box, h->obs.obst_off.get(), plan_discs, h->io.wp_id, h->ro.alive.get(),
-                         h->obs.ro_flag.get(), h->io.lb, h->io.ub, WallView{nullptr, nullptr, nullptr}, route, LookNone{});
-    if (int rc = launch_solve(h, sl, B, true, false)) return rc;  // (the plant step reads z and the status only)
-    if (plant)      // K3p: the plant in place of ro_drive
-      hipLaunchKernelGGL(mpmpc_advance_plant_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase,
-                         h->ro.Ts, h->tab.kappa.get(), h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter.get(), h->ro.alive.get(),
-                         h->ro.pose.get(), h->ro.s.get(), h->ro.u.get(), route, plant_view(h, h->rec.ro_steps));
-    else
-      hipLaunchKernelGGL(mpmpc_advance_kernel, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro.Ts,
-                         h->tab.kappa, h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter, h->ro.alive, h->ro.pose, h->ro.s, h->ro.u, route);
-    if (ahead_traffic) tlk_enqueue_tracks(h, sl, B, mv, route);      // K3t: the plans of this step, for the next one's K0ht
-    if (rec) {
-      const RoRecSrc src{h->ro.alive, h->rec.ain, h->io.wp_id, sl.status, h->ro.counter, h->io.x0, h->ro.u, h->io.cc, sl.z,
-                         h->cor.gx, h->cor.gy, h->cor.gtrig, per_car ? h->io.ub : h->tab.ub_tab, per_car ? h->io.lb : h->tab.lb_tab,
-                         per_car ? (long long)N : (long long)h->tab.n_cols, per_car ? 1 : 0, COR_TRIG, N, h->tab.n_wp, h->cfg.circular ? 1 : 0, route};
-      hipLaunchKernelGGL(mpmpc_record_write_kernel, dim3((unsigned)(((long)B * h->rec.lay.entries + 255) / 256)), dim3(256), 0,
-                         sl.stream, B, src, rec, h->rec.lay);
-      ++h->rec.count;
-    }
-    ++h->rec.ro_steps;
-  }
-  HIP_TRY(hipGetLastError());
-  if (n_steps > 0) h->obs.car_rows = h->obs.discs_live = per_car;
-  if (n_steps > 0 && perceiving) h->per.B = B;
-  if (n_steps > 0 && plant) h->pl.ran = true;
-  if (n_steps > 0) { h->look.ran_B = looking ? B : 0; h->look.ran_n = looking ? movers : 0; }
-  if (n_steps > 0) { h->tlk.ran_B = ahead_traffic ? B : 0; h->tlk.ran_S = ahead_traffic ? h->obs.tr_S : 0; h->tlk.tracks_live = ahead_traffic; }
   return MPMPC_OK;
 }
 

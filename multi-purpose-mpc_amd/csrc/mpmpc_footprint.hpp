@@ -1,5 +1,5 @@
 // The footprint audit of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind mpmpc_lidar.hpp):
-// the kernel K0f, its launch inside mpmpc_rollout_step (aud_enqueue_step, declared in mpmpc_closed_loop.hpp) and the entry
+// the kernel K0f, its launch inside mpmpc_rollout_step (aud_enqueue_step, called from mpmpc_rollout_step.hpp) and the entry
 // points - mpmpc_footprint_audit (no handle, like mpmpc_lidar_scan), mpmpc_rollout_set_audit and mpmpc_rollout_audit (the
 // accumulators of a handle's running rollout).  The law: footprint_core.hpp.
 #pragma once

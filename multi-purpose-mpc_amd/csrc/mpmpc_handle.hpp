@@ -56,6 +56,18 @@ struct CorState {
   bool built(const TabState& tab) const { return built_gen == base_gen && built_gen != 0 && tab.n_cols > 0 && line_cells; }
 };
 
+// what K0m / K0h take of the movers' block and K0t of the traffic block (host-side decodings of ObsState's two blocks)
+struct MoverView {
+  int n;                            // movers of the fleet (0: none in force)
+  long long step0;
+  const double* prm;                // [MOV_PARAMS][n]
+  const int *kind, *radius, *dst;   // [n] each; dst: the mover's slot in the cars' disc lists
+};
+struct TrafficView {
+  int S, range;                     // slots per car, range [cells]
+  const int *dense, *radius, *members, *goff;      // [tr_B] each, then the groups' offsets
+};
+
 // per-car discs, movers and traffic
 struct ObsState {
   Buf<int> obst_off, obst_discs, ro_flag;   // CSR lists on the device, per-car row verdicts
@@ -86,6 +98,17 @@ struct ObsState {
   // B of the per-car worlds in force (0: none - the shared table), and what the kernels take of the walls
   int world_B() const { return obst_B > 0 ? obst_B : wl_B; }
   WallView wall_view() const { return wl_B > 0 ? WallView{wl_off, wl_hdr, wl_tab} : WallView{nullptr, nullptr, nullptr}; }
+  MoverView mover_view() const {
+    const int n = obst_B > 0 && mv_B > 0 ? mv_n : 0;
+    const double* p = (const double*)mv_block.get();
+    const int* i = (const int*)(p + (size_t)MOV_PARAMS * n);
+    return MoverView{n, mv_step0, p, i, i + n, i + 2 * (size_t)n};
+  }
+  TrafficView traffic_view() const {
+    const int* t = tr_block.get();
+    const size_t nb = (size_t)tr_B;
+    return TrafficView{tr_S, tr_range, t, t + nb, t + 2 * nb, t + 3 * nb};
+  }
 };
 
 // closed-loop rollout state

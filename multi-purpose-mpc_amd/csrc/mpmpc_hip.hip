@@ -22,8 +22,11 @@
 //   K2rb2                       mpmpc_reduced_pair_block_kernel, with mpmpc_reduced_tail_pair_block_kernel and
 //                               mpmpc_reduced_t_pair_block_kernel - horizons 128 .. 255: two stages per lane on a workgroup of two
 //   The twelve solve kernels (K2 ...) are the same steps around their solvers: "the steps of a solve kernel" below.
-//   K0 / K3 / K4                corridor tables from the map and the closed-loop rollout (mpmpc_closed_loop.hpp, with their
-//                               entry points), the speed profile (mpmpc_speed_profile.hpp), the lidar K0l (mpmpc_lidar.hpp), the
+//   K0 / K3 / K4                corridor tables from the map and the closed-loop rollout (mpmpc_closed_loop.hpp: the kernels, the
+//                               setters and getters; mpmpc_rollout_step.hpp, behind the features it drives: the step itself - its
+//                               plan, one enqueue function per kernel, the loop), the plant K3n / K3p (mpmpc_plant.hpp), the
+//                               lookaheads' entry points (mpmpc_lookahead.hpp), perception K0s (mpmpc_perception.hpp),
+//                               the speed profile (mpmpc_speed_profile.hpp), the lidar K0l (mpmpc_lidar.hpp), the
 //                               footprint audit K0f (mpmpc_footprint.hpp), the walls K0w and K-world (mpmpc_walls.hpp), the
 //                               reference paths' static width K0p (mpmpc_path.hpp), the pose projection and the re-route of a
 //                               running rollout (mpmpc_project.hpp).
@@ -988,6 +991,7 @@ static int check_wp_ids(mpmpc_handle h, int B, const int32_t* wp_id) {
 #include "mpmpc_path.hpp"
 #include "mpmpc_perception.hpp"
 #include "mpmpc_footprint.hpp"
+#include "mpmpc_rollout_step.hpp"      // (behind every feature a step drives)
 #include "mpmpc_project.hpp"
 
 extern "C" {

@@ -1,6 +1,6 @@
 // Lookahead of the rollout, part of the one translation unit mpmpc_hip.hip (included behind mpmpc_closed_loop.hpp, which holds
 // K0h and the LEAD instantiations of K0c): the setting, the layout of K0h's tables for the movers in force, K0h's launch and
-// the getter.  The law: lookahead_core.hpp.  The state: the sub-state look of the handle (mpmpc_handle.hpp).
+// the getter (the step loop that calls look_* / tlk_*: mpmpc_rollout_step.hpp).  The law: lookahead_core.hpp.  The state: the sub-state look of the handle (mpmpc_handle.hpp).
 // Lookahead for traffic (the law: traffic_lookahead_core.hpp; the state: the sub-state tlk): the flag, the memory of the plan
 // tracks and of K0t's / K0ht's tables, the launches of K0ht and K3t and the two getters.
 #pragma once
@@ -52,13 +52,12 @@ static int look_check_step(mpmpc_handle h, int B, int movers, bool traffic, bool
 }
 
 // K0h of rollout step k on the slot's stream (behind K3a, in front of K0c)
-static void look_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, int movers, const MapView& mv, const PathGeom& pg,
-                              const MoverPath& mp, const int* route) {
-  const double* mv_p = (const double*)h->obs.mv_block.get();
-  const int* mv_i = (const int*)(mv_p + (size_t)MOV_PARAMS * movers);
-  hipLaunchKernelGGL(mpmpc_mover_horizon_kernel, dim3(B), dim3(64), 0, sl.stream, h->cfg.N, k, h->obs.mv_step0, h->ro.Ts, h->look.max_lead, mv,
-                     pg, mp, h->look.seg.get(), h->io.wp_id, movers, mv_i, mv_i + movers, mv_p, h->look.car.get(), h->look.lead.get(),
-                     h->look.tab.get(), route);
+static void look_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, const MapView& mv, const PathGeom& pg, const MoverPath& mp,
+                              const int* route) {
+  const MoverView m = h->obs.mover_view();
+  hipLaunchKernelGGL(mpmpc_mover_horizon_kernel, dim3(B), dim3(64), 0, sl.stream, h->cfg.N, k, m.step0, h->ro.Ts, h->look.max_lead, mv, pg, mp,
+                     h->look.seg.get(), h->io.wp_id, m.n, m.kind, m.radius, m.prm, h->look.car.get(), h->look.lead.get(), h->look.tab.get(),
+                     route);
 }
 
 // K0ht of a rollout step on the slot's stream (behind K0h, in front of K0c): the true lists, K0t's who, K0h's leads, the tracks

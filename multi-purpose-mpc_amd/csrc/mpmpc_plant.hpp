@@ -1,5 +1,5 @@
-// Plant models of the rollout, part of the one translation unit mpmpc_hip.hip (included in front of mpmpc_closed_loop.hpp, whose
-// step loop launches the two kernels): K3n (the measured poses K3a localises on), K3p (mpmpc_advance_kernel with the plant in
+// Plant models of the rollout, part of the one translation unit mpmpc_hip.hip (included in front of mpmpc_closed_loop.hpp; the
+// step loop of mpmpc_rollout_step.hpp launches the two kernels): K3n (the measured poses K3a localises on), K3p (mpmpc_advance_kernel with the plant in
 // place of ro_drive), the noise table without a handle, and the entry points mpmpc_rollout_set_plant / mpmpc_rollout_plant /
 // mpmpc_plant_noise.  The law: plant_core.hpp.  The state: the sub-state pl of the handle (mpmpc_handle.hpp).
 #pragma once
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void mpmpc_advance_plant_kernel(int B, int N, 
   const int st = status[i];
   if (ro_usable(st)) ro_plan_entry(N, L, z + (long)i * n, cc + (long)i * 2 * N, k);
   if (k != 0) return;
-  const long w = wp_id[i] + (route ? route[2 * i] : 0);
+  const long w = wp_id[i] + (int)route_view(route, i, 0, 0).first;      // (the global row; the route's length is not needed)
   double n4[4];
   pl_noise_drive(pv.seed, (uint32_t)(pv.car0 + i), pv.j, n4);
   const double px = pose[3L * i], py = pose[3L * i + 1];

@@ -46,6 +46,12 @@ struct MoverPath {
   const double* trig;             // [n_wp x trig_ld]: cos(psi), sin(psi), ...
   int n_wp, trig_ld, circular;
 };
+// route fleets: the path moved onto a car's view (corridor_core.hpp) - an along-the-path mover follows its car's route
+MPMPC_HD MoverPath route_path(MoverPath p, RouteView v) {
+  p.cum += v.first; p.x += v.first; p.y += v.first; p.trig += v.first * p.trig_ld;
+  v.lengths(p.n_wp, p.circular);
+  return p;
+}
 
 MPMPC_HOST_DEVICE inline bool mov_finite(double v) { return std::fabs(v) <= 1.7976931348623157e308; }
 

@@ -8,9 +8,7 @@
 #pragma once
 #include <cmath>
 
-#ifndef MPMPC_HD
-#define MPMPC_HD inline
-#endif
+#include "corridor_core.hpp"      // RouteView
 
 namespace mpmpc {
 
@@ -183,7 +181,9 @@ MPMPC_HD void ro_record_finish(const RoRecSrc& r, char* rec, const RoTraceLayout
       const int k = (is_y ? e - (N - 2) : e) + 2;      // stage 2 .. N-1
       double v = nan;
       if (ro_rec_pred(a_in, a, r.status[i])) {
-        const int nn = r.route ? r.route[2 * i + 1] : 0;      // the car's route: wrap / clamp inside it, its first row added last
+        // (the car's route: wrap / clamp inside it, its first row added last.  Written out, not route_view: the kernel's
+        // instructions change with every form of it - docs/HISTORY.md)
+        const int nn = r.route ? r.route[2 * i + 1] : 0;
         const int n = r.route ? (nn > 0 ? nn : -nn) : r.n_wp;
         const bool circular = r.route ? nn > 0 : r.circular != 0;
         int w = r.wp_id[i] + k;
@@ -202,7 +202,7 @@ MPMPC_HD void ro_record_finish(const RoRecSrc& r, char* rec, const RoTraceLayout
   if (l.ub >= 0 && e < 2 * N) {
     const bool is_lb = e >= N;
     const int k = is_lb ? e - N : e;
-    const long long row = r.per_car ? i : (solved ? r.wp_id[i] + (r.route ? r.route[2 * i] : 0) : 0);
+    const long long row = r.per_car ? i : (solved ? r.wp_id[i] + (int)route_view(r.route, i, r.n_wp, r.circular).first : 0);
     const double* src = is_lb ? r.row_lb : r.row_ub;
     ((double*)(rec + (is_lb ? l.lb : l.ub)))[(long long)N * i + k] = solved ? src[row * r.row_ld + k] : nan;
   }

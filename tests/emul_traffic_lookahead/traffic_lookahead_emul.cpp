@@ -11,19 +11,7 @@
 
 using namespace mpmpc;
 
-namespace {
-
-// the car's view of the path: route == NULL - the one path; else route[2 b] = first global row, route[2 b + 1] = the route's
-// length, negated when it is open (the device's car headers)
-struct View {
-  long f;
-  int n, circ;
-  View(const int32_t* route, int b, int n_wp, int circular)
-      : f(route ? route[2 * b] : 0), n(route ? (route[2 * b + 1] > 0 ? route[2 * b + 1] : -route[2 * b + 1]) : n_wp),
-        circ(route ? (route[2 * b + 1] > 0 ? 1 : 0) : circular) {}
-};
-
-}  // namespace
+// (the car's view of the path - route == NULL: the one path - is the kernels' own: route_view, corridor_core.hpp)
 
 extern "C" {
 
@@ -38,11 +26,11 @@ void tlk_emu_tracks(int B, int N, const double* z, const int32_t* wp_id, const i
   std::vector<double> trig((size_t)n_wp * COR_TRIG);
   for (int i = 0; i < n_wp; ++i) cor_trig_row(psi[i], trig.data() + (size_t)i * COR_TRIG);
   for (int n = 0; n < B; ++n) {
-    const View v(route, n, n_wp, circular);
+    const RouteView v = route_view(route, n, n_wp, circular);
     const double* zn = z + (size_t)(5 * N + 3) * n;
     valid[n] = tlk_valid(alive[n], status[n]) ? 1 : 0;
     for (int j = 0; j <= N; ++j) {
-      const long long w = tlk_stage_row(wp_id[n], j, v.n, v.circ != 0, v.f);
+      const long long w = tlk_stage_row(wp_id[n], j, v.n(), v.circular() != 0, v.first);
       tlk_stage_cell(m, x[w], y[w], trig[w * COR_TRIG], trig[w * COR_TRIG + 1], zn[3 * j], cells + ((size_t)n * (N + 1) + j) * 2);
     }
     tlk_times(N, zn, tm + (size_t)n * (N + 1));
@@ -115,19 +103,19 @@ int tlk_emu_rows(int h, int w, const int8_t* grid, double ox, double oy, double 
   std::vector<double> col_o((size_t)N * COR_WPC);
   std::vector<int> col_seg((size_t)N * 2 * COR_MAXSEG), col_cnt(N);
   for (int b = 0; b < n_start; ++b) {
-    const View v(route, b, n_wp, circular);
-    const PathGeom g{x + v.f, y + v.f, psi + v.f, ds_next + v.f, v.n, v.circ, trig.data() + v.f * COR_TRIG};
-    double* const r_segs = segs.data() + v.f * 4 * COR_MAXSEG;
-    double* const r_wpc = wpc.data() + v.f * COR_WPC;
-    int* const r_nseg = nseg.data() + v.f;
-    int* const r_cells = cells.data() + v.f * COR_CELL_CAP;
-    int* const r_box = box.data() + v.f * COR_LINE_BOX;
-    if (!built[v.f]) {                         // K0a on the car's route
-      built[v.f] = 1;
-      for (int i = 0; i < v.n; ++i) {
+    const RouteView v = route_view(route, b, n_wp, circular);
+    const PathGeom g = route_geom(PathGeom{x, y, psi, ds_next, n_wp, circular, trig.data()}, v);
+    double* const r_segs = segs.data() + v.first * 4 * COR_MAXSEG;
+    double* const r_wpc = wpc.data() + v.first * COR_WPC;
+    int* const r_nseg = nseg.data() + v.first;
+    int* const r_cells = cells.data() + v.first * COR_CELL_CAP;
+    int* const r_box = box.data() + v.first * COR_LINE_BOX;
+    if (!built[v.first]) {                         // K0a on the car's route
+      built[v.first] = 1;
+      for (int i = 0; i < v.n(); ++i) {
         int ux, uy, lx, ly;
-        cor_w2m(m, bub[2 * (v.f + i)], bub[2 * (v.f + i) + 1], ux, uy);
-        cor_w2m(m, blb[2 * (v.f + i)], blb[2 * (v.f + i) + 1], lx, ly);
+        cor_w2m(m, bub[2 * (v.first + i)], bub[2 * (v.first + i) + 1], ux, uy);
+        cor_w2m(m, blb[2 * (v.first + i)], blb[2 * (v.first + i) + 1], lx, ly);
         int* c = r_cells + (size_t)i * COR_CELL_CAP;
         const int n = cor_line_cells(ux, uy, lx, ly, c, COR_CELL_CAP);
         if (n > COR_CELL_CAP) return 1;
@@ -138,7 +126,7 @@ int tlk_emu_rows(int h, int w, const int8_t* grid, double ox, double oy, double 
         r_nseg[i] = cnt;
         cor_line_box(c, n, (ux + 1) | ((uy + 1) << 16), (lx + 1) | ((ly + 1) << 16), r_box + (size_t)i * COR_LINE_BOX);
       }
-      for (int i = 0; i < v.n; ++i)
+      for (int i = 0; i < v.n(); ++i)
         if (r_nseg[i] <= 1) cor_forced(g, r_segs, r_nseg, i, sm, r_wpc + (size_t)i * COR_WPC);
     }
     const int d0 = off ? off[b] : 0, nd = off ? off[b + 1] - d0 : 0;
