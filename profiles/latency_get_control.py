@@ -9,11 +9,11 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for d in ("multi-purpose-mpc_amd", "tests", "oracle"):
     sys.path.insert(0, os.path.join(ROOT, d))
-import test_host_mpc as H   # noqa: E402
+import mpmpc_testlib as T   # noqa: E402
 
 for mode in ("host", "device"):
-    m, rp, car = H.build_world()
-    mpc = H.make_mpc(car, 30, corridor=mode)
+    m, rp, car = T.build_world()
+    mpc = T.make_mpc(car, 30, corridor=mode)
     for _ in range(5):
         car.drive(mpc.get_control())
     pr = cProfile.Profile()

@@ -1,6 +1,5 @@
 // CPU twin of K0f (mpmpc_footprint_kernel): the same footprint_core.hpp code, one car and one cell after the other in plain
-// row order, no early exit, the host's libm for cos and sin.  Built by tests/test_footprint.py with the flags of
-// tests/test_lidar.py's twin.
+// row order, no early exit, the host's libm for cos and sin.  Built by tests/emul/Makefile (`make footprint`), loaded by tests/twins.py.
 #include <cmath>
 #include <cstdint>
 

@@ -1,5 +1,5 @@
 // CPU twin of K0l (mpmpc_lidar_scan_kernel): the same lidar_core.hpp code, one car and one cell after the other, the
-// host's libm for the atan2 of a cell's interval.  Built by tests/test_lidar.py with the flags of tests/emul/Makefile.
+// host's libm for the atan2 of a cell's interval.  Built by tests/emul/Makefile (`make lidar`), loaded by tests/twins.py.
 #include <cmath>
 #include <cstdint>
 #include <vector>

@@ -1,5 +1,5 @@
 // CPU twin of K0m (mpmpc_obstacle_move_kernel): the same obstacle_motion_core.hpp code, one mover after the other.
-// Built by tests/test_movers.py with the flags of tests/emul/Makefile.
+// Built by tests/emul/Makefile (`make movers`), loaded by tests/twins.py.
 #include <cstdint>
 #include <vector>
 

@@ -1,6 +1,6 @@
 // CPU twin of mpmpc_path_build: the host part is the library's own (path_core.hpp: path_check_build, path_rows), the
 // width is the per-line code of K0p (path_line_min, path_side_reduce) run in a loop, the walls' table the host's
-// wall_raster.  Built by tests/test_path_build.py with the flags of tests/emul/Makefile.
+// wall_raster.  Built by tests/emul/Makefile (`make path`), loaded by tests/twins.py.
 #include <cmath>
 #include <cstdint>
 #include <vector>

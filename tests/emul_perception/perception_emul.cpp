@@ -1,6 +1,6 @@
 // CPU twin of K0s (mpmpc_perception_kernel): the same perception_core.hpp code (and lidar_core / wall_core beneath it), one car,
 // one slot and one cell after the other, the host's libm for the atan2 of a cell's interval.  No sift, no queue, no enclosure:
-// every cell of the window is asked directly.  Built by tests/test_perception.py with the flags of tests/test_lidar.py's twin.
+// every cell of the window is asked directly.  Built by tests/emul/Makefile (`make perception`), loaded by tests/twins.py.
 #include <cmath>
 #include <cstdint>
 #include <vector>

@@ -1,5 +1,5 @@
 // CPU twin of K3n / K3p (mpmpc_plant.hpp): the same plant_core.hpp code, one car after the other.
-// Built by tests/test_plant.py with the flags of tests/emul/Makefile.
+// Built by tests/emul/Makefile (`make plant`), loaded by tests/twins.py.
 #include <cstdint>
 
 #include "plant_core.hpp"

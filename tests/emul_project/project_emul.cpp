@@ -1,7 +1,7 @@
 // CPU twin of the pose projection and of the re-route (tests/test_reroute.py): the library's own law (project_core.hpp) on 64
 // emulated lanes - every lane strides over the route's waypoints, then the six-step xor butterfly of mpmpc_project_kernel - and
-// the handle's route state (route_state.hpp) for the checks and the bookkeeping of mpmpc_rollout_reroute.  Built by the test's
-// fixture with the flags of tests/emul/Makefile.
+// the handle's route state (route_state.hpp) for the checks and the bookkeeping of mpmpc_rollout_reroute.  Built by
+// tests/emul/Makefile (`make project`), loaded by tests/twins.py.
 #include <cstdint>
 #include <vector>
 

@@ -1,7 +1,7 @@
 // CPU twin of the route view (tests/test_routes.py): the library's own gather_stage / assemble_fields (mpmpc_assemble.hpp) on
 // the emulated lanes - with a route header per instance on the concatenated tables, or without one on a route's own tables - and
-// the corridor's horizon walk (corridor_core.hpp) through a route's PathGeom view.  Built by the test's fixture with the flags of
-// tests/emul/Makefile.
+// the corridor's horizon walk (corridor_core.hpp) through a route's PathGeom view.  Built by tests/emul/Makefile
+// (`make routes`), loaded by tests/twins.py.
 #include <cstdint>
 #include <vector>
 

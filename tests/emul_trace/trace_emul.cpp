@@ -1,6 +1,6 @@
 // CPU twin of the rollout's recorder (mpmpc_record_snapshot_kernel / mpmpc_record_write_kernel): the same
 // rollout_core.hpp code, one car and one entry after the other, into a record laid out by ro_trace_layout.
-// Built by tests/test_rollout_trace.py with the flags of tests/emul/Makefile.
+// Built by tests/emul/Makefile (`make trace`), loaded by tests/twins.py.
 #include <cmath>
 #include <cstdint>
 #include <cstring>

@@ -1,5 +1,5 @@
 // CPU twin of K0t (mpmpc_traffic_kernel): the same traffic_core.hpp code, one car after the other.
-// Built by tests/test_traffic.py with the flags of tests/emul/Makefile.
+// Built by tests/emul/Makefile (`make traffic`), loaded by tests/twins.py.
 #include <cstdint>
 #include <vector>
 

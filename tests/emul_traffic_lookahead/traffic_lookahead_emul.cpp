@@ -1,13 +1,14 @@
 // CPU twin of the traffic lookahead kernels: K3t (mpmpc_plan_track_kernel), K0t with its occupants (mpmpc_traffic_kernel<true>),
 // K0ht (mpmpc_traffic_horizon_kernel) and K0c<WALLS, true, true> (mpmpc_car_corridor_kernel) - the same
 // traffic_lookahead_core.hpp code (and lookahead_core / traffic_core / corridor_core / wall_core beneath it), one car, one
-// stage, one column after the other.  Built by tests/test_traffic_lookahead.py with the flags of tests/test_movers.py's twins.
+// stage, one column after the other; K0c's rows: car_rows.hpp.  Built by tests/emul/Makefile (`make traffic_lookahead`), loaded by
+// tests/twins.py.
 #include <cmath>
 #include <cstdint>
 #include <vector>
 
+#include "../emul_car/car_rows.hpp"
 #include "traffic_lookahead_core.hpp"
-#include "wall_core.hpp"
 
 using namespace mpmpc;
 
@@ -89,46 +90,12 @@ int tlk_emu_rows(int h, int w, const int8_t* grid, double ox, double oy, double 
                  double min_width, double sm, int n_start, const int32_t* wp_id, const int32_t* off, const int32_t* discs,
                  const int32_t* woff, const int32_t* walls, const int32_t* route, const int32_t* look_car, const int32_t* hz, int S,
                  const int32_t* tz, double* ub, double* lb, int32_t* flag) {
-  const long n_walls = woff ? woff[n_start] : 0;
-  std::vector<int32_t> whdr((size_t)WALL_HDR * n_walls + 1), wtab;
-  wtab.assign((size_t)wall_layout(n_walls, walls, whdr.data()) + 1, 0);
-  for (long j = 0; j < n_walls; ++j)
-    if (!wall_raster(walls + 4 * j, whdr.data() + WALL_HDR * j, wtab.data())) return 3;
-  MapView m{grid, h, w, ox, oy, res};
-  std::vector<double> trig((size_t)n_wp * COR_TRIG);
-  for (int i = 0; i < n_wp; ++i) cor_trig_row(psi[i], trig.data() + (size_t)i * COR_TRIG);
-  std::vector<double> segs((size_t)n_wp * 4 * COR_MAXSEG, 0.0), wpc((size_t)n_wp * COR_WPC, 0.0);
-  std::vector<int> nseg(n_wp), cells((size_t)n_wp * COR_CELL_CAP), box((size_t)n_wp * COR_LINE_BOX);
-  std::vector<char> built(n_wp, 0);
-  std::vector<double> col_o((size_t)N * COR_WPC);
-  std::vector<int> col_seg((size_t)N * 2 * COR_MAXSEG), col_cnt(N);
+  const Walls ws(woff ? woff[n_start] : 0, walls);
+  if (!ws.ok) return 3;
+  TwinBase base(h, w, grid, ox, oy, res, n_wp, x, y, psi, ds_next, circular, bub, blb, min_width, sm);
   for (int b = 0; b < n_start; ++b) {
     const RouteView v = route_view(route, b, n_wp, circular);
-    const PathGeom g = route_geom(PathGeom{x, y, psi, ds_next, n_wp, circular, trig.data()}, v);
-    double* const r_segs = segs.data() + v.first * 4 * COR_MAXSEG;
-    double* const r_wpc = wpc.data() + v.first * COR_WPC;
-    int* const r_nseg = nseg.data() + v.first;
-    int* const r_cells = cells.data() + v.first * COR_CELL_CAP;
-    int* const r_box = box.data() + v.first * COR_LINE_BOX;
-    if (!built[v.first]) {                         // K0a on the car's route
-      built[v.first] = 1;
-      for (int i = 0; i < v.n(); ++i) {
-        int ux, uy, lx, ly;
-        cor_w2m(m, bub[2 * (v.first + i)], bub[2 * (v.first + i) + 1], ux, uy);
-        cor_w2m(m, blb[2 * (v.first + i)], blb[2 * (v.first + i) + 1], lx, ly);
-        int* c = r_cells + (size_t)i * COR_CELL_CAP;
-        const int n = cor_line_cells(ux, uy, lx, ly, c, COR_CELL_CAP);
-        if (n > COR_CELL_CAP) return 1;
-        const int cnt = cor_scan_cells(m, ux, uy, lx, ly, min_width, n, [&](int k, int& cx, int& cy) { cor_unpack_cell(c[k], cx, cy); },
-                                       [&](int k) { int cx, cy; cor_unpack_cell(c[k], cx, cy); return cor_cell_free(m, cx, cy); },
-                                       r_segs + (size_t)i * 4 * COR_MAXSEG);
-        if (cnt < 0) return 2;
-        r_nseg[i] = cnt;
-        cor_line_box(c, n, (ux + 1) | ((uy + 1) << 16), (lx + 1) | ((ly + 1) << 16), r_box + (size_t)i * COR_LINE_BOX);
-      }
-      for (int i = 0; i < v.n(); ++i)
-        if (r_nseg[i] <= 1) cor_forced(g, r_segs, r_nseg, i, sm, r_wpc + (size_t)i * COR_WPC);
-    }
+    if (int rc = base.build(v)) return rc;                         // K0a on the car's route
     const int d0 = off ? off[b] : 0, nd = off ? off[b + 1] - d0 : 0;
     const int32_t* dsc = discs + 3L * d0;
     int ns = 0, nm = 0;
@@ -142,59 +109,14 @@ int tlk_emu_rows(int h, int w, const int8_t* grid, double ox, double oy, double 
     const int ts = S < nd ? S : nd;
     const int32_t* tzb = tz ? tz + (long)b * S * N * 3 : nullptr;
     const int w0 = woff ? woff[b] : 0, nw = woff ? woff[b + 1] - w0 : 0;
-    auto hdr = [&](int j) { return (const int*)(whdr.data() + (size_t)WALL_HDR * (w0 + j)); };
-    const int wp = wp_id[b] + 1;
-    bool over = false;
-    for (int n = 0; n < N; ++n) {              // K0c, one car; column n in its own world
-      auto disc = [&](int j) {
+    auto hdr = [&](int j) { return (const int*)(ws.hdr.data() + (size_t)WALL_HDR * (w0 + j)); };
+    auto col_disc = [&](int n) {                                   // column n in its own world
+      return [=](int j) {
         if (tz) return tlk_col_disc(dsc, j, ns, nm, car_hz, nd, ts, tzb, N, n);
         return look_car ? look_col_disc(dsc, j, ns, nm, car_hz, N, n) : (const int*)(dsc + 3 * j);
       };
-      const int i = cor_wp(g, wp + n);
-      const int* bx = r_box + (size_t)i * COR_LINE_BOX;
-      double* o = col_o.data() + (size_t)n * COR_WPC;
-      if (wall_car_touches(bx, nd, disc, nw, hdr)) {
-        int* cs = col_seg.data() + (size_t)n * 2 * COR_MAXSEG;
-        double s0[4] = {0, 0, 0, 0};
-        const int cnt = wall_car_scan(m, min_width, r_cells + (size_t)i * COR_CELL_CAP, bx, nd, disc, nw, hdr, wtab.data(),
-                                      [&](int q, int sx, int sy, int ex, int ey, double ax, double ay, double bx2, double by) {
-                                        cs[2 * q] = (sx + 1) | ((sy + 1) << 16);
-                                        cs[2 * q + 1] = (ex + 1) | ((ey + 1) << 16);
-                                        if (q == 0) { s0[0] = ax; s0[1] = ay; s0[2] = bx2; s0[3] = by; }
-                                      });
-        if (cnt < 0) over = true;
-        else if (cnt <= 1) cor_forced_seg(g, i, cnt, s0, sm, o);
-        col_cnt[n] = cnt < 0 ? cnt : cnt + 1000;
-      } else {
-        const int cnt = r_nseg[i];
-        if (cnt <= 1)
-          for (int k = 0; k < COR_WPC; ++k) o[k] = r_wpc[(size_t)i * COR_WPC + k];
-        col_cnt[n] = cnt;
-      }
-    }
-    auto cnt = [&](int c) { const int q = col_cnt[c]; return q >= 1000 ? q - 1000 : q; };
-    auto forced = [&](int c, double* o) { for (int k = 0; k < COR_WPC; ++k) o[k] = col_o[(size_t)c * COR_WPC + k]; };
-    auto seg = [&](int c, int k, double* s) {
-      if (col_cnt[c] >= 1000) {
-        const int* cs = col_seg.data() + (size_t)c * 2 * COR_MAXSEG;
-        int cx, cy;
-        cor_unpack_cell(cs[2 * k], cx, cy);
-        cor_m2w(m, cx, cy, s[0], s[1]);
-        cor_unpack_cell(cs[2 * k + 1], cx, cy);
-        cor_m2w(m, cx, cy, s[2], s[3]);
-      } else {
-        const double* sg = r_segs + (size_t)cor_wp(g, wp + c) * 4 * COR_MAXSEG + 4 * k;
-        for (int j = 0; j < 4; ++j) s[j] = sg[j];
-      }
     };
-    const int verdict = cnt(0) == 0 ? COR_ROW_BLOCKED : (over ? COR_ROW_OVERFLOW : COR_ROW_OK);
-    for (int n = 0; n < N; ++n) {
-      double u = std::nan(""), l = std::nan("");
-      if (verdict == COR_ROW_OK) cor_select_car_one(g, wp, n, sm, cnt, forced, seg, &u, &l);
-      ub[(size_t)b * N + n] = u;
-      lb[(size_t)b * N + n] = l;
-    }
-    flag[b] = verdict;
+    flag[b] = car_rows<true>(base, v, wp_id[b], N, nd, col_disc, nw, hdr, ws.tab.data(), ub + (size_t)b * N, lb + (size_t)b * N);
   }
   return 0;
 }

@@ -17,16 +17,90 @@ for p in (PKG, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "bench_support")
 import mpmpc  # noqa: E402
 import scenarios  # noqa: E402
 
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_bp = C.POINTER(C.c_int8)
 
 
+# ---- what the test modules hand to ctypes entry points (None stays None: a NULL argument)
 def _d(a):
     return None if a is None else a.ctypes.data_as(_dp)
 
 
 def _i(a):
     return None if a is None else a.ctypes.data_as(_ip)
+
+
+def _b(a):
+    return None if a is None else a.ctypes.data_as(_bp)
+
+
+def _i32(a):
+    return None if a is None else np.ascontiguousarray(a, np.int32)
+
+
+def csr(lists, width, n=None, pad=True):
+    """Per-car lists of `width`-int rows (discs: 3, walls: 4) -> (offsets int32 [B + 1], rows int32 [total, width]); None ->
+    (None, None).  n: the number of lists the caller expects.  pad: when no list has a row, `rows` is ONE zero row (a buffer
+    an entry point may be handed) - without it, the empty [0, width] array."""
+    if lists is None:
+        return None, None
+    lists = [np.asarray(a, np.int32).reshape(-1, width) for a in lists]
+    assert n is None or len(lists) == n
+    off = np.zeros(len(lists) + 1, np.int32)
+    off[1:] = np.cumsum([a.shape[0] for a in lists])
+    flat = np.concatenate(lists) if off[-1] or not pad else np.zeros((1, width), np.int32)
+    return off, np.ascontiguousarray(flat, np.int32)
+
+
+_G1_WORLD = {}
+
+
+def g1_world(track):
+    """(g1, grid, origin, res) of golden G1 for track "sim" / "real": the tables, the free grid [h, w] int8, the map's frame.
+    Loaded once and shared: read only."""
+    if track not in _G1_WORLD:
+        g1 = np.load(os.path.join(GOLDEN, "g1_path_sim_track.npz" if track == "sim" else "g1_path_real_track.npz"))
+        h, w = g1["grid_shape"]
+        grid = np.ascontiguousarray(np.unpackbits(g1["grid_free"])[:h * w].reshape(h, w).astype(np.int8))
+        _G1_WORLD[track] = (g1, grid, tuple(float(v) for v in g1["origin"]), float(g1["resolution"][0]))
+    return _G1_WORLD[track]
+
+
+def safety_margin(track):
+    """the safety margin golden G3o's rows were built with"""
+    return float(np.load(os.path.join(GOLDEN, "g3o_%s_obstacles.npz" % track))["safety_margin"][0])
+
+
+def build_world(obstacles=True):
+    """Sim_Track with the host classes from the golden tables -> (Map, ReferencePath, BicycleModel)"""
+    from map import Map
+    from reference_path import ReferencePath
+    from spatial_bicycle_models import BicycleModel
+    g1 = np.load(os.path.join(GOLDEN, "g1_path_sim_track.npz"))
+    g2 = np.load(os.path.join(GOLDEN, "g2_speed_profile.npz"))
+    h, w = g1["grid_shape"]
+    grid = np.unpackbits(g1["grid_obstacles" if obstacles else "grid_free"])[:h * w].reshape(h, w).astype(np.int8)
+    m = Map.from_grid(grid, origin=[-1, -2], resolution=0.005)
+    rp = ReferencePath.from_tables(m, g1["x"], g1["y"], g1["psi"], g1["kappa"], circular=True, v_ref=g2["v_ref"],
+                                   border_ub=g1["border_ub"], border_lb=g1["border_lb"],
+                                   ub_static=g1["ub_static"], lb_static=g1["lb_static"])
+    car = BicycleModel(reference_path=rp, length=0.12, width=0.06, Ts=0.05)
+    return m, rp, car
+
+
+def make_mpc(car, N, backend=None, corridor="host", settings=None):
+    """The reference's controller (src/simulation.py:100-111) on `car`; backend "emu": the CPU emulation behind it"""
+    from scipy import sparse
+    from MPC import MPC
+    Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
+    ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
+    sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}
+    if backend == "emu":
+        cfg = stock_config(N)
+        backend = EmuBackend(cfg, settings or mpmpc.default_settings())
+    return MPC(car, N, Q, R, QN, sc, ic, 4.0, settings=settings, backend=backend, corridor=corridor)
 
 
 def stock_config(N, weights="stock", max_batch=1, circular=None, track=None):

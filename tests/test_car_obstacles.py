@@ -4,8 +4,6 @@ its own circular obstacles added, and its corridor row is rebuilt from that worl
 Against golden G3o / G6o (tests/golden/make_g3o.py: the reference's Map.add_obstacles + update_path_constraints, and its
 closed loop, in seeded obstacle worlds) and against the shared-table rollout run once per world."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,59 +12,23 @@ import mpc_np as M
 import mpmpc
 import mpmpc_testlib as T
 import scenarios
+import twins
 from map import Map, Obstacle
 from reference_path import ReferencePath
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-
-
-def _d(a):
-    return a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
+_d, _i, _g1, _sm = T._d, T._i, T.g1_world, T.safety_margin
 
 
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of K0c, built with the flags of tests/emul/Makefile."""
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libcar_corridor_emul.so")
-    src = os.path.join(ROOT, "tests", "emul_car", "car_corridor_emul.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, src], check=True)
-    lib = C.CDLL(so)
-    lib.car_emu_check.argtypes = [C.c_int, C.c_int, ip, ip, C.c_int, C.c_int, C.c_int]
-    lib.car_emu_rows.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double, C.c_int,
-                                 dp, dp, dp, dp, C.c_int, dp, dp, C.c_int, C.c_double, C.c_double, C.c_int, ip, ip, ip,
-                                 dp, dp, ip]
-    return lib
-
-
-def _g1(track):
-    g1 = np.load(M.GOLDEN + ("/g1_path_sim_track.npz" if track == "sim" else "/g1_path_real_track.npz"))
-    h, w = g1["grid_shape"]
-    grid = np.ascontiguousarray(np.unpackbits(g1["grid_free"])[:h * w].reshape(h, w).astype(np.int8))
-    origin = tuple(g1["origin"]) if "origin" in g1 else (-1.0, -2.0)
-    res = float(g1["resolution"][0]) if "resolution" in g1 else 0.005
-    return g1, grid, origin, res
-
-
-def _csr(disc_lists):
-    off = np.zeros(len(disc_lists) + 1, np.int32)
-    off[1:] = np.cumsum([len(d) for d in disc_lists])
-    flat = np.ascontiguousarray(np.concatenate([np.asarray(d, np.int32).reshape(-1, 3) for d in disc_lists]), np.int32)
-    return off, flat
+    """The CPU twin of K0c (tests/emul_car)."""
+    return twins.car()
 
 
 def _twin_rows(twin, track, grid, disc_lists, wp_ids, N, sm):
     g1, _, origin, res = _g1(track)
     arrs = [np.ascontiguousarray(g1[k], float) for k in ("x", "y", "psi", "ds_next", "border_ub", "border_lb")]
-    off, flat = _csr(disc_lists)
+    off, flat = T.csr(disc_lists, 3, pad=False)
     B = len(disc_lists)
     wp = np.ascontiguousarray(wp_ids, np.int32)
     ub, lb, flag = np.zeros((B, N)), np.zeros((B, N)), np.zeros(B, np.int32)
@@ -157,6 +119,54 @@ def test_twin_matches_host_classes_on_random_worlds(twin):
             assert flag[j] == 0 and np.array_equal(ub[j], u) and np.array_equal(lb[j], l)
 
 
+@pytest.mark.parametrize("track", ["sim", "real"])
+def test_the_four_k0c_entry_points_agree_with_every_feature_off(track, twin):
+    """car_emu_rows, wall_emu_rows, look_emu_rows and tlk_emu_rows are one restatement of K0c (tests/emul_car/car_rows.hpp) behind
+    four argument lists: without walls, routes, lookahead and traffic tables they return the same ub, lb and flag, bit for bit.
+    One car per start waypoint, 0 .. 6 discs each on the border lines of the waypoints 1 .. 29 ahead of it (seeded: count, then
+    per disc waypoint, fraction of the way from the upper to the lower border point, radius)."""
+    N = 30
+    g1, grid, origin, res = _g1(track)
+    sm, n = _sm(track), g1["x"].size
+    starts = np.arange(n if track == "sim" else n - N - 1)
+    rng = np.random.default_rng(5)
+    lists = []
+    for w in starts:
+        d = []
+        for _ in range(rng.integers(0, 7)):
+            i, f, r = (w + rng.integers(1, 30)) % n, rng.uniform(-0.1, 1.1), rng.integers(1, (39 if track == "sim" else 11) + 1)
+            p = g1["border_ub"][i] + f * (g1["border_lb"][i] - g1["border_ub"][i])
+            d.append([int(np.floor((p[0] - origin[0]) / res)), int(np.floor((p[1] - origin[1]) / res)), int(r)])
+        lists.append(np.asarray(d, np.int32).reshape(-1, 3))
+    B = starts.size
+    off, flat = T.csr(lists, 3)
+    arrs = [np.ascontiguousarray(g1[k], float) for k in ("x", "y", "psi", "ds_next", "border_ub", "border_lb")]
+    wp = np.ascontiguousarray(starts, np.int32)
+    head = (grid.shape[0], grid.shape[1], T._b(grid), origin[0], origin[1], res, n, *[_d(a) for a in arrs[:4]],
+            1 if track == "sim" else 0, _d(arrs[4]), _d(arrs[5]), N, 2 * sm, sm, B, _i(wp))
+    no_walls = T.csr([[]] * B, 4)
+
+    def rows(fn, off, flat, *rest):
+        ub, lb, flag = np.full((B, N), -7.0), np.full((B, N), -7.0), np.full(B, -7, np.int32)
+        assert fn(*head, _i(off), _i(flat), *rest, _d(ub), _d(lb), _i(flag)) == 0
+        return ub, lb, flag
+
+    car = rows(twin.car_emu_rows, off, flat)
+    others = dict(walls=rows(twins.walls().wall_emu_rows, off, flat, _i(no_walls[0]), _i(no_walls[1])),
+                  look=rows(twins.lookahead().look_emu_rows, off, flat, None, None, None, None, None),
+                  look_empty_walls=rows(twins.lookahead().look_emu_rows, off, flat, _i(no_walls[0]), _i(no_walls[1]), None, None, None),
+                  tlk=rows(twins.traffic_lookahead().tlk_emu_rows, off, flat, None, None, None, None, None, 0, None))
+    for name, got in others.items():
+        assert np.array_equal(got[0], car[0], equal_nan=True) and np.array_equal(got[1], car[1], equal_nan=True), name
+        assert np.array_equal(got[2], car[2]), name
+    # not an empty world: the discs change rows, and block some
+    free = rows(twin.car_emu_rows, *T.csr([[]] * B, 3))
+    changed = [not (np.array_equal(car[0][b], free[0][b], equal_nan=True) and np.array_equal(car[1][b], free[1][b], equal_nan=True)
+                    and car[2][b] == free[2][b]) for b in range(B)]
+    print("%s: %d of %d rows changed by the discs, %d cars blocked" % (track, sum(changed), B, int((car[2] == 1).sum())))
+    assert sum(changed) >= 100 and (car[2] == 1).sum() >= 1
+
+
 def test_set_obstacles_validation_without_device(twin, built_library):
     lib = mpmpc.load_library(built_library)
     off, d = np.array([0, 1], np.int32), np.array([[50, 50, 3]], np.int32)
@@ -192,10 +202,6 @@ def _handle(track, N, B, warm=False, settings=None):
     h.set_path_geometry(g1["x"], g1["y"], g1["psi"], g1["border_ub"], g1["border_lb"])
     h.rollout_warm_start(warm)
     return h, tr, g1, grid, origin, res
-
-
-def _sm(track):
-    return float(_g3o(track)["safety_margin"][0])
 
 
 def _world_grid(grid, discs):

@@ -164,11 +164,10 @@ def test_device_corridor_matches_reference_tables(key, track):
 @pytest.mark.gpu
 def test_batch_mpc_rebuilds_corridor_when_the_map_changes():
     """Dynamic map: stamp a new obstacle, rebuild on the device, compare with the host walk."""
-    import test_host_mpc as H
     from map import Obstacle
     from MPC import BatchMPC
     from scipy import sparse
-    m, rp, car = H.build_world(obstacles=False)
+    m, rp, car = T.build_world(obstacles=False)
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}

@@ -18,18 +18,16 @@ device against the twin: at most 5.6e-17 m where the bound is 8.5e-16 .. 4.9e-15
 Device against device has no exclusions and is bit-equal."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import mpc_np as M
 import mpmpc
+import mpmpc_testlib as T
+import twins
 from map import Map, Obstacle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int8)
+bp = C.POINTER(C.c_int8)
 E_ARG, E_HIP, E_STATE = -1, -2, -3
 TIE = 1e-9
 EPS = 2.2e-16
@@ -41,59 +39,21 @@ def clr_tol(reach, length, width, res):
     return 16 * EPS * (reach + length + width + 2 * res)
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
+_d, _i, _g1 = T._d, T._i, T.g1_world
 
 
 # ------------------------------------------------------------------------------------------------ worlds and fixtures
-_G1 = {}
-
-
-def _g1(track):
-    if track not in _G1:
-        g1 = np.load(M.GOLDEN + ("/g1_path_sim_track.npz" if track == "sim" else "/g1_path_real_track.npz"))
-        h, w = g1["grid_shape"]
-        grid = np.ascontiguousarray(np.unpackbits(g1["grid_free"])[:h * w].reshape(h, w).astype(np.int8))
-        _G1[track] = (g1, grid, tuple(float(v) for v in g1["origin"]), float(g1["resolution"][0]))
-    return _G1[track]
-
-
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of K0f, built with the flags of tests/test_lidar.py's twin."""
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libfootprint_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, os.path.join(ROOT, "tests", "emul_footprint", "footprint_emul.cpp")], check=True)
-    lib = C.CDLL(so)
-    lib.fp_emu_check.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_int, dp, ip, ip, C.c_double, C.c_double, C.c_double, ip, dp, ip]
-    lib.fp_emu_audit.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, ip, ip, C.c_double,
-                                 C.c_double, C.c_double, ip, dp]
-    return lib
-
-
-def _csr(discs, B):
-    if discs is None:
-        return None, None
-    lists = [np.asarray(d, np.int32).reshape(-1, 3) for d in discs]
-    assert len(lists) == B
-    off = np.zeros(B + 1, np.int32)
-    off[1:] = np.cumsum([a.shape[0] for a in lists])
-    flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((1, 3), np.int32), np.int32)
-    return off, flat
+    """The CPU twin of K0f (tests/emul_footprint)."""
+    return twins.footprint()
 
 
 def _twin_audit(twin, grid, origin, res, poses, car, discs=None):
     """car = (length, width, reach) -> contact [B] int32, clearance [B]"""
     poses = np.ascontiguousarray(poses, float).reshape(-1, 3)
     B = poses.shape[0]
-    off, flat = _csr(discs, B)
+    off, flat = T.csr(discs, 3, n=B)
     contact, clearance = np.full(B, -7, np.int32), np.full(B, -7.0)
     rc = twin.fp_emu_audit(grid.shape[0], grid.shape[1], grid.ctypes.data_as(bp), origin[0], origin[1], res, B, _d(poses), _i(off),
                            _i(flat), car[0], car[1], car[2], _i(contact), _d(clearance))
@@ -323,7 +283,6 @@ def test_twin_equals_the_restated_law_on_seeded_fleets(track, twin):
 
 
 def test_footprint_fields_and_drop_in(twin):
-    import test_host_mpc as H
     from footprint import Footprint
     from MPC import BatchMPC
     fp = Footprint(0.12, 0.06)
@@ -333,7 +292,7 @@ def test_footprint_fields_and_drop_in(twin):
     assert hasattr(Footprint, "audit") and hasattr(Footprint, "audit_batch")
     assert hasattr(mpmpc.Handle, "rollout_set_audit") and hasattr(mpmpc.Handle, "rollout_audit") and hasattr(mpmpc, "footprint_audit")
     assert hasattr(BatchMPC, "rollout_audit")
-    m, rp, car = H.build_world(obstacles=False)
+    m, rp, car = T.build_world(obstacles=False)
     fp = Footprint(car.length, car.width)
     if mpmpc.device_count() == 0:                                             # no CPU fallback: an error, never a result
         with pytest.raises(mpmpc.MpmpcError, match="rc=%d" % E_HIP):
@@ -635,7 +594,6 @@ def test_mode_two_ends_a_car_in_contact(runs):
 
 @pytest.mark.gpu
 def test_rollout_audit_state_errors_and_batch_mpc():
-    import test_host_mpc as H
     import test_traffic as TT
     from footprint import Footprint
     from MPC import BatchMPC
@@ -681,7 +639,7 @@ def test_rollout_audit_state_errors_and_batch_mpc():
     h2.rollout_step(1)
     h2.close()
     # BatchMPC: the audit as an argument of rollout
-    m, rp, car = H.build_world(obstacles=False)
+    m, rp, car = T.build_world(obstacles=False)
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}

@@ -263,19 +263,17 @@ def test_errors_are_loud(track):
 # host classes on the real library: the reference's drop-in surface
 # ---------------------------------------------------------------------------------------------
 def _world():
-    import test_host_mpc as H
-    return H.build_world()
+    return T.build_world()
 
 
 def test_mpc_get_control_replays_reference_lap_on_gpu():
     """MPC.get_control() through libmpmpc.so on the reference's own closed-loop trace (golden G6)."""
-    import test_host_mpc as H
     from spatial_bicycle_models import TemporalState
     g = np.load(M.GOLDEN + "/g6_closed_loop_N30.npz")
-    m, rp, car = H.build_world()
+    m, rp, car = T.build_world()
     # (G6 is the lap of the CERTIFIED stand-in - every proven infeasibility reported: phase1_accept = 0, as in the CPU twin
     #  tests/test_host_mpc.py; the default verdicts are pinned by the stock lap G6s below)
-    mpc = H.make_mpc(car, 30, settings=mpmpc.default_settings(phase1_accept=0))                       # real backend
+    mpc = T.make_mpc(car, 30, settings=mpmpc.default_settings(phase1_accept=0))                       # real backend
     assert isinstance(mpc.optimizer, mpmpc.Handle)
     n_inf = 0
     for t in range(0, g["s"].size, 2):
@@ -299,11 +297,10 @@ def test_free_running_lap_on_gpu():
     the solver golden G6 was driven by (every proven infeasibility reported) the free-running lap has the reference lap's
     length to the step; with the default verdicts (marginal instances come back as plans, like the reference's OSQP call) the
     car takes other branches at the marginal steps and the lap may differ by a few steps."""
-    import test_host_mpc as H
     g = np.load(M.GOLDEN + "/g6_closed_loop_N30.npz")
     for settings, slack in ((mpmpc.default_settings(phase1_accept=0), 0), (None, 10)):
-        m, rp, car = H.build_world()
-        mpc = H.make_mpc(car, 30, settings=settings)
+        m, rp, car = T.build_world()
+        mpc = T.make_mpc(car, 30, settings=settings)
         steps = 0
         while car.s < rp.length and steps < 400:
             u = mpc.get_control()
@@ -318,10 +315,9 @@ def test_device_corridor_in_the_single_car_loop():
     ReferencePath.update_path_constraints on the host.  Same controls as the host-corridor controller, step by
     step on identical states, before and after an obstacle is added to the map (the table is rebuilt)."""
     import time
-    import test_host_mpc as H
     from map import Obstacle
-    m, rp, car = H.build_world()
-    host, dev = H.make_mpc(car, 30), H.make_mpc(car, 30, corridor="device")
+    m, rp, car = T.build_world()
+    host, dev = T.make_mpc(car, 30), T.make_mpc(car, 30, corridor="device")
     t_host = t_dev = 0.0
     for step in range(60):
         if step == 30:
@@ -426,10 +422,9 @@ def test_default_path_takes_the_branch_stock_osqp_takes_on_device(N, track):
 
 
 def test_batch_mpc_matches_single_controller():
-    import test_host_mpc as H
     from MPC import BatchMPC
     from scipy import sparse
-    m, rp, car = H.build_world()
+    m, rp, car = T.build_world()
     g = np.load(M.GOLDEN + "/g6_closed_loop_N30.npz")
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}

@@ -19,10 +19,6 @@ N, B, STEPS, TS = 10, 6, 3, 0.05
 OBSTACLES = [(0.0, 0.0, 0.05), (-0.8, -0.5, 0.08), (-0.7, -1.5, 0.05), (-0.3, -1.0, 0.08), (0.27, -1.0, 0.05), (0.78, -1.47, 0.05)]
 
 
-def _sm():
-    return float(np.load(M.GOLDEN + "/g3o_sim_obstacles.npz")["safety_margin"][0])
-
-
 def _phase(large):
     """the whole set-up of a phase, as plain arrays"""
     tr = scenarios.sim_track()
@@ -65,7 +61,7 @@ def _phase(large):
 
 def _run(h, p):
     """a phase's set-up on `h` (fresh or used), three rollout steps, everything the handle reports"""
-    sm = _sm()
+    sm = T.safety_margin("sim")
     h.set_path(p["path"]["kappa"], p["path"]["v_ref"], p["path"]["ds_next"])
     h.set_map(p["grid"], p["origin"], p["res"])
     g = p["geom"]

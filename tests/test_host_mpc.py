@@ -8,37 +8,10 @@ import pytest
 import mpc_np as M
 import mpmpc
 import mpmpc_testlib as T
-import scenarios
-from map import Map
 from MPC import MPC
-from reference_path import ReferencePath
-from spatial_bicycle_models import BicycleModel, TemporalState
+from spatial_bicycle_models import TemporalState
 
 G = M.GOLDEN
-
-
-def build_world(obstacles=True):
-    g1 = np.load(G + "/g1_path_sim_track.npz")
-    g2 = np.load(G + "/g2_speed_profile.npz")
-    h, w = g1["grid_shape"]
-    grid = np.unpackbits(g1["grid_obstacles" if obstacles else "grid_free"])[:h * w].reshape(h, w).astype(np.int8)
-    m = Map.from_grid(grid, origin=[-1, -2], resolution=0.005)
-    rp = ReferencePath.from_tables(m, g1["x"], g1["y"], g1["psi"], g1["kappa"], circular=True, v_ref=g2["v_ref"],
-                                   border_ub=g1["border_ub"], border_lb=g1["border_lb"],
-                                   ub_static=g1["ub_static"], lb_static=g1["lb_static"])
-    car = BicycleModel(reference_path=rp, length=0.12, width=0.06, Ts=0.05)
-    return m, rp, car
-
-
-def make_mpc(car, N, backend=None, corridor="host", settings=None):
-    from scipy import sparse
-    Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
-    ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
-    sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}
-    if backend == "emu":
-        cfg = T.stock_config(N)
-        backend = T.EmuBackend(cfg, settings or mpmpc.default_settings())
-    return MPC(car, N, Q, R, QN, sc, ic, 4.0, settings=settings, backend=backend, corridor=corridor)
 
 
 @pytest.mark.parametrize("N,stride", [(10, 1), (30, 3)])
@@ -48,8 +21,8 @@ def test_get_control_reproduces_reference_lap(N, stride):
     phase1_accept = 0 is that solver's verdict semantics; the default (marginal infeasibility -> usable plan, like the
     reference's OSQP call at eps = 1e-3) is pinned by the STOCK lap below."""
     g = np.load(G + "/g6_closed_loop_N%d.npz" % N)
-    m, rp, car = build_world()
-    mpc = make_mpc(car, N, "emu", settings=mpmpc.default_settings(phase1_accept=0))
+    m, rp, car = T.build_world()
+    mpc = T.make_mpc(car, N, "emu", settings=mpmpc.default_settings(phase1_accept=0))
     steps = range(0, g["s"].size, stride)
     n_inf = 0
     for t in steps:
@@ -86,8 +59,8 @@ def test_default_path_takes_the_branch_stock_osqp_takes(N, stride):
     fallback - and keep the same infeasibility counter.  (OSQP at 1e-3 accepts corridor violations of millimetres; the
     default path returns MPMPC_SOLVED_INACCURATE for those instead of a Farkas verdict: mpmpc_settings::phase1_accept.)"""
     g = np.load(G + "/g6s_stock_loop_N%d.npz" % N)
-    m, rp, car = build_world()
-    mpc = make_mpc(car, N, "emu")
+    m, rp, car = T.build_world()
+    mpc = T.make_mpc(car, N, "emu")
     seen = set()
     for t in range(0, g["s"].size, stride):
         car.s = float(g["s"][t])
@@ -113,8 +86,8 @@ def test_exit_after_n_minus_one_infeasible_steps():
     """src/MPC.py:218-220: the reference's lap at N=10 ends with exit(1); so does ours."""
     g = np.load(G + "/g6_closed_loop_N10.npz")
     assert bool(g["exited"][0])
-    m, rp, car = build_world()
-    mpc = make_mpc(car, 10, "emu")
+    m, rp, car = T.build_world()
+    mpc = T.make_mpc(car, 10, "emu")
     t = g["s"].size - 1
     # replay the recorded last good state, then drive freely: the run must stop with SystemExit
     car.s = float(g["s"][t])
@@ -128,7 +101,7 @@ def test_exit_after_n_minus_one_infeasible_steps():
 
 
 def test_rejects_unsupported_weights_and_missing_profile():
-    m, rp, car = build_world()
+    m, rp, car = T.build_world()
     from scipy import sparse
     ic = {'umin': np.array([0.0, -1.0]), 'umax': np.array([1.0, 1.0])}
     sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}
@@ -152,6 +125,6 @@ def test_product_fails_loudly_without_device():
     device (this container) must raise, not silently compute elsewhere."""
     if mpmpc.device_count() > 0:
         pytest.skip("a GPU is present")
-    m, rp, car = build_world()
+    m, rp, car = T.build_world()
     with pytest.raises((mpmpc.MpmpcError, RuntimeError)):
-        make_mpc(car, 10, backend=None)
+        T.make_mpc(car, 10, backend=None)

@@ -15,44 +15,26 @@ that is compared must be bit-equal.  Caps: G9 none left out (the generator guara
 in 10 000.  Device against device has no exclusions."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import mpc_np as M
 import mpmpc
+import mpmpc_testlib as T
+import twins
 from map import Map, Obstacle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int8)
+bp = C.POINTER(C.c_int8)
 E_ARG, E_STATE = -1, -3
 TIE = 1e-9
 TS = 0.05
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
+_d, _i, _g1 = T._d, T._i, T.g1_world
 
 
 # ------------------------------------------------------------------------------------------------ worlds and fixtures
-_G1 = {}
-
-
-def _g1(track):
-    if track not in _G1:
-        g1 = np.load(M.GOLDEN + ("/g1_path_sim_track.npz" if track == "sim" else "/g1_path_real_track.npz"))
-        h, w = g1["grid_shape"]
-        grid = np.ascontiguousarray(np.unpackbits(g1["grid_free"])[:h * w].reshape(h, w).astype(np.int8))
-        _G1[track] = (g1, grid, tuple(float(v) for v in g1["origin"]), float(g1["resolution"][0]))
-    return _G1[track]
-
-
 def _angles(fov, reso):
     """the beam angles of LidarModel(FoV, ., resolution) (src/lidar_model.py:28-33)"""
     n = int(fov / reso + 1)
@@ -74,36 +56,15 @@ def g9():
 
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of K0l, built with the flags of tests/emul/Makefile."""
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "liblidar_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, os.path.join(ROOT, "tests", "emul_lidar", "lidar_emul.cpp")], check=True)
-    lib = C.CDLL(so)
-    lib.lid_emu_check.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_int, dp, ip, ip, C.c_int, dp, C.c_double, dp]
-    lib.lid_emu_scan.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, ip, ip, C.c_int, dp,
-                                 C.c_double, dp, ip, ip]
-    return lib
-
-
-def _csr(discs, B):
-    if discs is None:
-        return None, None
-    lists = [np.asarray(d, np.int32).reshape(-1, 3) for d in discs]
-    assert len(lists) == B
-    off = np.zeros(B + 1, np.int32)
-    off[1:] = np.cumsum([a.shape[0] for a in lists])
-    flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((1, 3), np.int32), np.int32)
-    return off, flat
+    """The CPU twin of K0l (tests/emul_lidar)."""
+    return twins.lidar()
 
 
 def _twin_scan(twin, grid, origin, res, poses, angles, rng, discs=None):
     poses = np.ascontiguousarray(poses, float).reshape(-1, 3)
     B = poses.shape[0]
     ang = np.ascontiguousarray(angles, float)
-    off, flat = _csr(discs, B)
+    off, flat = T.csr(discs, 3, n=B)
     out, skipped, enclosed = np.full((B, ang.size), -7.0), np.zeros(B, np.int32), np.zeros((B, 2), np.int32)
     rc = twin.lid_emu_scan(grid.shape[0], grid.shape[1], grid.ctypes.data_as(bp), origin[0], origin[1], res, B, _d(poses), _i(off),
                            _i(flat), ang.size, _d(ang), float(rng), _d(out), _i(skipped), _i(enclosed))
@@ -542,7 +503,6 @@ def test_scans_do_not_disturb_a_run():
 
 @pytest.mark.gpu
 def test_drop_in_use(g9, rollout_scans):
-    import test_host_mpc as H
     from lidar_model import LidarModel
     from MPC import BatchMPC
     from scipy import sparse
@@ -562,7 +522,7 @@ def test_drop_in_use(g9, rollout_scans):
     both = lm.scan_batch([s["pose"], s["pose"]], Map.from_grid(grid, origin, res), discs=[s["discs"], np.zeros((0, 3))])
     assert np.array_equal(both[0], s["ranges"]) and not np.array_equal(both[1], s["ranges"])
     # BatchMPC: one car parked at G9's pose on the map with G9's obstacles - a rollout of zero steps leaves it there
-    m, rp, car = H.build_world(obstacles=False)
+    m, rp, car = T.build_world(obstacles=False)
     m.data[:] = world.data
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}

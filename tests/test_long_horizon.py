@@ -352,7 +352,6 @@ def test_long_horizon_full_weights_and_host_class_on_device(track, emu):
     """Full weight matrices at N = 100 through the workgroup kernel (device = emulation, KKT on the dense data), and the
     reference's own loop (MPC.get_control) at N = 80 against the emulation-backed controller, step by step."""
     from test_emul_parity import full_weight_config
-    import test_host_mpc as H
     from spatial_bicycle_models import TemporalState
     N, B = 100, 48
     tw = T.wide_track(track, emu, N)
@@ -370,10 +369,10 @@ def test_long_horizon_full_weights_and_host_class_on_device(track, emu):
         P, q, A, l, u = T.qp_to_dense_full(qp[:, i, :], N, cfg)
         assert O.kkt_certificate(P, q, A, l, u, sol.z[i], sol.y[i])["ok_tol"](1e-8)
     # the host class: ten steps of the reference's loop at N = 80, the device against the emulation-backed controller
-    g = np.load(H.G + "/g6_closed_loop_N30.npz")
+    g = np.load(T.GOLDEN + "/g6_closed_loop_N30.npz")
     us = []
     for backend in (None, "emu"):
-        m, rp, car = H.build_world()
+        m, rp, car = T.build_world()
         from scipy import sparse
         Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
         ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}

@@ -9,7 +9,6 @@ frozen movers change nothing; infinite times are a plain rollout with step0 shif
 table, the rows and the verdicts are the restated law's and the twin's - with walls, with routes, under perception; one call
 equals the step-by-step loop; the refusals."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -20,46 +19,28 @@ import mpmpc_testlib as T
 import scenarios
 import test_movers as TM
 import test_routes as TR
+import twins
 
-dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int8)
+bp = C.POINTER(C.c_int8)
 E_ARG, E_STATE = -1, -3
 TS = TM.TS
 SHAPES = dict(sim=(30, 64, 12, 71), real=(70, 32, 8, 72))      # N, B, steps, seed (the seeds: chosen on the CPU, see test 3)
 MAX_LEAD = 40
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
+_d, _i = T._d, T._i
 
 
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of K0h and K0c<WALLS, LEAD>, built with the flags of tests/test_movers.py's twins."""
-    lib = TM._gxx("liblookahead_emul.so", os.path.join("emul_lookahead", "lookahead_emul.cpp"))
-    lib.look_emu_check.argtypes = [C.c_int, C.c_int, dp, C.c_int]
-    lib.look_emu_table_bytes.argtypes = [C.c_longlong, C.c_int]
-    lib.look_emu_table_bytes.restype = C.c_longlong
-    lib.look_emu_leads.argtypes = [C.c_int, C.c_int, ip, ip, C.c_int, C.c_int, dp, C.c_double, C.c_int, ip]
-    lib.look_emu_leads.restype = None
-    lib.look_emu_discs.argtypes = [C.c_int, C.c_int, ip, ip, ip, dp, C.c_int64, C.c_int64, ip, ip, C.c_int, C.c_int, C.c_double,
-                                   C.c_double, C.c_double, C.c_int, dp, dp, dp, dp, C.c_int, ip]
-    lib.look_emu_discs.restype = None
-    lib.look_emu_rows.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, dp, dp, C.c_int, dp, dp,
-                                  C.c_int, C.c_double, C.c_double, C.c_int, ip, ip, ip, ip, ip, ip, ip, ip, dp, dp, ip]
-    return lib
+    """The CPU twin of K0h and K0c<WALLS, LEAD> (tests/emul_lookahead)."""
+    return twins.lookahead()
 
 
 @pytest.fixture(scope="module")
 def car_twin():
     """The CPU twin of K0c (tests/emul_car): test_movers' Fleet draws cars again whose plain step-0 row it finds blocked."""
-    lib = TM._gxx("libcar_corridor_emul.so", os.path.join("emul_car", "car_corridor_emul.cpp"))
-    lib.car_emu_rows.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double, C.c_int,
-                                 dp, dp, dp, dp, C.c_int, dp, dp, C.c_int, C.c_double, C.c_double, C.c_int, ip, ip, ip, dp, dp, ip]
-    return lib
+    return twins.car()
 
 
 # ------------------------------------------------------------------------------------------------ worlds and the two sides
@@ -77,9 +58,9 @@ class Ctx:
 
     @classmethod
     def track(cls, track):
-        g1, grid, origin, res = TM._g1(track)
+        g1, grid, origin, res = T.g1_world(track)
         tr = scenarios.sim_track() if track == "sim" else scenarios.real_track()
-        return cls(grid, origin, res, TM._sm(track), g1, np.cumsum(g1["segment_lengths"]), track == "sim", tr.v_ref)
+        return cls(grid, origin, res, T.safety_margin(track), g1, np.cumsum(g1["segment_lengths"]), track == "sim", tr.v_ref)
 
     def headers(self, route):
         """the device's car headers {first row, length - negated when open} of cars on routes `route`, or None"""
@@ -133,14 +114,9 @@ class Ctx:
     # --- K0c's rows: disc_lists the lists K0c plans from at the step; look = (rows, hz) or None; walls: per-car [k, 4] or None
     def rows_twin(self, twin, wp, N, disc_lists, look=None, walls=None, route=None):
         B = len(disc_lists)
-        off = np.zeros(B + 1, np.int32)
-        off[1:] = np.cumsum([len(d) for d in disc_lists])
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(d, np.int32).reshape(-1, 3) for d in disc_lists]), np.int32)
-        woff = wflat = car = hz = None
-        if walls is not None:
-            woff = np.zeros(B + 1, np.int32)
-            woff[1:] = np.cumsum([len(w) for w in walls])
-            wflat = np.ascontiguousarray(np.concatenate([np.asarray(w, np.int32).reshape(-1, 4) for w in walls]), np.int32)
+        off, flat = T.csr(disc_lists, 3, pad=False)
+        woff, wflat = T.csr(walls, 4, pad=False)
+        car = hz = None
         if look is not None:
             rows, hz = look
             car = np.zeros((B + 1, 2), np.int32)
@@ -622,10 +598,9 @@ def test_refusals(car_twin):
 @pytest.mark.gpu
 def test_batch_mpc_rollout_takes_lookahead():
     import movers
-    import test_host_mpc as H
     from MPC import BatchMPC
     from scipy import sparse
-    m, rp, car = H.build_world()
+    m, rp, car = T.build_world()
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}

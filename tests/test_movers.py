@@ -8,79 +8,36 @@ evaluation; the argument checks.  GPU: one multi-step call against the step-by-s
 recorder's rows."""
 import ctypes as C
 import math
-import os
-import subprocess
 from bisect import bisect_right
 
 import numpy as np
 import pytest
 
-import mpc_np as M
 import mpmpc
 import mpmpc_testlib as T
 import scenarios
+import twins
 from map import Map, Obstacle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+lp = C.POINTER(C.c_int64)
 E_ARG, E_STATE = -1, -3
 TS = 0.05
 KEYS = ("s", "pose", "cc", "wp_id", "status", "counter", "alive")
 
 
-def _d(a):
-    return a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
-
-
-def _gxx(name, src):
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, name)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, os.path.join(ROOT, "tests", src)], check=True)
-    return C.CDLL(so)
+_d, _i, _g1, _sm = T._d, T._i, T.g1_world, T.safety_margin
 
 
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of K0m, built with the flags of tests/emul/Makefile."""
-    lib = _gxx("libmovers_emul.so", os.path.join("emul_movers", "movers_emul.cpp"))
-    lib.mov_emu_check.argtypes = [C.c_int, C.c_int, ip, ip, ip, dp, C.c_int, C.c_int, ip]
-    lib.mov_emu_check_combined.argtypes = [C.c_int, ip, C.c_int, ip]
-    lib.mov_emu_combine.argtypes = [C.c_int, ip, ip, ip, ip]
-    lib.mov_emu_combine.restype = None
-    lib.mov_emu_discs.argtypes = [C.c_int, ip, ip, dp, lp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
-                                  C.c_int, dp, dp, dp, dp, C.c_int, ip]
-    lib.mov_emu_discs.restype = None
-    return lib
+    """The CPU twin of K0m (tests/emul_movers)."""
+    return twins.movers()
 
 
 @pytest.fixture(scope="module")
 def car_twin():
     """The CPU twin of K0c (tests/emul_car), for the step-0 condition on the fleets."""
-    lib = _gxx("libcar_corridor_emul.so", os.path.join("emul_car", "car_corridor_emul.cpp"))
-    lib.car_emu_rows.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double, C.c_int,
-                                 dp, dp, dp, dp, C.c_int, dp, dp, C.c_int, C.c_double, C.c_double, C.c_int, ip, ip, ip,
-                                 dp, dp, ip]
-    return lib
-
-
-def _g1(track):
-    g1 = np.load(M.GOLDEN + ("/g1_path_sim_track.npz" if track == "sim" else "/g1_path_real_track.npz"))
-    h, w = g1["grid_shape"]
-    grid = np.ascontiguousarray(np.unpackbits(g1["grid_free"])[:h * w].reshape(h, w).astype(np.int8))
-    origin = tuple(float(v) for v in g1["origin"])
-    res = float(g1["resolution"][0])
-    return g1, grid, origin, res
-
-
-def _sm(track):
-    return float(np.load(M.GOLDEN + "/g3o_%s_obstacles.npz" % track)["safety_margin"][0])
+    return twins.car()
 
 
 # ------------------------------------------------------------------------------ the motion law, restated from the header
@@ -344,9 +301,7 @@ def _twin_flags(car_twin, track, disc_lists, wp_ids, N):
     g1, grid, origin, res = _g1(track)
     sm = _sm(track)
     arrs = [np.ascontiguousarray(g1[k], float) for k in ("x", "y", "psi", "ds_next", "border_ub", "border_lb")]
-    off = np.zeros(len(disc_lists) + 1, np.int32)
-    off[1:] = np.cumsum([len(d) for d in disc_lists])
-    flat = np.ascontiguousarray(np.concatenate([np.asarray(d, np.int32).reshape(-1, 3) for d in disc_lists]), np.int32)
+    off, flat = T.csr(disc_lists, 3, pad=False)
     B = len(disc_lists)
     wp = np.ascontiguousarray(wp_ids, np.int32)
     ub, lb, flag = np.zeros((B, N)), np.zeros((B, N)), np.zeros(B, np.int32)

@@ -15,47 +15,28 @@ A SIDE is tie-sensitive when a coordinate of its target, (t - o) / res, lies wit
 cos / sin against glibc's can then move the target cell).  Computed by the restatement alone; a condition, not a tolerance."""
 import ctypes as C
 import math
-import os
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 
-import mpc_np as M
 import mpmpc
+import mpmpc_testlib as T
+import twins
 from map import Map, Obstacle, line_aa
 from reference_path import ReferencePath
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int8)
+bp = C.POINTER(C.c_int8)
 E_ARG = -1
 TIE = 1e-9
 TABLES = ("x", "y", "psi", "kappa", "ds_next", "ub", "lb")
 TRACKS = {"sim": dict(r_p=0.05, sd=5, mw=0.23, circular=True, n_wp=200), "real": dict(r_p=0.20, sd=5, mw=1.50, circular=False, n_wp=302)}
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
+_d, _i, _g1 = T._d, T._i, T.g1_world
 
 
 # ------------------------------------------------------------------------------------------------ fixtures and callers
-_G1 = {}
-
-
-def _g1(track):
-    if track not in _G1:
-        g1 = np.load(M.GOLDEN + ("/g1_path_sim_track.npz" if track == "sim" else "/g1_path_real_track.npz"))
-        h, w = g1["grid_shape"]
-        grid = np.ascontiguousarray(np.unpackbits(g1["grid_free"])[:h * w].reshape(h, w).astype(np.int8))
-        _G1[track] = (g1, grid, tuple(float(v) for v in g1["origin"]), float(g1["resolution"][0]))
-    return _G1[track]
-
-
 def _route(track):
     g1 = _g1(track)[0]
     return np.ascontiguousarray(np.stack([g1["wp_x"], g1["wp_y"]], 1), float)
@@ -63,31 +44,8 @@ def _route(track):
 
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of mpmpc_path_build, built with the flags of tests/emul/Makefile."""
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libpath_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, os.path.join(ROOT, "tests", "emul_path", "path_emul.cpp")], check=True)
-    lib = C.CDLL(so)
-    lib.path_emu_count.argtypes = [C.c_int, dp, C.c_double, C.c_int]
-    lib.path_emu_mean.argtypes = [dp, C.c_int]
-    lib.path_emu_mean.restype = C.c_double
-    lib.path_emu_build.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, ip, dp, dp, ip, ip, ip, ip, ip,
-                                   C.c_int, ip, ip] + [dp] * 9
-    return lib
-
-
-def _csr(lists, k, P):
-    if lists is None:
-        return None, None
-    arrs = [np.asarray(a, np.int32).reshape(-1, k) for a in lists]
-    assert len(arrs) == P
-    off = np.zeros(P + 1, np.int32)
-    off[1:] = np.cumsum([a.shape[0] for a in arrs])
-    flat = np.ascontiguousarray(np.concatenate(arrs) if off[-1] else np.zeros((1, k), np.int32), np.int32)
-    return off, flat
+    """The CPU twin of mpmpc_path_build (tests/emul_path)."""
+    return twins.path()
 
 
 def _call(fn, grid, origin, res, routes, r_p, sd, mw, circular, discs=None, walls=None, cap=None, fill=-7.0, device=None, count=None):
@@ -103,8 +61,8 @@ def _call(fn, grid, origin, res, routes, r_p, sd, mw, circular, discs=None, wall
     ispec = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(sd), (Pa,)), np.broadcast_to(np.asarray(circular), (Pa,))], 1).astype(np.int32))
     if cap is None:
         cap = max(1, max(count(a.shape[0], _d(a), float(spec[p, 0]), int(ispec[p, 0])) for p, a in enumerate(lists)))
-    doff, dflat = _csr(discs, 3, P)
-    woff, wflat = _csr(walls, 4, P)
+    doff, dflat = T.csr(discs, 3, n=P)
+    woff, wflat = T.csr(walls, 4, n=P)
     rows = max(cap, 1)
     o = dict(n_wp=np.full(Pa, -7, np.int32), status=np.full(Pa, -7, np.int32), border=np.full((Pa, rows, 4), fill), length=np.full(Pa, fill))
     o.update({k: np.full((Pa, rows), fill) for k in TABLES})
@@ -530,7 +488,6 @@ def test_worlds(twin):
 def test_on_device_feeds_the_device_corridor():
     """T9: ReferencePath.on_device on Sim_Track -> set_path_geometry -> build_corridor on the obstacle grid, bit-equal to the
     corridor from the host constructor's tables on the same machine"""
-    import mpmpc_testlib as T
     g1, grid, origin, res = _g1("sim")
     h_, w_ = g1["grid_shape"]
     obst = np.ascontiguousarray(np.unpackbits(g1["grid_obstacles"])[:h_ * w_].reshape(h_, w_).astype(np.int8))

@@ -15,64 +15,43 @@ not a measurement - and the seeds are such that it leaves out at most 1 % of the
 compared as tests/test_lidar.py compares them.  Device against device has no exclusions."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import mpmpc
+import mpmpc_testlib as T
 import test_lidar as TL
+import twins
 from map import line_aa
-from test_traffic import car_twin  # noqa: F401  (the K0c twin, a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int8)
+bp = C.POINTER(C.c_int8)
 u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
 E_ARG, E_STATE = -1, -3
 TIE = 1e-9
 TS = 0.05
-_d, _i, _g1, _angles = TL._d, TL._i, TL._g1, TL._angles
+_d, _i, _g1, _angles = T._d, T._i, T.g1_world, TL._angles
 
 
 # -------------------------------------------------------------------------------------------------------- the twin
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of K0s, built with the flags of tests/test_lidar.py's twin."""
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libperception_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, os.path.join(ROOT, "tests", "emul_perception", "perception_emul.cpp")], check=True)
-    lib = C.CDLL(so)
-    lib.per_emu_check_scan.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_int, dp, ip, ip, ip, ip, C.c_int, dp, C.c_double, dp]
-    lib.per_emu_check_setting.argtypes = [C.c_int, dp, C.c_double, C.c_int, C.c_double]
-    lib.per_emu_scan.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, ip, ip, ip, ip, C.c_int, dp,
-                                 C.c_double, dp, u64p, u32p]
-    lib.per_emu_sequence.argtypes = [C.c_int] * 5 + [ip, u64p, u32p, C.c_int, C.c_int, C.c_int, u64p, u32p, ip, ip, ip, ip]
-    lib.per_emu_sequence.restype = None
-    lib.per_emu_lists.argtypes = [C.c_int, ip, C.c_uint64, C.c_int, ip, C.c_uint32, ip, ip]
-    lib.per_emu_lists.restype = None
-    return lib
+    """The CPU twin of K0s (tests/emul_perception)."""
+    return twins.perception()
 
 
-def _wcsr(walls, B):
-    if walls is None:
-        return None, None
-    lists = [np.asarray(w, np.int32).reshape(-1, 4) for w in walls]
-    assert len(lists) == B
-    off = np.zeros(B + 1, np.int32)
-    off[1:] = np.cumsum([a.shape[0] for a in lists])
-    return off, np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((1, 4), np.int32), np.int32)
+@pytest.fixture(scope="module")
+def car_twin():
+    """The CPU twin of K0c (tests/emul_car), for test_traffic's Fleet and rows."""
+    return twins.car()
 
 
 def _twin_scan(twin, grid, origin, res, poses, angles, rng, discs=None, walls=None):
     poses = np.ascontiguousarray(poses, float).reshape(-1, 3)
     B = poses.shape[0]
     ang = np.ascontiguousarray(angles, float)
-    off, flat = TL._csr(discs, B)
-    woff, wflat = _wcsr(walls, B)
+    off, flat = T.csr(discs, 3, n=B)
+    woff, wflat = T.csr(walls, 4, n=B)
     out, ds, ws = np.full((B, ang.size), -7.0), np.zeros(B, np.uint64), np.zeros(B, np.uint32)
     rc = twin.per_emu_scan(grid.shape[0], grid.shape[1], grid.ctypes.data_as(bp), origin[0], origin[1], res, B, _d(poses), _i(off),
                            _i(flat), _i(woff), _i(wflat), ang.size, _d(ang), float(rng), _d(out), ds.ctypes.data_as(u64p),
@@ -879,13 +858,12 @@ def test_state_errors(world):
 
 @pytest.mark.gpu
 def test_drop_in_use():
-    import test_host_mpc as H
     from lidar_model import LidarModel
     from map import Obstacle
     from MPC import BatchMPC
     from perception import Perception
     from scipy import sparse
-    m, rp, car = H.build_world(obstacles=False)
+    m, rp, car = T.build_world(obstacles=False)
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}

@@ -8,8 +8,6 @@ checks.  GPU: mpmpc_plant_noise, an identity plant against no plant, one call ag
 against the host loop of the project's host classes around Plant.apply, the consumers of the true pose, the error codes."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,11 +16,11 @@ import mpc_np as M
 import mpmpc
 import mpmpc_testlib as T
 import scenarios
+import twins
 from plant import IDENTITY, NAMES, Plant
 from spatial_bicycle_models import TemporalState, t2s_batch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip, lp, up = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint32)
+lp, up = C.POINTER(C.c_int64), C.POINTER(C.c_uint32)
 E_ARG, E_STATE = -1, -3
 TS, L_CAR = 0.05, 0.12
 KEYS = ("s", "pose", "cc", "wp_id", "x0", "u", "status", "counter", "alive")
@@ -31,36 +29,13 @@ NOISY = dict(speed_gain=0.97, steer_gain=1.03, steer_offset=0.01, wheelbase_scal
              speed_noise=0.02, steer_noise=0.01, position_noise=0.002, heading_noise=0.005)
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(dp)
-
-
-def _gxx(name, src):
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, name)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, os.path.join(ROOT, "tests", src)], check=True)
-    return C.CDLL(so)
+_d = T._d
 
 
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of K3n / K3p, built with the flags of tests/emul/Makefile."""
-    lib = _gxx("libplant_emul.so", os.path.join("emul_plant", "plant_emul.cpp"))
-    lib.pl_emu_philox.argtypes = [up, up, up]
-    lib.pl_emu_philox.restype = None
-    lib.pl_emu_noise.argtypes = [C.c_uint64, C.c_int32, C.c_int, C.c_int, lp, dp]
-    lib.pl_emu_noise.restype = None
-    lib.pl_emu_check.argtypes = [C.c_int, C.c_int, dp, dp]
-    lib.pl_emu_measure.argtypes = [dp, dp, dp, dp]
-    lib.pl_emu_measure.restype = None
-    lib.pl_emu_advance.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_int), dp, C.c_double, dp, dp, dp,
-                                   dp, dp, dp]
-    lib.pl_emu_stats.argtypes = [C.c_double] * 6 + [dp, dp, C.POINTER(C.c_int)]
-    lib.pl_emu_stats.restype = None
-    return lib
+    """The CPU twin of K3n / K3p (tests/emul_plant)."""
+    return twins.plant()
 
 
 # ------------------------------------------------------------------------- the draws, restated from the header's text
@@ -440,7 +415,6 @@ def test_one_call_equals_many_and_a_resumed_run():
 def test_closed_loop_matches_the_host_loop(N):
     """Every car against the reference's loop run with the project's host classes, one car at a time, with Plant.apply around
     get_control and the plant step."""
-    import test_host_mpc as H
     g1, g3, cum = _sim()
     steps, seed = 25, 12345
     starts = np.array([0, 12, 37, 88, 120, 150, 171])
@@ -448,8 +422,8 @@ def test_closed_loop_matches_the_host_loop(N):
     plant = Plant(seed=seed, **NOISY)
     host, statuses = [], []
     for i, w in enumerate(starts):
-        m, rp, car = H.build_world(obstacles=False)
-        mpc = H.make_mpc(car, N)
+        m, rp, car = T.build_world(obstacles=False)
+        mpc = T.make_mpc(car, N)
         one = plant.car(i)
         st = dict(pose=np.array([[rp.waypoints[w].x, rp.waypoints[w].y, rp.waypoints[w].psi]]), s=np.array([float(cum[w])]),
                   act=np.zeros((1, 2)))
@@ -577,11 +551,10 @@ def test_state_and_argument_errors():
 def test_batchmpc_rollout_takes_a_plant():
     """BatchMPC.rollout(..., plant=...) on a corridor table (no corridor='device'): an identity plant is the rollout without
     one, a noisy one returns its state under "plant", and the setting goes off again with the next call without one."""
-    import test_host_mpc as H
     from MPC import BatchMPC
     from scipy import sparse
     _, g3, cum = _sim()
-    m, rp, car = H.build_world(obstacles=False)
+    m, rp, car = T.build_world(obstacles=False)
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}

@@ -23,11 +23,7 @@ import scenarios
 
 G = M.GOLDEN
 N_WP = 302
-dp = C.POINTER(C.c_double)
-
-
-def _d(a):
-    return a.ctypes.data_as(dp)
+_d = T._d
 
 
 def _load(name):
@@ -76,7 +72,7 @@ def _weights(g4):
 
 
 def _real_world(obstacles=False):
-    """Real_Track with our host classes from the golden tables (as tests/test_host_mpc.py:build_world does for Sim_Track)."""
+    """Real_Track with our host classes from the golden tables (as tests/mpmpc_testlib.py:build_world does for Sim_Track)."""
     from map import Map
     from reference_path import ReferencePath
     from spatial_bicycle_models import BicycleModel

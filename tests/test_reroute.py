@@ -13,7 +13,6 @@ Fixture routes as in tests/test_routes.py, from the committed Sim_Track lap: L =
 on integer coordinates, where d2 is exact and ties are real ties."""
 import ctypes as C
 import os
-import subprocess
 import types
 
 import numpy as np
@@ -22,46 +21,21 @@ import pytest
 import mpmpc
 import mpmpc_testlib as T
 import scenarios
+import twins
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 E_ARG, E_STATE = -1, -3
 PI = np.pi
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
+_d, _i = T._d, T._i
 
 
 # ------------------------------------------------------------------------------------------------------------ fixtures
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of the projection and of the re-route, built with the flags of tests/emul/Makefile."""
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libproject_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, os.path.join(ROOT, "tests", "emul_project", "project_emul.cpp")], check=True)
-    lib = C.CDLL(so)
-    lib.project_emu.argtypes = [C.c_int, dp, dp, dp, dp, C.c_int, ip, C.c_int, dp, C.c_int, ip, C.c_double, ip, dp, dp, dp,
-                                C.POINTER(C.c_char_p)]
-    lib.reroute_twin_new.restype = C.c_void_p
-    lib.reroute_twin_new.argtypes = [C.c_int, C.c_int]
-    lib.reroute_twin_free.argtypes = [C.c_void_p]
-    lib.reroute_twin_why.restype = C.c_char_p
-    lib.reroute_twin_why.argtypes = [C.c_void_p]
-    lib.reroute_twin_set_routes.argtypes = [C.c_void_p, C.c_int, ip, ip]
-    lib.reroute_twin_set_car_routes.argtypes = [C.c_void_p, C.c_int, ip, ip]
-    lib.reroute_twin_rollout_init.argtypes = [C.c_void_p, C.c_int]
-    lib.reroute_twin_check_upload.argtypes = [C.c_void_p, C.c_int, ip, C.c_int]
-    lib.reroute_twin_routes.argtypes = [C.c_void_p, C.c_int, ip]
-    lib.reroute_twin_reroute.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, dp, dp, dp, dp, dp, ip, ip, dp, ip, dp, ip]
-    return lib
+    """The CPU twin of the projection and of the re-route (tests/emul_project)."""
+    return twins.project()
 
 
 SPANS = {"L": (0, 200, 1), "A": (0, 120, 0), "Bo": (100, 200, 0), "S": (0, 20, 1)}      # rows [lo, hi) of the lap, circular

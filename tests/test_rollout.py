@@ -10,11 +10,7 @@ import mpc_np as M
 import mpmpc
 import mpmpc_testlib as T
 
-dp = C.POINTER(C.c_double)
-
-
-def _d(a):
-    return a.ctypes.data_as(dp)
+_d = T._d
 
 
 def test_localise_and_advance_reproduce_reference_trace(emu):
@@ -66,7 +62,6 @@ def test_advance_ends_the_run_after_n_minus_one_fallbacks(emu):
 
 @pytest.mark.gpu
 def test_device_rollout_matches_host_loop():
-    import test_host_mpc as H
     g1 = np.load(M.GOLDEN + "/g1_path_sim_track.npz")
     g3 = np.load(M.GOLDEN + "/g3_corridor.npz")
     N, steps = 30, 25
@@ -76,8 +71,8 @@ def test_device_rollout_matches_host_loop():
     # ---- host: one controller per car, the reference's loop with our classes
     host = []
     for w in starts:
-        m, rp, car = H.build_world()
-        mpc = H.make_mpc(car, N)
+        m, rp, car = T.build_world()
+        mpc = T.make_mpc(car, N)
         car.s = float(cum[w])
         car.temporal_state.x, car.temporal_state.y, car.temporal_state.psi = rp.waypoints[w].x, rp.waypoints[w].y, rp.waypoints[w].psi
         for _ in range(steps):
@@ -107,7 +102,6 @@ def test_device_rollout_matches_host_loop():
 def test_device_rollout_matches_host_loop_at_a_long_horizon(emu):
     """The closed loop at N = 70 - one instance per WORKGROUP of two wavefronts on the device (reduced-native solver, general
     kernel on its tail), cold starts: every car follows the reference's own loop run with our host classes."""
-    import test_host_mpc as H
     g1 = np.load(M.GOLDEN + "/g1_path_sim_track.npz")
     tr = __import__("scenarios").sim_track()
     N, steps = 70, 6
@@ -117,8 +111,8 @@ def test_device_rollout_matches_host_loop_at_a_long_horizon(emu):
     B = starts.size
     host = []
     for w in starts:
-        m, rp, car = H.build_world()
-        mpc = H.make_mpc(car, N)
+        m, rp, car = T.build_world()
+        mpc = T.make_mpc(car, N)
         car.s = float(cum[w])
         car.temporal_state.x, car.temporal_state.y, car.temporal_state.psi = rp.waypoints[w].x, rp.waypoints[w].y, rp.waypoints[w].psi
         for _ in range(steps):

@@ -8,7 +8,6 @@ in a host loop on a second handle."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,9 +16,10 @@ import mpc_np as M
 import mpmpc
 import mpmpc_testlib as T
 import scenarios
+import twins
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+ip = C.POINTER(C.c_int32)
 E_ARG, E_STATE = -1, -3
 PLAN, PRED, ROWS = 1, 2, 4
 BASIC = ("s", "pose", "wp_id", "x0", "u", "status", "counter", "alive")
@@ -27,12 +27,7 @@ ALL = BASIC + ("plan", "pred_x", "pred_y", "ub", "lb")
 INTS = ("wp_id", "status", "counter", "alive")
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
+_d, _i = T._d, T._i
 
 
 def _usable(status):
@@ -47,21 +42,8 @@ def _eq(a, b):
 
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of the recorder kernels, built with the flags of tests/emul/Makefile."""
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libtrace_emul.so")
-    src = os.path.join(ROOT, "tests", "emul_trace", "trace_emul.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, src], check=True)
-    lib = C.CDLL(so)
-    lib.trace_emu_record_bytes.restype = C.c_longlong
-    lib.trace_emu_record_bytes.argtypes = [C.c_int] * 3
-    lib.trace_emu_entries.argtypes = [C.c_int] * 3
-    lib.trace_emu_record.argtypes = ([C.c_int] * 5 + [dp, dp, ip, ip, ip, ip, ip, dp, dp, dp, dp, dp, dp, dp, dp, dp,
-                                                      C.c_longlong, C.c_int] + [dp, dp, ip, dp, dp, ip, ip, ip, dp, dp, dp, dp, dp])
-    return lib
+    """The CPU twin of the recorder kernels (tests/emul_trace)."""
+    return twins.trace()
 
 
 def _twin_record(twin, N, fields, g1, circular, s, pose, a_in, alive, wp_id, status, counter, x0, u, cc, z, row_ub, row_lb,
@@ -516,10 +498,9 @@ def test_bookkeeping_of_the_trace():
 
 @pytest.mark.gpu
 def test_batch_mpc_rollout_returns_the_trace():
-    import test_host_mpc as H
     from MPC import BatchMPC
     from scipy import sparse
-    m, rp, car = H.build_world()
+    m, rp, car = T.build_world()
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}

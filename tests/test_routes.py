@@ -18,7 +18,6 @@ wp_id, status, alive, counter (and the audit's and perception's step indices and
 of the state, the audit and the trace to 1e-8 - the device-against-host rollout bound of DESIGN (K3)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -26,49 +25,21 @@ import pytest
 import mpmpc
 import mpmpc_testlib as T
 import scenarios
+import twins
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int8)
+bp = C.POINTER(C.c_int8)
 E_ARG, E_STATE = -1, -3
 NF = mpmpc.NUM_FIELDS
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
+_d, _i = T._d, T._i
 
 
 # ------------------------------------------------------------------------------------------------------------ fixtures
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of the route view, built with the flags of tests/emul/Makefile."""
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libroutes_emul.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, os.path.join(ROOT, "tests", "emul_routes", "routes_emul.cpp")], check=True)
-    lib = C.CDLL(so)
-    lib.routes_emu_fields.argtypes = [C.POINTER(mpmpc.Config), C.c_int, dp, dp, dp, C.c_int, dp, dp, ip, C.c_int, C.c_int, C.c_int,
-                                      ip, dp, dp, dp]
-    lib.routes_emu_current_waypoint.argtypes = [dp, C.c_int, C.c_int, C.c_double]
-    lib.routes_emu_past_open_end.argtypes = [C.c_int] * 4
-    lib.routes_emu_corridor.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, dp, dp, C.c_int,
-                                        ip, ip, dp, dp, C.c_int, C.c_double, C.c_double, dp, dp]
-    lib.routes_state_new.restype = C.c_void_p
-    lib.routes_state_new.argtypes = [C.c_int] * 3
-    lib.routes_state_free.argtypes = [C.c_void_p]
-    lib.routes_state_why.restype = C.c_char_p
-    lib.routes_state_why.argtypes = [C.c_void_p]
-    lib.routes_state_set_path.argtypes = [C.c_void_p, C.c_int]
-    lib.routes_state_set_routes.argtypes = [C.c_void_p, C.c_int, ip, ip, ip]
-    lib.routes_state_set_car_routes.argtypes = [C.c_void_p, C.c_int, ip, ip]
-    lib.routes_state_check_upload.argtypes = [C.c_void_p, C.c_int, ip]
-    lib.routes_state_check_batch.argtypes = [C.c_void_p, C.c_int]
-    return lib
+    """The CPU twin of the route view (tests/emul_routes)."""
+    return twins.routes()
 
 
 SPANS = {"L": (0, 200, 1), "A": (0, 120, 0), "Bo": (100, 200, 0), "S": (0, 20, 1)}      # rows [lo, hi) of the lap, circular
@@ -174,8 +145,8 @@ def test_twin_waypoint_arithmetic_on_route_slices(twin, track):
 
 
 def _g1_world(name="obstacles"):
-    g1 = np.load(os.path.join(ROOT, "tests", "golden", "g1_path_sim_track.npz"))
-    g3 = np.load(os.path.join(ROOT, "tests", "golden", "g3_corridor.npz"))
+    g1 = np.load(os.path.join(T.GOLDEN, "g1_path_sim_track.npz"))
+    g3 = np.load(os.path.join(T.GOLDEN, "g3_corridor.npz"))
     h, w = g1["grid_shape"]
     grid = np.ascontiguousarray(np.unpackbits(g1["grid_" + name])[:h * w].reshape(h, w).astype(np.int8))
     return g1, grid, float(g3["safety_margin"][0])
@@ -688,8 +659,8 @@ def test_batch_mpc_with_routes_end_to_end():
     from reference_path import ReferencePath
     from scipy import sparse
     from spatial_bicycle_models import BicycleModel
-    g1 = np.load(os.path.join(ROOT, "tests", "golden", "g1_path_sim_track.npz"))
-    g2 = np.load(os.path.join(ROOT, "tests", "golden", "g2_speed_profile.npz"))
+    g1 = np.load(os.path.join(T.GOLDEN, "g1_path_sim_track.npz"))
+    g2 = np.load(os.path.join(T.GOLDEN, "g2_speed_profile.npz"))
     hh, ww = g1["grid_shape"]
     grid = np.unpackbits(g1["grid_free"])[:hh * ww].reshape(hh, ww).astype(np.int8)
     m = Map.from_grid(grid, origin=[-1, -2], resolution=0.005)

@@ -98,10 +98,9 @@ def test_sharded_handles_at_long_horizons(N, weights, track, emu):
 @pytest.mark.gpu
 def test_sharded_batch_mpc_is_batch_mpc():
     """the class with the reference's constructor arguments, two handles on device 0, against BatchMPC"""
-    import test_host_mpc as H
     from MPC import BatchMPC
     from scipy import sparse
-    m, rp, car = H.build_world()
+    m, rp, car = T.build_world()
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     scn = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}
@@ -124,10 +123,9 @@ def test_non_diagonal_stage_weights_are_accepted_by_every_product_class():
     MPC, BatchMPC and ShardedBatchMPC take them and agree with each other; what is still refused - loudly, before anything is
     launched - is a matrix that is not symmetric or not positive semidefinite (ValueError from the host classes, MPMPC_E_ARG
     from the C side for a caller that fills mpmpc_config itself)."""
-    import test_host_mpc as H
     from MPC import MPC, BatchMPC
     from scipy import sparse
-    m, rp, car = H.build_world()
+    m, rp, car = T.build_world()
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     scn = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])

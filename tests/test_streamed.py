@@ -183,10 +183,9 @@ def test_streamed_batches_on_device_match_the_single_call(depth, track):
 def test_batch_mpc_stream_is_batch_mpc_call_by_call():
     """BatchMPC.get_control_stream: the class with the reference's constructor arguments, three calls in flight, against
     get_control_batch on the same batches (corridor from the controller's table, and corridor rows coming with the batch)."""
-    import test_host_mpc as H
     from MPC import BatchMPC
     from scipy import sparse
-    m, rp, car = H.build_world()
+    m, rp, car = T.build_world()
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     scn = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}
@@ -235,11 +234,10 @@ def test_batch_mpc_stream_ring_follows_corridor_and_settings():
     """the further handles of get_control_stream must carry what the controller's own handle carries - a corridor
     table built on the DEVICE (corridor="device"), a table rebuilt after the map changed, changed settings - and a ring of
     another depth closes the handles of the old one."""
-    import test_host_mpc as H
     from MPC import BatchMPC
     from map import Obstacle
     from scipy import sparse
-    m, rp, car = H.build_world(obstacles=False)
+    m, rp, car = T.build_world(obstacles=False)
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     scn = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}

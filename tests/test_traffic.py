@@ -8,86 +8,34 @@ discs (what cars reacting to each other cost before), all three settings togethe
 the recorder's rows from the trace alone."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import mpc_np as M
 import mpmpc
 import mpmpc_testlib as T
 import scenarios
+import twins
 from map import Map, Obstacle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 E_ARG, E_STATE = -1, -3
 TS = 0.05
 KEYS = ("s", "pose", "cc", "wp_id", "status", "counter", "alive")
 
 
-def _d(a):
-    return a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
-
-
-def _i32(a):
-    return None if a is None else np.ascontiguousarray(a, np.int32)
-
-
-def _gxx(name, src):
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, name)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, os.path.join(ROOT, "tests", src)], check=True)
-    return C.CDLL(so)
+_d, _i, _i32, _g1, _sm = T._d, T._i, T._i32, T.g1_world, T.safety_margin
 
 
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of K0t, built with the flags of tests/emul/Makefile."""
-    lib = _gxx("libtraffic_emul.so", os.path.join("emul_traffic", "traffic_emul.cpp"))
-    lib.tr_emu_check.argtypes = [C.c_int, C.c_int, ip, ip, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip]
-    lib.tr_emu_check_combined.argtypes = [C.c_int, ip, C.c_int, ip, C.c_int, C.c_int]
-    lib.tr_emu_check_movers.argtypes = [C.c_int, C.c_int, ip, ip, ip, dp, C.c_int, C.c_int, ip, C.c_int, C.c_int]
-    lib.tr_emu_layout.argtypes = [C.c_int, ip, ip, ip, ip]
-    lib.tr_emu_combine.argtypes = [C.c_int, ip, ip, C.c_int, ip, ip]
-    lib.tr_emu_combine.restype = None
-    lib.tr_emu_slots.argtypes = [C.c_int, dp, ip, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
-                                 C.c_double, ip]
-    return lib
+    """The CPU twin of K0t (tests/emul_traffic)."""
+    return twins.traffic()
 
 
 @pytest.fixture(scope="module")
 def car_twin():
     """The CPU twin of K0c (tests/emul_car): the step-0 condition on the fleets, the recorder's rows."""
-    lib = _gxx("libcar_corridor_emul.so", os.path.join("emul_car", "car_corridor_emul.cpp"))
-    lib.car_emu_rows.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double, C.c_int,
-                                 dp, dp, dp, dp, C.c_int, dp, dp, C.c_int, C.c_double, C.c_double, C.c_int, ip, ip, ip,
-                                 dp, dp, ip]
-    return lib
-
-
-_G1 = {}
-
-
-def _g1(track):
-    if track not in _G1:
-        g1 = np.load(M.GOLDEN + ("/g1_path_sim_track.npz" if track == "sim" else "/g1_path_real_track.npz"))
-        h, w = g1["grid_shape"]
-        grid = np.ascontiguousarray(np.unpackbits(g1["grid_free"])[:h * w].reshape(h, w).astype(np.int8))
-        _G1[track] = (g1, grid, tuple(float(v) for v in g1["origin"]), float(g1["resolution"][0]))
-    return _G1[track]
-
-
-def _sm(track):
-    return float(np.load(M.GOLDEN + "/g3o_%s_obstacles.npz" % track)["safety_margin"][0])
+    return twins.car()
 
 
 class Frame:
@@ -333,9 +281,7 @@ def _twin_rows(car_twin, track, disc_lists, wp_ids, N):
     g1, grid, origin, res = _g1(track)
     sm = _sm(track)
     arrs = [np.ascontiguousarray(g1[k], float) for k in ("x", "y", "psi", "ds_next", "border_ub", "border_lb")]
-    off = np.zeros(len(disc_lists) + 1, np.int32)
-    off[1:] = np.cumsum([len(d) for d in disc_lists])
-    flat = np.ascontiguousarray(np.concatenate([np.asarray(d, np.int32).reshape(-1, 3) for d in disc_lists]), np.int32)
+    off, flat = T.csr(disc_lists, 3, pad=False)
     B = len(disc_lists)
     wp = np.ascontiguousarray(wp_ids, np.int32)
     ub, lb, flag = np.zeros((B, N)), np.zeros((B, N)), np.zeros(B, np.int32)
@@ -671,11 +617,10 @@ def test_recorded_rows_follow_from_the_trace_alone(car_twin):
 
 @pytest.mark.gpu
 def test_batch_mpc_rollout_takes_traffic():
-    import test_host_mpc as H
     import traffic
     from MPC import BatchMPC
     from scipy import sparse
-    m, rp, car = H.build_world()
+    m, rp, car = T.build_world()
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}

@@ -10,7 +10,6 @@ After every step the tracks, the occupants, the horizon discs, the rows and the 
 plain, with walls, on two routes, under perception, with movers in the same fleet; off means off; zero times change nothing;
 one call equals single steps; the first step after rollout_init / rollout_reroute plans on frozen discs; the refusals."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -22,8 +21,9 @@ import scenarios
 import test_lookahead as TL
 import test_movers as TM
 import test_traffic as TT
+import twins
 
-dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int8)
+bp = C.POINTER(C.c_int8)
 E_ARG, E_STATE = -1, -3
 TS = TM.TS
 MAX_LEAD = TL.MAX_LEAD
@@ -35,45 +35,19 @@ OFF = LK.TRACK_OFF
 SHAPES = dict(sim=(30, 64, 12, 91, (2, 3, 4, 5, 6, 7, 8), 6), real=(70, 32, 8, 92, (2, 3, 4, 8), 4))
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
-
-
-def _i32(a):
-    return np.ascontiguousarray(a, np.int32)
+_d, _i, _i32 = T._d, T._i, T._i32
 
 
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of K3t, K0t<true>, K0ht and K0c<WALLS, true, true>, built with the flags of tests/test_movers.py's twins."""
-    lib = TM._gxx("libtraffic_lookahead_emul.so", os.path.join("emul_traffic_lookahead", "traffic_lookahead_emul.cpp"))
-    lib.tlk_emu_table_bytes.argtypes = [C.c_longlong, C.c_int, C.c_int]
-    lib.tlk_emu_table_bytes.restype = C.c_longlong
-    lib.tlk_emu_budget.restype = C.c_longlong
-    lib.tlk_emu_tracks.argtypes = [C.c_int, C.c_int, dp, ip, ip, ip, ip, C.c_int, C.c_int, dp, dp, dp, C.c_int, C.c_int, C.c_double,
-                                   C.c_double, C.c_double, ip, ip, dp]
-    lib.tlk_emu_tracks.restype = None
-    lib.tlk_emu_times_scan.argtypes = [C.c_int, dp, dp]
-    lib.tlk_emu_times_scan.restype = None
-    lib.tlk_emu_slots.argtypes = [C.c_int, dp, ip, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, ip, ip]
-    lib.tlk_emu_discs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, ip, ip, ip, ip, ip, dp, ip]
-    lib.tlk_emu_discs.restype = None
-    lib.tlk_emu_rows.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, dp, dp, C.c_int, dp, dp,
-                                 C.c_int, C.c_double, C.c_double, C.c_int, ip, ip, ip, ip, ip, ip, ip, ip, C.c_int, ip, dp, dp, ip]
-    return lib
+    """The CPU twin of K3t, K0t<true>, K0ht and K0c<WALLS, true, true> (tests/emul_traffic_lookahead)."""
+    return twins.traffic_lookahead()
 
 
 @pytest.fixture(scope="module")
 def car_twin():
     """The CPU twin of K0c (tests/emul_car): test_traffic's Fleet draws cars again whose plain step-0 row it finds blocked."""
-    lib = TM._gxx("libcar_corridor_emul.so", os.path.join("emul_car", "car_corridor_emul.cpp"))
-    lib.car_emu_rows.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int8), C.c_double, C.c_double, C.c_double, C.c_int,
-                                 dp, dp, dp, dp, C.c_int, dp, dp, C.c_int, C.c_double, C.c_double, C.c_int, ip, ip, ip, dp, dp, ip]
-    return lib
+    return twins.car()
 
 
 # ------------------------------------------------------------------------------------------------ the two sides of a step
@@ -147,14 +121,9 @@ def rows_twin(twin, c, wp, N, disc_lists, S=0, tz=None, look=None, walls=None, r
     """K0c's rows for one disc list per car (the lists K0c plans from at the step): S traffic slots at the end of every list and
     tz [B, S, N, 3] - the traffic rows; tz None - the plain-traffic rows.  look = (movers' rows per car, hz) or None."""
     B = len(disc_lists)
-    off = np.zeros(B + 1, np.int32)
-    off[1:] = np.cumsum([len(d) for d in disc_lists])
-    flat = _i32(np.concatenate([np.asarray(d, np.int32).reshape(-1, 3) for d in disc_lists]))
-    woff = wflat = car = hz = None
-    if walls is not None:
-        woff = np.zeros(B + 1, np.int32)
-        woff[1:] = np.cumsum([len(w) for w in walls])
-        wflat = _i32(np.concatenate([np.asarray(w, np.int32).reshape(-1, 4) for w in walls]))
+    off, flat = T.csr(disc_lists, 3, pad=False)
+    woff, wflat = T.csr(walls, 4, pad=False)
+    car = hz = None
     if look is not None:
         rows, hz = look
         car = np.zeros((B + 1, 2), np.int32)
@@ -752,11 +721,10 @@ def test_refusals(car_twin):
 
 @pytest.mark.gpu
 def test_batch_mpc_rollout_takes_lookahead_traffic():
-    import test_host_mpc as H
     import traffic
     from MPC import BatchMPC
     from scipy import sparse
-    m, rp, car = H.build_world()
+    m, rp, car = T.build_world()
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}

@@ -11,10 +11,6 @@ one static border point 55 % of the way to the other, sides alternating - and a 
 third gate.  The host classes alone give, for Sim_Track / Real_Track: 200 / 271 start waypoints, 198 / 204 rows that differ
 from the wall-free ones, 1 / 1 blocked by the barrier, 29 / 29 with a closed (0, 0) column; the tests assert >= 100, >= 1
 and >= 10, so that no comparison passes on empty worlds."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -22,11 +18,10 @@ import mpc_np as M
 import mpmpc
 import mpmpc_testlib as T
 import scenarios
+import twins
 from map import Map, Obstacle, line_aa
 from reference_path import ReferencePath
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int8)
 E_ARG, E_STATE = -1, -3
 N = 30
 TS = 0.05
@@ -34,80 +29,20 @@ KEYS = ("s", "pose", "cc", "wp_id", "status", "counter", "alive")
 CARS = dict(sim=(0.12, 0.06, 0.05), real=(0.3, 0.2, 0.3))      # length, width, reach of the footprint
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(dp)
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(ip)
-
-
-def _b(a):
-    return a.ctypes.data_as(bp)
+_d, _i, _b, _g1, _sm, _csr = T._d, T._i, T._b, T.g1_world, T.safety_margin, T.csr
 
 
 # ------------------------------------------------------------------------------------------------ fixtures and worlds
-_G1 = {}
-
-
-def _g1(track):
-    if track not in _G1:
-        g1 = np.load(M.GOLDEN + ("/g1_path_sim_track.npz" if track == "sim" else "/g1_path_real_track.npz"))
-        h, w = g1["grid_shape"]
-        grid = np.ascontiguousarray(np.unpackbits(g1["grid_free"])[:h * w].reshape(h, w).astype(np.int8))
-        _G1[track] = (g1, grid, tuple(float(v) for v in g1["origin"]), float(g1["resolution"][0]))
-    return _G1[track]
-
-
-def _sm(track):
-    return float(np.load(M.GOLDEN + "/g3o_%s_obstacles.npz" % track)["safety_margin"][0])
-
-
-def _build(name, src):
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, name)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-mfma", "-mavx2", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "multi-purpose-mpc_amd", "csrc"),
-                    "-shared", "-o", so, os.path.join(ROOT, "tests", src)], check=True)
-    return C.CDLL(so)
-
-
 @pytest.fixture(scope="module")
 def twin():
-    """The CPU twin of the wall kernels, built like tests/test_footprint.py's twin."""
-    lib = _build("libwalls_emul.so", os.path.join("emul_walls", "walls_emul.cpp"))
-    lib.wall_emu_check.argtypes = [C.c_int, C.c_int, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.wall_emu_cells.argtypes = [ip, ip, ip, C.c_long, ip]
-    lib.wall_emu_cells.restype = C.c_long
-    lib.wall_emu_world_grid.argtypes = [C.c_int, C.c_int, bp, C.c_int, ip, C.c_int, ip, bp]
-    lib.wall_emu_rows.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, dp, dp, C.c_int, dp, dp,
-                                  C.c_int, C.c_double, C.c_double, C.c_int, ip, ip, ip, ip, ip, dp, dp, ip]
-    lib.wall_emu_scan.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, ip, ip, ip, ip, C.c_int, dp,
-                                  C.c_double, dp]
-    lib.wall_emu_audit.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, ip, ip, ip, ip, C.c_double,
-                                   C.c_double, C.c_double, ip, dp]
-    return lib
+    """The CPU twin of the wall kernels (tests/emul_walls)."""
+    return twins.walls()
 
 
 @pytest.fixture(scope="module")
 def old_twins():
     """the twins of K0l and K0f as they stand (tests/emul_lidar, tests/emul_footprint): no walls"""
-    lid = _build("liblidar_emul.so", os.path.join("emul_lidar", "lidar_emul.cpp"))
-    lid.lid_emu_scan.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, ip, ip, C.c_int, dp, C.c_double,
-                                 dp, ip, ip]
-    fpl = _build("libfootprint_emul.so", os.path.join("emul_footprint", "footprint_emul.cpp"))
-    fpl.fp_emu_audit.argtypes = [C.c_int, C.c_int, bp, C.c_double, C.c_double, C.c_double, C.c_int, dp, ip, ip, C.c_double, C.c_double,
-                                 C.c_double, ip, dp]
-    return lid, fpl
-
-
-def _csr(lists, width):
-    lists = [np.asarray(a, np.int32).reshape(-1, width) for a in lists]
-    off = np.zeros(len(lists) + 1, np.int32)
-    off[1:] = np.cumsum([a.shape[0] for a in lists])
-    flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros((1, width), np.int32), np.int32)
-    return off, flat
+    return twins.lidar(), twins.footprint()
 
 
 def _gates(track):
@@ -728,10 +663,9 @@ def test_six_steps_at_once_equal_six_single_steps_with_walls():
 @pytest.mark.gpu
 def test_batchmpc_rollout_takes_walls():
     """BatchMPC.rollout(..., walls=...): boundaries in world coordinates per car; a later rollout is wall-free again"""
-    import test_host_mpc as H
     from scipy import sparse
     from MPC import BatchMPC
-    m, rp, car = H.build_world(obstacles=False)
+    m, rp, car = T.build_world(obstacles=False)
     Q, R, QN = sparse.diags([1.0, 0.0, 0.0]), sparse.diags([0.5, 0.0]), sparse.diags([1.0, 0.0, 0.0])
     ic = {'umin': np.array([0.0, -np.tan(0.66) / car.length]), 'umax': np.array([1.0, np.tan(0.66) / car.length])}
     sc = {'xmin': np.array([-np.inf] * 3), 'xmax': np.array([np.inf] * 3)}
