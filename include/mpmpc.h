@@ -562,6 +562,41 @@ int mpmpc_rollout_set_plant(mpmpc_handle h, int32_t B, const double* params, uin
                             const double* act0);
 int mpmpc_rollout_plant(mpmpc_handle h, int32_t B, double* act, double* meas, double* ey_max, double* ey_sq, int32_t* steps);
 int mpmpc_plant_noise(int32_t device, uint64_t seed, int32_t car0, int32_t B, int64_t j0, int32_t n_steps, double* out);
+/* Actuation delay and its compensation, per car and off by default - the one plant defect feedback alone cannot absorb: compute,
+ * radio and servo latency of a few control steps.  Per car: delay d (a command issued at step k reaches the wheels at step
+ * k + d) and assumed c (what the controller compensates for), integers in [0, MPMPC_DELAY_MAX]; c > d and c < d are legal.
+ * Every car carries a shift register of its last MPMPC_DELAY_MAX issued commands (v, delta), the newest first.
+ *    predict (K3d, in front of K3a, behind K3n; cars with alive == 1): from the pose the controller localises on (the plant's
+ *              measured pose, else the true one) and s, the controller's NOMINAL model is stepped through the c commands still
+ *              in flight, the oldest first, re-localising between the steps; K3a then localises on the predicted pose and s, so
+ *              wp_id, x0, the corridor, the QP and the plan belong to where the car will be when the command takes effect.
+ *              `now` keeps (e_y, e_psi, kappa) of the waypoint the car IS at.  A prediction that passes the end of the path
+ *              finishes the car (alive = 0) up to c steps early.
+ *    drive   (K3q, in place of K3b / K3p): the command, the infeasibility counter, u (the COMMANDED control) and the N - 1 ending
+ *              as without a delay (a run that ends there leaves the register untouched); exec = d > 0 ? queue[d - 1] : command;
+ *              the register shifts by one and takes the command; exec drives the car (through the plant when one is in force);
+ *              s advances by the odometry of `now`, not of the predicted x0.
+ * The exact operation order is stated in csrc/delay_core.hpp.  d = c = 0 reproduces the rollout without the setting bit for
+ * bit (with and without a plant); with no plant, d = c and a car driven on every step, pred_pose / pred_s of step k are
+ * bit-equal to pose / s at the beginning of step k + c.
+ * The audit, mpmpc_rollout_scan, perception, traffic, the movers, the recorder's pose and mpmpc_rollout_reroute keep reading
+ * the true pose; x0 and wp_id (state, recorder) are the predicted pose's.  A step with a delay and a lookahead
+ * (mpmpc_rollout_set_lookahead) both in force returns MPMPC_E_STATE: lookahead under delay is not supported.
+ *   mpmpc_rollout_set_delay  delay == NULL: off.  assumed == NULL: assumed = delay.  queue0 [B][MPMPC_DELAY_MAX][2]: the
+ *                           commands in flight, queue0[b][i] issued i + 1 steps ago (the first d executions are queue0[b][d-1]
+ *                           .. queue0[b][0]), or NULL for zeros: the car stands for d steps.  Validated on the host before
+ *                           anything is touched - MPMPC_E_ARG: d or c outside [0, MPMPC_DELAY_MAX], queue0 not finite, B outside
+ *                           [1, max_batch]; a refused call leaves the previous setting in force.  A step whose B differs returns
+ *                           MPMPC_E_STATE.  May be called before mpmpc_rollout_init or between steps; mpmpc_rollout_init with a
+ *                           delay in force keeps d and c and zeroes the registers - a resumed run sets the delay (with the saved
+ *                           register as queue0) after it.
+ *   mpmpc_rollout_delay     any pointer may be NULL.  queue [B][MPMPC_DELAY_MAX][2]: the registers; pred_pose [B][3], pred_s [B]:
+ *                           what K3a saw in the last step; now [B][3]: (e_y, e_psi, kappa) of where the car was in the last step
+ *                           (cars that were running).  MPMPC_E_STATE unless a step of B cars ran under the setting in force.
+ * A rollout without the setting launches exactly what it launched before. */
+#define MPMPC_DELAY_MAX 8
+int mpmpc_rollout_set_delay(mpmpc_handle h, int32_t B, const int32_t* delay, const int32_t* assumed, const double* queue0);
+int mpmpc_rollout_delay(mpmpc_handle h, int32_t B, double* queue, double* pred_pose, double* pred_s, double* now);
 
 /* Recorder: while the cars drive, the rollout appends one record per car and recorded step to a device-resident trace
  * (what src/simulation.py:117-157 logs per step on the host: x_log / y_log / v_log and MPC.current_prediction), and

@@ -381,7 +381,7 @@ class BatchMPC:
         return self.handle.rollout_reroute(routes, max_dist, max_heading)
 
     def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
-                walls=None, perception=None, routes=None, lookahead=None, plant=None):
+                walls=None, perception=None, routes=None, lookahead=None, plant=None, delay=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -431,6 +431,13 @@ class BatchMPC:
         else keeps the TRUE pose, "pose" of the returned dict: the audit, rollout_scan, perception, traffic and its plan
         tracks, the recorder's pose and `reroute`.  The returned dict also holds "plant": handle.rollout_plant() - act, meas,
         ey_max, ey_sq, steps (None when n_steps = 0).
+        delay: None - a command reaches the wheels in the step that issues it; a delay.Delay - per car, the command issued at
+        step k reaches the wheels at step k + steps, and the controller predicts its pose through the `assumed` commands in
+        flight with its own model and plans from there (K3d / K3q on the device, csrc/delay_core.hpp).  Combines with `plant`
+        (the prediction starts from the measured pose, the delayed command drives the plant); not with `lookahead`
+        (ValueError).  wp_id / x0 of the returned dict belong to the PREDICTED pose, "pose" and everything that senses or
+        judges the car stay true.  The returned dict also holds "delay": handle.rollout_delay() - queue, pred_pose, pred_s, now
+        (None when n_steps = 0).
         record: None - nothing is recorded; True or a dict of mpmpc.Handle.rollout_record's keyword arguments (capacity,
         plan, prediction, rows, stride; capacity defaults to the records `n_steps` yields) - the run is recorded on the
         device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of the whole run, arrays
@@ -479,6 +486,8 @@ class BatchMPC:
             raise ValueError("perception needs corridor='device' (update_corridor_from_map): the map lives on the device")
         if lookahead is not None and self.corridor_cols is None:
             raise ValueError("lookahead needs corridor='device' (update_corridor_from_map): it anticipates movers")
+        if delay is not None and lookahead is not None:
+            raise ValueError("delay and lookahead cannot be combined: the column leads would have to be offset by the assumed delay")
         if fleet is not None:
             self.handle.set_car_routes(routes)      # (the routes' geometry went up with set_routes)
         elif getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
@@ -524,12 +533,14 @@ class BatchMPC:
         elif getattr(self, "_plant_set", False):      # (off again; a controller that never had a plant calls nothing new)
             self.handle.rollout_set_plant(None)
             self._plant_set = False
+        delay_arrays = None if delay is None else delay.arrays(np.asarray(s).size)
         if cum is None:
             cum = np.cumsum(rp.segment_lengths)
         perceived = perception is not None and int(n_steps) > 0 and any(
             v is not None for v in (obstacles, movers, traffic, walls))
         if record is None or record is False:
             self.handle.rollout_init(self.model.Ts, cum, s, poses, cc0)
+            self._set_delay(delay_arrays)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             if audit is not None:
@@ -538,6 +549,8 @@ class BatchMPC:
                 out["perception"] = self.handle.rollout_perception() if perceived else None
             if plant is not None:
                 out["plant"] = self.handle.rollout_plant() if int(n_steps) > 0 else None
+            if delay is not None:
+                out["delay"] = self.handle.rollout_delay() if int(n_steps) > 0 else None
             return out
         kw = dict(record) if isinstance(record, dict) else {}
         stride = int(kw.get("stride", 1))
@@ -545,6 +558,7 @@ class BatchMPC:
         self.handle.rollout_record(B=np.asarray(s).size, **kw)
         try:
             self.handle.rollout_init(self.model.Ts, cum, s, poses, cc0)
+            self._set_delay(delay_arrays)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             out["trace"] = self.handle.rollout_trace()
@@ -554,9 +568,21 @@ class BatchMPC:
                 out["perception"] = self.handle.rollout_perception() if perceived else None
             if plant is not None:
                 out["plant"] = self.handle.rollout_plant() if int(n_steps) > 0 else None
+            if delay is not None:
+                out["delay"] = self.handle.rollout_delay() if int(n_steps) > 0 else None
         finally:
             self.handle.rollout_record(0, B=np.asarray(s).size)      # later rollouts are unrecorded again
         return out
+
+    def _set_delay(self, arrays):
+        """behind rollout_init, which zeroes the registers: the delay of this run (Delay.arrays) with its commands in flight, or
+        - None - off again"""
+        if arrays is not None:
+            self.handle.rollout_set_delay(*arrays)
+            self._delay_set = True
+        elif getattr(self, "_delay_set", False):      # (off again; a controller that never had a delay calls nothing new)
+            self.handle.rollout_set_delay(None)
+            self._delay_set = False
 
     def rollout_scan(self, lidar):
         """Lidar scans of the cars of the last `rollout`, where it left them and in the worlds of its last step (the map

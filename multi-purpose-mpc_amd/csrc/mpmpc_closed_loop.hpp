@@ -737,6 +737,9 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   if (h->pl.B > 0) {              // a plant in force keeps its parameters; its actuators and accumulators start over
     if (int rc = plant_reset(h, sl, h->pl.B, nullptr)) return rc;
   }
+  if (h->dl.B > 0) {              // ... and a delay in force keeps d and c; its registers start over (zeros: the cars stand for d steps)
+    if (int rc = delay_reset(h, sl, h->dl.B, nullptr)) return rc;
+  }
   return aud_reset(h, B);         // ... and so does the audit (mpmpc_footprint.hpp)
 }
 

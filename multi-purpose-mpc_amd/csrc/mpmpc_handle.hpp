@@ -216,6 +216,20 @@ struct PlantState {
   bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_plant)
 };
 
+// actuation delay of the rollout and its compensation (mpmpc_rollout_set_delay; the law: delay_core.hpp): the setting, the cars'
+// command registers, the predicted poses and arc lengths K3a localises on and the spatial state of where the cars are - memory
+// of its own, sized by max_batch when first set
+struct DelayState {
+  int B = 0;                // > 0: a delay is in force for B cars
+  Buf<int> delay, assumed;  // [max_batch] each: d and c
+  Buf<double> queue;        // [max_batch][DL_MAX][2]: the issued (v, delta), the newest first
+  Buf<double> pred_pose;    // [max_batch][3]: the pose K3a saw in the last step
+  Buf<double> pred_s;       // [max_batch]: ... and the arc length
+  Buf<double> now;          // [max_batch][3]: x0[0], x0[1] and kappa of the waypoint the car was at in the last step
+  Buf<int> now_wp;          // [max_batch]: that waypoint's global row
+  bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_delay)
+};
+
 // per-batch inputs and host staging
 struct IoState {
   // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
@@ -262,6 +276,7 @@ struct mpmpc_handle_s {
   LookState look;
   TlkState tlk;
   PlantState pl;
+  DelayState dl;
   IoState io;
   // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
   // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that

@@ -1,5 +1,5 @@
 // mpmpc_rollout_step of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind every feature of a
-// step: mpmpc_closed_loop.hpp - the kernels K0c, K0m, K0t, K3a, K3b, K3r -, mpmpc_plant.hpp, mpmpc_lookahead.hpp,
+// step: mpmpc_closed_loop.hpp - the kernels K0c, K0m, K0t, K3a, K3b, K3r -, mpmpc_plant.hpp, mpmpc_delay.hpp, mpmpc_lookahead.hpp,
 // mpmpc_perception.hpp and mpmpc_footprint.hpp).  A step is decided once (plan_step: every check and lay-out, in a fixed order),
 // then its kernels are enqueued in stream order, each from the one enqueue_* function that launches it, then the handle
 // remembers what ran (step_ran).  DESIGN.md section 4, "A rollout step", is the same list.
@@ -7,7 +7,7 @@
 
 // What the step loop needs, and nothing else (host only).
 struct StepPlan {
-  bool per_car, discs, walls, traffic, perceiving, plant, auditing, looking, ahead_traffic, recording;
+  bool per_car, discs, walls, traffic, perceiving, plant, delaying, auditing, looking, ahead_traffic, recording;
   int movers;
   MapView map;
   PathGeom geom;
@@ -20,8 +20,8 @@ struct StepPlan {
 };
 
 // Every check and lay-out of a step of B cars, in this order (the first refusal that applies is the call's): the rollout's
-// state, n_steps, the per-car settings' B, stale generations, the recorder's B and capacity, the plant's B, the audit,
-// perception, the routes, the lookahead.
+// state, n_steps, the per-car settings' B, stale generations, the recorder's B and capacity, the plant's B, the delay's B, the
+// audit, perception, the routes, the lookahead, the delay under a lookahead.
 static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
                               "call mpmpc_rollout_init again (or use a second handle for single solves)")) return rc;
@@ -45,6 +45,8 @@ static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   }
   p.plant = h->pl.B > 0;
   if (p.plant && h->pl.B != B) return fail(MPMPC_E_STATE, "the plant was set for another number of cars (mpmpc_rollout_set_plant)");
+  p.delaying = h->dl.B > 0;
+  if (p.delaying && h->dl.B != B) return fail(MPMPC_E_STATE, "the delay was set for another number of cars (mpmpc_rollout_set_delay)");
   if (int rc = aud_check_step(h, B)) return rc;
   p.auditing = h->aud.mode != FP_MODE_OFF;
   HIP_TRY(hipSetDevice(h->cfg.device));
@@ -71,6 +73,9 @@ static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
     if (int rc = look_check_step(h, B, p.movers, p.traffic, &p.looking, &p.ahead_traffic)) return rc;
   }
   p.look = LookTrafficView{h->look.car.get(), h->look.tab.get(), h->tlk.tz.get(), o.tr_S};
+  if (p.delaying && h->look.max_lead > 0)      // (column leads and plan tracks would have to be offset by c: out of scope)
+    return fail(MPMPC_E_STATE, "a delay and a lookahead are both in force: lookahead under delay is not supported "
+                               "(mpmpc_rollout_set_delay / mpmpc_rollout_set_lookahead: switch one off)");
   return MPMPC_OK;
 }
 
@@ -101,11 +106,20 @@ static void enqueue_movers(mpmpc_handle h, Slot& sl, int B, long long k, const S
                      m.radius, m.prm, m.dst, h->obs.obst_discs.get(), h->obs.obst_off.get(), B, p.route);
 }
 
-// K3a; with a plant it localises on the poses K3n measured
+// K3d: from the poses K3n measured (plant) or the true ones, through the commands in flight
+static void enqueue_delay_predict(mpmpc_handle h, Slot& sl, int B, const StepPlan& p) {
+  hipLaunchKernelGGL(mpmpc_delay_predict_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.wheelbase, h->ro.Ts,
+                     h->ro.cum.get(), h->cor.gx.get(), h->cor.gy.get(), h->cor.gpsi.get(), h->tab.kappa.get(), h->ro.s.get(),
+                     p.plant ? h->pl.meas.get() : h->ro.pose.get(), h->ro.alive.get(), h->dl.assumed.get(), h->dl.queue.get(),
+                     h->dl.pred_pose.get(), h->dl.pred_s.get(), h->dl.now.get(), h->dl.now_wp.get(), p.route);
+}
+
+// K3a; with a plant it localises on the poses K3n measured, with a delay on what K3d predicted from them
 static void enqueue_localise(mpmpc_handle h, Slot& sl, int B, const StepPlan& p) {
+  const double* s = p.delaying ? h->dl.pred_s.get() : h->ro.s.get();
+  const double* pose = p.delaying ? h->dl.pred_pose.get() : p.plant ? h->pl.meas.get() : h->ro.pose.get();
   hipLaunchKernelGGL(mpmpc_localise_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.N, h->cfg.circular ? 1 : 0,
-                     h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, h->ro.s, p.plant ? h->pl.meas.get() : h->ro.pose.get(), h->ro.alive,
-                     h->io.wp_id, h->io.x0, h->ro.shift, p.route);
+                     h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, s, pose, h->ro.alive, h->io.wp_id, h->io.x0, h->ro.shift, p.route);
 }
 
 // K0c: one argument pack, and one choice of its six instantiations by (walls, looking, ahead_traffic)
@@ -123,10 +137,20 @@ static void enqueue_car_corridor(mpmpc_handle h, Slot& sl, int B, const StepPlan
   else p.walls ? launch_car_corridor<true, false, false>(h, sl, B, p, LookNone{}) : launch_car_corridor<false, false, false>(h, sl, B, p, LookNone{});
 }
 
-// K3b, or - with a plant - K3p in its place
+// K3q, in place of K3b (PLANT = false) or K3p (true)
+template <bool PLANT>
+static void enqueue_advance_delay(mpmpc_handle h, Slot& sl, int B, const PlantView& pv) {
+  hipLaunchKernelGGL(mpmpc_advance_delay_kernel<PLANT>, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase,
+                     h->ro.Ts, sl.status, sl.z, h->io.cc, h->ro.counter.get(), h->ro.alive.get(), h->ro.pose.get(), h->ro.s.get(), h->ro.u.get(),
+                     delay_view(h), pv);
+}
+
+// K3b, or - with a plant - K3p in its place, or - with a delay - K3q in place of either
 static void enqueue_advance(mpmpc_handle h, Slot& sl, int B, long long k, const StepPlan& p) {
   const dim3 grid((B * h->cfg.N + 255) / 256);
-  if (p.plant)
+  if (p.delaying)
+    p.plant ? enqueue_advance_delay<true>(h, sl, B, plant_view(h, k)) : enqueue_advance_delay<false>(h, sl, B, PlantView{});
+  else if (p.plant)
     hipLaunchKernelGGL(mpmpc_advance_plant_kernel, grid, dim3(256), 0, sl.stream, B, h->cfg.N, h->cfg.wheelbase, h->ro.Ts, h->tab.kappa.get(),
                        h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter.get(), h->ro.alive.get(), h->ro.pose.get(), h->ro.s.get(),
                        h->ro.u.get(), p.route, plant_view(h, k));
@@ -151,6 +175,7 @@ static void step_ran(mpmpc_handle h, int B, const StepPlan& p) {
   h->obs.car_rows = h->obs.discs_live = p.per_car;
   if (p.perceiving) h->per.B = B;
   if (p.plant) h->pl.ran = true;
+  if (p.delaying) h->dl.ran = true;
   h->look.ran_B = p.looking ? B : 0;
   h->look.ran_n = p.looking ? p.movers : 0;
   h->tlk.ran_B = p.ahead_traffic ? B : 0;
@@ -173,6 +198,7 @@ extern "C" int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     if (p.perceiving && p.movers > 0) enqueue_movers(h, sl, B, k, p);                      // K0m
     if (p.perceiving) per_enqueue_step(h, sl, B, k);                                       // K0s
     if (p.plant) plant_enqueue_measure(h, sl, B, k);                                       // K3n
+    if (p.delaying) enqueue_delay_predict(h, sl, B, p);                                    // K3d
     enqueue_localise(h, sl, B, p);                                                         // K3a
     if (!p.perceiving && p.movers > 0) enqueue_movers(h, sl, B, k, p);                     // K0m
     if (p.auditing) aud_enqueue_step(h, sl, B, k, p.per_car);                              // K0f: pose k in world k

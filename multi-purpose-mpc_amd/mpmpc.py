@@ -186,6 +186,8 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_set_plant.argtypes = [h, C.c_int32, _dp, C.c_uint64, C.c_int32, C.c_int64, _dp]
     lib.mpmpc_rollout_plant.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp, _ip]
     lib.mpmpc_plant_noise.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _dp]
+    lib.mpmpc_rollout_set_delay.argtypes = [h, C.c_int32, _ip, _ip, _dp]
+    lib.mpmpc_rollout_delay.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp]
     lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_recorded.argtypes = [h, _ip, _ip]
     lib.mpmpc_rollout_trace.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
@@ -251,6 +253,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_check_routes", "mpmpc_set_routes", "mpmpc_set_car_routes",
            "mpmpc_project", "mpmpc_rollout_reroute", "mpmpc_rollout_routes",
            "mpmpc_rollout_set_plant", "mpmpc_rollout_plant", "mpmpc_plant_noise",
+           "mpmpc_rollout_set_delay", "mpmpc_rollout_delay",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -656,6 +659,41 @@ class Handle:
         out = dict(act=np.zeros((B, 2)), meas=np.zeros((B, 3)), ey_max=np.zeros(B), ey_sq=np.zeros(B), steps=np.zeros(B, np.int32))
         self._check(self.lib.mpmpc_rollout_plant(self._h, B, _d(out["act"]), _d(out["meas"]), _d(out["ey_max"]), _d(out["ey_sq"]),
                                                  _i(out["steps"])))
+        return out
+
+    # --- actuation delay of the rollout and its compensation, per car
+    DELAY_FIELDS = ("queue", "pred_pose", "pred_s", "now")
+
+    def rollout_set_delay(self, delay, assumed=None, queue0=None):
+        """The latency of the rollouts that follow (K3d / K3q; the law: csrc/delay_core.hpp): delay [B] ints in [0, 8] - the
+        command a car's controller issues at step k reaches its wheels at step k + delay - or None for no delay (the default);
+        assumed [B] ints in [0, 8]: the delay the controller compensates for by predicting its pose through the commands in
+        flight (None: assumed = delay; zeros: no compensation); queue0 [B, 8, 2]: the commands (v, delta) in flight, queue0[:, i]
+        issued i + 1 steps ago (None: zeros, the car stands for `delay` steps).  delay.Delay.arrays(B) gives all three.  The true
+        pose stays rollout_state()["pose"]; wp_id and x0 are those of the predicted pose (rollout_delay()["pred_pose"]).  Not
+        together with a lookahead.  May be called before rollout_init or between rollout_step calls; rollout_init zeroes the
+        registers, so a resumed run sets the delay after it."""
+        if delay is None:
+            self._check(self.lib.mpmpc_rollout_set_delay(self._h, 0, None, None, None))
+            return
+        d = np.asarray(delay)
+        a = d if assumed is None else np.asarray(assumed)
+        if d.ndim != 1 or a.shape != d.shape:
+            raise ValueError("delay and assumed must be [B]")
+        for v in (d, a):
+            if v.size and (not np.array_equal(v, np.floor(v)) or np.any(np.abs(v) > 2 ** 30)):
+                raise ValueError("delay and assumed must be integers")
+        d, a = (np.ascontiguousarray(v, dtype=np.int32) for v in (d, a))
+        q = None if queue0 is None else np.ascontiguousarray(queue0, dtype=np.float64).reshape(d.size, 8, 2)
+        self._check(self.lib.mpmpc_rollout_set_delay(self._h, d.size, _i(d), _i(a), _d(q)))
+
+    def rollout_delay(self):
+        """-> dict of the delay's per-car state: queue [B, 8, 2] the issued (v, delta), the newest first; pred_pose [B, 3] and
+        pred_s [B] what the controller localised on in the last step; now [B, 3] = (e_y, e_psi, kappa) of the waypoint the car
+        was at in the last step."""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        out = dict(queue=np.zeros((B, 8, 2)), pred_pose=np.zeros((B, 3)), pred_s=np.zeros(B), now=np.zeros((B, 3)))
+        self._check(self.lib.mpmpc_rollout_delay(self._h, B, _d(out["queue"]), _d(out["pred_pose"]), _d(out["pred_s"]), _d(out["now"])))
         return out
 
     # --- footprint audit of the rollout: contact and clearance of every car, every step, accumulated on the device
