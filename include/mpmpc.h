@@ -597,6 +597,45 @@ int mpmpc_plant_noise(int32_t device, uint64_t seed, int32_t car0, int32_t B, in
 #define MPMPC_DELAY_MAX 8
 int mpmpc_rollout_set_delay(mpmpc_handle h, int32_t B, const int32_t* delay, const int32_t* assumed, const double* queue0);
 int mpmpc_rollout_delay(mpmpc_handle h, int32_t B, double* queue, double* pred_pose, double* pred_s, double* now);
+/* Pose estimator, per car and off by default: a 3-state extended Kalman filter on the world pose (x, y, psi) in the controller's
+ * NOMINAL model, between the measurement and the controller (K3e, behind K3n and in front of K3d / K3a; cars with alive == 1).
+ * With it everything the controller localises on takes the ESTIMATE instead of the measured (plant) or true pose: K3a without a
+ * delay, K3d's starting pose with one.  The audit, mpmpc_rollout_scan, perception, traffic and its tracks, the recorder,
+ * mpmpc_rollout_reroute and the plant's statistics keep the true pose.  Per car and step k, j = k - step0, z = the plant's
+ * measured pose (else the true one):
+ *    not primed:   est = z, cov = diag(p0_xy, p0_xy, p0_psi), primed - whatever the schedule says
+ *    time update:  the nominal model's pose step on est with the command the controller believes reached the wheels in step
+ *                  k - 1 (without a delay u of the state; with one entry c of the register, c the car's assumed delay);
+ *                  P <- F P F^T + diag(q_xy, q_xy, q_psi) with the model's Jacobian F at the heading before the step
+ *    measurement:  if j mod period == 0 and the measurement is not dropped (probability drop; a draw of (seed, car0 + car, j)):
+ *                  three sequential scalar updates in the order x, y, psi, the heading innovation wrapped to [-pi, pi)
+ *    statistics:   from the true pose as the step finds it
+ * The exact operation order is stated in csrc/estimator_core.hpp.  With an identity or absent plant, no noise and no delay (or
+ * assumed == delay, every car driven) every innovation is exactly 0: est keeps the bits of the true pose and the rollout is the
+ * rollout without the estimator, bit for bit.  Results depend on (seed, car0 + car, j) and the car's own state only.
+ *   mpmpc_rollout_set_estimator  params == NULL: off.  params [B][MPMPC_ESTIMATOR_PARAMS] = q_xy, q_psi (finite, >= 0), r_xy,
+ *                           r_psi (finite, > 0), p0_xy, p0_psi (finite, >= 0), period (an integer >= 1, as a double), drop in
+ *                           [0, 1).  est0 [B][3] and cov0 [B][6] (the upper triangle Pxx, Pxy, Pxp, Pyy, Pyp, Ppp): both or
+ *                           neither; given, they prime the cars - a saved run is resumed with what mpmpc_rollout_estimator
+ *                           returned, step0 = -(the step of the save) and, for the command of the last step, the saved register
+ *                           as mpmpc_rollout_set_delay's queue0 (mpmpc_rollout_init zeroes u: without a delay the first time
+ *                           update of a resumed run is taken with the command (0, 0)).  Validated on the host before anything
+ *                           is touched - MPMPC_E_ARG, and the previous setting stays in force.  A step whose B differs returns
+ *                           MPMPC_E_STATE; so does a step under a delay with a car whose assumed delay is MPMPC_DELAY_MAX (the
+ *                           command of the last step has left the register).  May be called before mpmpc_rollout_init or
+ *                           between steps; mpmpc_rollout_init keeps the parameters, un-primes every car and zeroes the
+ *                           statistics - a resumed run sets the estimator after it.
+ *   mpmpc_rollout_estimator any pointer may be NULL.  est [B][3], cov [B][6]: as the last step's K3e left them; err2_max, err2_sum
+ *                           [B]: maximum and sum over the car's steps of (est_x - x)^2 + (est_y - y)^2; meas2_sum [B]: the same
+ *                           sum of z (every step, used or not); head2_sum [B]: the sum of the wrapped heading error of the
+ *                           estimate, squared; used, steps [B]: measurements taken (priming included) and K3e steps.
+ *                           MPMPC_E_STATE unless a step of B cars ran under the setting in force.
+ * A rollout without the setting launches exactly what it launched before. */
+#define MPMPC_ESTIMATOR_PARAMS 8
+int mpmpc_rollout_set_estimator(mpmpc_handle h, int32_t B, const double* params, uint64_t seed, int32_t car0, int64_t step0,
+                                const double* est0, const double* cov0);
+int mpmpc_rollout_estimator(mpmpc_handle h, int32_t B, double* est, double* cov, double* err2_max, double* err2_sum, double* meas2_sum,
+                            double* head2_sum, int32_t* used, int32_t* steps);
 
 /* Recorder: while the cars drive, the rollout appends one record per car and recorded step to a device-resident trace
  * (what src/simulation.py:117-157 logs per step on the host: x_log / y_log / v_log and MPC.current_prediction), and

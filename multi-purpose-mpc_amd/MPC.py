@@ -381,7 +381,7 @@ class BatchMPC:
         return self.handle.rollout_reroute(routes, max_dist, max_heading)
 
     def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
-                walls=None, perception=None, routes=None, lookahead=None, plant=None, delay=None):
+                walls=None, perception=None, routes=None, lookahead=None, plant=None, delay=None, estimator=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -438,6 +438,15 @@ class BatchMPC:
         (ValueError).  wp_id / x0 of the returned dict belong to the PREDICTED pose, "pose" and everything that senses or
         judges the car stay true.  The returned dict also holds "delay": handle.rollout_delay() - queue, pred_pose, pred_s, now
         (None when n_steps = 0).
+        estimator: None - the controller localises on the measured pose (plant) or the true one; an estimator.Estimator - per
+        car a 3-state extended Kalman filter on the world pose in the controller's nominal model, with a measurement schedule
+        (period, random dropouts), between the measurement and the controller (K3e on the device, csrc/estimator_core.hpp):
+        every step it takes the model's step with the command believed executed in the last step and, when the measurement is
+        available, the measured pose; the controller localises on the ESTIMATE (under `delay` it predicts from it).  Combines
+        with every other option (not with an assumed delay of 8: ValueError); with no noise and nothing to estimate the
+        estimate keeps the bits of the true pose.  "pose" and everything that senses or judges the car stay true.  The returned
+        dict also holds "estimator": handle.rollout_estimator() - est, cov, err2_max, err2_sum, meas2_sum, head2_sum, used,
+        steps (None when n_steps = 0).
         record: None - nothing is recorded; True or a dict of mpmpc.Handle.rollout_record's keyword arguments (capacity,
         plan, prediction, rows, stride; capacity defaults to the records `n_steps` yields) - the run is recorded on the
         device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of the whole run, arrays
@@ -488,6 +497,9 @@ class BatchMPC:
             raise ValueError("lookahead needs corridor='device' (update_corridor_from_map): it anticipates movers")
         if delay is not None and lookahead is not None:
             raise ValueError("delay and lookahead cannot be combined: the column leads would have to be offset by the assumed delay")
+        if estimator is not None and delay is not None and np.any(delay.arrays(np.asarray(s).size)[1] >= 8):
+            raise ValueError("estimator and an assumed delay of 8 cannot be combined: the command that reached the wheels in the "
+                             "last step has left the register by then")
         if fleet is not None:
             self.handle.set_car_routes(routes)      # (the routes' geometry went up with set_routes)
         elif getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
@@ -534,6 +546,7 @@ class BatchMPC:
             self.handle.rollout_set_plant(None)
             self._plant_set = False
         delay_arrays = None if delay is None else delay.arrays(np.asarray(s).size)
+        est_args = None if estimator is None else (estimator.params(np.asarray(s).size), estimator.seed, estimator.car0, estimator.step0)
         if cum is None:
             cum = np.cumsum(rp.segment_lengths)
         perceived = perception is not None and int(n_steps) > 0 and any(
@@ -541,6 +554,7 @@ class BatchMPC:
         if record is None or record is False:
             self.handle.rollout_init(self.model.Ts, cum, s, poses, cc0)
             self._set_delay(delay_arrays)
+            self._set_estimator(est_args)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             if audit is not None:
@@ -551,6 +565,8 @@ class BatchMPC:
                 out["plant"] = self.handle.rollout_plant() if int(n_steps) > 0 else None
             if delay is not None:
                 out["delay"] = self.handle.rollout_delay() if int(n_steps) > 0 else None
+            if estimator is not None:
+                out["estimator"] = self.handle.rollout_estimator() if int(n_steps) > 0 else None
             return out
         kw = dict(record) if isinstance(record, dict) else {}
         stride = int(kw.get("stride", 1))
@@ -559,6 +575,7 @@ class BatchMPC:
         try:
             self.handle.rollout_init(self.model.Ts, cum, s, poses, cc0)
             self._set_delay(delay_arrays)
+            self._set_estimator(est_args)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             out["trace"] = self.handle.rollout_trace()
@@ -570,6 +587,8 @@ class BatchMPC:
                 out["plant"] = self.handle.rollout_plant() if int(n_steps) > 0 else None
             if delay is not None:
                 out["delay"] = self.handle.rollout_delay() if int(n_steps) > 0 else None
+            if estimator is not None:
+                out["estimator"] = self.handle.rollout_estimator() if int(n_steps) > 0 else None
         finally:
             self.handle.rollout_record(0, B=np.asarray(s).size)      # later rollouts are unrecorded again
         return out
@@ -583,6 +602,15 @@ class BatchMPC:
         elif getattr(self, "_delay_set", False):      # (off again; a controller that never had a delay calls nothing new)
             self.handle.rollout_set_delay(None)
             self._delay_set = False
+
+    def _set_estimator(self, args):
+        """behind rollout_init, like the delay: the estimator of this run (params, seed, car0, step0), or - None - off again"""
+        if args is not None:
+            self.handle.rollout_set_estimator(*args)
+            self._estimator_set = True
+        elif getattr(self, "_estimator_set", False):      # (off again; a controller that never had an estimator calls nothing new)
+            self.handle.rollout_set_estimator(None)
+            self._estimator_set = False
 
     def rollout_scan(self, lidar):
         """Lidar scans of the cars of the last `rollout`, where it left them and in the worlds of its last step (the map

@@ -740,6 +740,9 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   if (h->dl.B > 0) {              // ... and a delay in force keeps d and c; its registers start over (zeros: the cars stand for d steps)
     if (int rc = delay_reset(h, sl, h->dl.B, nullptr)) return rc;
   }
+  if (h->es.B > 0) {              // ... and an estimator in force keeps its parameters; every car is un-primed, the statistics start over
+    if (int rc = est_reset(h, sl, h->es.B, nullptr, nullptr)) return rc;
+  }
   return aud_reset(h, B);         // ... and so does the audit (mpmpc_footprint.hpp)
 }
 

@@ -107,6 +107,11 @@ int mpmpc_rollout_set_delay(mpmpc_handle h, int32_t B, const int32_t* delay, con
   if (int rc = delay_reset(h, sl, B, queue0)) return rc;
   HIP_TRY(hipStreamSynchronize(sl.stream));      // the caller's arrays have been read
   h->dl.B = B;
+  h->dl.max_assumed = 0;      // (kept on the host: a step under an estimator refuses c = DL_MAX)
+  for (int i = 0; i < B; ++i) {
+    const int c = (assumed ? assumed : delay)[i];
+    if (c > h->dl.max_assumed) h->dl.max_assumed = c;
+  }
   return MPMPC_OK;
 }
 

@@ -228,6 +228,23 @@ struct DelayState {
   Buf<double> now;          // [max_batch][3]: x0[0], x0[1] and kappa of the waypoint the car was at in the last step
   Buf<int> now_wp;          // [max_batch]: that waypoint's global row
   bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_delay)
+  int max_assumed = 0;      // the largest c of the cars the setting is in force for (host copy: plan_step)
+};
+
+// pose estimator of the rollout (mpmpc_rollout_set_estimator; the law: estimator_core.hpp): the setting, every car's estimate,
+// covariance and statistics - memory of its own, sized by max_batch when first set
+struct EstState {
+  int B = 0;                // > 0: an estimator is in force for B cars
+  unsigned long long seed = 0;
+  int car0 = 0;
+  long long step0 = 0;
+  Buf<double> prm;          // [max_batch][ES_PARAMS]
+  Buf<double> est;          // [max_batch][3]: the pose the controller localises on
+  Buf<double> cov;          // [max_batch][ES_COV]: the upper triangle Pxx, Pxy, Pxp, Pyy, Pyp, Ppp
+  Buf<int> primed;          // [max_batch]
+  Buf<double> stats;        // [ES_STATS][max_batch]: err2_max, err2_sum, meas2_sum, head2_sum
+  Buf<int> count;           // [2][max_batch]: used, steps
+  bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_estimator)
 };
 
 // per-batch inputs and host staging
@@ -277,6 +294,7 @@ struct mpmpc_handle_s {
   TlkState tlk;
   PlantState pl;
   DelayState dl;
+  EstState es;
   IoState io;
   // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
   // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that

@@ -1,5 +1,5 @@
 // mpmpc_rollout_step of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind every feature of a
-// step: mpmpc_closed_loop.hpp - the kernels K0c, K0m, K0t, K3a, K3b, K3r -, mpmpc_plant.hpp, mpmpc_delay.hpp, mpmpc_lookahead.hpp,
+// step: mpmpc_closed_loop.hpp - the kernels K0c, K0m, K0t, K3a, K3b, K3r -, mpmpc_plant.hpp, mpmpc_delay.hpp, mpmpc_estimator.hpp, mpmpc_lookahead.hpp,
 // mpmpc_perception.hpp and mpmpc_footprint.hpp).  A step is decided once (plan_step: every check and lay-out, in a fixed order),
 // then its kernels are enqueued in stream order, each from the one enqueue_* function that launches it, then the handle
 // remembers what ran (step_ran).  DESIGN.md section 4, "A rollout step", is the same list.
@@ -7,7 +7,7 @@
 
 // What the step loop needs, and nothing else (host only).
 struct StepPlan {
-  bool per_car, discs, walls, traffic, perceiving, plant, delaying, auditing, looking, ahead_traffic, recording;
+  bool per_car, discs, walls, traffic, perceiving, plant, delaying, estimating, auditing, looking, ahead_traffic, recording;
   int movers;
   MapView map;
   PathGeom geom;
@@ -21,7 +21,8 @@ struct StepPlan {
 
 // Every check and lay-out of a step of B cars, in this order (the first refusal that applies is the call's): the rollout's
 // state, n_steps, the per-car settings' B, stale generations, the recorder's B and capacity, the plant's B, the delay's B, the
-// audit, perception, the routes, the lookahead, the delay under a lookahead.
+// estimator's B, the audit, perception, the routes, the lookahead, the delay under a lookahead, the estimator under an assumed
+// delay of DL_MAX.
 static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
                               "call mpmpc_rollout_init again (or use a second handle for single solves)")) return rc;
@@ -47,6 +48,9 @@ static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   if (p.plant && h->pl.B != B) return fail(MPMPC_E_STATE, "the plant was set for another number of cars (mpmpc_rollout_set_plant)");
   p.delaying = h->dl.B > 0;
   if (p.delaying && h->dl.B != B) return fail(MPMPC_E_STATE, "the delay was set for another number of cars (mpmpc_rollout_set_delay)");
+  p.estimating = h->es.B > 0;
+  if (p.estimating && h->es.B != B)
+    return fail(MPMPC_E_STATE, "the estimator was set for another number of cars (mpmpc_rollout_set_estimator)");
   if (int rc = aud_check_step(h, B)) return rc;
   p.auditing = h->aud.mode != FP_MODE_OFF;
   HIP_TRY(hipSetDevice(h->cfg.device));
@@ -76,6 +80,10 @@ static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   if (p.delaying && h->look.max_lead > 0)      // (column leads and plan tracks would have to be offset by c: out of scope)
     return fail(MPMPC_E_STATE, "a delay and a lookahead are both in force: lookahead under delay is not supported "
                                "(mpmpc_rollout_set_delay / mpmpc_rollout_set_lookahead: switch one off)");
+  if (p.estimating && p.delaying && h->dl.max_assumed >= DL_MAX)      // (K3e reads entry c of the register, which has DL_MAX entries)
+    return fail(MPMPC_E_STATE, "an estimator is in force and a car's assumed delay is " + std::to_string(DL_MAX) +
+                               ": the command that reached the wheels in the last step has left the register by then "
+                               "(mpmpc_rollout_set_estimator / mpmpc_rollout_set_delay: assume at most " + std::to_string(DL_MAX - 1) + ")");
   return MPMPC_OK;
 }
 
@@ -106,18 +114,31 @@ static void enqueue_movers(mpmpc_handle h, Slot& sl, int B, long long k, const S
                      m.radius, m.prm, m.dst, h->obs.obst_discs.get(), h->obs.obst_off.get(), B, p.route);
 }
 
-// K3d: from the poses K3n measured (plant) or the true ones, through the commands in flight
+// what the controller localises on: the estimate, else the pose K3n measured (plant), else the true one
+static const double* localise_pose(mpmpc_handle h, const StepPlan& p) {
+  return p.estimating ? h->es.est.get() : p.plant ? h->pl.meas.get() : h->ro.pose.get();
+}
+
+// K3e: filters the poses K3n measured (plant) or the true ones; the last step's command is u or - delaying - in the register
+static void enqueue_estimate(mpmpc_handle h, Slot& sl, int B, long long k, const StepPlan& p) {
+  hipLaunchKernelGGL(mpmpc_estimate_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.wheelbase, h->ro.Ts,
+                     p.plant ? h->pl.meas.get() : h->ro.pose.get(), h->ro.pose.get(), h->ro.alive.get(), h->ro.u.get(),
+                     p.delaying ? h->dl.queue.get() : nullptr, p.delaying ? h->dl.assumed.get() : nullptr, est_view(h, k));
+}
+
+// K3d: from the estimate, else the poses K3n measured (plant), else the true ones, through the commands in flight
 static void enqueue_delay_predict(mpmpc_handle h, Slot& sl, int B, const StepPlan& p) {
   hipLaunchKernelGGL(mpmpc_delay_predict_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.wheelbase, h->ro.Ts,
                      h->ro.cum.get(), h->cor.gx.get(), h->cor.gy.get(), h->cor.gpsi.get(), h->tab.kappa.get(), h->ro.s.get(),
-                     p.plant ? h->pl.meas.get() : h->ro.pose.get(), h->ro.alive.get(), h->dl.assumed.get(), h->dl.queue.get(),
+                     localise_pose(h, p), h->ro.alive.get(), h->dl.assumed.get(), h->dl.queue.get(),
                      h->dl.pred_pose.get(), h->dl.pred_s.get(), h->dl.now.get(), h->dl.now_wp.get(), p.route);
 }
 
-// K3a; with a plant it localises on the poses K3n measured, with a delay on what K3d predicted from them
+// K3a; with a plant it localises on the poses K3n measured, with an estimator on K3e's estimate of them, with a delay on what K3d
+// predicted from either
 static void enqueue_localise(mpmpc_handle h, Slot& sl, int B, const StepPlan& p) {
   const double* s = p.delaying ? h->dl.pred_s.get() : h->ro.s.get();
-  const double* pose = p.delaying ? h->dl.pred_pose.get() : p.plant ? h->pl.meas.get() : h->ro.pose.get();
+  const double* pose = p.delaying ? h->dl.pred_pose.get() : localise_pose(h, p);
   hipLaunchKernelGGL(mpmpc_localise_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.N, h->cfg.circular ? 1 : 0,
                      h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, s, pose, h->ro.alive, h->io.wp_id, h->io.x0, h->ro.shift, p.route);
 }
@@ -176,6 +197,7 @@ static void step_ran(mpmpc_handle h, int B, const StepPlan& p) {
   if (p.perceiving) h->per.B = B;
   if (p.plant) h->pl.ran = true;
   if (p.delaying) h->dl.ran = true;
+  if (p.estimating) h->es.ran = true;
   h->look.ran_B = p.looking ? B : 0;
   h->look.ran_n = p.looking ? p.movers : 0;
   h->tlk.ran_B = p.ahead_traffic ? B : 0;
@@ -198,6 +220,7 @@ extern "C" int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     if (p.perceiving && p.movers > 0) enqueue_movers(h, sl, B, k, p);                      // K0m
     if (p.perceiving) per_enqueue_step(h, sl, B, k);                                       // K0s
     if (p.plant) plant_enqueue_measure(h, sl, B, k);                                       // K3n
+    if (p.estimating) enqueue_estimate(h, sl, B, k, p);                                    // K3e
     if (p.delaying) enqueue_delay_predict(h, sl, B, p);                                    // K3d
     enqueue_localise(h, sl, B, p);                                                         // K3a
     if (!p.perceiving && p.movers > 0) enqueue_movers(h, sl, B, k, p);                     // K0m

@@ -188,6 +188,8 @@ def load_library(path: str | None = None):
     lib.mpmpc_plant_noise.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _dp]
     lib.mpmpc_rollout_set_delay.argtypes = [h, C.c_int32, _ip, _ip, _dp]
     lib.mpmpc_rollout_delay.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp]
+    lib.mpmpc_rollout_set_estimator.argtypes = [h, C.c_int32, _dp, C.c_uint64, C.c_int32, C.c_int64, _dp, _dp]
+    lib.mpmpc_rollout_estimator.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
     lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_recorded.argtypes = [h, _ip, _ip]
     lib.mpmpc_rollout_trace.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
@@ -254,6 +256,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_project", "mpmpc_rollout_reroute", "mpmpc_rollout_routes",
            "mpmpc_rollout_set_plant", "mpmpc_rollout_plant", "mpmpc_plant_noise",
            "mpmpc_rollout_set_delay", "mpmpc_rollout_delay",
+           "mpmpc_rollout_set_estimator", "mpmpc_rollout_estimator",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -694,6 +697,46 @@ class Handle:
         B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
         out = dict(queue=np.zeros((B, 8, 2)), pred_pose=np.zeros((B, 3)), pred_s=np.zeros(B), now=np.zeros((B, 3)))
         self._check(self.lib.mpmpc_rollout_delay(self._h, B, _d(out["queue"]), _d(out["pred_pose"]), _d(out["pred_s"]), _d(out["now"])))
+        return out
+
+    # --- pose estimator of the rollout, per car
+    ESTIMATOR_FIELDS = ("est", "cov", "err2_max", "err2_sum", "meas2_sum", "head2_sum", "used", "steps")
+
+    def rollout_set_estimator(self, params, seed=0, car0=0, step0=0, est0=None, cov0=None):
+        """The pose filter of the rollouts that follow (K3e; the law: csrc/estimator_core.hpp): params [B, 8] = q_xy, q_psi
+        (process variances per step, >= 0), r_xy, r_psi (measurement variances, > 0), p0_xy, p0_psi (the variances a car is
+        primed with, >= 0), period (the measurement is scheduled when (k - step0) mod period == 0; an integer >= 1), drop in
+        [0, 1) (the probability that a scheduled measurement is lost; a draw of (seed, car0 + car, k - step0)) - or None for no
+        estimator (the default).  estimator.Estimator.params(B) gives the block.  Per step every running car's filter takes the
+        nominal model's step with the command believed executed in the last step, then - if available - the measurement (the
+        plant's measured pose, else the true one), and the controller localises on the ESTIMATE (under a delay: predicts from
+        it); the true pose stays rollout_state()["pose"].  est0 [B, 3] and cov0 [B, 6] (Pxx, Pxy, Pxp, Pyy, Pyp, Ppp), both or
+        neither: the cars start primed with them (a resumed run).  May be called before rollout_init or between rollout_step
+        calls; rollout_init un-primes every car and zeroes the statistics, so a resumed run sets the estimator after it.  Not
+        together with an assumed delay of 8."""
+        if params is None:
+            self._check(self.lib.mpmpc_rollout_set_estimator(self._h, 0, None, 0, 0, 0, None, None))
+            return
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 8:
+            raise ValueError("estimator params must be [B, 8]")
+        B = p.shape[0]
+        e0 = None if est0 is None else np.ascontiguousarray(est0, dtype=np.float64).reshape(B, 3)
+        c0 = None if cov0 is None else np.ascontiguousarray(cov0, dtype=np.float64).reshape(B, 6)
+        self._check(self.lib.mpmpc_rollout_set_estimator(self._h, B, _d(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(car0), int(step0),
+                                                         _d(e0), _d(c0)))
+
+    def rollout_estimator(self):
+        """-> dict of the estimator's per-car state: est [B, 3] and cov [B, 6] (the upper triangle Pxx, Pxy, Pxp, Pyy, Pyp, Ppp)
+        as the last step left them - est is what the controller localised on in that step; err2_max and err2_sum, maximum and
+        sum over the car's steps of the squared position error of the estimate against the true pose; meas2_sum, the same sum
+        for what was measured (every step, whether or not the filter saw it); head2_sum, the sum of the squared wrapped heading
+        error of the estimate; used, the measurements taken (priming included); steps, the filter's steps."""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        out = dict(est=np.zeros((B, 3)), cov=np.zeros((B, 6)), err2_max=np.zeros(B), err2_sum=np.zeros(B), meas2_sum=np.zeros(B),
+                   head2_sum=np.zeros(B), used=np.zeros(B, np.int32), steps=np.zeros(B, np.int32))
+        self._check(self.lib.mpmpc_rollout_estimator(self._h, B, _d(out["est"]), _d(out["cov"]), _d(out["err2_max"]), _d(out["err2_sum"]),
+                                                     _d(out["meas2_sum"]), _d(out["head2_sum"]), _i(out["used"]), _i(out["steps"])))
         return out
 
     # --- footprint audit of the rollout: contact and clearance of every car, every step, accumulated on the device
