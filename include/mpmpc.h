@@ -636,6 +636,59 @@ int mpmpc_rollout_set_estimator(mpmpc_handle h, int32_t B, const double* params,
                                 const double* est0, const double* cov0);
 int mpmpc_rollout_estimator(mpmpc_handle h, int32_t B, double* est, double* cov, double* err2_max, double* err2_sum, double* meas2_sum,
                             double* head2_sum, int32_t* used, int32_t* steps);
+/* Lidar localisation, per fleet and off by default: scan matching (K0d, K3l; the law and the exact operation order:
+ * csrc/localiser_core.hpp).  Every scheduled step each running car scans its TRUE world with K0l itself - base map, discs,
+ * movers at step k, traffic and walls - and matches the scan against the map it knows in advance, the BASE map, from dead
+ * reckoning; the FIX takes the place of the measured pose: the estimator measures it, and the controller localises on the
+ * estimate, else on the fix (else on the plant's measured pose, else on the true one).  A plant still measures (its `meas` and
+ * mpmpc_rollout_plant are unchanged), but nothing plans on that then.  The audit, mpmpc_rollout_scan, perception, traffic, the
+ * recorder and mpmpc_rollout_reroute keep the true pose.
+ *    the field    F[j][i] = min(cap, the smallest squared cell distance <= D^2 to an occupied cell of the grid), cap = D^2 + 1,
+ *                 one byte per cell; outside the grid: cap
+ *    prior        not primed: the true pose (the step counts, no scan is used); else the nominal model's step on the last fix
+ *                 with the command believed executed in step k - 1 (the estimator's rule)
+ *    schedule     (k - step0) mod period != 0: fix = prior, no scan
+ *    scan         beam b is a hit iff ranges[b] < range_m; a hit's range takes sigma_r * n_b, n_b a triangular variate of
+ *                 (seed, car0 + car, k - step0, b); fewer than min_hits hits or a prior that is not finite: fix = prior, lost
+ *    match        headings psi_t = prior_psi + t * step_psi, t in [-T, T]; every hit's endpoint cell from the prior under psi_t;
+ *                 score(a, c, t) = sum over the hits of F(cell + (a, c) * m), a, c in [-W, W]; the winner: the smallest
+ *                 (score, a^2 + c^2, t^2, idx), idx = ((t + T)(2W + 1) + (c + W))(2W + 1) + (a + W);
+ *                 fix = (prior_x + a m res, prior_y + c m res, psi_t); a winner on the window's border counts as edge
+ *    statistics   from the true pose as the step finds it
+ *   mpmpc_distance_field   K0d without a handle: data [height][width] (1 free / 0 occupied), D in [1, 15] -> field_out
+ *                          [height][width] bytes.
+ *   mpmpc_scan_match       scan and match (no noise) of B (prior, scan) pairs without a handle: prior [B][3], ranges
+ *                          [B][n_beams] -> fix_out [B][3], score_out, cand_out (idx; both -1 without a match), hits_out [B].
+ *   mpmpc_rollout_set_localiser  B = 0: off.  n_beams, angles, range_m under mpmpc_lidar_scan's checks; D in [1, 15]; m >= 1
+ *                          cells; W in [0, 16]; T in [0, 8]; step_psi >= 0 (> 0 when T > 0); min_hits >= 1; sigma_r >= 0;
+ *                          period >= 1; (2T + 1) n_beams <= 8192; fix0 [B][3] or NULL - given, it primes the cars (a saved run is
+ *                          resumed with the fix mpmpc_rollout_localiser returned and step0 = -(the step of the save)).  Validated
+ *                          before anything is touched - MPMPC_E_ARG, and the previous setting stays in force.  Needs
+ *                          mpmpc_set_map (MPMPC_E_STATE); the field is built by this call, and a step after mpmpc_set_map /
+ *                          mpmpc_set_path / mpmpc_set_path_geometry returns MPMPC_E_STATE until it is set again.  So does a step
+ *                          whose B differs, and one under a delay with an assumed delay of MPMPC_DELAY_MAX.  May be called
+ *                          before mpmpc_rollout_init or between steps; mpmpc_rollout_init keeps the setting, un-primes every car
+ *                          and zeroes the statistics - a resumed run sets the localiser after it.
+ *   mpmpc_rollout_localiser  any pointer may be NULL.  fix, prior [B][3], cand, score, hits [B] as the car's last step left them
+ *                          (cand, score: -1 without a match; hits: -1 without a scan); ranges [B][n_beams]: the scans of the
+ *                          last scheduled step, the hits noisy; err2_max, err2_sum [B]: maximum and sum of the fix's squared
+ *                          position error; head2_sum: the sum of its wrapped heading error squared; prior2_sum: err2_sum of the
+ *                          prior; steps, matched, lost, edge [B].  MPMPC_E_STATE unless a step of B cars ran under the setting.
+ * The scan is mpmpc_lidar_scan's, the reference's lidar: at headings above 0 (and unwrapped ones beyond pi) it mirrors the cells
+ * behind the car on its right onto the beams behind it on its left, and the match follows what the sensor reports.
+ * Out of scope: per-car settings, matching against discs, walls or perceived worlds, sub-cell refinement, the fix in the trace.
+ * A rollout without the setting launches exactly what it launched before. */
+int mpmpc_distance_field(int32_t device, int32_t height, int32_t width, const int8_t* data, int32_t D, uint8_t* field_out);
+int mpmpc_scan_match(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y, double resolution,
+                     int32_t B, const double* prior, const double* ranges, int32_t n_beams, const double* angles, double range_m, int32_t D,
+                     int32_t m, int32_t W, int32_t T, double step_psi, int32_t min_hits, double* fix_out, int32_t* score_out,
+                     int32_t* cand_out, int32_t* hits_out);
+int mpmpc_rollout_set_localiser(mpmpc_handle h, int32_t B, int32_t n_beams, const double* angles, double range_m, int32_t D, int32_t m,
+                                int32_t W, int32_t T, double step_psi, int32_t min_hits, double sigma_r, int32_t period, uint64_t seed,
+                                int32_t car0, int64_t step0, const double* fix0);
+int mpmpc_rollout_localiser(mpmpc_handle h, int32_t B, double* fix, double* prior, int32_t* cand, int32_t* score, int32_t* hits, double* ranges,
+                            double* err2_max, double* err2_sum, double* head2_sum, double* prior2_sum, int32_t* steps, int32_t* matched,
+                            int32_t* lost, int32_t* edge);
 
 /* Recorder: while the cars drive, the rollout appends one record per car and recorded step to a device-resident trace
  * (what src/simulation.py:117-157 logs per step on the host: x_log / y_log / v_log and MPC.current_prediction), and

@@ -381,7 +381,7 @@ class BatchMPC:
         return self.handle.rollout_reroute(routes, max_dist, max_heading)
 
     def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
-                walls=None, perception=None, routes=None, lookahead=None, plant=None, delay=None, estimator=None):
+                walls=None, perception=None, routes=None, lookahead=None, plant=None, delay=None, estimator=None, localiser=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -447,6 +447,15 @@ class BatchMPC:
         estimate keeps the bits of the true pose.  "pose" and everything that senses or judges the car stay true.  The returned
         dict also holds "estimator": handle.rollout_estimator() - est, cov, err2_max, err2_sum, meas2_sum, head2_sum, used,
         steps (None when n_steps = 0).
+        localiser: None - the pose is measured by the plant's noise model or not at all; a localiser.Localiser - one setting for
+        the fleet: every scheduled step each running car scans its TRUE world with the lidar (K0l: base map, obstacles, movers,
+        traffic, walls) and matches the scan against the distance field of the BASE map around dead reckoning (K0d, K3l on the
+        device, csrc/localiser_core.hpp); the FIX is what `estimator` measures and what the controller localises on (the
+        estimate, else the fix; under `delay` it predicts from it), so the measurement error depends on what the car can see.
+        Needs corridor='device'; composes with `plant`, `delay`, `estimator`, `perception` and `routes` (not with an assumed delay
+        of 8: ValueError).  A plant still measures, but nothing plans on that.  "pose" and everything that senses or judges the car
+        stay true.  The returned dict also holds "localiser": handle.rollout_localiser() - fix, prior, cand, score, hits, ranges,
+        err2_max, err2_sum, head2_sum, prior2_sum, steps, matched, lost, edge (None when n_steps = 0).
         record: None - nothing is recorded; True or a dict of mpmpc.Handle.rollout_record's keyword arguments (capacity,
         plan, prediction, rows, stride; capacity defaults to the records `n_steps` yields) - the run is recorded on the
         device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of the whole run, arrays
@@ -499,6 +508,11 @@ class BatchMPC:
             raise ValueError("delay and lookahead cannot be combined: the column leads would have to be offset by the assumed delay")
         if estimator is not None and delay is not None and np.any(delay.arrays(np.asarray(s).size)[1] >= 8):
             raise ValueError("estimator and an assumed delay of 8 cannot be combined: the command that reached the wheels in the "
+                             "last step has left the register by then")
+        if localiser is not None and self.corridor_cols is None:
+            raise ValueError("localiser needs corridor='device' (update_corridor_from_map): the map lives on the device")
+        if localiser is not None and delay is not None and np.any(delay.arrays(np.asarray(s).size)[1] >= 8):
+            raise ValueError("localiser and an assumed delay of 8 cannot be combined: the command that reached the wheels in the "
                              "last step has left the register by then")
         if fleet is not None:
             self.handle.set_car_routes(routes)      # (the routes' geometry went up with set_routes)
@@ -555,6 +569,7 @@ class BatchMPC:
             self.handle.rollout_init(self.model.Ts, cum, s, poses, cc0)
             self._set_delay(delay_arrays)
             self._set_estimator(est_args)
+            self._set_localiser(localiser, np.asarray(s).size)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             if audit is not None:
@@ -567,6 +582,8 @@ class BatchMPC:
                 out["delay"] = self.handle.rollout_delay() if int(n_steps) > 0 else None
             if estimator is not None:
                 out["estimator"] = self.handle.rollout_estimator() if int(n_steps) > 0 else None
+            if localiser is not None:
+                out["localiser"] = self.handle.rollout_localiser() if int(n_steps) > 0 else None
             return out
         kw = dict(record) if isinstance(record, dict) else {}
         stride = int(kw.get("stride", 1))
@@ -576,6 +593,7 @@ class BatchMPC:
             self.handle.rollout_init(self.model.Ts, cum, s, poses, cc0)
             self._set_delay(delay_arrays)
             self._set_estimator(est_args)
+            self._set_localiser(localiser, np.asarray(s).size)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             out["trace"] = self.handle.rollout_trace()
@@ -589,6 +607,8 @@ class BatchMPC:
                 out["delay"] = self.handle.rollout_delay() if int(n_steps) > 0 else None
             if estimator is not None:
                 out["estimator"] = self.handle.rollout_estimator() if int(n_steps) > 0 else None
+            if localiser is not None:
+                out["localiser"] = self.handle.rollout_localiser() if int(n_steps) > 0 else None
         finally:
             self.handle.rollout_record(0, B=np.asarray(s).size)      # later rollouts are unrecorded again
         return out
@@ -611,6 +631,15 @@ class BatchMPC:
         elif getattr(self, "_estimator_set", False):      # (off again; a controller that never had an estimator calls nothing new)
             self.handle.rollout_set_estimator(None)
             self._estimator_set = False
+
+    def _set_localiser(self, localiser, B):
+        """behind rollout_init and every map or path setter, like the estimator: the localiser of this run, or - None - off again"""
+        if localiser is not None:
+            self.handle.rollout_set_localiser(B, **localiser.setting())
+            self._localiser_set = True
+        elif getattr(self, "_localiser_set", False):      # (off again; a controller that never localised calls nothing new)
+            self.handle.rollout_set_localiser(0)
+            self._localiser_set = False
 
     def rollout_scan(self, lidar):
         """Lidar scans of the cars of the last `rollout`, where it left them and in the worlds of its last step (the map

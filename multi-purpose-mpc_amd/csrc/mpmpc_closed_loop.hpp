@@ -743,6 +743,9 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   if (h->es.B > 0) {              // ... and an estimator in force keeps its parameters; every car is un-primed, the statistics start over
     if (int rc = est_reset(h, sl, h->es.B, nullptr, nullptr)) return rc;
   }
+  if (h->lc.B > 0) {              // ... and so does a localiser in force: its setting and its field stay
+    if (int rc = loc_reset(h, sl, h->lc.B, nullptr)) return rc;
+  }
   return aud_reset(h, B);         // ... and so does the audit (mpmpc_footprint.hpp)
 }
 

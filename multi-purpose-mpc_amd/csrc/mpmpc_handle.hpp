@@ -247,6 +247,30 @@ struct EstState {
   bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_estimator)
 };
 
+// lidar localisation of the rollout (mpmpc_rollout_set_localiser; the law: localiser_core.hpp): the setting - per fleet -, the
+// distance field of the base map it was made on, every car's fix and statistics - memory of its own, sized by max_batch, the
+// map and the beams when set
+struct LocState {
+  int B = 0;                // > 0: the localiser is in force for B cars
+  unsigned gen = 0;         // base_gen the field was built against
+  LcSet set{};
+  int n_beams = 0;
+  double range = 0;
+  long long period = 1;
+  unsigned long long seed = 0;
+  int car0 = 0;
+  long long step0 = 0;
+  Buf<uint8_t> field;       // [map_h][map_w]: K0d's capped squared distances
+  Buf<double> angles;       // [LID_MAX_BEAMS]
+  Buf<double> ranges;       // [max_batch][n_beams]: K0l's scans of the last scheduled step, the hits noisy
+  Buf<double> fix, prior;   // [max_batch][3] each: the pose the controller localises on, and dead reckoning's
+  Buf<int> primed;          // [max_batch]
+  Buf<int> out;             // [3][max_batch]: cand, score, hits of the last step
+  Buf<double> stats;        // [LC_STATS][max_batch]: err2_max, err2_sum, head2_sum, prior2_sum
+  Buf<int> count;           // [LC_COUNTS][max_batch]: steps, matched, lost, edge
+  bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_localiser)
+};
+
 // per-batch inputs and host staging
 struct IoState {
   // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
@@ -295,6 +319,7 @@ struct mpmpc_handle_s {
   PlantState pl;
   DelayState dl;
   EstState es;
+  LocState lc;
   IoState io;
   // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
   // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that

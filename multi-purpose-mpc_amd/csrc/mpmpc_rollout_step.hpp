@@ -1,5 +1,5 @@
 // mpmpc_rollout_step of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind every feature of a
-// step: mpmpc_closed_loop.hpp - the kernels K0c, K0m, K0t, K3a, K3b, K3r -, mpmpc_plant.hpp, mpmpc_delay.hpp, mpmpc_estimator.hpp, mpmpc_lookahead.hpp,
+// step: mpmpc_closed_loop.hpp - the kernels K0c, K0m, K0t, K3a, K3b, K3r -, mpmpc_plant.hpp, mpmpc_delay.hpp, mpmpc_estimator.hpp, mpmpc_localiser.hpp, mpmpc_lookahead.hpp, mpmpc_lidar.hpp,
 // mpmpc_perception.hpp and mpmpc_footprint.hpp).  A step is decided once (plan_step: every check and lay-out, in a fixed order),
 // then its kernels are enqueued in stream order, each from the one enqueue_* function that launches it, then the handle
 // remembers what ran (step_ran).  DESIGN.md section 4, "A rollout step", is the same list.
@@ -7,7 +7,7 @@
 
 // What the step loop needs, and nothing else (host only).
 struct StepPlan {
-  bool per_car, discs, walls, traffic, perceiving, plant, delaying, estimating, auditing, looking, ahead_traffic, recording;
+  bool per_car, discs, walls, traffic, perceiving, plant, delaying, estimating, localising, auditing, looking, ahead_traffic, recording;
   int movers;
   MapView map;
   PathGeom geom;
@@ -21,8 +21,8 @@ struct StepPlan {
 
 // Every check and lay-out of a step of B cars, in this order (the first refusal that applies is the call's): the rollout's
 // state, n_steps, the per-car settings' B, stale generations, the recorder's B and capacity, the plant's B, the delay's B, the
-// estimator's B, the audit, perception, the routes, the lookahead, the delay under a lookahead, the estimator under an assumed
-// delay of DL_MAX.
+// estimator's B, the localiser's B, map and generation, the audit, perception, the routes, the lookahead, the delay under a
+// lookahead, the estimator and the localiser under an assumed delay of DL_MAX.
 static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
                               "call mpmpc_rollout_init again (or use a second handle for single solves)")) return rc;
@@ -51,6 +51,13 @@ static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   p.estimating = h->es.B > 0;
   if (p.estimating && h->es.B != B)
     return fail(MPMPC_E_STATE, "the estimator was set for another number of cars (mpmpc_rollout_set_estimator)");
+  p.localising = h->lc.B > 0;
+  if (p.localising) {
+    if (h->lc.B != B) return fail(MPMPC_E_STATE, "the localiser was set for another number of cars (mpmpc_rollout_set_localiser)");
+    if (!h->cor.map) return fail(MPMPC_E_STATE, "the localiser needs mpmpc_set_map first");
+    if (h->lc.gen != h->cor.base_gen)      // (the field is the map's of the setting)
+      return fail(MPMPC_E_STATE, "map, path or geometry changed since mpmpc_rollout_set_localiser: set the localiser again");
+  }
   if (int rc = aud_check_step(h, B)) return rc;
   p.auditing = h->aud.mode != FP_MODE_OFF;
   HIP_TRY(hipSetDevice(h->cfg.device));
@@ -84,6 +91,10 @@ static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
     return fail(MPMPC_E_STATE, "an estimator is in force and a car's assumed delay is " + std::to_string(DL_MAX) +
                                ": the command that reached the wheels in the last step has left the register by then "
                                "(mpmpc_rollout_set_estimator / mpmpc_rollout_set_delay: assume at most " + std::to_string(DL_MAX - 1) + ")");
+  if (p.localising && p.delaying && h->dl.max_assumed >= DL_MAX)      // (K3l reads the same entry)
+    return fail(MPMPC_E_STATE, "a localiser is in force and a car's assumed delay is " + std::to_string(DL_MAX) +
+                               ": the command that reached the wheels in the last step has left the register by then "
+                               "(mpmpc_rollout_set_localiser / mpmpc_rollout_set_delay: assume at most " + std::to_string(DL_MAX - 1) + ")");
   return MPMPC_OK;
 }
 
@@ -107,26 +118,51 @@ static void enqueue_traffic(mpmpc_handle h, Slot& sl, int B, const StepPlan& p) 
   else launch_traffic<false>(h, sl, B, p, LookNone{});
 }
 
-// K0m: in front of K0s when the step perceives (K0s reads alive as the step finds it, K0m reads nothing K3a writes), else behind K3a
+// K0m: in front of K0s when the step perceives (K0s reads alive as the step finds it, K0m reads nothing K3a writes) and in front
+// of K0l when it localises (the scan sees the movers of step k), else behind K3a
 static void enqueue_movers(mpmpc_handle h, Slot& sl, int B, long long k, const StepPlan& p) {
   const MoverView m = h->obs.mover_view();
   hipLaunchKernelGGL(mpmpc_obstacle_move_kernel, dim3((m.n + 255) / 256), dim3(256), 0, sl.stream, m.n, k, m.step0, p.map, p.path, m.kind,
                      m.radius, m.prm, m.dst, h->obs.obst_discs.get(), h->obs.obst_off.get(), B, p.route);
 }
 
-// what the controller localises on: the estimate, else the pose K3n measured (plant), else the true one
+// what measures the pose: K3l's fix, else the pose K3n measured (plant), else the true one
+static const double* measured_pose(mpmpc_handle h, const StepPlan& p) {
+  return p.localising ? h->lc.fix.get() : p.plant ? h->pl.meas.get() : h->ro.pose.get();
+}
+// what the controller localises on: the estimate, else that
 static const double* localise_pose(mpmpc_handle h, const StepPlan& p) {
-  return p.estimating ? h->es.est.get() : p.plant ? h->pl.meas.get() : h->ro.pose.get();
+  return p.estimating ? h->es.est.get() : measured_pose(h, p);
 }
 
-// K3e: filters the poses K3n measured (plant) or the true ones; the last step's command is u or - delaying - in the register
+// K0l of a scheduled localising step: every car's TRUE pose in its TRUE world of step k (behind K0t and K0m), into the localiser's ranges
+template <bool WALLS>
+static void launch_localiser_scan(mpmpc_handle h, Slot& sl, int B, const StepPlan& p, WallView wv) {
+  hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<WALLS>, dim3(B), dim3(K0L_THREADS), 0, sl.stream, p.map, B, h->ro.pose.get(),
+                     p.discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), h->lc.n_beams, h->lc.angles.get(), h->lc.range,
+                     h->lc.ranges.get(), wv);
+}
+static void enqueue_localiser_scan(mpmpc_handle h, Slot& sl, int B, const StepPlan& p) {
+  if (p.walls) launch_localiser_scan<true>(h, sl, B, p, h->obs.wall_view());
+  else launch_localiser_scan<false>(h, sl, B, p, WallView{nullptr, nullptr, nullptr});
+}
+
+// K3l: the fix of every running car; the last step's command is u or - delaying - in the register, as K3e takes it
+static void enqueue_scan_localise(mpmpc_handle h, Slot& sl, int B, const StepPlan& p, const LocView& lv) {
+  hipLaunchKernelGGL(mpmpc_scan_localise_kernel, dim3(B), dim3(LC_THREADS), loc_lds(lv.set.T, lv.n_beams), sl.stream, p.map, B,
+                     h->cfg.wheelbase, h->ro.Ts, h->ro.pose.get(), h->ro.alive.get(), h->ro.u.get(), p.delaying ? h->dl.queue.get() : nullptr,
+                     p.delaying ? h->dl.assumed.get() : nullptr, lv);
+}
+
+// K3e: filters K3l's fixes, else the poses K3n measured (plant), else the true ones; the last step's command is u or - delaying -
+// in the register
 static void enqueue_estimate(mpmpc_handle h, Slot& sl, int B, long long k, const StepPlan& p) {
   hipLaunchKernelGGL(mpmpc_estimate_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.wheelbase, h->ro.Ts,
-                     p.plant ? h->pl.meas.get() : h->ro.pose.get(), h->ro.pose.get(), h->ro.alive.get(), h->ro.u.get(),
+                     measured_pose(h, p), h->ro.pose.get(), h->ro.alive.get(), h->ro.u.get(),
                      p.delaying ? h->dl.queue.get() : nullptr, p.delaying ? h->dl.assumed.get() : nullptr, est_view(h, k));
 }
 
-// K3d: from the estimate, else the poses K3n measured (plant), else the true ones, through the commands in flight
+// K3d: from the estimate, else K3l's fix, else the poses K3n measured (plant), else the true ones, through the commands in flight
 static void enqueue_delay_predict(mpmpc_handle h, Slot& sl, int B, const StepPlan& p) {
   hipLaunchKernelGGL(mpmpc_delay_predict_kernel, dim3((B + 255) / 256), dim3(256), 0, sl.stream, B, h->tab.n_wp, h->cfg.wheelbase, h->ro.Ts,
                      h->ro.cum.get(), h->cor.gx.get(), h->cor.gy.get(), h->cor.gpsi.get(), h->tab.kappa.get(), h->ro.s.get(),
@@ -134,8 +170,8 @@ static void enqueue_delay_predict(mpmpc_handle h, Slot& sl, int B, const StepPla
                      h->dl.pred_pose.get(), h->dl.pred_s.get(), h->dl.now.get(), h->dl.now_wp.get(), p.route);
 }
 
-// K3a; with a plant it localises on the poses K3n measured, with an estimator on K3e's estimate of them, with a delay on what K3d
-// predicted from either
+// K3a; with a plant it localises on the poses K3n measured, with a localiser on K3l's fixes, with an estimator on K3e's estimate
+// of either, with a delay on what K3d predicted from any of them
 static void enqueue_localise(mpmpc_handle h, Slot& sl, int B, const StepPlan& p) {
   const double* s = p.delaying ? h->dl.pred_s.get() : h->ro.s.get();
   const double* pose = p.delaying ? h->dl.pred_pose.get() : localise_pose(h, p);
@@ -198,6 +234,7 @@ static void step_ran(mpmpc_handle h, int B, const StepPlan& p) {
   if (p.plant) h->pl.ran = true;
   if (p.delaying) h->dl.ran = true;
   if (p.estimating) h->es.ran = true;
+  if (p.localising) h->lc.ran = true;
   h->look.ran_B = p.looking ? B : 0;
   h->look.ran_n = p.looking ? p.movers : 0;
   h->tlk.ran_B = p.ahead_traffic ? B : 0;
@@ -217,13 +254,19 @@ extern "C" int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     char* rec = p.recording && k % h->rec.stride == 0 ? h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)h->rec.count : nullptr;
     if (rec) enqueue_record_snapshot(h, sl, B, rec);                                       // K3r snapshot
     if (p.traffic) enqueue_traffic(h, sl, B, p);                                           // K0t: pose and alive as the step finds them
-    if (p.perceiving && p.movers > 0) enqueue_movers(h, sl, B, k, p);                      // K0m
+    const bool movers_first = p.perceiving || p.localising;
+    if (movers_first && p.movers > 0) enqueue_movers(h, sl, B, k, p);                      // K0m
     if (p.perceiving) per_enqueue_step(h, sl, B, k);                                       // K0s
     if (p.plant) plant_enqueue_measure(h, sl, B, k);                                       // K3n
+    if (p.localising) {
+      const LocView lv = loc_view(h, k);
+      if (lv.scheduled) enqueue_localiser_scan(h, sl, B, p);                               // K0l: pose k in world k
+      enqueue_scan_localise(h, sl, B, p, lv);                                              // K3l
+    }
     if (p.estimating) enqueue_estimate(h, sl, B, k, p);                                    // K3e
     if (p.delaying) enqueue_delay_predict(h, sl, B, p);                                    // K3d
     enqueue_localise(h, sl, B, p);                                                         // K3a
-    if (!p.perceiving && p.movers > 0) enqueue_movers(h, sl, B, k, p);                     // K0m
+    if (!movers_first && p.movers > 0) enqueue_movers(h, sl, B, k, p);                     // K0m
     if (p.auditing) aud_enqueue_step(h, sl, B, k, p.per_car);                              // K0f: pose k in world k
     if (p.looking) look_enqueue_step(h, sl, B, k, p.map, p.geom, p.path, p.route);         // K0h
     if (p.ahead_traffic) tlk_enqueue_horizon(h, sl, B, p.map);                             // K0ht

@@ -19,7 +19,8 @@
 //   bit for bit.  Block 0 yields (n_v, n_delta, n_x, n_y) from its words 0 .. 3, word 0 of block 1 yields n_psi; the
 //   other words of block 1 and all further blocks are reserved.  A draw depends on (seed, car0 + car, j, channel) only -
 //   not on B, not on how many steps one call makes, not on what other cars do.  Of the reserved blocks, word 0 of block 2 is
-//   the pose estimator's dropout draw (estimator_core.hpp, under the estimator's own seed, car0 and step0).
+//   the pose estimator's dropout draw (estimator_core.hpp, under the estimator's own seed, car0 and step0).  Blocks 16 .. 527 are
+//   the lidar localiser's range noise, four beams a block (localiser_core.hpp, under the localiser's own seed, car0 and step0).
 //
 // PARAMETERS.  PL_PARAMS = 11 doubles per car (PL_*), identity 1, 1, 0, 1, 1, 1, +inf, 0, 0, 0, 0 (pl_check_params):
 //   0 speed_gain g_v (finite)       1 steer_gain g_d (finite)        2 steer_offset b_d [rad] (finite)

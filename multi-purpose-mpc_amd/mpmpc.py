@@ -190,6 +190,14 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_delay.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp]
     lib.mpmpc_rollout_set_estimator.argtypes = [h, C.c_int32, _dp, C.c_uint64, C.c_int32, C.c_int64, _dp, _dp]
     lib.mpmpc_rollout_estimator.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
+    _i8p, _u8p = C.POINTER(C.c_int8), C.POINTER(C.c_uint8)
+    lib.mpmpc_distance_field.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i8p, C.c_int32, _u8p]
+    lib.mpmpc_scan_match.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i8p, C.c_double, C.c_double, C.c_double, C.c_int32, _dp, _dp,
+                                     C.c_int32, _dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                     _dp, _ip, _ip, _ip]
+    lib.mpmpc_rollout_set_localiser.argtypes = [h, C.c_int32, C.c_int32, _dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.c_int32, C.c_int64, _dp]
+    lib.mpmpc_rollout_localiser.argtypes = [h, C.c_int32, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _ip]
     lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_recorded.argtypes = [h, _ip, _ip]
     lib.mpmpc_rollout_trace.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
@@ -257,6 +265,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_rollout_set_plant", "mpmpc_rollout_plant", "mpmpc_plant_noise",
            "mpmpc_rollout_set_delay", "mpmpc_rollout_delay",
            "mpmpc_rollout_set_estimator", "mpmpc_rollout_estimator",
+           "mpmpc_distance_field", "mpmpc_scan_match", "mpmpc_rollout_set_localiser", "mpmpc_rollout_localiser",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -739,6 +748,52 @@ class Handle:
                                                      _d(out["meas2_sum"]), _d(out["head2_sum"]), _i(out["used"]), _i(out["steps"])))
         return out
 
+    # --- lidar localisation of the rollout, per fleet
+    LOCALISER_FIELDS = ("fix", "prior", "cand", "score", "hits", "ranges", "err2_max", "err2_sum", "head2_sum", "prior2_sum", "steps",
+                        "matched", "lost", "edge")
+
+    def rollout_set_localiser(self, B, angles=None, range_m=0.0, D=1, m=1, W=0, T=0, step_psi=0.0, min_hits=1, sigma_r=0.0, period=1,
+                              seed=0, car0=0, step0=0, fix0=None):
+        """The scan matcher of the rollouts that follow (K0d, K3l; the law: csrc/localiser_core.hpp), one setting for the B cars -
+        or B = 0 / None for none (the default).  localiser.Localiser.setting() gives the keyword arguments.  Every step with
+        (k - step0) mod period == 0 each running car scans its TRUE world (angles [n] ascending, range_m in metres) and matches
+        the scan against the distance field of the BASE map (reach D cells, built by this call: needs set_map) around dead
+        reckoning: headings t * step_psi, t in [-T, T], translations (a, c) * m cells, a, c in [-W, W]; fewer than min_hits hits
+        and the car keeps dead reckoning; a hit's range takes sigma_r times a triangular variate of (seed, car0 + car,
+        k - step0, beam).  The FIX is what the estimator measures and what the controller localises on (the estimate, else
+        the fix); the true pose stays rollout_state()["pose"].  fix0 [B, 3]: the cars start primed with it (a resumed run).
+        May be called before rollout_init or between rollout_step calls; rollout_init un-primes every car and zeroes the
+        statistics.  After set_map / set_path / set_path_geometry it must be set again.  Not together with an assumed delay
+        of 8."""
+        if not B or angles is None:
+            self._check(self.lib.mpmpc_rollout_set_localiser(self._h, 0, 0, None, 0.0, 0, 0, 0, 0, 0.0, 0, 0.0, 0, 0, 0, 0, None))
+            self._lc_beams = 0
+            return
+        ang = np.ascontiguousarray(angles, dtype=np.float64).ravel()
+        f0 = None if fix0 is None else np.ascontiguousarray(fix0, dtype=np.float64).reshape(int(B), 3)
+        self._check(self.lib.mpmpc_rollout_set_localiser(self._h, int(B), ang.size, _d(ang), float(range_m), int(D), int(m), int(W), int(T),
+                                                         float(step_psi), int(min_hits), float(sigma_r), int(period),
+                                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(car0), int(step0), _d(f0)))
+        self._lc_beams = ang.size
+
+    def rollout_localiser(self):
+        """-> dict of the localiser's per-car state: fix, prior [B, 3], cand, score, hits [B] as the car's last step left them
+        (cand, the winner's index, and score: -1 on a step without a match; hits: -1 on a step without a scan); ranges
+        [B, n_beams], the scans of the last scheduled step with the hits noisy; err2_max and err2_sum, maximum and sum over the
+        car's steps of the squared position error of the fix against the true pose; head2_sum, the sum of its squared wrapped
+        heading error; prior2_sum, err2_sum of the prior - dead reckoning alone; steps, matched, lost, edge: the counters."""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        n = int(getattr(self, "_lc_beams", 0))
+        out = dict(fix=np.zeros((B, 3)), prior=np.zeros((B, 3)), cand=np.zeros(B, np.int32), score=np.zeros(B, np.int32),
+                   hits=np.zeros(B, np.int32), ranges=np.zeros((B, n)), err2_max=np.zeros(B), err2_sum=np.zeros(B), head2_sum=np.zeros(B),
+                   prior2_sum=np.zeros(B), steps=np.zeros(B, np.int32), matched=np.zeros(B, np.int32), lost=np.zeros(B, np.int32),
+                   edge=np.zeros(B, np.int32))
+        self._check(self.lib.mpmpc_rollout_localiser(self._h, B, _d(out["fix"]), _d(out["prior"]), _i(out["cand"]), _i(out["score"]),
+                                                     _i(out["hits"]), _d(out["ranges"]) if out["ranges"].size else None, _d(out["err2_max"]),
+                                                     _d(out["err2_sum"]), _d(out["head2_sum"]), _d(out["prior2_sum"]), _i(out["steps"]),
+                                                     _i(out["matched"]), _i(out["lost"]), _i(out["edge"])))
+        return out
+
     # --- footprint audit of the rollout: contact and clearance of every car, every step, accumulated on the device
     AUDIT_FIELDS = ("contact_steps", "first_contact", "min_clearance", "min_step", "last_contact", "last_clearance")
 
@@ -958,6 +1013,45 @@ def plant_noise(seed, car0, B, j0, n_steps, device=0):
                                _d(out) if out.size else _d(np.zeros(1)))
     if rc != 0:
         raise MpmpcError("mpmpc_plant_noise: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    return out
+
+
+def distance_field(grid, D, device=0):
+    """The capped squared-distance field of a grid on the device (K0d; the law: csrc/localiser_core.hpp): grid [H, W] int8 (1 free /
+    0 occupied), D in [1, 15] cells -> uint8 [H, W], min(D^2 + 1, the smallest squared cell distance <= D^2 to an occupied cell).
+    localiser.Localiser.field is the numpy evaluation."""
+    lib = load_library()
+    grid = np.ascontiguousarray(grid, dtype=np.int8)
+    if grid.ndim != 2:
+        raise ValueError("map grid must be 2-D [height, width]")
+    out = np.zeros(grid.shape, np.uint8)
+    rc = lib.mpmpc_distance_field(int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)), int(D),
+                                  out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise MpmpcError("mpmpc_distance_field: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    return out
+
+
+def scan_match(grid, origin, resolution, priors, ranges, angles, range_m, D, m, W, T, step_psi, min_hits=1, device=0):
+    """Scan matching of B (prior, scan) pairs on the device (K0d, then K3l's match; the law: csrc/localiser_core.hpp, steps 3 -
+    the hits, no noise - and 4): grid [H, W] int8 with its origin and resolution, priors [B, 3], ranges [B, n] of the beams
+    angles [n] (ascending) with range_m -> dict(fix [B, 3], score, cand, hits [B]); cand = score = -1 and fix = prior where there
+    is no match.  localiser.Localiser.match is the numpy evaluation."""
+    lib = load_library()
+    grid = np.ascontiguousarray(grid, dtype=np.int8)
+    if grid.ndim != 2:
+        raise ValueError("map grid must be 2-D [height, width]")
+    priors = np.ascontiguousarray(priors, dtype=np.float64).reshape(-1, 3)
+    ang = np.ascontiguousarray(angles, dtype=np.float64).ravel()
+    B = priors.shape[0]
+    rg = np.ascontiguousarray(ranges, dtype=np.float64).reshape(B, ang.size)
+    out = dict(fix=np.zeros((B, 3)), score=np.zeros(B, np.int32), cand=np.zeros(B, np.int32), hits=np.zeros(B, np.int32))
+    rc = lib.mpmpc_scan_match(int(device), grid.shape[0], grid.shape[1], grid.ctypes.data_as(C.POINTER(C.c_int8)), float(origin[0]),
+                              float(origin[1]), float(resolution), B, _d(priors), _d(rg), ang.size, _d(ang), float(range_m), int(D),
+                              int(m), int(W), int(T), float(step_psi), int(min_hits), _d(out["fix"]), _i(out["score"]), _i(out["cand"]),
+                              _i(out["hits"]))
+    if rc != 0:
+        raise MpmpcError("mpmpc_scan_match: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
     return out
 
 
