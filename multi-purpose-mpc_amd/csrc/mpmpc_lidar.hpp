@@ -242,6 +242,19 @@ __global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_kernel(MapView m
   k0l_scan_car<WALLS, 0>(map, B, pose, off, discs, n_beams, angles, range_m, ranges, wv, K0sArgs{});
 }
 
+// K0l of a localising rollout step (mpmpc_rollout_step.hpp): the same scan, of the running cars alone.  A car with alive != 1
+// keeps the ranges of its last scan - those K3l matched, the hits noisy -, as K3l keeps everything else of it.
+template <bool WALLS>
+__global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_running_kernel(MapView map, int B, const double* __restrict__ pose,
+                                                                               const int* __restrict__ alive,
+                                                                               const int* __restrict__ off,
+                                                                               const int* __restrict__ discs, int n_beams,
+                                                                               const double* __restrict__ angles, double range_m,
+                                                                               double* __restrict__ ranges, WallView wv) {
+  if ((int)blockIdx.x < B && alive[blockIdx.x] != 1) return;      // (uniform, in front of the scan's first barrier)
+  k0l_scan_car<WALLS, 0>(map, B, pose, off, discs, n_beams, angles, range_m, ranges, wv, K0sArgs{});
+}
+
 // device scratch of mpmpc_lidar_scan, kept between calls like the speed profile's (SpScratch: one per device, each behind
 // its own mutex, never freed)
 static SpScratch g_lid_dev[SP_MAX_DEVICES];

@@ -135,12 +135,13 @@ static const double* localise_pose(mpmpc_handle h, const StepPlan& p) {
   return p.estimating ? h->es.est.get() : measured_pose(h, p);
 }
 
-// K0l of a scheduled localising step: every car's TRUE pose in its TRUE world of step k (behind K0t and K0m), into the localiser's ranges
+// K0l of a scheduled localising step: every running car's TRUE pose in its TRUE world of step k (behind K0t and K0m), into the
+// localiser's ranges; a car that is not running keeps its last scan
 template <bool WALLS>
 static void launch_localiser_scan(mpmpc_handle h, Slot& sl, int B, const StepPlan& p, WallView wv) {
-  hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<WALLS>, dim3(B), dim3(K0L_THREADS), 0, sl.stream, p.map, B, h->ro.pose.get(),
-                     p.discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), h->lc.n_beams, h->lc.angles.get(), h->lc.range,
-                     h->lc.ranges.get(), wv);
+  hipLaunchKernelGGL(mpmpc_lidar_scan_running_kernel<WALLS>, dim3(B), dim3(K0L_THREADS), 0, sl.stream, p.map, B, h->ro.pose.get(),
+                     h->ro.alive.get(), p.discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), h->lc.n_beams,
+                     h->lc.angles.get(), h->lc.range, h->lc.ranges.get(), wv);
 }
 static void enqueue_localiser_scan(mpmpc_handle h, Slot& sl, int B, const StepPlan& p) {
   if (p.walls) launch_localiser_scan<true>(h, sl, B, p, h->obs.wall_view());
