@@ -676,7 +676,8 @@ int mpmpc_rollout_estimator(mpmpc_handle h, int32_t B, double* est, double* cov,
  *                          prior; steps, matched, lost, edge [B].  MPMPC_E_STATE unless a step of B cars ran under the setting.
  * The scan is mpmpc_lidar_scan's, the reference's lidar: at headings above 0 (and unwrapped ones beyond pi) it mirrors the cells
  * behind the car on its right onto the beams behind it on its left, and the match follows what the sensor reports.
- * Out of scope: per-car settings, matching against discs, walls or perceived worlds, sub-cell refinement, the fix in the trace.
+ * Out of scope: per-car settings, matching against discs, walls or perceived worlds, sub-cell refinement.  (The fix and the scan of every
+ * step: MPMPC_REC_FIX / MPMPC_REC_SCAN of mpmpc_rollout_record.)
  * A rollout without the setting launches exactly what it launched before. */
 int mpmpc_distance_field(int32_t device, int32_t height, int32_t width, const int8_t* data, int32_t D, uint8_t* field_out);
 int mpmpc_scan_match(int32_t device, int32_t height, int32_t width, const int8_t* data, double origin_x, double origin_y, double resolution,
@@ -729,6 +730,39 @@ int mpmpc_rollout_recorded(mpmpc_handle h, int32_t* n_records, int32_t* n_steps)
 int mpmpc_rollout_trace(mpmpc_handle h, int32_t B, int32_t first, int32_t count, double* s, double* pose, int32_t* wp_id,
                         double* x0, double* u, int32_t* status, int32_t* counter, int32_t* alive, double* plan,
                         double* pred_x, double* pred_y, double* ub, double* lb);
+/* The pose chain in the trace: five more bits for `fields`, each the state of one feature that stands between the car's true pose
+ * and the pose its controller plans on.  Every value is the one the matching getter (mpmpc_rollout_plant / _delay / _estimator /
+ * _localiser) would return if it were called right after that step, so one multi-step mpmpc_rollout_step yields the time series
+ * that otherwise takes one step per call and a download of every getter in between.
+ *   bit  macro             per car and record
+ *     8  MPMPC_REC_PLANT   act [2], meas [3]
+ *    16  MPMPC_REC_DELAY   queue [MPMPC_DELAY_MAX][2], pred_pose [3], pred_s, now [3]
+ *    32  MPMPC_REC_EST     est [3], cov [6], used (int32)
+ *    64  MPMPC_REC_FIX     fix [3], prior [3], cand, score, hits (int32 each)
+ *   128  MPMPC_REC_SCAN    ranges [n_beams]: the localiser's scan of the step, the hits noisy
+ * Masks, with a_in the car's `alive` before the step ("empty": NaN for doubles, -2 for cand / score / hits - where -1 keeps its
+ * meanings "no match" / "no scan this step" -, -1 for used):
+ *   act, queue, used   state that outlives a step: as it stands after the step, for every car, like `counter`
+ *   meas, pred_pose, pred_s, now, est, cov, fix, prior, cand, score, hits
+ *                      the step's own: empty if a_in != 1 (K3n, K3d, K3e and K3l run for the cars the step finds running)
+ *   ranges             empty unless the record's own hits >= 0 (a_in == 1 and the step was a scheduled one)
+ *   feature off        a whole group - act and meas, queue .. now, est .. used, fix .. hits and ranges - is empty for every car at
+ *                      a step its feature is not in force for; settings may change between mpmpc_rollout_step calls
+ * mpmpc_rollout_record with MPMPC_REC_SCAN needs a localiser in force (MPMPC_E_STATE otherwise): a record holds that setting's
+ * n_beams ranges per car, and a step under a localiser with another n_beams while such a trace is open returns MPMPC_E_STATE
+ * before it launches anything.  Bits above 255: MPMPC_E_ARG.  A rollout that records no chain bit launches what it launched
+ * before; one that does gets one more kernel per recorded step, which reads the features' own buffers.
+ *   mpmpc_rollout_trace_chain  records first .. first + count - 1 into host arrays [count][B][...], as mpmpc_rollout_trace does
+ *                      for the other fields and with the trace's lifetime.  Any pointer may be NULL; a field whose bit was not
+ *                      selected, or records beyond those held: MPMPC_E_STATE. */
+#define MPMPC_REC_PLANT 8
+#define MPMPC_REC_DELAY 16
+#define MPMPC_REC_EST 32
+#define MPMPC_REC_FIX 64
+#define MPMPC_REC_SCAN 128
+int mpmpc_rollout_trace_chain(mpmpc_handle h, int32_t B, int32_t first, int32_t count, double* act, double* meas, double* queue,
+                              double* pred_pose, double* pred_s, double* now, double* est, double* cov, int32_t* used, double* fix,
+                              double* prior, int32_t* cand, int32_t* score, int32_t* hits, double* ranges);
 
 /* replaces MPC._init_problem (src/MPC.py:61-155) for B instances: LTV linearisation
  * (src/spatial_bicycle_models.py:391-417) around waypoints wp_id+0..N-1, offsets, speed cap from

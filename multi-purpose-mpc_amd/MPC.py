@@ -457,10 +457,13 @@ class BatchMPC:
         stay true.  The returned dict also holds "localiser": handle.rollout_localiser() - fix, prior, cand, score, hits, ranges,
         err2_max, err2_sum, head2_sum, prior2_sum, steps, matched, lost, edge (None when n_steps = 0).
         record: None - nothing is recorded; True or a dict of mpmpc.Handle.rollout_record's keyword arguments (capacity,
-        plan, prediction, rows, stride; capacity defaults to the records `n_steps` yields) - the run is recorded on the
-        device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of the whole run, arrays
-        [records, B, ...] with the state every recorded step started from, its control, status, ... (what
-        src/simulation.py:117-157 logs per step)."""
+        plan, prediction, rows, stride, plant, delay, estimator, fix, scan, chain; capacity defaults to the records `n_steps`
+        yields) - the run is recorded on the device and the returned dict also holds "trace": mpmpc.Handle.rollout_trace() of
+        the whole run, arrays [records, B, ...] with the state every recorded step started from, its control, status, ...
+        (what src/simulation.py:117-157 logs per step).  The pose chain of every recorded step, each value what the feature's
+        getter would return right after that step: plant - act, meas; delay - queue, pred_pose, pred_s, now; estimator - est,
+        cov, used; fix - fix, prior, cand, score, hits; chain=True - these four; scan - ranges, the localiser's scan (needs
+        `localiser`).  A group is empty (NaN; cand / score / hits -2, used -1) where its feature is off."""
         rp = self._path
         fleet = getattr(self, "_routes", None)      # (getattr: tests call rollout on stand-ins without __init__)
         if (fleet is None) != (routes is None):
@@ -514,6 +517,8 @@ class BatchMPC:
         if localiser is not None and delay is not None and np.any(delay.arrays(np.asarray(s).size)[1] >= 8):
             raise ValueError("localiser and an assumed delay of 8 cannot be combined: the command that reached the wheels in the "
                              "last step has left the register by then")
+        if isinstance(record, dict) and record.get("scan") and localiser is None:
+            raise ValueError("record=dict(scan=True) needs a localiser: the scan recorded is the localiser's")
         if fleet is not None:
             self.handle.set_car_routes(routes)      # (the routes' geometry went up with set_routes)
         elif getattr(self.handle, "_n_wp", None) != rp.n_waypoints:
@@ -588,6 +593,8 @@ class BatchMPC:
         kw = dict(record) if isinstance(record, dict) else {}
         stride = int(kw.get("stride", 1))
         kw.setdefault("capacity", max(1, -(-int(n_steps) // max(stride, 1))))
+        if kw.get("scan"):      # (the record's layout takes the n_beams of the localiser in force; set again behind rollout_init)
+            self._set_localiser(localiser, np.asarray(s).size)
         self.handle.rollout_record(B=np.asarray(s).size, **kw)
         try:
             self.handle.rollout_init(self.model.Ts, cum, s, poses, cc0)

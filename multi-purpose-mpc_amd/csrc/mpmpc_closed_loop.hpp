@@ -568,6 +568,16 @@ __global__ __launch_bounds__(256) void mpmpc_record_write_kernel(int B, RoRecSrc
   if (i >= B) return;
   ro_record_finish(src, rec, lay, i, e);
 }
+// ... and a third launch behind `write` when a chain bit is selected (MPMPC_REC_PLANT .. MPMPC_REC_SCAN): the pose chain of the step
+// from the features' own buffers (ro_record_chain; none of them is written again between its kernel and the end of the step), the
+// same thread layout.  `rec` is the address of the record's chain.  No LDS, no scratch.
+static_assert(RO_CHAIN_QUEUE == DL_MAX && RO_CHAIN_COV == ES_COV, "rollout_core.hpp disagrees with delay_core.hpp / estimator_core.hpp");
+__global__ __launch_bounds__(256) void mpmpc_record_chain_kernel(int B, RoChainSrc src, char* __restrict__ rec, RoChainLayout lay) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  const int i = (int)(g / lay.entries), e = (int)(g - (long)i * lay.entries);
+  if (i >= B) return;
+  ro_record_chain(src, rec, lay, i, e);
+}
 
 // the footprint audit (mpmpc_footprint.hpp, which follows this header): its accumulators start over with a rollout
 static int aud_reset(mpmpc_handle h, int B);
@@ -753,20 +763,25 @@ int mpmpc_rollout_record(mpmpc_handle h, int32_t B, int32_t capacity, int32_t fi
   if (int rc = enter(h)) return rc;
   if (capacity < 0) return fail(MPMPC_E_ARG, "capacity must be >= 0");
   if (stride < 1) return fail(MPMPC_E_ARG, "stride must be >= 1");
-  if (fields & ~RO_REC_ALL) return fail(MPMPC_E_ARG, "unknown bits in fields");
+  if (fields & ~RO_REC_EVERY) return fail(MPMPC_E_ARG, "unknown bits in fields");
   if (B < 1 || B > h->cfg.max_batch) return fail(MPMPC_E_ARG, "B must be in [1, max_batch]");
+  if (capacity > 0 && (fields & RO_REC_SCAN) && h->lc.B == 0)      // (the layout takes the setting's n_beams)
+    return fail(MPMPC_E_STATE, "MPMPC_REC_SCAN needs a localiser in force (mpmpc_rollout_set_localiser)");
   HIP_TRY(hipSetDevice(h->cfg.device));
   HIP_TRY(hipStreamSynchronize(h->last().stream));
   h->rec.buf.reset();
   h->rec.cap = h->rec.count = 0;
   if (capacity == 0) return MPMPC_OK;
   const RoTraceLayout lay = ro_trace_layout(h->cfg.N, B, fields);
+  const RoChainLayout chain = ro_chain_layout(B, fields, h->lc.n_beams);
+  const size_t bytes = (size_t)lay.bytes + (size_t)chain.bytes;
   if (!h->rec.ain) HIP_TRY(h->rec.ain.alloc((size_t)h->cfg.max_batch));
-  if (h->rec.buf.alloc((size_t)lay.bytes * (size_t)capacity)) {
+  if (h->rec.buf.alloc(bytes * (size_t)capacity)) {
     (void)hipGetLastError();
-    return fail(MPMPC_E_HIP, "no device memory for " + std::to_string(capacity) + " records of " + std::to_string(lay.bytes) + " bytes");
+    return fail(MPMPC_E_HIP, "no device memory for " + std::to_string(capacity) + " records of " + std::to_string(bytes) + " bytes");
   }
   h->rec.lay = lay;
+  h->rec.chain = chain;
   h->rec.cap = capacity;
   h->rec.B = B;
   h->rec.fields = fields;
@@ -783,9 +798,9 @@ int mpmpc_rollout_recorded(mpmpc_handle h, int32_t* n_records, int32_t* n_steps)
 
 // field `off` of records first .. first + count - 1 -> host [count][bytes]: one strided copy
 static int pull_field(mpmpc_handle h, void* dst, long long off, size_t bytes, int first, int count) {
-  const char* src = h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)first + off;
+  const char* src = h->rec.buf + h->rec.rec_bytes() * (size_t)first + off;
   if (count == 1) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->last().stream));
-  else HIP_TRY(hipMemcpy2DAsync(dst, bytes, src, (size_t)h->rec.lay.bytes, bytes, (size_t)count, hipMemcpyDeviceToHost, h->last().stream));
+  else HIP_TRY(hipMemcpy2DAsync(dst, bytes, src, h->rec.rec_bytes(), bytes, (size_t)count, hipMemcpyDeviceToHost, h->last().stream));
   return MPMPC_OK;
 }
 
@@ -810,6 +825,36 @@ int mpmpc_rollout_trace(mpmpc_handle h, int32_t B, int32_t first, int32_t count,
     PULL(status, l.status, 4); PULL(counter, l.counter, 4); PULL(alive, l.alive, 4);
     PULL(plan, l.plan, 16 * N); PULL(pred_x, l.pred_x, 8 * (N - 2)); PULL(pred_y, l.pred_y, 8 * (N - 2));
     PULL(ub, l.ub, 8 * N); PULL(lb, l.lb, 8 * N);
+#undef PULL
+  }
+  HIP_TRY(hipStreamSynchronize(h->last().stream));
+  return MPMPC_OK;
+}
+
+int mpmpc_rollout_trace_chain(mpmpc_handle h, int32_t B, int32_t first, int32_t count, double* act, double* meas, double* queue,
+                              double* pred_pose, double* pred_s, double* now, double* est, double* cov, int32_t* used, double* fix,
+                              double* prior, int32_t* cand, int32_t* score, int32_t* hits, double* ranges) {
+  if (int rc = enter(h)) return rc;
+  if (first < 0 || count < 0) return fail(MPMPC_E_ARG, "first and count must be >= 0");
+  if (h->rec.cap == 0) return fail(MPMPC_E_STATE, "recording is off (mpmpc_rollout_record)");
+  if (B != h->rec.B) return fail(MPMPC_E_STATE, "mpmpc_rollout_record was set up for another number of cars");
+  if ((long long)first + count > h->rec.count)
+    return fail(MPMPC_E_STATE, "records " + std::to_string(first) + " .. " + std::to_string((long long)first + count - 1) +
+                                   " asked for, " + std::to_string(h->rec.count) + " held");
+  const RoChainLayout& l = h->rec.chain;
+  if (((act || meas) && l.act < 0) || ((queue || pred_pose || pred_s || now) && l.queue < 0) || ((est || cov || used) && l.est < 0) ||
+      ((fix || prior || cand || score || hits) && l.fix < 0) || (ranges && l.ranges < 0))
+    return fail(MPMPC_E_STATE, "a field was asked for that mpmpc_rollout_record did not select");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if (count > 0) {
+    const size_t nb = (size_t)B;
+    const long long at = h->rec.lay.bytes;      // the chain's start in a record
+#define PULL(dst, off, per_car) if (dst) { if (int rc = pull_field(h, dst, at + off, (per_car) * nb, first, count)) return rc; }
+    PULL(act, l.act, 16); PULL(meas, l.meas, 24);
+    PULL(queue, l.queue, 16 * (size_t)RO_CHAIN_QUEUE); PULL(pred_pose, l.pred_pose, 24); PULL(pred_s, l.pred_s, 8); PULL(now, l.now, 24);
+    PULL(est, l.est, 24); PULL(cov, l.cov, 8 * (size_t)RO_CHAIN_COV); PULL(used, l.used, 4);
+    PULL(fix, l.fix, 24); PULL(prior, l.prior, 24); PULL(cand, l.cand, 4); PULL(score, l.score, 4); PULL(hits, l.hits, 4);
+    PULL(ranges, l.ranges, 8 * (size_t)l.n_beams);
 #undef PULL
   }
   HIP_TRY(hipStreamSynchronize(h->last().stream));

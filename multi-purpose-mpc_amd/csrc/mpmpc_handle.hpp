@@ -128,11 +128,13 @@ struct RoState {
   }
 };
 
-// recorder (mpmpc_rollout_record): the trace has its own memory, [cap] records of lay.bytes each
+// recorder (mpmpc_rollout_record): the trace has its own memory, [cap] records of rec_bytes() each
 struct RecState {
   Buf<char> buf;
   Buf<int> ain;             // [B] alive before the step being recorded
   RoTraceLayout lay{};
+  RoChainLayout chain{};    // the pose chain behind it (chain.bytes == 0: no chain bit selected)
+  size_t rec_bytes() const { return (size_t)lay.bytes + (size_t)chain.bytes; }      // a record's stride
   int cap = 0, B = 0, fields = 0, stride = 1;
   int count = 0;            // records held
   long long ro_steps = 0;   // rollout steps since mpmpc_rollout_init

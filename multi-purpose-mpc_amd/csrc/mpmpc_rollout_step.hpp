@@ -21,7 +21,7 @@ struct StepPlan {
 
 // Every check and lay-out of a step of B cars, in this order (the first refusal that applies is the call's): the rollout's
 // state, n_steps, the per-car settings' B, stale generations, the recorder's B and capacity, the plant's B, the delay's B, the
-// estimator's B, the localiser's B, map and generation, the audit, perception, the routes, the lookahead, the delay under a
+// estimator's B, the localiser's B, map and generation, the beams of a recorded scan, the audit, perception, the routes, the lookahead, the delay under a
 // lookahead, the estimator and the localiser under an assumed delay of DL_MAX.
 static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
@@ -57,6 +57,9 @@ static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
     if (!h->cor.map) return fail(MPMPC_E_STATE, "the localiser needs mpmpc_set_map first");
     if (h->lc.gen != h->cor.base_gen)      // (the field is the map's of the setting)
       return fail(MPMPC_E_STATE, "map, path or geometry changed since mpmpc_rollout_set_localiser: set the localiser again");
+    if (p.recording && h->rec.chain.ranges >= 0 && h->lc.n_beams != h->rec.chain.n_beams)
+      return fail(MPMPC_E_STATE, "the trace records scans of " + std::to_string(h->rec.chain.n_beams) + " beams, the localiser in force has " +
+                                     std::to_string(h->lc.n_beams) + " (mpmpc_rollout_record with MPMPC_REC_SCAN: set it up again)");
   }
   if (int rc = aud_check_step(h, B)) return rc;
   p.auditing = h->aud.mode != FP_MODE_OFF;
@@ -228,6 +231,23 @@ static void enqueue_record_write(mpmpc_handle h, Slot& sl, int B, const StepPlan
                      rec, h->rec.lay);
 }
 
+// K3r, chain: the pose chain of the step behind the record, from the buffers of the features in force at this step (the others'
+// groups are empty: a null first pointer); only when a chain bit is selected
+static void enqueue_record_chain(mpmpc_handle h, Slot& sl, int B, const StepPlan& p, char* chain) {
+  const size_t mb = (size_t)h->cfg.max_batch;
+  RoChainSrc src{};
+  src.a_in = h->rec.ain;
+  if (p.plant) { src.act = h->pl.act; src.meas = h->pl.meas; }
+  if (p.delaying) { src.queue = h->dl.queue; src.pred_pose = h->dl.pred_pose; src.pred_s = h->dl.pred_s; src.now = h->dl.now; }
+  if (p.estimating) { src.est = h->es.est; src.cov = h->es.cov; src.used = h->es.count; }
+  if (p.localising) {
+    src.fix = h->lc.fix; src.prior = h->lc.prior; src.ranges = h->lc.ranges;
+    src.cand = h->lc.out; src.score = h->lc.out + mb; src.hits = h->lc.out + 2 * mb;
+  }
+  hipLaunchKernelGGL(mpmpc_record_chain_kernel, dim3((unsigned)(((long)B * h->rec.chain.entries + 255) / 256)), dim3(256), 0, sl.stream, B, src,
+                     chain, h->rec.chain);
+}
+
 // what the handle remembers of a call that ran at least one step
 static void step_ran(mpmpc_handle h, int B, const StepPlan& p) {
   h->obs.car_rows = h->obs.discs_live = p.per_car;
@@ -252,7 +272,7 @@ extern "C" int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     HIP_TRY(hipMemsetAsync(h->tlk.valid, 0, sizeof(int) * (size_t)h->cfg.max_batch, sl.stream));
   for (int t = 0; t < n_steps; ++t) {
     const long long k = h->rec.ro_steps;
-    char* rec = p.recording && k % h->rec.stride == 0 ? h->rec.buf + (size_t)h->rec.lay.bytes * (size_t)h->rec.count : nullptr;
+    char* rec = p.recording && k % h->rec.stride == 0 ? h->rec.buf + h->rec.rec_bytes() * (size_t)h->rec.count : nullptr;
     if (rec) enqueue_record_snapshot(h, sl, B, rec);                                       // K3r snapshot
     if (p.traffic) enqueue_traffic(h, sl, B, p);                                           // K0t: pose and alive as the step finds them
     const bool movers_first = p.perceiving || p.localising;
@@ -277,6 +297,7 @@ extern "C" int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     if (p.ahead_traffic) tlk_enqueue_tracks(h, sl, B, p.map, p.route);                     // K3t: this step's plans, for the next one's K0ht
     if (rec) {
       enqueue_record_write(h, sl, B, p, rec);                                              // K3r write
+      if (h->rec.chain.bytes > 0) enqueue_record_chain(h, sl, B, p, rec + h->rec.lay.bytes);  // K3r chain
       ++h->rec.count;
     }
     ++h->rec.ro_steps;

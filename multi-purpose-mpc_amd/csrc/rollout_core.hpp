@@ -208,4 +208,105 @@ MPMPC_HD void ro_record_finish(const RoRecSrc& r, char* rec, const RoTraceLayout
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The pose chain in the record (include/mpmpc.h, MPMPC_REC_PLANT .. MPMPC_REC_SCAN): what the plant, the delay, the estimator and
+// the localiser left in their own buffers when the step ended - every value the one the feature's getter would return right
+// after the step.  The chain lies BEHIND the record ro_trace_layout describes (RoTraceLayout and the two kernels that take it by
+// value do not know of it): its offsets count from the chain's start, which is RoTraceLayout::bytes into the record, and a
+// record's stride is the sum of the two.
+//   ro_record_chain    after advance, behind ro_record_finish: one ENTRY of one car, like the two above
+// "Empty": NaN for doubles, -2 for cand / score / hits (-1 keeps its meanings there), -1 for used.
+constexpr int RO_REC_PLANT = 8, RO_REC_DELAY = 16, RO_REC_EST = 32, RO_REC_FIX = 64, RO_REC_SCAN = 128;
+constexpr int RO_REC_CHAIN = RO_REC_PLANT | RO_REC_DELAY | RO_REC_EST | RO_REC_FIX | RO_REC_SCAN, RO_REC_EVERY = RO_REC_ALL | RO_REC_CHAIN;
+constexpr int RO_CHAIN_QUEUE = 8;      // the command register's entries (DL_MAX of delay_core.hpp, which includes this header)
+constexpr int RO_CHAIN_COV = 6;        // the covariance's upper triangle (ES_COV of estimator_core.hpp)
+
+struct RoChainLayout {
+  long long act, meas, queue, pred_pose, pred_s, now, est, cov, used, fix, prior, cand, score, hits, ranges;      // -1: not recorded
+  long long bytes;      // of the chain of one record (a multiple of 256; 0: no chain bit)
+  int entries;          // per car in ro_record_chain
+  int n_beams;          // of `ranges`
+};
+inline RoChainLayout ro_chain_layout(int B, int fields, int n_beams) {
+  RoChainLayout l;
+  long long at = 0;
+  auto take = [&](int bit, long long per_car) {
+    if (!(fields & bit)) return -1LL;
+    const long long o = at;
+    at += (per_car * B + 255) / 256 * 256;
+    return o;
+  };
+  l.act = take(RO_REC_PLANT, 16); l.meas = take(RO_REC_PLANT, 24);
+  l.queue = take(RO_REC_DELAY, 16LL * RO_CHAIN_QUEUE); l.pred_pose = take(RO_REC_DELAY, 24); l.pred_s = take(RO_REC_DELAY, 8);
+  l.now = take(RO_REC_DELAY, 24);
+  l.est = take(RO_REC_EST, 24); l.cov = take(RO_REC_EST, 8LL * RO_CHAIN_COV); l.used = take(RO_REC_EST, 4);
+  l.fix = take(RO_REC_FIX, 24); l.prior = take(RO_REC_FIX, 24); l.cand = take(RO_REC_FIX, 4); l.score = take(RO_REC_FIX, 4);
+  l.hits = take(RO_REC_FIX, 4);
+  l.ranges = take(RO_REC_SCAN, 8LL * n_beams);
+  l.bytes = at;
+  l.n_beams = (fields & RO_REC_SCAN) ? n_beams : 0;
+  l.entries = ((fields & RO_REC_PLANT) ? 5 : 0) + ((fields & RO_REC_DELAY) ? 2 * RO_CHAIN_QUEUE + 7 : 0) +
+              ((fields & RO_REC_EST) ? 4 + RO_CHAIN_COV : 0) + ((fields & RO_REC_FIX) ? 9 : 0) + l.n_beams;
+  return l;
+}
+
+// what ro_record_chain reads: a_in (ro_record_begin kept it) and the features' own buffers as the step leaves them.  A group's
+// first pointer is null when its feature is not in force at the step: the whole group is then empty for every car.
+struct RoChainSrc {
+  const int* a_in;
+  const double *act, *meas;                          // plant: [B][2], [B][3]
+  const double *queue, *pred_pose, *pred_s, *now;    // delay: [B][RO_CHAIN_QUEUE][2], [B][3], [B], [B][3]
+  const double *est, *cov;                           // estimator: [B][3], [B][RO_CHAIN_COV]
+  const int* used;                                   //   [B]
+  const double *fix, *prior;                         // localiser: [B][3] each
+  const int *cand, *score, *hits;                    //   [B] each
+  const double* ranges;                              //   [B][n_beams], n_beams the layout's
+};
+
+// entry e of car i, in the order act[2], meas[3] / queue[2 RO_CHAIN_QUEUE], pred_pose[3], pred_s, now[3] / est[3], cov[RO_CHAIN_COV], used /
+// fix[3], prior[3], cand, score, hits / ranges[n_beams], as recorded.  act, queue and used outlive a step and are recorded for every
+// car as they stand; the others are the step's own and K3n, K3d, K3e and K3l write them for the cars the step finds running
+// (alive == 1) alone; the scan is the step's where its hits are counted (hits >= 0).
+MPMPC_HD void ro_record_chain(const RoChainSrc& r, char* rec, const RoChainLayout& l, int i, int e) {
+  const bool ran = ro_rec_state(r.a_in[i]);
+  const double nan = ro_rec_nan();
+  if (l.act >= 0) {
+    if (e < 2) { ((double*)(rec + l.act))[2LL * i + e] = r.act ? r.act[2LL * i + e] : nan; return; }
+    if (e < 5) { ((double*)(rec + l.meas))[3LL * i + e - 2] = r.act && ran ? r.meas[3LL * i + e - 2] : nan; return; }
+    e -= 5;
+  }
+  if (l.queue >= 0) {
+    const bool have = r.queue && ran;
+    constexpr int Q = 2 * RO_CHAIN_QUEUE;
+    if (e < Q) { ((double*)(rec + l.queue))[(long long)Q * i + e] = r.queue ? r.queue[(long long)Q * i + e] : nan; return; }
+    if (e < Q + 3) { ((double*)(rec + l.pred_pose))[3LL * i + e - Q] = have ? r.pred_pose[3LL * i + e - Q] : nan; return; }
+    if (e == Q + 3) { ((double*)(rec + l.pred_s))[i] = have ? r.pred_s[i] : nan; return; }
+    if (e < Q + 7) { ((double*)(rec + l.now))[3LL * i + e - Q - 4] = have ? r.now[3LL * i + e - Q - 4] : nan; return; }
+    e -= Q + 7;
+  }
+  if (l.est >= 0) {
+    const bool have = r.est && ran;
+    if (e < 3) { ((double*)(rec + l.est))[3LL * i + e] = have ? r.est[3LL * i + e] : nan; return; }
+    if (e < 3 + RO_CHAIN_COV) {
+      ((double*)(rec + l.cov))[(long long)RO_CHAIN_COV * i + e - 3] = have ? r.cov[(long long)RO_CHAIN_COV * i + e - 3] : nan;
+      return;
+    }
+    if (e == 3 + RO_CHAIN_COV) { ((int*)(rec + l.used))[i] = r.est ? r.used[i] : -1; return; }
+    e -= 4 + RO_CHAIN_COV;
+  }
+  if (l.fix >= 0) {
+    const bool have = r.fix && ran;
+    if (e < 3) { ((double*)(rec + l.fix))[3LL * i + e] = have ? r.fix[3LL * i + e] : nan; return; }
+    if (e < 6) { ((double*)(rec + l.prior))[3LL * i + e - 3] = have ? r.prior[3LL * i + e - 3] : nan; return; }
+    if (e == 6) { ((int*)(rec + l.cand))[i] = have ? r.cand[i] : -2; return; }
+    if (e == 7) { ((int*)(rec + l.score))[i] = have ? r.score[i] : -2; return; }
+    if (e == 8) { ((int*)(rec + l.hits))[i] = have ? r.hits[i] : -2; return; }
+    e -= 9;
+  }
+  if (l.ranges >= 0 && e < l.n_beams) {
+    const bool have = r.fix && ran && r.hits[i] >= 0;
+    ((double*)(rec + l.ranges))[(long long)l.n_beams * i + e] = have ? r.ranges[(long long)l.n_beams * i + e] : nan;
+  }
+}
+
 }  // namespace mpmpc

@@ -20,6 +20,7 @@ MAX_HORIZON = 255
 SOLVED, SOLVED_INACCURATE = 1, 2
 MAX_ITER_REACHED, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE, UNSOLVED = -2, -3, -4, -10
 REC_PLAN, REC_PRED, REC_ROWS = 1, 2, 4      # optional fields of a rollout record (mpmpc_rollout_record)
+REC_PLANT, REC_DELAY, REC_EST, REC_FIX, REC_SCAN = 8, 16, 32, 64, 128      # ... and the pose chain (mpmpc_rollout_trace_chain)
 
 
 class Config(C.Structure):
@@ -201,6 +202,8 @@ def load_library(path: str | None = None):
     lib.mpmpc_rollout_record.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.mpmpc_rollout_recorded.argtypes = [h, _ip, _ip]
     lib.mpmpc_rollout_trace.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
+    lib.mpmpc_rollout_trace_chain.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _ip,
+                                              _ip, _ip, _dp]
     lib.mpmpc_assemble.argtypes = [h, C.c_int32, _ip, _dp, _dp, _dp, _dp, _dp]
     lib.mpmpc_stage_ld.argtypes = [C.c_int32]
     lib.mpmpc_stage_ld.restype = C.c_int32
@@ -254,7 +257,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_rollout_set_movers", "mpmpc_rollout_obstacles", "mpmpc_rollout_set_traffic",
            "mpmpc_rollout_set_lookahead", "mpmpc_rollout_lookahead",
            "mpmpc_rollout_set_lookahead_traffic", "mpmpc_rollout_tracks", "mpmpc_rollout_lookahead_traffic",
-           "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams", "mpmpc_launch_plan",
+           "mpmpc_rollout_record", "mpmpc_rollout_recorded", "mpmpc_rollout_trace", "mpmpc_rollout_trace_chain", "mpmpc_assemble", "mpmpc_stage_ld", "mpmpc_solve", "mpmpc_upload", "mpmpc_solve_resident", "mpmpc_set_outputs", "mpmpc_set_pipeline", "mpmpc_hw_queue_budget", "mpmpc_pipeline_streams", "mpmpc_launch_plan",
            "mpmpc_sync", "mpmpc_download", "mpmpc_solve_resident_timed", "mpmpc_solve_resident_profile", "mpmpc_assemble_resident_timed", "mpmpc_speed_profile", "mpmpc_lidar_scan", "mpmpc_rollout_scan",
            "mpmpc_footprint_audit", "mpmpc_rollout_set_audit", "mpmpc_rollout_audit", "mpmpc_rollout_set_walls",
            "mpmpc_lidar_scan_world", "mpmpc_footprint_audit_world", "mpmpc_world_grid", "mpmpc_staging",
@@ -820,19 +823,25 @@ class Handle:
     # --- recorder of the rollout: one record per car and recorded step, kept on the device
     TRACE_BASIC = ("s", "pose", "wp_id", "x0", "u", "status", "counter", "alive")
 
-    def rollout_record(self, capacity, plan=False, prediction=False, rows=False, stride=1, B=None):
+    def rollout_record(self, capacity, plan=False, prediction=False, rows=False, stride=1, B=None, plant=False, delay=False,
+                       estimator=False, fix=False, scan=False, chain=False):
         """Record every `stride`-th step of the rollouts that follow into a device-resident trace of `capacity` records:
         always s, pose (the state the step started from), wp_id, x0, u, status, counter, alive; optionally the plan after
         the step, the predicted path (world x / y of stages 2 .. N-1, MPC.update_prediction) and the corridor row the QP
-        used.  capacity = 0 switches recording off and frees the memory.  B: cars per record (default: the rollout's, so
+        used; and optionally the pose chain, each value the one the feature's getter would return right after the step:
+        plant (act, meas), delay (queue, pred_pose, pred_s, now), estimator (est, cov, used), fix (fix, prior, cand, score,
+        hits), scan (ranges: needs a localiser in force now, whose n_beams the records take); chain=True selects the first
+        four.  capacity = 0 switches recording off and frees the memory.  B: cars per record (default: the rollout's, so
         before the first rollout_init it must be given).  A rollout_step that would overflow the trace raises and does
         nothing; rollout_init keeps the configuration and empties the trace."""
         B = int(B if B is not None else getattr(self, "_ro_B", 0))
         if B < 1:
             raise ValueError("rollout_record before rollout_init needs B")
-        fields = (REC_PLAN if plan else 0) | (REC_PRED if prediction else 0) | (REC_ROWS if rows else 0)
+        fields = (REC_PLAN if plan else 0) | (REC_PRED if prediction else 0) | (REC_ROWS if rows else 0) | \
+            (REC_PLANT if plant or chain else 0) | (REC_DELAY if delay or chain else 0) | (REC_EST if estimator or chain else 0) | \
+            (REC_FIX if fix or chain else 0) | (REC_SCAN if scan else 0)
         self._check(self.lib.mpmpc_rollout_record(self._h, B, int(capacity), fields, int(stride)))
-        self._rec = (B, fields) if capacity else None
+        self._rec = (B, fields, int(getattr(self, "_lc_beams", 0)) if fields & REC_SCAN else 0) if capacity else None
 
     def rollout_recorded(self):
         """-> (records held, rollout steps taken since rollout_init)"""
@@ -840,33 +849,48 @@ class Handle:
         self._check(self.lib.mpmpc_rollout_recorded(self._h, C.byref(n), C.byref(k)))
         return n.value, k.value
 
+    # the pose chain's fields by the bit that records them, in mpmpc_rollout_trace_chain's order
+    TRACE_CHAIN = ((REC_PLANT, ("act", "meas")), (REC_DELAY, ("queue", "pred_pose", "pred_s", "now")), (REC_EST, ("est", "cov", "used")),
+                   (REC_FIX, ("fix", "prior", "cand", "score", "hits")), (REC_SCAN, ("ranges",)))
+
     def rollout_trace(self, first=0, count=None, fields=None):
         """Records first .. first + count - 1 (default: all from `first`) -> dict of arrays [count, B, ...]: s, pose [.., 3],
         wp_id, x0 [.., 3], u [.., 2], status, counter, alive, and - where recorded - plan [.., 2N], pred_x / pred_y [.., N-2],
-        ub / lb [.., N].  fields: names to fetch (default: everything recorded; asking for one that was not raises).  Entries
-        a step did not produce for a car are empty - NaN, wp_id -1, status 0 (include/mpmpc.h has the table)."""
+        ub / lb [.., N], and the pose chain: act [.., 2], meas [.., 3], queue [.., 8, 2], pred_pose [.., 3], pred_s, now [.., 3],
+        est [.., 3], cov [.., 6], used, fix / prior [.., 3], cand, score, hits, ranges [.., n_beams].  fields: names to fetch
+        (default: everything recorded; asking for one that was not raises).  Entries a step did not produce for a car are
+        empty - NaN, wp_id -1, status 0, cand / score / hits -2, used -1 (include/mpmpc.h has the tables)."""
         if getattr(self, "_rec", None) is None:
             raise MpmpcError("mpmpc error -3: recording is off (rollout_record)")
-        B, rec = self._rec
+        B, rec, n_beams = self._rec
         N = self.N
         if count is None:
             count = self.rollout_recorded()[0] - int(first)
         count = int(count)
         names = list(self.TRACE_BASIC) + (["plan"] if rec & REC_PLAN else []) + (["pred_x", "pred_y"] if rec & REC_PRED else []) + \
-            (["ub", "lb"] if rec & REC_ROWS else [])
+            (["ub", "lb"] if rec & REC_ROWS else []) + [k for bit, group in self.TRACE_CHAIN if rec & bit for k in group]
         if fields is not None:
             names = list(fields)
         shape = dict(s=(), pose=(3,), wp_id=(), x0=(3,), u=(2,), status=(), counter=(), alive=(), plan=(2 * N,),
                      pred_x=(N - 2,), pred_y=(N - 2,), ub=(N,), lb=(N,))
-        ints = ("wp_id", "status", "counter", "alive")
+        chain = dict(act=(2,), meas=(3,), queue=(8, 2), pred_pose=(3,), pred_s=(), now=(3,), est=(3,), cov=(6,), used=(),
+                     fix=(3,), prior=(3,), cand=(), score=(), hits=(), ranges=(n_beams,))
+        ints = ("wp_id", "status", "counter", "alive", "used", "cand", "score", "hits")
         for k in names:
-            if k not in shape:
+            if k not in shape and k not in chain:
                 raise ValueError("unknown trace field %r" % (k,))
-        out = {k: np.zeros((max(count, 0), B) + shape[k], np.int32 if k in ints else np.float64) for k in names}
-        a = {k: (_i(out[k]) if k in ints else _d(out[k])) if k in out else None for k in shape}
-        self._check(self.lib.mpmpc_rollout_trace(self._h, B, int(first), count, a["s"], a["pose"], a["wp_id"], a["x0"], a["u"],
-                                                 a["status"], a["counter"], a["alive"], a["plan"], a["pred_x"], a["pred_y"],
-                                                 a["ub"], a["lb"]))
+        out = {k: np.zeros((max(count, 0), B) + (shape[k] if k in shape else chain[k]), np.int32 if k in ints else np.float64) for k in names}
+        a = {k: (_i(out[k]) if k in ints else _d(out[k])) if k in out else None for k in list(shape) + list(chain)}
+        if any(k in shape for k in names) or not names:
+            self._check(self.lib.mpmpc_rollout_trace(self._h, B, int(first), count, a["s"], a["pose"], a["wp_id"], a["x0"], a["u"],
+                                                     a["status"], a["counter"], a["alive"], a["plan"], a["pred_x"], a["pred_y"],
+                                                     a["ub"], a["lb"]))
+        if any(k in chain for k in names):
+            if "ranges" in out and not (rec & REC_SCAN):      # (no beams to size the array by: the library's own refusal)
+                raise MpmpcError("mpmpc error -3: a field was asked for that mpmpc_rollout_record did not select")
+            self._check(self.lib.mpmpc_rollout_trace_chain(self._h, B, int(first), count, a["act"], a["meas"], a["queue"], a["pred_pose"],
+                                                           a["pred_s"], a["now"], a["est"], a["cov"], a["used"], a["fix"], a["prior"],
+                                                           a["cand"], a["score"], a["hits"], a["ranges"]))
         return out
 
     def _inputs(self, wp_id, x0, cc_prev, lb, ub):
