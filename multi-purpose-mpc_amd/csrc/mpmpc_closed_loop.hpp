@@ -796,8 +796,9 @@ int mpmpc_rollout_recorded(mpmpc_handle h, int32_t* n_records, int32_t* n_steps)
   return MPMPC_OK;
 }
 
-// field `off` of records first .. first + count - 1 -> host [count][bytes]: one strided copy
+// field `off` of records first .. first + count - 1 -> host [count][bytes]: one strided copy (dst == nullptr: not asked for)
 static int pull_field(mpmpc_handle h, void* dst, long long off, size_t bytes, int first, int count) {
+  if (!dst) return MPMPC_OK;
   const char* src = h->rec.buf + h->rec.rec_bytes() * (size_t)first + off;
   if (count == 1) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->last().stream));
   else HIP_TRY(hipMemcpy2DAsync(dst, bytes, src, h->rec.rec_bytes(), bytes, (size_t)count, hipMemcpyDeviceToHost, h->last().stream));
@@ -820,12 +821,13 @@ int mpmpc_rollout_trace(mpmpc_handle h, int32_t B, int32_t first, int32_t count,
   HIP_TRY(hipSetDevice(h->cfg.device));
   if (count > 0) {
     const size_t N = (size_t)h->cfg.N, nb = (size_t)B;
-#define PULL(dst, off, per_car) if (dst) { if (int rc = pull_field(h, dst, off, (per_car) * nb, first, count)) return rc; }
-    PULL(s, l.s, 8); PULL(pose, l.pose, 24); PULL(wp_id, l.wp_id, 4); PULL(x0, l.x0, 24); PULL(u, l.u, 16);
-    PULL(status, l.status, 4); PULL(counter, l.counter, 4); PULL(alive, l.alive, 4);
-    PULL(plan, l.plan, 16 * N); PULL(pred_x, l.pred_x, 8 * (N - 2)); PULL(pred_y, l.pred_y, 8 * (N - 2));
-    PULL(ub, l.ub, 8 * N); PULL(lb, l.lb, 8 * N);
-#undef PULL
+    int rc = MPMPC_OK;      // (of the first copy that failed: nothing is enqueued behind it)
+    auto field = [&](void* dst, long long off, size_t per_car) { if (!rc) rc = pull_field(h, dst, off, per_car * nb, first, count); };
+    field(s, l.s, 8); field(pose, l.pose, 24); field(wp_id, l.wp_id, 4); field(x0, l.x0, 24); field(u, l.u, 16);
+    field(status, l.status, 4); field(counter, l.counter, 4); field(alive, l.alive, 4);
+    field(plan, l.plan, 16 * N); field(pred_x, l.pred_x, 8 * (N - 2)); field(pred_y, l.pred_y, 8 * (N - 2));
+    field(ub, l.ub, 8 * N); field(lb, l.lb, 8 * N);
+    if (rc) return rc;
   }
   HIP_TRY(hipStreamSynchronize(h->last().stream));
   return MPMPC_OK;
@@ -849,13 +851,14 @@ int mpmpc_rollout_trace_chain(mpmpc_handle h, int32_t B, int32_t first, int32_t 
   if (count > 0) {
     const size_t nb = (size_t)B;
     const long long at = h->rec.lay.bytes;      // the chain's start in a record
-#define PULL(dst, off, per_car) if (dst) { if (int rc = pull_field(h, dst, at + off, (per_car) * nb, first, count)) return rc; }
-    PULL(act, l.act, 16); PULL(meas, l.meas, 24);
-    PULL(queue, l.queue, 16 * (size_t)RO_CHAIN_QUEUE); PULL(pred_pose, l.pred_pose, 24); PULL(pred_s, l.pred_s, 8); PULL(now, l.now, 24);
-    PULL(est, l.est, 24); PULL(cov, l.cov, 8 * (size_t)RO_CHAIN_COV); PULL(used, l.used, 4);
-    PULL(fix, l.fix, 24); PULL(prior, l.prior, 24); PULL(cand, l.cand, 4); PULL(score, l.score, 4); PULL(hits, l.hits, 4);
-    PULL(ranges, l.ranges, 8 * (size_t)l.n_beams);
-#undef PULL
+    int rc = MPMPC_OK;      // (of the first copy that failed: nothing is enqueued behind it)
+    auto field = [&](void* dst, long long off, size_t per_car) { if (!rc) rc = pull_field(h, dst, at + off, per_car * nb, first, count); };
+    field(act, l.act, 16); field(meas, l.meas, 24);
+    field(queue, l.queue, 16 * (size_t)RO_CHAIN_QUEUE); field(pred_pose, l.pred_pose, 24); field(pred_s, l.pred_s, 8); field(now, l.now, 24);
+    field(est, l.est, 24); field(cov, l.cov, 8 * (size_t)RO_CHAIN_COV); field(used, l.used, 4);
+    field(fix, l.fix, 24); field(prior, l.prior, 24); field(cand, l.cand, 4); field(score, l.score, 4); field(hits, l.hits, 4);
+    field(ranges, l.ranges, 8 * (size_t)l.n_beams);
+    if (rc) return rc;
   }
   HIP_TRY(hipStreamSynchronize(h->last().stream));
   return MPMPC_OK;
@@ -1086,18 +1089,16 @@ int mpmpc_rollout_state(mpmpc_handle h, int32_t B, double* s, double* pose, doub
   if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
                               "call mpmpc_rollout_init again")) return rc;
   HIP_TRY(hipSetDevice(h->cfg.device));
-  const int N = h->cfg.N;
-#define PULL(dst, src, bytes) if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.stream))
-  PULL(s, h->ro.s, sizeof(double) * B);
-  PULL(pose, h->ro.pose, sizeof(double) * 3 * B);
-  PULL(cc, h->io.cc, sizeof(double) * 2 * N * B);
-  PULL(wp_id, h->io.wp_id, sizeof(int) * B);
-  PULL(x0, h->io.x0, sizeof(double) * 3 * B);
-  PULL(u_last, h->ro.u, sizeof(double) * 2 * B);
-  PULL(status, sl.status, sizeof(int) * B);
-  PULL(counter, h->ro.counter, sizeof(int) * B);
-  PULL(alive, h->ro.alive, sizeof(int) * B);
-#undef PULL
+  const size_t N = (size_t)h->cfg.N, nb = (size_t)B;
+  HIP_TRY(pull(sl.stream, s, h->ro.s, nb));
+  HIP_TRY(pull(sl.stream, pose, h->ro.pose, 3 * nb));
+  HIP_TRY(pull(sl.stream, cc, h->io.cc, 2 * N * nb));
+  HIP_TRY(pull(sl.stream, wp_id, h->io.wp_id, nb));
+  HIP_TRY(pull(sl.stream, x0, h->io.x0, 3 * nb));
+  HIP_TRY(pull(sl.stream, u_last, h->ro.u, 2 * nb));
+  HIP_TRY(pull(sl.stream, status, sl.status, nb));
+  HIP_TRY(pull(sl.stream, counter, h->ro.counter, nb));
+  HIP_TRY(pull(sl.stream, alive, h->ro.alive, nb));
   HIP_TRY(hipStreamSynchronize(sl.stream));
   return MPMPC_OK;
 }

@@ -122,12 +122,11 @@ int mpmpc_rollout_delay(mpmpc_handle h, int32_t B, double* queue, double* pred_p
   if (h->dl.B != B || !h->dl.ran)
     return fail(MPMPC_E_STATE, "no rollout step of B cars ran under the delay in force (mpmpc_rollout_set_delay)");
   HIP_TRY(hipSetDevice(h->cfg.device));
-#define PULL(dst, src, bytes) if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.stream))
-  PULL(queue, h->dl.queue, sizeof(double) * 2 * DL_MAX * B);
-  PULL(pred_pose, h->dl.pred_pose, sizeof(double) * 3 * B);
-  PULL(pred_s, h->dl.pred_s, sizeof(double) * B);
-  PULL(now, h->dl.now, sizeof(double) * 3 * B);
-#undef PULL
+  const size_t nb = (size_t)B;
+  HIP_TRY(pull(sl.stream, queue, h->dl.queue, 2 * DL_MAX * nb));
+  HIP_TRY(pull(sl.stream, pred_pose, h->dl.pred_pose, 3 * nb));
+  HIP_TRY(pull(sl.stream, pred_s, h->dl.pred_s, nb));
+  HIP_TRY(pull(sl.stream, now, h->dl.now, 3 * nb));
   HIP_TRY(hipStreamSynchronize(sl.stream));
   return MPMPC_OK;
 }

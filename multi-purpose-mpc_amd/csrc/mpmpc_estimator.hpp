@@ -107,17 +107,15 @@ int mpmpc_rollout_estimator(mpmpc_handle h, int32_t B, double* est, double* cov,
   if (h->es.B != B || !h->es.ran)
     return fail(MPMPC_E_STATE, "no rollout step of B cars ran under the estimator in force (mpmpc_rollout_set_estimator)");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  const size_t mb = (size_t)h->cfg.max_batch;
-#define PULL(dst, src, bytes) if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.stream))
-  PULL(est, h->es.est, sizeof(double) * 3 * B);
-  PULL(cov, h->es.cov, sizeof(double) * ES_COV * B);
-  PULL(err2_max, h->es.stats, sizeof(double) * B);
-  PULL(err2_sum, h->es.stats + mb, sizeof(double) * B);
-  PULL(meas2_sum, h->es.stats + 2 * mb, sizeof(double) * B);
-  PULL(head2_sum, h->es.stats + 3 * mb, sizeof(double) * B);
-  PULL(used, h->es.count, sizeof(int) * B);
-  PULL(steps, h->es.count + mb, sizeof(int) * B);
-#undef PULL
+  const size_t mb = (size_t)h->cfg.max_batch, nb = (size_t)B;
+  HIP_TRY(pull(sl.stream, est, h->es.est, 3 * nb));
+  HIP_TRY(pull(sl.stream, cov, h->es.cov, ES_COV * nb));
+  HIP_TRY(pull(sl.stream, err2_max, h->es.stats, nb));
+  HIP_TRY(pull(sl.stream, err2_sum, h->es.stats + mb, nb));
+  HIP_TRY(pull(sl.stream, meas2_sum, h->es.stats + 2 * mb, nb));
+  HIP_TRY(pull(sl.stream, head2_sum, h->es.stats + 3 * mb, nb));
+  HIP_TRY(pull(sl.stream, used, h->es.count, nb));
+  HIP_TRY(pull(sl.stream, steps, h->es.count + mb, nb));
   HIP_TRY(hipStreamSynchronize(sl.stream));
   return MPMPC_OK;
 }

@@ -140,8 +140,15 @@ __global__ __launch_bounds__(64) void mpmpc_footprint_kernel(MapView map, int B,
   }
 }
 
-// device scratch of mpmpc_footprint_audit, kept between calls like the lidar's (SpScratch: one per device, each behind its own
-// mutex, never freed)
+// K0f of B cars on the stream: `walls` chooses the instantiation, `a` is the kernel's argument list (map .. wv; without walls
+// wv is WALLS_NONE)
+template <class... A>
+static void enqueue_footprint(hipStream_t stream, int B, bool walls, A... a) {
+  if (walls) hipLaunchKernelGGL(mpmpc_footprint_kernel<true>, dim3(B), dim3(64), 0, stream, a...);
+  else hipLaunchKernelGGL(mpmpc_footprint_kernel<false>, dim3(B), dim3(64), 0, stream, a...);
+}
+
+// device scratch of mpmpc_footprint_audit (device_scratch.hpp)
 static SpScratch g_fp_dev[SP_MAX_DEVICES];
 
 // the accumulators at the start of a run: nothing counted, min_clearance = reach_m, the last verdict (0, NaN)
@@ -182,17 +189,10 @@ static int aud_check_step(mpmpc_handle h, int B) {
 static void aud_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k, bool per_car) {
   AudState& a = h->aud;
   const size_t mb = (size_t)h->cfg.max_batch;
-  const bool discs = per_car && h->obs.obst_B > 0;
-  if (per_car && h->obs.wl_B > 0)
-    hipLaunchKernelGGL(mpmpc_footprint_kernel<true>, dim3(B), dim3(64), 0, sl.stream, h->cor.map_view(), B, h->ro.pose.get(),
-                       discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), a.length, a.width, a.reach, a.R, a.mode,
-                       (int)k, h->ro.alive.get(), a.ints + 3 * mb, a.dbls + mb, a.ints.get(), a.ints + mb, a.dbls.get(), a.ints + 2 * mb,
-                       h->obs.wall_view());
-  else
-    hipLaunchKernelGGL(mpmpc_footprint_kernel<false>, dim3(B), dim3(64), 0, sl.stream, h->cor.map_view(), B, h->ro.pose.get(),
-                       discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), a.length, a.width, a.reach, a.R, a.mode,
-                       (int)k, h->ro.alive.get(), a.ints + 3 * mb, a.dbls + mb, a.ints.get(), a.ints + mb, a.dbls.get(), a.ints + 2 * mb,
-                       WallView{nullptr, nullptr, nullptr});
+  const bool discs = per_car && h->obs.obst_B > 0, walls = per_car && h->obs.wl_B > 0;
+  enqueue_footprint(sl.stream, B, walls, h->cor.map_view(), B, h->ro.pose.get(), discs ? h->obs.obst_off.get() : nullptr,
+                    h->obs.obst_discs.get(), a.length, a.width, a.reach, a.R, a.mode, (int)k, h->ro.alive.get(), a.ints + 3 * mb,
+                    a.dbls + mb, a.ints.get(), a.ints + mb, a.dbls.get(), a.ints + 2 * mb, walls ? h->obs.wall_view() : WALLS_NONE);
 }
 
 extern "C" {
@@ -215,49 +215,25 @@ int mpmpc_footprint_audit_world(int32_t device, int32_t height, int32_t width, c
     return fail(MPMPC_E_ARG, why);
   if (wall_offsets && wall_check_lists(B, wall_offsets, walls, width, height, &why)) return fail(MPMPC_E_ARG, why);
   if (!mov_finite(origin_x) || !mov_finite(origin_y)) return fail(MPMPC_E_ARG, "the map's origin is not finite");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
-  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the footprint scratch table");
-  HIP_TRY(hipSetDevice(device));
-  const size_t nb = (size_t)B, n_disc = offsets ? (size_t)offsets[B] : 0;
-  const size_t o_pose = 0, o_clr = o_pose + sizeof(double) * 3 * nb, o_con = o_clr + sizeof(double) * nb,
-               o_off = o_con + pad8(sizeof(int) * nb), o_disc = o_off + pad8(sizeof(int) * (nb + 1)),
-               o_map = o_disc + pad8(sizeof(int) * 3 * n_disc), o_wall = o_map + pad8((size_t)height * width);
-  WallBlock wb = wall_block(o_wall, B, wall_offsets, walls);
-  const size_t need = wb.end;
-  SpScratch& g = g_fp_dev[device];
-  std::lock_guard<std::mutex> lock(g.mu);
-  if (g.bytes < need) {
-    if (g.block) (void)device_free(g.block);
-    g.block = nullptr; g.bytes = 0;
-    HIP_TRY(device_alloc((void**)&g.block, need));
-    g.bytes = need;
-  }
-  if (!g.stream) HIP_TRY(hipStreamCreate(&g.stream));
-  hipStream_t stream = g.stream;
-  char* blk = g.block;
-  HIP_TRY(hipMemcpyAsync(blk + o_pose, pose, sizeof(double) * 3 * nb, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_map, data, (size_t)height * width, hipMemcpyHostToDevice, stream));
-  if (offsets) HIP_TRY(hipMemcpyAsync(blk + o_off, offsets, sizeof(int) * (nb + 1), hipMemcpyHostToDevice, stream));
-  if (n_disc > 0) HIP_TRY(hipMemcpyAsync(blk + o_disc, discs, sizeof(int) * 3 * n_disc, hipMemcpyHostToDevice, stream));
-  if (int rc = wall_block_enqueue(blk, wb, B, wall_offsets, walls, stream)) return rc;      // K0w first, on the same stream
-  const MapView mv{(const int8_t*)(blk + o_map), height, width, origin_x, origin_y, resolution};
-  if (wall_offsets)
-    hipLaunchKernelGGL(mpmpc_footprint_kernel<true>, dim3(B), dim3(64), 0, stream, mv, B, (const double*)(blk + o_pose),
-                       offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), length, car_width, reach_m, R,
-                       FP_MODE_AUDIT, 0, (int*)nullptr, (int*)(blk + o_con), (double*)(blk + o_clr), (int*)nullptr, (int*)nullptr,
-                       (double*)nullptr, (int*)nullptr, wall_block_view(blk, wb, wall_offsets));
-  else
-    hipLaunchKernelGGL(mpmpc_footprint_kernel<false>, dim3(B), dim3(64), 0, stream, mv, B, (const double*)(blk + o_pose),
-                       offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), length, car_width, reach_m, R,
-                       FP_MODE_AUDIT, 0, (int*)nullptr, (int*)(blk + o_con), (double*)(blk + o_clr), (int*)nullptr, (int*)nullptr,
-                       (double*)nullptr, (int*)nullptr, WallView{nullptr, nullptr, nullptr});
+  const size_t nb = (size_t)B;
+  Layout L;
+  const auto r_pose = L.add<double>(3 * nb), r_clr = L.add<double>(nb);
+  const auto r_con = L.add<int>(nb);
+  WorldBlock wd = world_block(L, height, width, data, B, offsets, discs, wall_offsets, walls);
+  Scratch sc;
+  if (int rc = scratch_acquire(g_fp_dev, device, L.bytes(), "footprint", &sc)) return rc;
+  hipStream_t stream = sc.stream;
+  char* blk = sc.blk;
+  HIP_TRY(hipMemcpyAsync(r_pose.at(blk), pose, r_pose.bytes(), hipMemcpyHostToDevice, stream));
+  if (int rc = wd.enqueue(blk, stream)) return rc;
+  enqueue_footprint(stream, B, wall_offsets != nullptr, wd.map(blk, origin_x, origin_y, resolution), B, r_pose.at(blk), wd.offsets(blk),
+                    wd.discs(blk), length, car_width, reach_m, R, FP_MODE_AUDIT, 0, nullptr, r_con.at(blk), r_clr.at(blk), nullptr,
+                    nullptr, nullptr, nullptr, wd.walls.view(blk));      // (no alive, no accumulators: the verdicts alone)
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(contact_out, blk + o_con, sizeof(int) * nb, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(clearance_out, blk + o_clr, sizeof(double) * nb, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(pull(stream, contact_out, r_con.at(blk), nb));
+  HIP_TRY(pull(stream, clearance_out, r_clr.at(blk), nb));
   HIP_TRY(hipStreamSynchronize(stream));
-  return wall_block_verdict(wb);
+  return wd.verdict();
 }
 
 int mpmpc_rollout_set_audit(mpmpc_handle h, int32_t mode, double length, double car_width, double reach_m) {
@@ -285,12 +261,12 @@ int mpmpc_rollout_audit(mpmpc_handle h, int32_t B, int32_t* contact_steps, int32
   HIP_TRY(hipSetDevice(h->cfg.device));
   const size_t mb = (size_t)h->cfg.max_batch, nb = (size_t)B;
   hipStream_t st = h->last().stream;
-  int32_t* iq[4] = {contact_steps, first_contact, min_step, last_contact};
-  double* dq[2] = {min_clearance, last_clearance};
-  for (int q = 0; q < 4; ++q)
-    if (iq[q]) HIP_TRY(hipMemcpyAsync(iq[q], a.ints + q * mb, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-  for (int q = 0; q < 2; ++q)
-    if (dq[q]) HIP_TRY(hipMemcpyAsync(dq[q], a.dbls + q * mb, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+  HIP_TRY(pull(st, contact_steps, a.ints, nb));
+  HIP_TRY(pull(st, first_contact, a.ints + mb, nb));
+  HIP_TRY(pull(st, min_step, a.ints + 2 * mb, nb));
+  HIP_TRY(pull(st, last_contact, a.ints + 3 * mb, nb));
+  HIP_TRY(pull(st, min_clearance, a.dbls, nb));
+  HIP_TRY(pull(st, last_clearance, a.dbls + mb, nb));
   HIP_TRY(hipStreamSynchronize(st));
   return MPMPC_OK;
 }

@@ -4,6 +4,7 @@
 // Field names: a field drops the prefix that names its own sub-state (ro.s, rec.cap); every other name is kept.
 #pragma once
 #include "device_buf.hpp"
+#include "device_scratch.hpp"
 #include "route_state.hpp"
 
 static thread_local std::string g_err;
@@ -18,6 +19,37 @@ static int fail(int code, const std::string& msg) {
     if (e_ != hipSuccess)                                                                          \
       return fail(MPMPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
   } while (0)
+
+// An entry point without a handle takes its scratch (device_scratch.hpp) here: `table` is the entry point's own, `word` names it
+// in the message.  One order for all of them: the device count, the two range checks, the device is set, the scratch locked,
+// grown to `need` bytes and given its stream.  The lock is held while `Scratch` lives - declare it where the call should end.
+struct Scratch {
+  std::unique_lock<std::mutex> lock;
+  char* blk = nullptr;
+  hipStream_t stream = nullptr;
+};
+static int scratch_acquire(SpScratch* table, int device, size_t need, const char* word, Scratch* out) {
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
+  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, std::string("device ordinal beyond the ") + word + " scratch table");
+  HIP_TRY(hipSetDevice(device));
+  SpScratch& g = table[device];
+  out->lock = std::unique_lock<std::mutex>(g.mu);
+  HIP_TRY(grow(g, need));
+  if (!g.stream) HIP_TRY(hipStreamCreate(&g.stream));
+  out->blk = g.block;
+  out->stream = g.stream;
+  return MPMPC_OK;
+}
+
+// `count` elements of T, device -> host, on the stream; a getter's output that the caller left NULL is skipped.  The byte count
+// comes from T: where a block is read as another type than it is kept in, the cast stands at the call.
+// (`src` takes no part in deducing T, so that a Buf<T> converts)
+template <class T>
+static hipError_t pull(hipStream_t stream, T* dst, const typename std::common_type<T>::type* src, size_t count) {
+  return dst ? hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, stream) : hipSuccess;
+}
 
 // path and corridor tables
 struct TabState {

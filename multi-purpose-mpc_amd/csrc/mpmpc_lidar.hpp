@@ -255,8 +255,15 @@ __global__ __launch_bounds__(K0L_THREADS) void mpmpc_lidar_scan_running_kernel(M
   k0l_scan_car<WALLS, 0>(map, B, pose, off, discs, n_beams, angles, range_m, ranges, wv, K0sArgs{});
 }
 
-// device scratch of mpmpc_lidar_scan, kept between calls like the speed profile's (SpScratch: one per device, each behind
-// its own mutex, never freed)
+// K0l of B cars on the stream: `walls` chooses the instantiation, `a` is the kernel's argument list (map .. wv;
+// without walls wv is a null view)
+template <class... A>
+static void enqueue_lidar_scan(hipStream_t stream, int B, bool walls, A... a) {
+  if (walls) hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<true>, dim3(B), dim3(K0L_THREADS), 0, stream, a...);
+  else hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<false>, dim3(B), dim3(K0L_THREADS), 0, stream, a...);
+}
+
+// device scratch of mpmpc_lidar_scan (device_scratch.hpp)
 static SpScratch g_lid_dev[SP_MAX_DEVICES];
 
 extern "C" {
@@ -277,47 +284,23 @@ int mpmpc_lidar_scan_world(int32_t device, int32_t height, int32_t width, const 
     return fail(MPMPC_E_ARG, why);
   if (wall_offsets && wall_check_lists(B, wall_offsets, walls, width, height, &why)) return fail(MPMPC_E_ARG, why);
   if (!mov_finite(origin_x) || !mov_finite(origin_y)) return fail(MPMPC_E_ARG, "the map's origin is not finite");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
-  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the lidar scratch table");
-  HIP_TRY(hipSetDevice(device));
-  const size_t nb = (size_t)B, n_disc = offsets ? (size_t)offsets[B] : 0;
-  const size_t o_pose = 0, o_ang = o_pose + sizeof(double) * 3 * nb, o_out = o_ang + sizeof(double) * (size_t)n_beams,
-               o_off = o_out + sizeof(double) * nb * (size_t)n_beams, o_disc = o_off + pad8(sizeof(int) * (nb + 1)),
-               o_map = o_disc + pad8(sizeof(int) * 3 * n_disc), o_wall = o_map + pad8((size_t)height * width);
-  WallBlock wb = wall_block(o_wall, B, wall_offsets, walls);
-  const size_t need = wb.end;
-  SpScratch& g = g_lid_dev[device];
-  std::lock_guard<std::mutex> lock(g.mu);
-  if (g.bytes < need) {
-    if (g.block) (void)device_free(g.block);
-    g.block = nullptr; g.bytes = 0;
-    HIP_TRY(device_alloc((void**)&g.block, need));
-    g.bytes = need;
-  }
-  if (!g.stream) HIP_TRY(hipStreamCreate(&g.stream));
-  hipStream_t stream = g.stream;
-  char* blk = g.block;
-  HIP_TRY(hipMemcpyAsync(blk + o_pose, pose, sizeof(double) * 3 * nb, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_ang, angles, sizeof(double) * (size_t)n_beams, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_map, data, (size_t)height * width, hipMemcpyHostToDevice, stream));
-  if (offsets) HIP_TRY(hipMemcpyAsync(blk + o_off, offsets, sizeof(int) * (nb + 1), hipMemcpyHostToDevice, stream));
-  if (n_disc > 0) HIP_TRY(hipMemcpyAsync(blk + o_disc, discs, sizeof(int) * 3 * n_disc, hipMemcpyHostToDevice, stream));
-  if (int rc = wall_block_enqueue(blk, wb, B, wall_offsets, walls, stream)) return rc;      // K0w first, on the same stream
-  const MapView mv{(const int8_t*)(blk + o_map), height, width, origin_x, origin_y, resolution};
-  if (wall_offsets)
-    hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<true>, dim3(B), dim3(K0L_THREADS), 0, stream, mv, B, (const double*)(blk + o_pose),
-                       offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), n_beams,
-                       (const double*)(blk + o_ang), range_m, (double*)(blk + o_out), wall_block_view(blk, wb, wall_offsets));
-  else
-    hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<false>, dim3(B), dim3(K0L_THREADS), 0, stream, mv, B, (const double*)(blk + o_pose),
-                       offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), n_beams,
-                       (const double*)(blk + o_ang), range_m, (double*)(blk + o_out), WallView{nullptr, nullptr, nullptr});
+  const size_t nb = (size_t)B;
+  Layout L;
+  const auto r_pose = L.add<double>(3 * nb), r_ang = L.add<double>((size_t)n_beams), r_out = L.add<double>(nb * (size_t)n_beams);
+  WorldBlock wd = world_block(L, height, width, data, B, offsets, discs, wall_offsets, walls);
+  Scratch sc;
+  if (int rc = scratch_acquire(g_lid_dev, device, L.bytes(), "lidar", &sc)) return rc;
+  hipStream_t stream = sc.stream;
+  char* blk = sc.blk;
+  HIP_TRY(hipMemcpyAsync(r_pose.at(blk), pose, r_pose.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_ang.at(blk), angles, r_ang.bytes(), hipMemcpyHostToDevice, stream));
+  if (int rc = wd.enqueue(blk, stream)) return rc;
+  enqueue_lidar_scan(stream, B, wall_offsets != nullptr, wd.map(blk, origin_x, origin_y, resolution), B, r_pose.at(blk), wd.offsets(blk),
+                     wd.discs(blk), n_beams, r_ang.at(blk), range_m, r_out.at(blk), wd.walls.view(blk));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(ranges_out, blk + o_out, sizeof(double) * nb * (size_t)n_beams, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(pull(stream, ranges_out, r_out.at(blk), r_out.count));
   HIP_TRY(hipStreamSynchronize(stream));
-  return wall_block_verdict(wb);
+  return wd.verdict();
 }
 
 int mpmpc_rollout_scan(mpmpc_handle h, int32_t B, int32_t n_beams, const double* angles, double range_m, double* ranges_out) {
@@ -329,7 +312,7 @@ int mpmpc_rollout_scan(mpmpc_handle h, int32_t B, int32_t n_beams, const double*
   if (!h->cor.map) return fail(MPMPC_E_STATE, "needs mpmpc_set_map first");
   const char* why = "";
   if (lid_check_beams(n_beams, angles, range_m, h->cor.map_res, &why)) return fail(MPMPC_E_ARG, why);
-  const bool per_car = h->obs.world_B() > 0, discs = h->obs.obst_B > 0;
+  const bool per_car = h->obs.world_B() > 0, discs = h->obs.obst_B > 0, walls = h->obs.wl_B > 0;
   if (per_car && (!h->obs.car_rows || !h->obs.discs_live || h->obs.world_B() != B))
     return fail(MPMPC_E_STATE, "per-car obstacles / movers / traffic are set, but no rollout step of B cars has used them yet, or they were "
                                "set anew since the last step: the cars' worlds are those of a step (mpmpc_rollout_step)");
@@ -338,18 +321,14 @@ int mpmpc_rollout_scan(mpmpc_handle h, int32_t B, int32_t n_beams, const double*
   if (h->lid.angles.count() < (size_t)n_beams) HIP_TRY(h->lid.angles.alloc((size_t)LID_MAX_BEAMS));
   if (h->lid.ranges.count() < n_out) HIP_TRY(h->lid.ranges.alloc(n_out));
   HIP_TRY(hipMemcpyAsync(h->lid.angles, angles, sizeof(double) * (size_t)n_beams, hipMemcpyHostToDevice, sl.stream));
-  if (h->obs.wl_B > 0)
-    hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<true>, dim3(B), dim3(K0L_THREADS), 0, sl.stream, h->cor.map_view(), B, h->ro.pose.get(),
-                       discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), n_beams, h->lid.angles.get(), range_m,
-                       h->lid.ranges.get(), h->obs.wall_view());
-  else
-    hipLaunchKernelGGL(mpmpc_lidar_scan_kernel<false>, dim3(B), dim3(K0L_THREADS), 0, sl.stream, h->cor.map_view(), B, h->ro.pose.get(),
-                       discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), n_beams, h->lid.angles.get(), range_m,
-                       h->lid.ranges.get(), WallView{nullptr, nullptr, nullptr});
+  enqueue_lidar_scan(sl.stream, B, walls, h->cor.map_view(), B, h->ro.pose.get(), discs ? h->obs.obst_off.get() : nullptr,
+                     h->obs.obst_discs.get(), n_beams, h->lid.angles.get(), range_m, h->lid.ranges.get(),
+                     h->obs.wall_view());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(ranges_out, h->lid.ranges, sizeof(double) * n_out, hipMemcpyDeviceToHost, sl.stream));
+  HIP_TRY(pull(sl.stream, ranges_out, h->lid.ranges, n_out));
   HIP_TRY(hipStreamSynchronize(sl.stream));
   return MPMPC_OK;
 }
 
 }  // extern "C"
+

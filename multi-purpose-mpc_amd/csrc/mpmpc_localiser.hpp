@@ -239,28 +239,8 @@ static LocView loc_view(mpmpc_handle h, long long k) {
                  lc.fix, lc.prior, lc.primed, lc.out, lc.stats, lc.count, (long)h->cfg.max_batch};
 }
 
-// device scratch of mpmpc_distance_field and mpmpc_scan_match (SpScratch: one per device, each behind its own mutex, never freed)
+// device scratch of mpmpc_distance_field and mpmpc_scan_match, which share it (device_scratch.hpp)
 static SpScratch g_loc_dev[SP_MAX_DEVICES];
-
-// the device's scratch, locked and at least `need` bytes large
-static int loc_scratch(int device, size_t need, std::unique_lock<std::mutex>& lock, SpScratch** out) {
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
-  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the localiser scratch table");
-  HIP_TRY(hipSetDevice(device));
-  SpScratch& g = g_loc_dev[device];
-  lock = std::unique_lock<std::mutex>(g.mu);
-  if (g.bytes < need) {
-    if (g.block) (void)device_free(g.block);
-    g.block = nullptr; g.bytes = 0;
-    HIP_TRY(device_alloc((void**)&g.block, need));
-    g.bytes = need;
-  }
-  if (!g.stream) HIP_TRY(hipStreamCreate(&g.stream));
-  *out = &g;
-  return MPMPC_OK;
-}
 
 static int loc_check_map(int height, int width, const int8_t* data, const char** why) {
   if (height < 1 || width < 1) { *why = "map needs positive size"; return -1; }
@@ -281,15 +261,17 @@ int mpmpc_distance_field(int32_t device, int32_t height, int32_t width, const in
   if (loc_check_map(height, width, data, &why)) return fail(MPMPC_E_ARG, why);
   if (!field_out) return fail(MPMPC_E_ARG, "field_out must not be NULL");
   if (D < 1 || D > LC_MAX_D) return fail(MPMPC_E_ARG, "localiser: D must be in [1, 15] cells");
-  const size_t cells = (size_t)height * width, o_map = 0, o_f = pad8(cells), need = o_f + pad8(cells);
-  std::unique_lock<std::mutex> lock;
-  SpScratch* g = nullptr;
-  if (int rc = loc_scratch(device, need, lock, &g)) return rc;
-  HIP_TRY(hipMemcpyAsync(g->block + o_map, data, cells, hipMemcpyHostToDevice, g->stream));
-  loc_enqueue_field(MapView{(const int8_t*)(g->block + o_map), height, width, 0.0, 0.0, 1.0}, D, (uint8_t*)(g->block + o_f), g->stream);
+  const size_t cells = (size_t)height * width;
+  Layout L;
+  const auto r_map = L.add<int8_t>(cells);
+  const auto r_f = L.add<uint8_t>(cells);
+  Scratch sc;
+  if (int rc = scratch_acquire(g_loc_dev, device, L.bytes(), "localiser", &sc)) return rc;
+  HIP_TRY(hipMemcpyAsync(r_map.at(sc.blk), data, cells, hipMemcpyHostToDevice, sc.stream));
+  loc_enqueue_field(MapView{r_map.at(sc.blk), height, width, 0.0, 0.0, 1.0}, D, r_f.at(sc.blk), sc.stream);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(field_out, g->block + o_f, cells, hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));
+  HIP_TRY(pull(sc.stream, field_out, r_f.at(sc.blk), cells));
+  HIP_TRY(hipStreamSynchronize(sc.stream));
   return MPMPC_OK;
 }
 
@@ -307,28 +289,30 @@ int mpmpc_scan_match(int32_t device, int32_t height, int32_t width, const int8_t
   const LcSet set{D, m, W, T, min_hits, step_psi, 0.0};
   if (lc_check_setting(n_beams, angles, range_m, resolution, set, 1, B, nullptr, &why)) return fail(MPMPC_E_ARG, why);
   const size_t cells = (size_t)height * width, nb = (size_t)B;
-  const size_t o_map = 0, o_f = pad8(cells), o_ang = o_f + pad8(cells), o_prior = o_ang + sizeof(double) * (size_t)n_beams,
-               o_rg = o_prior + sizeof(double) * 3 * nb, o_fix = o_rg + sizeof(double) * nb * (size_t)n_beams,
-               o_out = o_fix + sizeof(double) * 3 * nb, need = o_out + pad8(sizeof(int) * 3 * nb);
-  std::unique_lock<std::mutex> lock;
-  SpScratch* g = nullptr;
-  if (int rc = loc_scratch(device, need, lock, &g)) return rc;
-  char* blk = g->block;
-  hipStream_t stream = g->stream;
-  HIP_TRY(hipMemcpyAsync(blk + o_map, data, cells, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_ang, angles, sizeof(double) * (size_t)n_beams, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_prior, prior, sizeof(double) * 3 * nb, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_rg, ranges, sizeof(double) * nb * (size_t)n_beams, hipMemcpyHostToDevice, stream));
-  const MapView mv{(const int8_t*)(blk + o_map), height, width, origin_x, origin_y, resolution};
-  loc_enqueue_field(mv, D, (uint8_t*)(blk + o_f), stream);
-  hipLaunchKernelGGL(mpmpc_scan_match_kernel, dim3(B), dim3(LC_THREADS), loc_lds(T, n_beams), stream, mv, (const uint8_t*)(blk + o_f), set,
-                     (int)B, (int)n_beams, (const double*)(blk + o_ang), range_m, (const double*)(blk + o_prior),
-                     (const double*)(blk + o_rg), (double*)(blk + o_fix), (int*)(blk + o_out));
+  Layout L;
+  const auto r_map = L.add<int8_t>(cells);
+  const auto r_f = L.add<uint8_t>(cells);
+  const auto r_ang = L.add<double>((size_t)n_beams), r_prior = L.add<double>(3 * nb), r_rg = L.add<double>(nb * (size_t)n_beams),
+             r_fix = L.add<double>(3 * nb);
+  // the kernel's `out` is ONE region [3][B]: score, candidate, hits
+  const auto r_out = L.add<int>(3 * nb), r_score = r_out.part(0, nb), r_cand = r_out.part(nb, nb), r_hits = r_out.part(2 * nb, nb);
+  Scratch sc;
+  if (int rc = scratch_acquire(g_loc_dev, device, L.bytes(), "localiser", &sc)) return rc;
+  char* blk = sc.blk;
+  hipStream_t stream = sc.stream;
+  HIP_TRY(hipMemcpyAsync(r_map.at(blk), data, cells, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_ang.at(blk), angles, r_ang.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_prior.at(blk), prior, r_prior.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_rg.at(blk), ranges, r_rg.bytes(), hipMemcpyHostToDevice, stream));
+  const MapView mv{r_map.at(blk), height, width, origin_x, origin_y, resolution};
+  loc_enqueue_field(mv, D, r_f.at(blk), stream);
+  hipLaunchKernelGGL(mpmpc_scan_match_kernel, dim3(B), dim3(LC_THREADS), loc_lds(T, n_beams), stream, mv, r_f.at(blk), set, (int)B,
+                     (int)n_beams, r_ang.at(blk), range_m, r_prior.at(blk), r_rg.at(blk), r_fix.at(blk), r_out.at(blk));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(fix_out, blk + o_fix, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(score_out, blk + o_out, sizeof(int) * nb, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(cand_out, blk + o_out + sizeof(int) * nb, sizeof(int) * nb, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(hits_out, blk + o_out + sizeof(int) * 2 * nb, sizeof(int) * nb, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(pull(stream, fix_out, r_fix.at(blk), 3 * nb));
+  HIP_TRY(pull(stream, score_out, r_score.at(blk), nb));
+  HIP_TRY(pull(stream, cand_out, r_cand.at(blk), nb));
+  HIP_TRY(pull(stream, hits_out, r_hits.at(blk), nb));
   HIP_TRY(hipStreamSynchronize(stream));
   return MPMPC_OK;
 }
@@ -385,23 +369,21 @@ int mpmpc_rollout_localiser(mpmpc_handle h, int32_t B, double* fix, double* prio
   if (lc.B != B || !lc.ran)
     return fail(MPMPC_E_STATE, "no rollout step of B cars ran under the localiser in force (mpmpc_rollout_set_localiser)");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  const size_t mb = (size_t)h->cfg.max_batch;
-#define PULL(dst, src, bytes) if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.stream))
-  PULL(fix, lc.fix, sizeof(double) * 3 * B);
-  PULL(prior, lc.prior, sizeof(double) * 3 * B);
-  PULL(cand, lc.out, sizeof(int) * B);
-  PULL(score, lc.out + mb, sizeof(int) * B);
-  PULL(hits, lc.out + 2 * mb, sizeof(int) * B);
-  PULL(ranges, lc.ranges, sizeof(double) * (size_t)B * (size_t)lc.n_beams);
-  PULL(err2_max, lc.stats, sizeof(double) * B);
-  PULL(err2_sum, lc.stats + mb, sizeof(double) * B);
-  PULL(head2_sum, lc.stats + 2 * mb, sizeof(double) * B);
-  PULL(prior2_sum, lc.stats + 3 * mb, sizeof(double) * B);
-  PULL(steps, lc.count, sizeof(int) * B);
-  PULL(matched, lc.count + mb, sizeof(int) * B);
-  PULL(lost, lc.count + 2 * mb, sizeof(int) * B);
-  PULL(edge, lc.count + 3 * mb, sizeof(int) * B);
-#undef PULL
+  const size_t mb = (size_t)h->cfg.max_batch, nb = (size_t)B;
+  HIP_TRY(pull(sl.stream, fix, lc.fix, 3 * nb));
+  HIP_TRY(pull(sl.stream, prior, lc.prior, 3 * nb));
+  HIP_TRY(pull(sl.stream, cand, lc.out, nb));
+  HIP_TRY(pull(sl.stream, score, lc.out + mb, nb));
+  HIP_TRY(pull(sl.stream, hits, lc.out + 2 * mb, nb));
+  HIP_TRY(pull(sl.stream, ranges, lc.ranges, nb * (size_t)lc.n_beams));
+  HIP_TRY(pull(sl.stream, err2_max, lc.stats, nb));
+  HIP_TRY(pull(sl.stream, err2_sum, lc.stats + mb, nb));
+  HIP_TRY(pull(sl.stream, head2_sum, lc.stats + 2 * mb, nb));
+  HIP_TRY(pull(sl.stream, prior2_sum, lc.stats + 3 * mb, nb));
+  HIP_TRY(pull(sl.stream, steps, lc.count, nb));
+  HIP_TRY(pull(sl.stream, matched, lc.count + mb, nb));
+  HIP_TRY(pull(sl.stream, lost, lc.count + 2 * mb, nb));
+  HIP_TRY(pull(sl.stream, edge, lc.count + 3 * mb, nb));
   HIP_TRY(hipStreamSynchronize(sl.stream));
   return MPMPC_OK;
 }

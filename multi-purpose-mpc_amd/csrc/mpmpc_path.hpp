@@ -116,63 +116,45 @@ static int path_build_impl(int32_t device, int32_t height, int32_t width, const 
   }
   if (ms) ms[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   // step 5 on the device
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
-  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the path scratch table");
-  HIP_TRY(hipSetDevice(device));
-  WallBlock wb;
+  // (a call without a row to fill still takes the scratch: the device ordinal is checked whatever the routes are)
+  const size_t np = (size_t)P;
+  Layout L;
+  const auto r_xy = L.add<double>(2 * rows), r_maxw = L.add<double>(np), r_out = L.add<double>(PATH_WP_OUT * rows);
+  const auto r_cells = L.add<int>(PATH_WP_INTS * rows), r_flags = L.add<int>(2 * rows), r_blk = L.add<int>(2 * n_blk),
+             r_row = L.add<int>(np + 1);
+  WorldBlock wd = world_block(L, height, width, data, P, disc_offsets, discs, wall_offsets, walls);
+  Scratch sc;
+  if (int rc = scratch_acquire(g_path_dev, device, rows > 0 ? L.bytes() : 0, "path", &sc)) return rc;
   if (rows > 0) {
-    const size_t np = (size_t)P, n_disc = disc_offsets ? (size_t)disc_offsets[P] : 0;
-    const size_t o_xy = 0, o_maxw = o_xy + sizeof(double) * 2 * rows, o_out = o_maxw + sizeof(double) * np,
-                 o_cells = o_out + sizeof(double) * PATH_WP_OUT * rows, o_flags = o_cells + pad8(sizeof(int) * PATH_WP_INTS * rows),
-                 o_blk = o_flags + pad8(sizeof(int) * 2 * rows), o_row = o_blk + pad8(sizeof(int) * 2 * n_blk),
-                 o_off = o_row + pad8(sizeof(int) * (np + 1)), o_disc = o_off + pad8(sizeof(int) * (np + 1)),
-                 o_map = o_disc + pad8(sizeof(int) * 3 * n_disc), o_wall = o_map + pad8((size_t)height * width);
-    wb = wall_block(o_wall, P, wall_offsets, walls);
-    const size_t need = wb.end + 8;
-    SpScratch& g = g_path_dev[device];
-    std::lock_guard<std::mutex> lock(g.mu);
-    if (g.bytes < need) {
-      if (g.block) (void)device_free(g.block);
-      g.block = nullptr; g.bytes = 0;
-      HIP_TRY(device_alloc((void**)&g.block, need));
-      g.bytes = need;
-    }
-    if (!g.stream) HIP_TRY(hipStreamCreate(&g.stream));
-    hipStream_t stream = g.stream;
-    char* blk_dev = g.block;
+    hipStream_t stream = sc.stream;
+    char* dev = sc.blk;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     if (ms)
       for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipMemcpyAsync(blk_dev + o_xy, xy.data(), sizeof(double) * 2 * rows, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(blk_dev + o_maxw, maxw.data(), sizeof(double) * np, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(blk_dev + o_cells, cells.data(), sizeof(int) * PATH_WP_INTS * rows, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(blk_dev + o_blk, blk.data(), sizeof(int) * 2 * n_blk, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(blk_dev + o_row, row_off.data(), sizeof(int) * (np + 1), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(blk_dev + o_map, data, (size_t)height * width, hipMemcpyHostToDevice, stream));
-    if (disc_offsets) HIP_TRY(hipMemcpyAsync(blk_dev + o_off, disc_offsets, sizeof(int) * (np + 1), hipMemcpyHostToDevice, stream));
-    if (n_disc > 0) HIP_TRY(hipMemcpyAsync(blk_dev + o_disc, discs, sizeof(int) * 3 * n_disc, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(r_xy.at(dev), xy.data(), r_xy.bytes(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(r_maxw.at(dev), maxw.data(), r_maxw.bytes(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(r_cells.at(dev), cells.data(), r_cells.bytes(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(r_blk.at(dev), blk.data(), r_blk.bytes(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(r_row.at(dev), row_off.data(), r_row.bytes(), hipMemcpyHostToDevice, stream));
+    if (int rc = wd.upload(dev, stream)) return rc;
     if (ms) HIP_TRY(hipEventRecord(ev[0], stream));
-    if (int rc = wall_block_enqueue(blk_dev, wb, P, wall_offsets, walls, stream)) return rc;      // K0w first, on the same stream
+    if (int rc = wd.walls.enqueue(dev, stream)) return rc;      // K0w first, on the same stream
     if (ms) HIP_TRY(hipEventRecord(ev[1], stream));
-    const MapView mv{(const int8_t*)(blk_dev + o_map), height, width, origin_x, origin_y, resolution};
-    hipLaunchKernelGGL(mpmpc_path_width_kernel, dim3((unsigned)n_blk), dim3(K0P_THREADS), 0, stream, mv, (int)n_blk,
-                       (const int*)(blk_dev + o_blk), (const int*)(blk_dev + o_row), (const double*)(blk_dev + o_maxw),
-                       (const double*)(blk_dev + o_xy), (const int*)(blk_dev + o_cells),
-                       disc_offsets ? (const int*)(blk_dev + o_off) : nullptr, (const int*)(blk_dev + o_disc),
-                       wall_block_view(blk_dev, wb, wall_offsets), (double*)(blk_dev + o_out), (int*)(blk_dev + o_flags));
+    hipLaunchKernelGGL(mpmpc_path_width_kernel, dim3((unsigned)n_blk), dim3(K0P_THREADS), 0, stream,
+                       wd.map(dev, origin_x, origin_y, resolution), (int)n_blk, r_blk.at(dev), r_row.at(dev), r_maxw.at(dev),
+                       r_xy.at(dev), r_cells.at(dev), wd.offsets(dev), wd.discs(dev), wd.walls.view(dev), r_out.at(dev),
+                       r_flags.at(dev));
     HIP_TRY(hipGetLastError());
     if (ms) HIP_TRY(hipEventRecord(ev[2], stream));
-    HIP_TRY(hipMemcpyAsync(res_out.data(), blk_dev + o_out, sizeof(double) * PATH_WP_OUT * rows, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), blk_dev + o_flags, sizeof(int) * 2 * rows, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(pull(stream, res_out.data(), r_out.at(dev), r_out.count));
+    HIP_TRY(pull(stream, flags.data(), r_flags.at(dev), r_flags.count));
     HIP_TRY(hipStreamSynchronize(stream));
     if (ms) {
       HIP_TRY(hipEventElapsedTime(&ms[1], ev[0], ev[1]));
       HIP_TRY(hipEventElapsedTime(&ms[2], ev[1], ev[2]));
       for (auto& e : ev) HIP_TRY(hipEventDestroy(e));
     }
-    if (int rc = wall_block_verdict(wb)) return rc;
+    if (int rc = wd.verdict()) return rc;
   } else if (ms) {
     ms[1] = ms[2] = 0.0f;
   }

@@ -17,7 +17,15 @@ __global__ __launch_bounds__(K0L_THREADS) void mpmpc_perception_kernel(MapView m
   k0l_scan_car<WALLS, PER>(map, B, pose, off, discs, n_beams, angles, range_m, ranges, wv, pa);
 }
 
-// device scratch of mpmpc_perception_scan (SpScratch: one per device, each behind its own mutex, never freed)
+// K0s of B cars on the stream: `walls` chooses the instantiation, `a` is the kernel's argument list (map .. pa;
+// without walls wv is a null view)
+template <int PER, class... A>
+static void enqueue_perception(hipStream_t stream, int B, bool walls, A... a) {
+  if (walls) hipLaunchKernelGGL((mpmpc_perception_kernel<true, PER>), dim3(B), dim3(K0L_THREADS), 0, stream, a...);
+  else hipLaunchKernelGGL((mpmpc_perception_kernel<false, PER>), dim3(B), dim3(K0L_THREADS), 0, stream, a...);
+}
+
+// device scratch of mpmpc_perception_scan (device_scratch.hpp)
 static SpScratch g_per_dev[SP_MAX_DEVICES];
 
 // mpmpc_rollout_step, before it enqueues anything: perception is on - may steps of B cars perceive?  *active: they do (a per-car
@@ -53,16 +61,10 @@ static int per_check_step(mpmpc_handle h, int B, bool per_car, bool* active) {
 // K0s of rollout step k on the slot's stream (behind K0t and K0m, in front of K3a and K0c)
 static void per_enqueue_step(mpmpc_handle h, Slot& sl, int B, long long k) {
   PerState& p = h->per;
-  const bool discs = h->obs.obst_B > 0;
+  const bool discs = h->obs.obst_B > 0, walls = h->obs.wl_B > 0;
   const K0sArgs pa{h->ro.alive.get(), p.mem.get(), h->cfg.max_batch, (int)k, p.hold};
-  if (h->obs.wl_B > 0)
-    hipLaunchKernelGGL((mpmpc_perception_kernel<true, 2>), dim3(B), dim3(K0L_THREADS), 0, sl.stream, h->cor.map_view(), B, h->ro.pose.get(),
-                       discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), p.n_beams, p.angles.get(), p.range,
-                       (double*)nullptr, h->obs.wall_view(), pa);
-  else
-    hipLaunchKernelGGL((mpmpc_perception_kernel<false, 2>), dim3(B), dim3(K0L_THREADS), 0, sl.stream, h->cor.map_view(), B, h->ro.pose.get(),
-                       discs ? h->obs.obst_off.get() : nullptr, h->obs.obst_discs.get(), p.n_beams, p.angles.get(), p.range,
-                       (double*)nullptr, WallView{nullptr, nullptr, nullptr}, pa);
+  enqueue_perception<2>(sl.stream, B, walls, h->cor.map_view(), B, h->ro.pose.get(), discs ? h->obs.obst_off.get() : nullptr,
+                        h->obs.obst_discs.get(), p.n_beams, p.angles.get(), p.range, nullptr, h->obs.wall_view(), pa);
 }
 
 static const int* per_plan_discs(mpmpc_handle h) { return h->per.mem + (size_t)K0S_DISCS * (size_t)h->cfg.max_batch; }
@@ -81,52 +83,29 @@ int mpmpc_perception_scan(int32_t device, int32_t height, int32_t width, const i
     return fail(MPMPC_E_ARG, why);
   if (wall_offsets && wall_check_lists(B, wall_offsets, walls, width, height, &why)) return fail(MPMPC_E_ARG, why);
   if (!mov_finite(origin_x) || !mov_finite(origin_y)) return fail(MPMPC_E_ARG, "the map's origin is not finite");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
-  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the perception scratch table");
-  HIP_TRY(hipSetDevice(device));
-  const size_t nb = (size_t)B, n_disc = offsets ? (size_t)offsets[B] : 0;
-  const size_t o_pose = 0, o_ang = o_pose + sizeof(double) * 3 * nb, o_out = o_ang + sizeof(double) * (size_t)n_beams,
-               o_dseen = o_out + sizeof(double) * nb * (size_t)n_beams, o_wseen = o_dseen + sizeof(uint64_t) * nb,
-               o_off = o_wseen + pad8(sizeof(uint32_t) * nb), o_disc = o_off + pad8(sizeof(int) * (nb + 1)),
-               o_map = o_disc + pad8(sizeof(int) * 3 * n_disc), o_wall = o_map + pad8((size_t)height * width);
-  WallBlock wb = wall_block(o_wall, B, wall_offsets, walls);
-  const size_t need = wb.end;
-  SpScratch& g = g_per_dev[device];
-  std::lock_guard<std::mutex> lock(g.mu);
-  if (g.bytes < need) {
-    if (g.block) (void)device_free(g.block);
-    g.block = nullptr; g.bytes = 0;
-    HIP_TRY(device_alloc((void**)&g.block, need));
-    g.bytes = need;
-  }
-  if (!g.stream) HIP_TRY(hipStreamCreate(&g.stream));
-  hipStream_t stream = g.stream;
-  char* blk = g.block;
-  HIP_TRY(hipMemcpyAsync(blk + o_pose, pose, sizeof(double) * 3 * nb, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_ang, angles, sizeof(double) * (size_t)n_beams, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_map, data, (size_t)height * width, hipMemcpyHostToDevice, stream));
-  if (offsets) HIP_TRY(hipMemcpyAsync(blk + o_off, offsets, sizeof(int) * (nb + 1), hipMemcpyHostToDevice, stream));
-  if (n_disc > 0) HIP_TRY(hipMemcpyAsync(blk + o_disc, discs, sizeof(int) * 3 * n_disc, hipMemcpyHostToDevice, stream));
-  if (int rc = wall_block_enqueue(blk, wb, B, wall_offsets, walls, stream)) return rc;      // K0w first, on the same stream
-  const MapView mv{(const int8_t*)(blk + o_map), height, width, origin_x, origin_y, resolution};
-  const K0sArgs pa{nullptr, (int*)(blk + o_dseen), B, 0, 0};      // (the walls' masks follow the discs': o_wseen = o_dseen + 8 B)
-  double* d_out = ranges_out ? (double*)(blk + o_out) : nullptr;
-  if (wall_offsets)
-    hipLaunchKernelGGL((mpmpc_perception_kernel<true, 1>), dim3(B), dim3(K0L_THREADS), 0, stream, mv, B, (const double*)(blk + o_pose),
-                       offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), n_beams,
-                       (const double*)(blk + o_ang), range_m, d_out, wall_block_view(blk, wb, wall_offsets), pa);
-  else
-    hipLaunchKernelGGL((mpmpc_perception_kernel<false, 1>), dim3(B), dim3(K0L_THREADS), 0, stream, mv, B, (const double*)(blk + o_pose),
-                       offsets ? (const int*)(blk + o_off) : nullptr, (const int*)(blk + o_disc), n_beams,
-                       (const double*)(blk + o_ang), range_m, d_out, WallView{nullptr, nullptr, nullptr}, pa);
+  const size_t nb = (size_t)B;
+  Layout L;
+  const auto r_pose = L.add<double>(3 * nb), r_ang = L.add<double>((size_t)n_beams), r_out = L.add<double>(nb * (size_t)n_beams);
+  // K0s's memory is ONE region (K0sArgs::mem): the discs' masks [B][2], the walls' [B] right behind them
+  const auto r_seen = L.add<int>(3 * nb), r_dseen = r_seen.part(0, 2 * nb), r_wseen = r_seen.part(2 * nb, nb);
+  WorldBlock wd = world_block(L, height, width, data, B, offsets, discs, wall_offsets, walls);
+  Scratch sc;
+  if (int rc = scratch_acquire(g_per_dev, device, L.bytes(), "perception", &sc)) return rc;
+  hipStream_t stream = sc.stream;
+  char* blk = sc.blk;
+  HIP_TRY(hipMemcpyAsync(r_pose.at(blk), pose, r_pose.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_ang.at(blk), angles, r_ang.bytes(), hipMemcpyHostToDevice, stream));
+  if (int rc = wd.enqueue(blk, stream)) return rc;
+  double* d_out = ranges_out ? r_out.at(blk) : nullptr;
+  enqueue_perception<1>(stream, B, wall_offsets != nullptr, wd.map(blk, origin_x, origin_y, resolution), B, r_pose.at(blk),
+                        wd.offsets(blk), wd.discs(blk), n_beams, r_ang.at(blk), range_m, d_out, wd.walls.view(blk),
+                        K0sArgs{nullptr, r_seen.at(blk), B, 0, 0});
   HIP_TRY(hipGetLastError());
-  if (ranges_out) HIP_TRY(hipMemcpyAsync(ranges_out, blk + o_out, sizeof(double) * nb * (size_t)n_beams, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(disc_seen_out, blk + o_dseen, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(wall_seen_out, blk + o_wseen, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(pull(stream, ranges_out, r_out.at(blk), r_out.count));
+  HIP_TRY(pull(stream, disc_seen_out, (const uint64_t*)r_dseen.at(blk), nb));      // (bit q of the 64: slot q - two ints per car)
+  HIP_TRY(pull(stream, wall_seen_out, (const uint32_t*)r_wseen.at(blk), nb));
   HIP_TRY(hipStreamSynchronize(stream));
-  return wall_block_verdict(wb);
+  return wd.verdict();
 }
 
 int mpmpc_rollout_set_perception(mpmpc_handle h, int32_t n_beams, const double* angles, double range_m, int32_t hold) {
@@ -164,14 +143,12 @@ int mpmpc_rollout_perception(mpmpc_handle h, int32_t B, int32_t* disc_first, int
   const size_t mb = (size_t)h->cfg.max_batch, nb = (size_t)B;
   hipStream_t st = h->last().stream;
   const int* mem = p.mem.get();
-#define PULL(dst, src, bytes) if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st))
-  PULL(disc_first, mem + K0S_DISC_FIRST * mb, sizeof(int) * COR_MAX_DISCS * nb);
-  PULL(disc_last, mem + K0S_DISC_LAST * mb, sizeof(int) * COR_MAX_DISCS * nb);
-  PULL(wall_first, mem + K0S_WALL_FIRST * mb, sizeof(int) * COR_MAX_WALLS * nb);
-  PULL(wall_last, mem + K0S_WALL_LAST * mb, sizeof(int) * COR_MAX_WALLS * nb);
-  PULL(disc_known, mem + K0S_DISC_KNOWN * mb, sizeof(uint64_t) * nb);
-  PULL(wall_known, mem + K0S_WALL_KNOWN * mb, sizeof(uint32_t) * nb);
-#undef PULL
+  HIP_TRY(pull(st, disc_first, mem + K0S_DISC_FIRST * mb, COR_MAX_DISCS * nb));
+  HIP_TRY(pull(st, disc_last, mem + K0S_DISC_LAST * mb, COR_MAX_DISCS * nb));
+  HIP_TRY(pull(st, wall_first, mem + K0S_WALL_FIRST * mb, COR_MAX_WALLS * nb));
+  HIP_TRY(pull(st, wall_last, mem + K0S_WALL_LAST * mb, COR_MAX_WALLS * nb));
+  HIP_TRY(pull(st, disc_known, (const uint64_t*)(mem + K0S_DISC_KNOWN * mb), nb));
+  HIP_TRY(pull(st, wall_known, (const uint32_t*)(mem + K0S_WALL_KNOWN * mb), nb));
   HIP_TRY(hipStreamSynchronize(st));
   return MPMPC_OK;
 }

@@ -135,14 +135,12 @@ int mpmpc_rollout_plant(mpmpc_handle h, int32_t B, double* act, double* meas, do
   if (h->pl.B != B || !h->pl.ran)
     return fail(MPMPC_E_STATE, "no rollout step of B cars ran under the plant in force (mpmpc_rollout_set_plant)");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  const size_t mb = (size_t)h->cfg.max_batch;
-#define PULL(dst, src, bytes) if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sl.stream))
-  PULL(act, h->pl.act, sizeof(double) * 2 * B);
-  PULL(meas, h->pl.meas, sizeof(double) * 3 * B);
-  PULL(ey_max, h->pl.ey, sizeof(double) * B);
-  PULL(ey_sq, h->pl.ey + mb, sizeof(double) * B);
-  PULL(steps, h->pl.steps, sizeof(int) * B);
-#undef PULL
+  const size_t mb = (size_t)h->cfg.max_batch, nb = (size_t)B;
+  HIP_TRY(pull(sl.stream, act, h->pl.act, 2 * nb));
+  HIP_TRY(pull(sl.stream, meas, h->pl.meas, 3 * nb));
+  HIP_TRY(pull(sl.stream, ey_max, h->pl.ey, nb));
+  HIP_TRY(pull(sl.stream, ey_sq, h->pl.ey + mb, nb));
+  HIP_TRY(pull(sl.stream, steps, h->pl.steps, nb));
   HIP_TRY(hipStreamSynchronize(sl.stream));
   return MPMPC_OK;
 }
@@ -153,26 +151,15 @@ int mpmpc_plant_noise(int32_t device, uint64_t seed, int32_t car0, int32_t B, in
   const long total = (long)B * n_steps;
   if (total > PL_NOISE_MAX_ROWS) return fail(MPMPC_E_ARG, "plant noise: more than 2^26 (step, car) rows in one call");
   if (total == 0) return MPMPC_OK;
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
-  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the plant scratch table");
-  HIP_TRY(hipSetDevice(device));
-  const size_t need = sizeof(double) * PL_NOISE * (size_t)total;
-  SpScratch& g = g_plant_dev[device];
-  std::lock_guard<std::mutex> lock(g.mu);
-  if (g.bytes < need) {
-    if (g.block) (void)device_free(g.block);
-    g.block = nullptr; g.bytes = 0;
-    HIP_TRY(device_alloc((void**)&g.block, need));
-    g.bytes = need;
-  }
-  if (!g.stream) HIP_TRY(hipStreamCreate(&g.stream));
-  hipLaunchKernelGGL(mpmpc_plant_noise_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g.stream, total, (int)B,
-                     (unsigned long long)seed, (int)car0, (long long)j0, (double*)g.block);
+  Layout L;
+  const auto r_out = L.add<double>(PL_NOISE * (size_t)total);
+  Scratch sc;
+  if (int rc = scratch_acquire(g_plant_dev, device, L.bytes(), "plant", &sc)) return rc;
+  hipLaunchKernelGGL(mpmpc_plant_noise_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sc.stream, total, (int)B,
+                     (unsigned long long)seed, (int)car0, (long long)j0, r_out.at(sc.blk));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, g.block, need, hipMemcpyDeviceToHost, g.stream));
-  HIP_TRY(hipStreamSynchronize(g.stream));
+  HIP_TRY(pull(sc.stream, out, r_out.at(sc.blk), r_out.count));
+  HIP_TRY(hipStreamSynchronize(sc.stream));
   return MPMPC_OK;
 }
 

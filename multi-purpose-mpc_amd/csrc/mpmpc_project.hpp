@@ -77,43 +77,30 @@ int mpmpc_project(int32_t device, int32_t n_wp, const double* x, const double* y
   } else {
     first = one;
   }
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
-  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the projection scratch table");
-  HIP_TRY(hipSetDevice(device));
-  const size_t d = sizeof(double), n = (size_t)n_wp, pairs = (size_t)B * K;
-  const size_t o_x = 0, o_y = o_x + d * n, o_psi = o_y + d * n, o_cum = o_psi + d * n, o_pose = o_cum + d * n, o_dist = o_pose + d * 3 * B,
-               o_x0 = o_dist + d * pairs, o_s = o_x0 + d * 3 * pairs, o_wp = o_s + d * pairs, o_first = o_wp + pad8(sizeof(int) * pairs),
-               o_cand = o_first + pad8(sizeof(int) * ((size_t)routes + 1)), need = o_cand + pad8(sizeof(int) * pairs);
-  SpScratch& g = g_proj_dev[device];
-  std::lock_guard<std::mutex> lock(g.mu);
-  if (g.bytes < need) {
-    if (g.block) (void)device_free(g.block);
-    g.block = nullptr; g.bytes = 0;
-    HIP_TRY(device_alloc((void**)&g.block, need));
-    g.bytes = need;
-  }
-  if (!g.stream) HIP_TRY(hipStreamCreate(&g.stream));
-  hipStream_t stream = g.stream;
-  char* blk = g.block;
-  HIP_TRY(hipMemcpyAsync(blk + o_x, x, d * n, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_y, y, d * n, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_psi, psi, d * n, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_cum, cum, d * n, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_pose, pose, d * 3 * B, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + o_first, first, sizeof(int) * ((size_t)routes + 1), hipMemcpyHostToDevice, stream));
-  if (cand) HIP_TRY(hipMemcpyAsync(blk + o_cand, cand, sizeof(int) * pairs, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(mpmpc_project_kernel, dim3((unsigned)pairs), dim3(64), 0, stream, (int)pairs, K,
-                     cand ? (const int*)(blk + o_cand) : nullptr, (const int*)(blk + o_first), (const double*)(blk + o_x),
-                     (const double*)(blk + o_y), (const double*)(blk + o_psi), (const double*)(blk + o_cum),
-                     (const double*)(blk + o_pose), (const int*)nullptr, max_heading, (int*)(blk + o_wp), (double*)(blk + o_dist),
-                     (double*)(blk + o_x0), (double*)(blk + o_s));
+  const size_t n = (size_t)n_wp, nb = (size_t)B, pairs = nb * K;
+  Layout L;
+  const auto r_x = L.add<double>(n), r_y = L.add<double>(n), r_psi = L.add<double>(n), r_cum = L.add<double>(n), r_pose = L.add<double>(3 * nb),
+             r_dist = L.add<double>(pairs), r_x0 = L.add<double>(3 * pairs), r_s = L.add<double>(pairs);
+  const auto r_wp = L.add<int>(pairs), r_first = L.add<int>((size_t)routes + 1), r_cand = L.add<int>(cand ? pairs : 0);
+  Scratch sc;
+  if (int rc = scratch_acquire(g_proj_dev, device, L.bytes(), "projection", &sc)) return rc;
+  hipStream_t stream = sc.stream;
+  char* blk = sc.blk;
+  HIP_TRY(hipMemcpyAsync(r_x.at(blk), x, r_x.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_y.at(blk), y, r_y.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_psi.at(blk), psi, r_psi.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_cum.at(blk), cum, r_cum.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_pose.at(blk), pose, r_pose.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_first.at(blk), first, r_first.bytes(), hipMemcpyHostToDevice, stream));
+  if (cand) HIP_TRY(hipMemcpyAsync(r_cand.at(blk), cand, r_cand.bytes(), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(mpmpc_project_kernel, dim3((unsigned)pairs), dim3(64), 0, stream, (int)pairs, K, cand ? r_cand.at(blk) : nullptr,
+                     r_first.at(blk), r_x.at(blk), r_y.at(blk), r_psi.at(blk), r_cum.at(blk), r_pose.at(blk), nullptr, max_heading,
+                     r_wp.at(blk), r_dist.at(blk), r_x0.at(blk), r_s.at(blk));
   HIP_TRY(hipGetLastError());
-  if (wp_out) HIP_TRY(hipMemcpyAsync(wp_out, blk + o_wp, sizeof(int) * pairs, hipMemcpyDeviceToHost, stream));
-  if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out, blk + o_dist, d * pairs, hipMemcpyDeviceToHost, stream));
-  if (x0_out) HIP_TRY(hipMemcpyAsync(x0_out, blk + o_x0, d * 3 * pairs, hipMemcpyDeviceToHost, stream));
-  if (s_out) HIP_TRY(hipMemcpyAsync(s_out, blk + o_s, d * pairs, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(pull(stream, wp_out, r_wp.at(blk), pairs));
+  HIP_TRY(pull(stream, dist_out, r_dist.at(blk), pairs));
+  HIP_TRY(pull(stream, x0_out, r_x0.at(blk), 3 * pairs));
+  HIP_TRY(pull(stream, s_out, r_s.at(blk), pairs));
   HIP_TRY(hipStreamSynchronize(stream));
   return MPMPC_OK;
 }

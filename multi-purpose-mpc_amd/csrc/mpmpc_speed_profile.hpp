@@ -57,70 +57,44 @@ __global__ __launch_bounds__(64) void mpmpc_speed_profile_wave_kernel(int B, int
   if (threadIdx.x == 0) { status[p] = st; iters[p] = it; }
 }
 
-// device scratch of mpmpc_speed_profile, kept between calls (a call is a set-up step, and without this its cost was
-// allocation: 3.5 of 4 ms for a single path).  One scratch per device, each behind its own mutex: callers on
-// different devices neither serialise nor free each other's block.
-// The block is a RAW pointer and is never freed: the table has static storage, and an owner's destructor at process exit would
-// call into a HIP runtime that may already be torn down.
-struct SpScratch {
-  std::mutex mu;
-  size_t bytes = 0;
-  char* block = nullptr;
-  hipStream_t stream = nullptr;
-};
-constexpr int SP_MAX_DEVICES = 64;
+// device scratch of mpmpc_speed_profile (device_scratch.hpp: one per device, kept between calls, never freed)
 static SpScratch g_sp_dev[SP_MAX_DEVICES];
 
 extern "C" int mpmpc_speed_profile(int32_t device, int32_t B, int32_t n, const double* li, const double* kappa,
                         const double* limits, double eps, double* v, int32_t* status, int32_t* iters) {
   if (B < 1 || n < 2) return fail(MPMPC_E_ARG, "speed profile needs B >= 1 paths of n >= 2 segments");
   if (!li || !kappa || !limits || !v || !status) return fail(MPMPC_E_ARG, "li, kappa, limits, v, status must not be NULL");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
-  HIP_TRY(hipSetDevice(device));
-  const size_t vec = sizeof(double) * (size_t)B * n;
+  const size_t nb = (size_t)B, vec = nb * n;
   const size_t lds_wave = sizeof(double) * (SP_ARRAYS + sp_cr_arrays(n)) * (size_t)n;
   // one wavefront per path while its arrays fit 156 KiB of LDS: n <= 384, where 8 (25 + 9 + 2 * 9) 384 = 159 744 B is
   // 156 KiB exactly; beyond that one thread per path.  (A kernel that ran one thread per path out of 64 KiB of LDS,
   // 25 * 8 n <= 65 536: n <= 327, could never be chosen - the wave kernel takes every such n - and is gone.)
   const bool wave = lds_wave <= 156 * 1024;
-  // one block: li, kappa, v, limits, status, iters (+ the HBM workspace of the thread-per-path kernel)
-  const size_t o_li = 0, o_kappa = vec, o_v = 2 * vec, o_lim = 3 * vec, o_status = o_lim + pad8(sizeof(double) * 5 * B),
-               o_iters = o_status + pad8(sizeof(int) * (size_t)B), o_work = o_iters + pad8(sizeof(int) * (size_t)B),
-               need = o_work + (wave ? 0 : vec * SP_ARRAYS);
-  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the speed-profile scratch table");
-  SpScratch& g_sp = g_sp_dev[device];
-  std::lock_guard<std::mutex> lock(g_sp.mu);
-  if (g_sp.bytes < need) {
-    if (g_sp.block) (void)device_free(g_sp.block);
-    g_sp.block = nullptr; g_sp.bytes = 0;
-    HIP_TRY(device_alloc((void**)&g_sp.block, need));
-    g_sp.bytes = need;
-  }
-  if (!g_sp.stream) HIP_TRY(hipStreamCreate(&g_sp.stream));
-  hipStream_t stream = g_sp.stream;
-  char* blk = g_sp.block;
-  double *d_li = (double*)(blk + o_li), *d_kappa = (double*)(blk + o_kappa), *d_v = (double*)(blk + o_v),
-         *d_lim = (double*)(blk + o_lim), *d_work = (double*)(blk + o_work);
-  int *d_status = (int*)(blk + o_status), *d_iters = (int*)(blk + o_iters);
-  HIP_TRY(hipMemcpyAsync(d_li, li, vec, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_kappa, kappa, vec, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_lim, limits, sizeof(double) * 5 * B, hipMemcpyHostToDevice, stream));
+  Layout L;
+  const auto r_li = L.add<double>(vec), r_kappa = L.add<double>(vec), r_v = L.add<double>(vec), r_lim = L.add<double>(5 * nb),
+             r_work = L.add<double>(wave ? 0 : vec * SP_ARRAYS);      // (the HBM workspace of the thread-per-path kernel)
+  const auto r_status = L.add<int>(nb), r_iters = L.add<int>(nb);
+  Scratch sc;
+  if (int rc = scratch_acquire(g_sp_dev, device, L.bytes(), "speed-profile", &sc)) return rc;
+  hipStream_t stream = sc.stream;
+  char* blk = sc.blk;
+  HIP_TRY(hipMemcpyAsync(r_li.at(blk), li, r_li.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_kappa.at(blk), kappa, r_kappa.bytes(), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(r_lim.at(blk), limits, r_lim.bytes(), hipMemcpyHostToDevice, stream));
   if (wave) {
     // one wavefront per path (any batch size): lane-parallel arithmetic, cyclic reduction for the tridiagonal solves
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mpmpc_speed_profile_wave_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wave));
-    hipLaunchKernelGGL(mpmpc_speed_profile_wave_kernel, dim3(B), dim3(64), lds_wave, stream, B, n, d_li, d_kappa, d_lim,
-                       eps, d_v, d_status, d_iters);
+    hipLaunchKernelGGL(mpmpc_speed_profile_wave_kernel, dim3(B), dim3(64), lds_wave, stream, B, n, r_li.at(blk), r_kappa.at(blk),
+                       r_lim.at(blk), eps, r_v.at(blk), r_status.at(blk), r_iters.at(blk));
   } else {
-    hipLaunchKernelGGL(mpmpc_speed_profile_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, B, n, d_li, d_kappa, d_lim,
-                       eps, d_work, d_v, d_status, d_iters);
+    hipLaunchKernelGGL(mpmpc_speed_profile_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, B, n, r_li.at(blk), r_kappa.at(blk),
+                       r_lim.at(blk), eps, r_work.at(blk), r_v.at(blk), r_status.at(blk), r_iters.at(blk));
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(v, d_v, vec, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
-  if (iters) HIP_TRY(hipMemcpyAsync(iters, d_iters, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(pull(stream, v, r_v.at(blk), vec));
+  HIP_TRY(pull(stream, status, r_status.at(blk), nb));
+  HIP_TRY(pull(stream, iters, r_iters.at(blk), nb));
   HIP_TRY(hipStreamSynchronize(stream));
   return MPMPC_OK;
 }

@@ -39,51 +39,91 @@ __global__ __launch_bounds__(256) void mpmpc_world_grid_kernel(MapView map, int 
   out[c] = occ ? 0 : 1;
 }
 
-// A fleet's walls inside a scratch block (mpmpc_lidar_scan_world, mpmpc_footprint_audit_world, mpmpc_world_grid): where its
-// five arrays lie from byte `start` on, the headers (host), and the block's end.
+constexpr WallView WALLS_NONE{nullptr, nullptr, nullptr};      // what a kernel instantiated without WALLS is handed
+
+// A fleet's walls inside a scratch block, for the entry points that need no handle: its five arrays, reserved in the block's
+// layout (device_scratch.hpp), the caller's lists and the headers (host).  off == nullptr: no walls, and nothing is reserved.
 struct WallBlock {
-  size_t n = 0, total = 0;
-  size_t o_off = 0, o_hdr = 0, o_raw = 0, o_tab = 0, o_ok = 0, end = 0;
+  const int32_t *off = nullptr, *walls = nullptr;
+  size_t n = 0;
+  Region<int> r_off, r_hdr, r_raw, r_tab, r_ok;
   std::vector<int32_t> hdr, ok;
+  // uploads them and runs K0w on the stream, in front of the kernel that reads them; `ok` arrives with the stream's next
+  // synchronisation (verdict)
+  int enqueue(char* blk, hipStream_t stream) {
+    if (!off) return MPMPC_OK;
+    HIP_TRY(hipMemcpyAsync(r_off.at(blk), off, r_off.bytes(), hipMemcpyHostToDevice, stream));
+    if (n == 0) return MPMPC_OK;
+    HIP_TRY(hipMemcpyAsync(r_hdr.at(blk), hdr.data(), r_hdr.bytes(), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(r_raw.at(blk), walls, r_raw.bytes(), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(mpmpc_wall_raster_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, (int)n, r_raw.at(blk),
+                       r_hdr.at(blk), r_tab.at(blk), r_ok.at(blk));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(pull(stream, ok.data(), r_ok.at(blk), n));
+    return MPMPC_OK;
+  }
+  WallView view(char* blk) const {
+    if (!off) return WALLS_NONE;
+    return WallView{r_off.at(blk), r_hdr.at(blk), r_tab.at(blk)};
+  }
+  int verdict() const {
+    for (size_t j = 0; j < n; ++j)
+      if (ok[j] != 1) return fail(MPMPC_E_ARG, "wall " + std::to_string(j) + " does not fit the wall table (csrc/wall_core.hpp, step 3)");
+    return MPMPC_OK;
+  }
 };
-static WallBlock wall_block(size_t start, int B, const int32_t* off, const int32_t* walls) {
+static WallBlock wall_block(Layout& L, int B, const int32_t* off, const int32_t* walls) {
   WallBlock w;
-  w.end = start;
   if (!off) return w;
+  w.off = off; w.walls = walls;
   w.n = (size_t)off[B];
   w.hdr.assign(WALL_HDR * w.n + 1, 0);
   w.ok.assign(w.n + 1, 1);
-  w.total = (size_t)wall_layout((long)w.n, walls, w.hdr.data());
-  w.o_off = start;
-  w.o_hdr = w.o_off + pad8(sizeof(int) * ((size_t)B + 1));
-  w.o_raw = w.o_hdr + pad8(sizeof(int) * WALL_HDR * w.n);
-  w.o_tab = w.o_raw + pad8(sizeof(int) * 4 * w.n);
-  w.o_ok = w.o_tab + pad8(sizeof(int) * w.total);
-  w.end = w.o_ok + pad8(sizeof(int) * w.n);
+  const size_t total = (size_t)wall_layout((long)w.n, walls, w.hdr.data());
+  w.r_off = L.add<int>((size_t)B + 1);
+  w.r_hdr = L.add<int>(WALL_HDR * w.n);
+  w.r_raw = L.add<int>(4 * w.n);
+  w.r_tab = L.add<int>(total);
+  w.r_ok = L.add<int>(w.n);
   return w;
 }
-// uploads them and runs K0w on the stream, in front of the kernel that reads them; w.ok arrives with the stream's next
-// synchronisation (wall_block_verdict)
-static int wall_block_enqueue(char* blk, WallBlock& w, int B, const int32_t* off, const int32_t* walls, hipStream_t stream) {
-  if (!off) return MPMPC_OK;
-  HIP_TRY(hipMemcpyAsync(blk + w.o_off, off, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, stream));
-  if (w.n == 0) return MPMPC_OK;
-  HIP_TRY(hipMemcpyAsync(blk + w.o_hdr, w.hdr.data(), sizeof(int) * WALL_HDR * w.n, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(blk + w.o_raw, walls, sizeof(int) * 4 * w.n, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(mpmpc_wall_raster_kernel, dim3((unsigned)((w.n + 63) / 64)), dim3(64), 0, stream, (int)w.n, (const int*)(blk + w.o_raw),
-                     (const int*)(blk + w.o_hdr), (int*)(blk + w.o_tab), (int*)(blk + w.o_ok));
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(w.ok.data(), blk + w.o_ok, sizeof(int) * w.n, hipMemcpyDeviceToHost, stream));
-  return MPMPC_OK;
-}
-static WallView wall_block_view(char* blk, const WallBlock& w, const int32_t* off) {
-  if (!off) return WallView{nullptr, nullptr, nullptr};
-  return WallView{(const int*)(blk + w.o_off), (const int*)(blk + w.o_hdr), (const int*)(blk + w.o_tab)};
-}
-static int wall_block_verdict(const WallBlock& w) {
-  for (size_t j = 0; j < w.n; ++j)
-    if (w.ok[j] != 1) return fail(MPMPC_E_ARG, "wall " + std::to_string(j) + " does not fit the wall table (csrc/wall_core.hpp, step 3)");
-  return MPMPC_OK;
+
+// The worlds of B cars inside a scratch block (mpmpc_lidar_scan_world, mpmpc_footprint_audit_world, mpmpc_perception_scan,
+// mpmpc_path_build; mpmpc_world_grid with B = 1): the map, the cars' discs (off == nullptr: none) and their walls.
+struct WorldBlock {
+  int height = 0, width = 0;
+  const int8_t* data = nullptr;
+  const int32_t *off = nullptr, *disc_list = nullptr;
+  Region<int8_t> r_map;
+  Region<int> r_off, r_disc;
+  WallBlock walls;
+  int upload(char* blk, hipStream_t stream) {
+    HIP_TRY(hipMemcpyAsync(r_map.at(blk), data, r_map.bytes(), hipMemcpyHostToDevice, stream));
+    if (off) HIP_TRY(hipMemcpyAsync(r_off.at(blk), off, r_off.bytes(), hipMemcpyHostToDevice, stream));
+    if (r_disc.count > 0) HIP_TRY(hipMemcpyAsync(r_disc.at(blk), disc_list, r_disc.bytes(), hipMemcpyHostToDevice, stream));
+    return MPMPC_OK;
+  }
+  // everything onto the stream, K0w included: the kernel that reads the worlds comes behind
+  int enqueue(char* blk, hipStream_t stream) {
+    if (int rc = upload(blk, stream)) return rc;
+    return walls.enqueue(blk, stream);
+  }
+  MapView map(char* blk, double origin_x, double origin_y, double resolution) const {
+    return MapView{r_map.at(blk), height, width, origin_x, origin_y, resolution};
+  }
+  const int* offsets(char* blk) const { return off ? r_off.at(blk) : nullptr; }
+  const int* discs(char* blk) const { return r_disc.at(blk); }
+  int verdict() const { return walls.verdict(); }
+};
+static WorldBlock world_block(Layout& L, int height, int width, const int8_t* data, int B, const int32_t* off, const int32_t* discs,
+                              const int32_t* wall_off, const int32_t* walls) {
+  WorldBlock w;
+  w.height = height; w.width = width; w.data = data; w.off = off; w.disc_list = discs;
+  w.r_off = L.add<int>((size_t)B + 1);
+  w.r_disc = L.add<int>(off ? 3 * (size_t)off[B] : 0);
+  w.r_map = L.add<int8_t>((size_t)height * width);
+  w.walls = wall_block(L, B, wall_off, walls);
+  return w;
 }
 
 static SpScratch g_world_dev[SP_MAX_DEVICES];
@@ -100,35 +140,19 @@ extern "C" int mpmpc_world_grid(int32_t device, int32_t height, int32_t width, c
   const char* why = "";
   if (lid_check_discs(1, d_off, discs, width, height, &why)) return fail(MPMPC_E_ARG, why);
   if (wall_check_lists(1, w_off, walls, width, height, &why)) return fail(MPMPC_E_ARG, why);
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(MPMPC_E_HIP, "no such HIP device");
-  if (device >= SP_MAX_DEVICES) return fail(MPMPC_E_ARG, "device ordinal beyond the world scratch table");
-  HIP_TRY(hipSetDevice(device));
   const size_t cells = (size_t)height * width;
-  const size_t o_map = 0, o_out = o_map + pad8(cells), o_disc = o_out + pad8(cells), o_wall = o_disc + pad8(sizeof(int) * 3 * (size_t)n_discs);
-  WallBlock wb = wall_block(o_wall, 1, w_off, walls);
-  const size_t need = wb.end + 8;
-  SpScratch& g = g_world_dev[device];
-  std::lock_guard<std::mutex> lock(g.mu);
-  if (g.bytes < need) {
-    if (g.block) (void)device_free(g.block);
-    g.block = nullptr; g.bytes = 0;
-    HIP_TRY(device_alloc((void**)&g.block, need));
-    g.bytes = need;
-  }
-  if (!g.stream) HIP_TRY(hipStreamCreate(&g.stream));
-  hipStream_t stream = g.stream;
-  char* blk = g.block;
-  HIP_TRY(hipMemcpyAsync(blk + o_map, data, cells, hipMemcpyHostToDevice, stream));
-  if (n_discs > 0) HIP_TRY(hipMemcpyAsync(blk + o_disc, discs, sizeof(int) * 3 * (size_t)n_discs, hipMemcpyHostToDevice, stream));
-  if (int rc = wall_block_enqueue(blk, wb, 1, w_off, walls, stream)) return rc;
-  const MapView mv{(const int8_t*)(blk + o_map), height, width, origin_x, origin_y, resolution};
-  hipLaunchKernelGGL(mpmpc_world_grid_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, mv, n_discs,
-                     (const int*)(blk + o_disc), n_walls, (const int*)(blk + wb.o_hdr), (const int*)(blk + wb.o_tab),
-                     (int8_t*)(blk + o_out));
+  Layout L;
+  WorldBlock wd = world_block(L, height, width, data, 1, d_off, discs, w_off, walls);      // one car's world: the lists of a fleet of one
+  const auto r_out = L.add<int8_t>(cells);
+  Scratch sc;
+  if (int rc = scratch_acquire(g_world_dev, device, L.bytes(), "world", &sc)) return rc;
+  if (int rc = wd.enqueue(sc.blk, sc.stream)) return rc;
+  const WallView wv = wd.walls.view(sc.blk);
+  hipLaunchKernelGGL(mpmpc_world_grid_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, sc.stream,
+                     wd.map(sc.blk, origin_x, origin_y, resolution), n_discs, wd.discs(sc.blk), n_walls, wv.hdr, wv.tab,
+                     r_out.at(sc.blk));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(grid_out, blk + o_out, cells, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return wall_block_verdict(wb);
+  HIP_TRY(pull(sc.stream, grid_out, r_out.at(sc.blk), cells));
+  HIP_TRY(hipStreamSynchronize(sc.stream));
+  return wd.verdict();
 }
