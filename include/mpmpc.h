@@ -597,6 +597,43 @@ int mpmpc_plant_noise(int32_t device, uint64_t seed, int32_t car0, int32_t B, in
 #define MPMPC_DELAY_MAX 8
 int mpmpc_rollout_set_delay(mpmpc_handle h, int32_t B, const int32_t* delay, const int32_t* assumed, const double* queue0);
 int mpmpc_rollout_delay(mpmpc_handle h, int32_t B, double* queue, double* pred_pose, double* pred_s, double* now);
+/* Dynamic single-track plant, per car and off by default: a car with mass, yaw inertia and tyres that slip and saturate, behind
+ * a speed controller that needs time and traction - the questions about grip that a kinematic plant cannot be asked.  The
+ * controller, the estimator's and the localiser's dead reckoning, the delay's prediction and the lookahead stay on the nominal
+ * kinematic model.  Needs a plant in force for the same B cars (the identity will do; else a step returns MPMPC_E_STATE): K3y
+ * drives the car in place of K3p, or of K3q under a delay.  The plant's gains, noise, lags and rate limit yield (v_act, d_act) as
+ * before; then, per car with the state (vx, vy, r) - body-frame velocity at the centre of gravity and yaw rate, carried from step
+ * to step - below v_dyn the car is kinematic at the speed its speed controller reaches, above it n explicit sub-steps integrate
+ * the single-track model with linear tyres clipped to the friction ellipse (rear driven, static axle loads); s advances by the
+ * odometry of the step's final vx.  params [B][11] per car, in this order:
+ *    0 mass [kg] > 0          3 Cf [N/rad] > 0     6 speed_gain [1/s] > 0, +inf: ideal    9 v_dyn [m/s] > 0, +inf: never dynamic
+ *    1 inertia [kg m^2] > 0   4 Cr [N/rad] > 0     7 a_drive [m/s^2] > 0, +inf allowed    10 substeps: an integer in [1, 64]
+ *    2 lf [m] in (0, Lp)      5 mu > 0, +inf: none 8 a_brake [m/s^2] > 0, +inf allowed
+ * Lp = wheelbase * wheelbase_scale is the plant's wheelbase.  The exact operation order is stated in csrc/dynamics_core.hpp.
+ * v_dyn = +inf with speed_gain = +inf reproduces the plant alone bit for bit.  The audit, mpmpc_rollout_scan, perception,
+ * traffic, the localiser's scan and the recorder keep the true pose; the plant's statistics go on as under K3p / K3q.
+ *   mpmpc_rollout_set_dynamics  params == NULL: off.  state0 [B][3] or NULL for zeros.  Validated on the host before anything is
+ *                           touched - MPMPC_E_ARG: a parameter outside its range, state0 not finite, B outside [1, max_batch]; a
+ *                           refused call leaves the previous setting in force.  The first step that knows Ts, the plant and the
+ *                           parameters returns MPMPC_E_STATE before any kernel is launched if a car's lf is not below its Lp or
+ *                           the explicit sub-step is unstable: with lambda = max((Cf + Cr) / (m v_dyn), (lf^2 Cf + lr^2 Cr) /
+ *                           (Iz v_dyn)) a run needs lambda * Ts / substeps <= 1 (v_dyn = +inf passes).  May be called before
+ *                           mpmpc_rollout_init or between steps; mpmpc_rollout_init keeps the parameters and starts the state
+ *                           and the accumulators over - a resumed run sets the dynamics (with the saved state) after it.
+ *   mpmpc_rollout_dynamics  any pointer may be NULL.  state [B][3]; counts [3][B]: the steps that took the dynamic branch, and
+ *                           those in which some sub-step clipped the front / the rear axle; peaks [3][B]: max |front slip angle|,
+ *                           max |rear slip angle| [rad] and max lateral acceleration |Fyf cos(delta) + Fyr| / m over all
+ *                           sub-steps (driven steps only).  MPMPC_E_STATE unless a step of B cars ran under the setting in force.
+ *   mpmpc_dynamics_drive    without a handle, open loop: B cars from state0 (NULL: zeros) and pose0 [B][3] through
+ *                           cmds [n_steps][B][2] = (v_act, d_act) on the wheelbase L - step steer, skidpad, launch.  Out: state
+ *                           [B][3], pose [B][3], counts [3][B], peaks [3][B] and trace [n_steps][B][3], the pose after every step
+ *                           (each may be NULL).  MPMPC_E_ARG for what the other two refuse, the stability bound included.
+ * A rollout without the setting launches exactly what it launched before. */
+int mpmpc_rollout_set_dynamics(mpmpc_handle h, int32_t B, const double* params, const double* state0);
+int mpmpc_rollout_dynamics(mpmpc_handle h, int32_t B, double* state, int32_t* counts, double* peaks);
+int mpmpc_dynamics_drive(int32_t device, int32_t B, int32_t n_steps, double L, double Ts, const double* params, const double* state0,
+                         const double* pose0, const double* cmds, double* state, double* pose, int32_t* counts, double* peaks,
+                         double* trace);
 /* Pose estimator, per car and off by default: a 3-state extended Kalman filter on the world pose (x, y, psi) in the controller's
  * NOMINAL model, between the measurement and the controller (K3e, behind K3n and in front of K3d / K3a; cars with alive == 1).
  * With it everything the controller localises on takes the ESTIMATE instead of the measured (plant) or true pose: K3a without a

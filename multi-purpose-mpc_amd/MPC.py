@@ -381,7 +381,8 @@ class BatchMPC:
         return self.handle.rollout_reroute(routes, max_dist, max_heading)
 
     def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
-                walls=None, perception=None, routes=None, lookahead=None, plant=None, delay=None, estimator=None, localiser=None):
+                walls=None, perception=None, routes=None, lookahead=None, plant=None, delay=None, estimator=None, localiser=None,
+                dynamics=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -438,6 +439,12 @@ class BatchMPC:
         (ValueError).  wp_id / x0 of the returned dict belong to the PREDICTED pose, "pose" and everything that senses or
         judges the car stay true.  The returned dict also holds "delay": handle.rollout_delay() - queue, pred_pose, pred_s, now
         (None when n_steps = 0).
+        dynamics: None - the plant (if any) drives a kinematic car; a dynamics.Dynamics - per car, mass, yaw inertia, tyres with
+        slip and a friction limit and a speed controller with a gain and traction (K3y on the device, csrc/dynamics_core.hpp),
+        behind the plant's actuators; without `plant` an identity plant.Plant() is put in force (and "plant" is returned too).
+        Combines with `delay`; the controller, the estimator and the delay's prediction keep the kinematic model.  The returned
+        dict also holds "dynamics": handle.rollout_dynamics() - state, dyn_steps, sat_front, sat_rear, slip_max, alat_max (None
+        with n_steps = 0).  A later rollout without it has none again.
         estimator: None - the controller localises on the measured pose (plant) or the true one; an estimator.Estimator - per
         car a 3-state extended Kalman filter on the world pose in the controller's nominal model, with a measurement schedule
         (period, random dropouts), between the measurement and the controller (K3e on the device, csrc/estimator_core.hpp):
@@ -558,6 +565,15 @@ class BatchMPC:
         if ahead_traffic or getattr(self, "_lookahead_traffic_set", False):      # (the same rule for the flag)
             self.handle.rollout_set_lookahead_traffic(ahead_traffic)
             self._lookahead_traffic_set = ahead_traffic
+        if dynamics is not None and plant is None:      # (K3y drives the plant's actuators: the identity plant changes no bit)
+            from plant import Plant
+            plant = Plant()
+        if dynamics is not None:
+            self.handle.rollout_set_dynamics(dynamics.params(np.asarray(s).size))
+            self._dynamics_set = True
+        elif getattr(self, "_dynamics_set", False):      # (off again; a controller that never had dynamics calls nothing new)
+            self.handle.rollout_set_dynamics(None)
+            self._dynamics_set = False
         if plant is not None:
             self.handle.rollout_set_plant(plant.params(np.asarray(s).size), plant.seed, plant.car0, plant.step0)
             self._plant_set = True
@@ -585,6 +601,8 @@ class BatchMPC:
                 out["plant"] = self.handle.rollout_plant() if int(n_steps) > 0 else None
             if delay is not None:
                 out["delay"] = self.handle.rollout_delay() if int(n_steps) > 0 else None
+            if dynamics is not None:
+                out["dynamics"] = self.handle.rollout_dynamics() if int(n_steps) > 0 else None
             if estimator is not None:
                 out["estimator"] = self.handle.rollout_estimator() if int(n_steps) > 0 else None
             if localiser is not None:
@@ -612,6 +630,8 @@ class BatchMPC:
                 out["plant"] = self.handle.rollout_plant() if int(n_steps) > 0 else None
             if delay is not None:
                 out["delay"] = self.handle.rollout_delay() if int(n_steps) > 0 else None
+            if dynamics is not None:
+                out["dynamics"] = self.handle.rollout_dynamics() if int(n_steps) > 0 else None
             if estimator is not None:
                 out["estimator"] = self.handle.rollout_estimator() if int(n_steps) > 0 else None
             if localiser is not None:

@@ -750,6 +750,10 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   if (h->dl.B > 0) {              // ... and a delay in force keeps d and c; its registers start over (zeros: the cars stand for d steps)
     if (int rc = delay_reset(h, sl, h->dl.B, nullptr)) return rc;
   }
+  if (h->dy.B > 0) {              // ... and dynamics in force keep their parameters; the velocity states and accumulators start over
+    if (int rc = dynamics_reset(h, sl, h->dy.B, nullptr)) return rc;
+  }
+  h->dy.verified = false;         // (Ts may have changed)
   if (h->es.B > 0) {              // ... and an estimator in force keeps its parameters; every car is un-primed, the statistics start over
     if (int rc = est_reset(h, sl, h->es.B, nullptr, nullptr)) return rc;
   }

@@ -248,6 +248,20 @@ struct PlantState {
   Buf<double> ey;           // [2][max_batch]: ey_max, ey_sq
   Buf<int> steps;           // [max_batch]
   bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_plant)
+  std::vector<double> host_scale;      // [B]: every car's wheelbase_scale (host copy: the dynamics' check of a step)
+};
+
+// dynamic single-track plant of the rollout (mpmpc_rollout_set_dynamics; the law: dynamics_core.hpp): the setting, the cars'
+// velocity states and the accumulators - memory of its own, sized by max_batch when first set
+struct DynState {
+  int B = 0;                // > 0: dynamics are in force for B cars
+  Buf<double> prm;          // [max_batch][DY_PARAMS]
+  Buf<double> state;        // [max_batch][DY_STATE]: (vx, vy, r) after the last driven step
+  Buf<int> counts;          // [DY_COUNTS][max_batch]: dyn_steps, sat_front, sat_rear
+  Buf<double> peaks;        // [DY_PEAKS][max_batch]: slip_f, slip_r, alat
+  bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_dynamics)
+  std::vector<double> host_prm;      // [B][DY_PARAMS] (host copy: the check of a step needs Ts and the plant's wheelbase)
+  bool verified = false;    // dy_check_run passed for the setting, the plant and the Ts in force
 };
 
 // actuation delay of the rollout and its compensation (mpmpc_rollout_set_delay; the law: delay_core.hpp): the setting, the cars'
@@ -352,6 +366,7 @@ struct mpmpc_handle_s {
   TlkState tlk;
   PlantState pl;
   DelayState dl;
+  DynState dy;
   EstState es;
   LocState lc;
   IoState io;

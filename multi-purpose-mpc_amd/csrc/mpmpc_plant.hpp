@@ -121,6 +121,9 @@ int mpmpc_rollout_set_plant(mpmpc_handle h, int32_t B, const double* params, uin
   HIP_TRY(hipMemcpyAsync(h->pl.prm, params, sizeof(double) * PL_PARAMS * B, hipMemcpyHostToDevice, sl.stream));
   if (int rc = plant_reset(h, sl, B, act0)) return rc;
   HIP_TRY(hipStreamSynchronize(sl.stream));      // the caller's arrays have been read
+  h->pl.host_scale.resize((size_t)B);
+  for (int i = 0; i < B; ++i) h->pl.host_scale[(size_t)i] = params[(long)PL_PARAMS * i + PL_WHEELBASE_SCALE];
+  h->dy.verified = false;      // (the dynamics' lf and stability are checked against the plant's wheelbase)
   h->pl.B = B;
   h->pl.seed = seed;
   h->pl.car0 = car0;

@@ -7,7 +7,7 @@
 
 // What the step loop needs, and nothing else (host only).
 struct StepPlan {
-  bool per_car, discs, walls, traffic, perceiving, plant, delaying, estimating, localising, auditing, looking, ahead_traffic, recording;
+  bool per_car, discs, walls, traffic, perceiving, plant, delaying, dynamic, estimating, localising, auditing, looking, ahead_traffic, recording;
   int movers;
   MapView map;
   PathGeom geom;
@@ -21,7 +21,7 @@ struct StepPlan {
 
 // Every check and lay-out of a step of B cars, in this order (the first refusal that applies is the call's): the rollout's
 // state, n_steps, the per-car settings' B, stale generations, the recorder's B and capacity, the plant's B, the delay's B, the
-// estimator's B, the localiser's B, map and generation, the beams of a recorded scan, the audit, perception, the routes, the lookahead, the delay under a
+// dynamics' B, plant and stability, the estimator's B, the localiser's B, map and generation, the beams of a recorded scan, the audit, perception, the routes, the lookahead, the delay under a
 // lookahead, the estimator and the localiser under an assumed delay of DL_MAX.
 static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
@@ -48,6 +48,10 @@ static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   if (p.plant && h->pl.B != B) return fail(MPMPC_E_STATE, "the plant was set for another number of cars (mpmpc_rollout_set_plant)");
   p.delaying = h->dl.B > 0;
   if (p.delaying && h->dl.B != B) return fail(MPMPC_E_STATE, "the delay was set for another number of cars (mpmpc_rollout_set_delay)");
+  p.dynamic = h->dy.B > 0;
+  if (p.dynamic) {
+    if (int rc = dynamics_check_step(h, B)) return rc;
+  }
   p.estimating = h->es.B > 0;
   if (p.estimating && h->es.B != B)
     return fail(MPMPC_E_STATE, "the estimator was set for another number of cars (mpmpc_rollout_set_estimator)");
@@ -206,8 +210,21 @@ static void enqueue_advance_delay(mpmpc_handle h, Slot& sl, int B, const PlantVi
                      delay_view(h), pv);
 }
 
-// K3b, or - with a plant - K3p in its place, or - with a delay - K3q in place of either
+// K3y, in place of K3p (DELAY = false) or K3q<true> (true)
+template <bool DELAY>
+static void enqueue_advance_dynamics(mpmpc_handle h, Slot& sl, int B, long long k, const StepPlan& p) {
+  hipLaunchKernelGGL(mpmpc_advance_dynamics_kernel<DELAY>, dim3((B * h->cfg.N + 255) / 256), dim3(256), 0, sl.stream, B, h->cfg.N,
+                     h->cfg.wheelbase, h->ro.Ts, h->tab.kappa.get(), h->io.wp_id, h->io.x0, sl.status, sl.z, h->io.cc, h->ro.counter.get(),
+                     h->ro.alive.get(), h->ro.pose.get(), h->ro.s.get(), h->ro.u.get(), p.route, DELAY ? delay_view(h) : DelayView{},
+                     plant_view(h, k), dynamics_view(h));
+}
+
+// K3b, or - with a plant - K3p in its place, or - with a delay - K3q in place of either, or - with dynamics - K3y in place of K3p / K3q
 static void enqueue_advance(mpmpc_handle h, Slot& sl, int B, long long k, const StepPlan& p) {
+  if (p.dynamic) {
+    p.delaying ? enqueue_advance_dynamics<true>(h, sl, B, k, p) : enqueue_advance_dynamics<false>(h, sl, B, k, p);
+    return;
+  }
   const dim3 grid((B * h->cfg.N + 255) / 256);
   if (p.delaying)
     p.plant ? enqueue_advance_delay<true>(h, sl, B, plant_view(h, k)) : enqueue_advance_delay<false>(h, sl, B, PlantView{});
@@ -254,6 +271,7 @@ static void step_ran(mpmpc_handle h, int B, const StepPlan& p) {
   if (p.perceiving) h->per.B = B;
   if (p.plant) h->pl.ran = true;
   if (p.delaying) h->dl.ran = true;
+  if (p.dynamic) h->dy.ran = true;
   if (p.estimating) h->es.ran = true;
   if (p.localising) h->lc.ran = true;
   h->look.ran_B = p.looking ? B : 0;
@@ -293,7 +311,7 @@ extern "C" int mpmpc_rollout_step(mpmpc_handle h, int32_t B, int32_t n_steps) {
     if (p.ahead_traffic) tlk_enqueue_horizon(h, sl, B, p.map);                             // K0ht
     if (p.per_car) enqueue_car_corridor(h, sl, B, p);                                      // K0c
     if (int rc = launch_solve(h, sl, B, true, false)) return rc;                           // (the plant step reads z and the status only)
-    enqueue_advance(h, sl, B, k, p);                                                       // K3b / K3p
+    enqueue_advance(h, sl, B, k, p);                                                       // K3b / K3p / K3q / K3y
     if (p.ahead_traffic) tlk_enqueue_tracks(h, sl, B, p.map, p.route);                     // K3t: this step's plans, for the next one's K0ht
     if (rec) {
       enqueue_record_write(h, sl, B, p, rec);                                              // K3r write

@@ -189,6 +189,9 @@ def load_library(path: str | None = None):
     lib.mpmpc_plant_noise.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _dp]
     lib.mpmpc_rollout_set_delay.argtypes = [h, C.c_int32, _ip, _ip, _dp]
     lib.mpmpc_rollout_delay.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp]
+    lib.mpmpc_rollout_set_dynamics.argtypes = [h, C.c_int32, _dp, _dp]
+    lib.mpmpc_rollout_dynamics.argtypes = [h, C.c_int32, _dp, _ip, _dp]
+    lib.mpmpc_dynamics_drive.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]
     lib.mpmpc_rollout_set_estimator.argtypes = [h, C.c_int32, _dp, C.c_uint64, C.c_int32, C.c_int64, _dp, _dp]
     lib.mpmpc_rollout_estimator.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
     _i8p, _u8p = C.POINTER(C.c_int8), C.POINTER(C.c_uint8)
@@ -267,6 +270,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_project", "mpmpc_rollout_reroute", "mpmpc_rollout_routes",
            "mpmpc_rollout_set_plant", "mpmpc_rollout_plant", "mpmpc_plant_noise",
            "mpmpc_rollout_set_delay", "mpmpc_rollout_delay",
+           "mpmpc_rollout_set_dynamics", "mpmpc_rollout_dynamics", "mpmpc_dynamics_drive",
            "mpmpc_rollout_set_estimator", "mpmpc_rollout_estimator",
            "mpmpc_distance_field", "mpmpc_scan_match", "mpmpc_rollout_set_localiser", "mpmpc_rollout_localiser",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
@@ -711,6 +715,34 @@ class Handle:
         self._check(self.lib.mpmpc_rollout_delay(self._h, B, _d(out["queue"]), _d(out["pred_pose"]), _d(out["pred_s"]), _d(out["now"])))
         return out
 
+    # --- dynamic single-track plant of the rollout, per car
+    DYNAMICS_FIELDS = ("state", "dyn_steps", "sat_front", "sat_rear", "slip_max", "alat_max")
+
+    def rollout_set_dynamics(self, params, state0=None):
+        """The dynamic plant of the rollouts that follow (K3y; the law: csrc/dynamics_core.hpp): params [B, 11] per car -
+        dynamics.Dynamics.params(B): mass, inertia, lf, Cf, Cr, mu, speed_gain, a_drive, a_brake, v_dyn, substeps - or None for
+        none (the default).  state0 [B, 3]: the (vx, vy, r) the cars start from (None: zeros).  Needs a plant in force for the
+        same cars at the step (rollout_set_plant; plant.Plant() is the identity).  The controller keeps its kinematic model;
+        everything that senses or judges the car keeps the true pose.  May be called before rollout_init or between
+        rollout_step calls; rollout_init starts the state over, so a resumed run sets the dynamics after it."""
+        if params is None:
+            self._check(self.lib.mpmpc_rollout_set_dynamics(self._h, 0, None, None))
+            return
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 11:
+            raise ValueError("dynamics parameters must be [B, 11] (dynamics.Dynamics.params)")
+        s0 = None if state0 is None else np.ascontiguousarray(state0, dtype=np.float64).reshape(p.shape[0], 3)
+        self._check(self.lib.mpmpc_rollout_set_dynamics(self._h, p.shape[0], _d(p), _d(s0)))
+
+    def rollout_dynamics(self):
+        """-> dict of the dynamics' per-car state: state [B, 3] = (vx, vy, r) after the last driven step; dyn_steps / sat_front
+        / sat_rear [B]: the driven steps that took the dynamic branch and those in which a sub-step clipped the front / rear
+        axle; slip_max [B, 2]: max |front|, |rear| slip angle [rad]; alat_max [B]: max lateral acceleration [m/s^2]."""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        state, counts, peaks = np.zeros((B, 3)), np.zeros((3, B), np.int32), np.zeros((3, B))
+        self._check(self.lib.mpmpc_rollout_dynamics(self._h, B, _d(state), _i(counts), _d(peaks)))
+        return _dynamics_dict(state, counts, peaks)
+
     # --- pose estimator of the rollout, per car
     ESTIMATOR_FIELDS = ("est", "cov", "err2_max", "err2_sum", "meas2_sum", "head2_sum", "used", "steps")
 
@@ -1037,6 +1069,40 @@ def plant_noise(seed, car0, B, j0, n_steps, device=0):
                                _d(out) if out.size else _d(np.zeros(1)))
     if rc != 0:
         raise MpmpcError("mpmpc_plant_noise: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    return out
+
+
+def _dynamics_dict(state, counts, peaks):
+    return dict(state=state, dyn_steps=counts[0].copy(), sat_front=counts[1].copy(), sat_rear=counts[2].copy(),
+                slip_max=np.ascontiguousarray(peaks[:2].T), alat_max=peaks[2].copy())
+
+
+def dynamics_drive(params, cmds, length, Ts, state0=None, pose0=None, trace=False, device=0):
+    """The dynamic plant open loop on the device (csrc/dynamics_core.hpp, steps 2 - 4): params [B, 11]
+    (dynamics.Dynamics.params), cmds [n_steps, B, 2] = (v_act, d_act) what the actuators do at every step, length the wheelbase,
+    state0 [B, 3] / pose0 [B, 3] (None: zeros) -> dict(state, pose, dyn_steps, sat_front, sat_rear, slip_max, alat_max) after the
+    last step and - trace - "trace" [n_steps, B, 3], the pose after every step.  dynamics.Dynamics.step is the host evaluation."""
+    lib = load_library()
+    p = np.ascontiguousarray(params, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 11:
+        raise ValueError("dynamics parameters must be [B, 11] (dynamics.Dynamics.params)")
+    B = p.shape[0]
+    c = np.ascontiguousarray(cmds, dtype=np.float64)
+    if c.ndim != 3 or c.shape[1:] != (B, 2):
+        raise ValueError("cmds must be [n_steps, B, 2]")
+    n = c.shape[0]
+    s0 = None if state0 is None else np.ascontiguousarray(state0, dtype=np.float64).reshape(B, 3)
+    p0 = np.zeros((B, 3)) if pose0 is None else np.ascontiguousarray(pose0, dtype=np.float64).reshape(B, 3)
+    state, pose, counts, peaks = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros((3, B), np.int32), np.zeros((3, B))
+    tr = np.zeros((n, B, 3)) if trace else None
+    rc = lib.mpmpc_dynamics_drive(int(device), B, n, float(length), float(Ts), _d(p), _d(s0), _d(p0), _d(c) if c.size else _d(np.zeros(2)),
+                                  _d(state), _d(pose), _i(counts), _d(peaks), _d(tr) if trace and tr.size else None)
+    if rc != 0:
+        raise MpmpcError("mpmpc_dynamics_drive: %s (rc=%d)" % (lib.mpmpc_last_error().decode(), rc))
+    out = _dynamics_dict(state, counts, peaks)
+    out["pose"] = pose
+    if trace:
+        out["trace"] = tr
     return out
 
 
