@@ -497,6 +497,45 @@ int mpmpc_rollout_set_traffic(mpmpc_handle h, int32_t B, const int32_t* group, c
 int mpmpc_rollout_set_lookahead_traffic(mpmpc_handle h, int32_t enable);
 int mpmpc_rollout_tracks(mpmpc_handle h, int32_t B, int32_t* valid_out, int32_t* cells_out, double* tm_out);
 int mpmpc_rollout_lookahead_traffic(mpmpc_handle h, int32_t B, int32_t* who_out, int32_t* discs_out);
+/* Corridor commitment (K0k): K0c builds a car's row from nothing at every step, as ReferencePath.update_path_constraints does -
+ * the largest free segment at column 0, then the segment nearest the projection of the previous column's - so a waypoint can
+ * sit on one side of an obstacle while it is a far column and change sides in the step it becomes column 0, next to the
+ * obstacle.  With the setting, per car and off by default, a waypoint that was in the car's horizon in the step before chooses,
+ * among its free segments, the one nearest to what it chose then:
+ *   keep[B]          0: the car is off, its rows are the reference's bit for bit; a value in [1, +inf]: on, with that switch_ratio
+ *   memory           per car N entries, one per column of its last row: wp = cor_wp(wp_id + 1 + c), local to the car's route,
+ *                    or -1 (empty: the column had no free segment, or the car had no row), and the six numbers cor_bounds gave
+ *                    for the column (ub, lb and the border cells of the selection without the margin: x, y of the upper, x, y of
+ *                    the lower).  The memory of waypoint i is the entry with wp == i in the lowest column.
+ *   choice           at a column of waypoint i with two or more free segments, on a car that is on, when waypoint i has memory m:
+ *                    off = (|s_ub - m_ub| + |s_lb - m_lb|) / 2 over the candidates' border cells against the remembered ones -
+ *                    the reference's measure without the forward projection - and the first minimum is kept; if switch_ratio is
+ *                    finite and the longest candidate (column 0's span and tie rule) is longer than switch_ratio times the kept
+ *                    one, the longest is taken instead.  Every other column is decided as without the setting: forced with at
+ *                    most one segment, else the largest segment at column 0, else the nearest to the projection of the column
+ *                    before - whatever decided that one.
+ *   counters         three per car, accumulated for every car of the setting, the off cars included (a fleet is its own A/B):
+ *                    kept - columns decided from memory; switched - of those, where the ratio left the nearest candidate; moved -
+ *                    columns whose waypoint has memory, neither this step's (ub, lb) nor the remembered one collapsed (ub == lb),
+ *                    and ub < lb_mem || lb > ub_mem: the corridor of the waypoint jumped to a disjoint interval.
+ * The exact statement: csrc/commitment_core.hpp.  No kernel is added: a committed step runs another instantiation of K0c.  The
+ * verdicts -3 / -4, mpmpc_rollout_corridor and the recorder's rows are those of the committed rows.  The per-car world setters
+ * keep the memory - worlds that change under a committed car are the point; mpmpc_rollout_init and the setter empty it and zero
+ * the counters; mpmpc_rollout_reroute empties the memory of the cars it accepts.
+ *   mpmpc_rollout_set_commitment   keep == NULL: off.  mem_wp [B x N] and mem_rows [B x N x 6]: the memory of a resumed run (both
+ *                           or neither; NULL: empty).  MPMPC_E_ARG: B outside [1, max_batch], a keep that is neither 0 nor in
+ *                           [1, +inf] (NaN included), a mem_wp below -1, only one of the two memory pointers, or a block above
+ *                           256 MiB (B x N x 104 + B x 20 bytes).  A refused call leaves the previous setting in force.  May be
+ *                           called between mpmpc_rollout_step calls; after a change of map, path, routes or geometry the next
+ *                           step returns MPMPC_E_STATE until it is set again, like the per-car settings.  A step under the
+ *                           setting returns MPMPC_E_STATE without a per-car world in force for the same B (rows of the shared
+ *                           table have no per-car memory; empty disc lists will do) and with mpmpc_rollout_set_lookahead in force.
+ *   mpmpc_rollout_commitment   any pointer may be NULL.  counts_out [3][B]: kept, switched, moved; wp_out [B x N], rows_out
+ *                           [B x N x 6]: the memory the next step will read.  MPMPC_E_STATE unless a step of B cars ran under the
+ *                           setting in force.
+ * A rollout without the setting launches exactly what it launched before. */
+int mpmpc_rollout_set_commitment(mpmpc_handle h, int32_t B, const double* keep, const int32_t* mem_wp, const double* mem_rows);
+int mpmpc_rollout_commitment(mpmpc_handle h, int32_t B, int32_t* counts_out, int32_t* wp_out, double* rows_out);
 /* Walls: the second primitive of a car's world beside the discs - Map.add_boundary of the reference (src/map.py:139-155): a
  * line between two world points, stamped with skimage's line_aa.  A wall is (x0, y0, x1, y1) in map cells, the w2m of its
  * two end points, and occupies exactly the cells line_aa(x0, y0, x1, y1) produces (the law: csrc/wall_core.hpp).  A cell

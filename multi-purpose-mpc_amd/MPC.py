@@ -382,7 +382,7 @@ class BatchMPC:
 
     def rollout(self, s, poses, n_steps, cc0=None, obstacles=None, record=None, movers=None, traffic=None, audit=None,
                 walls=None, perception=None, routes=None, lookahead=None, plant=None, delay=None, estimator=None, localiser=None,
-                dynamics=None):
+                dynamics=None, commitment=None):
         """Drive B cars `n_steps` control steps on the device (localise, assemble, solve, fallback,
         plant update: the loop of src/simulation.py:134-140) and return the final state dict
         (s, pose, cc, wp_id, x0, u, status, counter, alive).  Needs a corridor table.
@@ -445,6 +445,13 @@ class BatchMPC:
         Combines with `delay`; the controller, the estimator and the delay's prediction keep the kinematic model.  The returned
         dict also holds "dynamics": handle.rollout_dynamics() - state, dyn_steps, sat_front, sat_rear, slip_max, alat_max (None
         with n_steps = 0).  A later rollout without it has none again.
+        commitment: None - every step builds a car's corridor row from nothing, as the reference does; a commitment.Commitment -
+        per car, a waypoint that was in the car's horizon in the step before chooses, among its free segments, the one nearest
+        to what it chose then (K0k: the KEEP instantiations of K0c, csrc/commitment_core.hpp), so that the car does not change
+        sides of an obstacle in the step it reaches it.  Needs corridor='device'; with no per-car world given an empty list of
+        obstacles per car is put in force (the rows then are the table's, built per car).  Not with `lookahead` (ValueError).
+        The returned dict also holds "commitment": handle.rollout_commitment() - kept, switched, moved, wp, rows (None with
+        n_steps = 0).  A later rollout without it has none again.
         estimator: None - the controller localises on the measured pose (plant) or the true one; an estimator.Estimator - per
         car a 3-state extended Kalman filter on the world pose in the controller's nominal model, with a measurement schedule
         (period, random dropouts), between the measurement and the controller (K3e on the device, csrc/estimator_core.hpp):
@@ -510,6 +517,16 @@ class BatchMPC:
             if len(walls) != np.asarray(s).size:
                 raise ValueError("walls must hold one list of boundaries per car")
             wall_cells = [rp.map.boundary_walls(w) for w in walls]
+        if commitment is not None:
+            if self.corridor_cols is None:
+                raise ValueError("commitment needs corridor='device' (update_corridor_from_map): the rows are built per car")
+            if lookahead is not None:
+                raise ValueError("commitment and lookahead cannot be combined: the anticipating instantiations of the corridor "
+                                 "kernel keep no memory")
+            keep = commitment.keep(np.asarray(s).size)
+            if all(v is None for v in (obstacles, movers, traffic, walls)):      # (a per-car world with nothing in it)
+                obstacles = [[] for _ in range(np.asarray(s).size)]
+                discs = [rp.map.obstacle_discs(obs) for obs in obstacles]
         if perception is not None and self.corridor_cols is None:
             raise ValueError("perception needs corridor='device' (update_corridor_from_map): the map lives on the device")
         if lookahead is not None and self.corridor_cols is None:
@@ -591,6 +608,7 @@ class BatchMPC:
             self._set_delay(delay_arrays)
             self._set_estimator(est_args)
             self._set_localiser(localiser, np.asarray(s).size)
+            self._set_commitment(None if commitment is None else keep)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             if audit is not None:
@@ -603,6 +621,8 @@ class BatchMPC:
                 out["delay"] = self.handle.rollout_delay() if int(n_steps) > 0 else None
             if dynamics is not None:
                 out["dynamics"] = self.handle.rollout_dynamics() if int(n_steps) > 0 else None
+            if commitment is not None:
+                out["commitment"] = self.handle.rollout_commitment() if int(n_steps) > 0 else None
             if estimator is not None:
                 out["estimator"] = self.handle.rollout_estimator() if int(n_steps) > 0 else None
             if localiser is not None:
@@ -619,6 +639,7 @@ class BatchMPC:
             self._set_delay(delay_arrays)
             self._set_estimator(est_args)
             self._set_localiser(localiser, np.asarray(s).size)
+            self._set_commitment(None if commitment is None else keep)
             self.handle.rollout_step(n_steps)
             out = self.handle.rollout_state()
             out["trace"] = self.handle.rollout_trace()
@@ -632,6 +653,8 @@ class BatchMPC:
                 out["delay"] = self.handle.rollout_delay() if int(n_steps) > 0 else None
             if dynamics is not None:
                 out["dynamics"] = self.handle.rollout_dynamics() if int(n_steps) > 0 else None
+            if commitment is not None:
+                out["commitment"] = self.handle.rollout_commitment() if int(n_steps) > 0 else None
             if estimator is not None:
                 out["estimator"] = self.handle.rollout_estimator() if int(n_steps) > 0 else None
             if localiser is not None:
@@ -639,6 +662,15 @@ class BatchMPC:
         finally:
             self.handle.rollout_record(0, B=np.asarray(s).size)      # later rollouts are unrecorded again
         return out
+
+    def _set_commitment(self, keep):
+        """behind rollout_init, which empties the memory: the commitment of this run (Commitment.keep), or - None - off again"""
+        if keep is not None:
+            self.handle.rollout_set_commitment(keep)
+            self._commitment_set = True
+        elif getattr(self, "_commitment_set", False):      # (off again; a controller that never committed calls nothing new)
+            self.handle.rollout_set_commitment(None)
+            self._commitment_set = False
 
     def _set_delay(self, arrays):
         """behind rollout_init, which zeroes the registers: the delay of this run (Delay.arrays) with its commands in flight, or

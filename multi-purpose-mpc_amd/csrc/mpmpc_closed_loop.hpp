@@ -114,7 +114,13 @@ struct LookTrafficView {
   const int* tz;       // [B][S][N][3]: K0ht's horizon discs of the cars' traffic slots (through L2, like tab)
   int S;               // traffic slots per car
 };
-template <bool WALLS, bool LEAD = false, bool TRAF = false>
+// KEEP (mpmpc_rollout_set_commitment; the law: commitment_core.hpp): the car's memory of the step before - the waypoints of its N
+// entries staged in LDS behind everything else (N ints), the entries' rows read from memory where a column has one - decides
+// multi-segment columns by rule 1 (cmt_select_car_one in place of cor_select_car_one), and every lane writes the entries of its
+// columns into the OTHER buffer of the memory (the host swaps the two per step: no lane reads what another writes) and counts
+// kept / switched / moved, reduced over the wave and added to the car's counters by lane 0.  A fourth template parameter and an
+// empty view otherwise (KeepNone / KeepView: mpmpc_commitment.hpp): the instantiations <., ., ., false> keep their instructions.
+template <bool WALLS, bool LEAD = false, bool TRAF = false, bool KEEP = false>
 __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, PathGeom g, int N, double min_width,
                                                                 double safety_margin, const double* __restrict__ segs,
                                                                 const int* __restrict__ nseg, const double* __restrict__ wpc,
@@ -125,8 +131,10 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
                                                                 int* __restrict__ flag, double* __restrict__ lb,
                                                                 double* __restrict__ ub, WallView wv,
                                                                 const int* __restrict__ route,
-                                                                std::conditional_t<TRAF, LookTrafficView, std::conditional_t<LEAD, LookView, LookNone>> lk) {
+                                                                std::conditional_t<TRAF, LookTrafficView, std::conditional_t<LEAD, LookView, LookNone>> lk,
+                                                                std::conditional_t<KEEP, KeepView, KeepNone> km) {
   static_assert(LEAD || !TRAF, "the traffic horizon needs the leads");
+  static_assert(!KEEP || !LEAD, "commitment under a lookahead is not supported");
   constexpr int PENDING = -1000000;
   // Route fleets: the car's view of the path - the geometry's base pointers and K0a's caches (indexed by GLOBAL row) moved to the
   // first row of its route, n_wp and circular the route's (route_view: corridor_core.hpp); wp_id is local.
@@ -172,6 +180,9 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
     ts = lk.S < nd ? lk.S : nd;     // (the layout gives every car S slots)
     tzb = lk.tz + (long)b * lk.S * N * 3;
   }
+  int* mwp = whd + (WALLS ? WALL_HDR * COR_MAX_WALLS : 0);           // [N] the waypoints of the car's memory (KEEP only)
+  if constexpr (KEEP)
+    for (int k = lane; k < N; k += 64) mwp[k] = km.wp_old[(long)b * N + k];
   if (lane == 0) s_over = 0;
   __syncthreads();
   const int wp = wp_id[b] + 1;
@@ -276,11 +287,49 @@ __global__ __launch_bounds__(64) void mpmpc_car_corridor_kernel(MapView map, Pat
     }
   };
   const int verdict = cnt(0) == 0 ? COR_ROW_BLOCKED : (s_over ? COR_ROW_OVERFLOW : COR_ROW_OK);   // the reference raises at column 0 first
-  for (int n = lane; n < N; n += 64) {
-    double u = 0.0, l = 0.0;
-    if (verdict == COR_ROW_OK) cor_select_car_one(g, wp, n, safety_margin, cnt, forced, seg, &u, &l);
-    ub[(long)b * N + n] = u;
-    lb[(long)b * N + n] = l;
+  if constexpr (KEEP) {
+    const double keep = km.keep[b];
+    const double* mrow = km.rows_old + (long)b * N * COR_WPC;
+    auto mem_wp = [&](int c) { return mwp[c]; };
+    auto mem = [&](int i, double* m) {
+      const int c = cmt_find(N, mem_wp, i);
+      if (c < 0) return false;
+      for (int k = 0; k < COR_WPC; ++k) m[k] = mrow[(long)c * COR_WPC + k];
+      return true;
+    };
+    int n_kept = 0, n_switched = 0, n_moved = 0;
+    for (int n = lane; n < N; n += 64) {
+      double o[COR_WPC] = {0, 0, 0, 0, 0, 0};
+      int how = 0;
+      if (verdict == COR_ROW_OK) cmt_select_car_one(g, wp, n, safety_margin, keep, cnt, forced, seg, mem, o, &how);
+      ub[(long)b * N + n] = o[0];
+      lb[(long)b * N + n] = o[1];
+      const int i = cor_wp(g, wp + n);
+      const bool held = verdict == COR_ROW_OK && cnt(n) >= 1;      // the entry of column n (else: empty)
+      km.wp_new[(long)b * N + n] = held ? i : CMT_EMPTY;
+      for (int k = 0; k < COR_WPC; ++k) km.rows_new[((long)b * N + n) * COR_WPC + k] = held ? o[k] : 0.0;
+      n_kept += how & CMT_KEPT ? 1 : 0;
+      n_switched += how & CMT_SWITCHED ? 1 : 0;
+      const int c = cmt_find(N, mem_wp, i);
+      if (c >= 0 && cmt_moved(o[0], o[1], mrow[(long)c * COR_WPC], mrow[(long)c * COR_WPC + 1])) ++n_moved;
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+      n_kept += __shfl_down(n_kept, d);
+      n_switched += __shfl_down(n_switched, d);
+      n_moved += __shfl_down(n_moved, d);
+    }
+    if (lane == 0) {
+      km.counts[b] += n_kept;
+      km.counts[km.stride + b] += n_switched;
+      km.counts[2 * km.stride + b] += n_moved;
+    }
+  } else {
+    for (int n = lane; n < N; n += 64) {
+      double u = 0.0, l = 0.0;
+      if (verdict == COR_ROW_OK) cor_select_car_one(g, wp, n, safety_margin, cnt, forced, seg, &u, &l);
+      ub[(long)b * N + n] = u;
+      lb[(long)b * N + n] = l;
+    }
   }
   if (lane == 0) {
     flag[b] = verdict;
@@ -759,6 +808,9 @@ int mpmpc_rollout_init(mpmpc_handle h, int32_t B, double Ts, const double* cum_l
   }
   if (h->lc.B > 0) {              // ... and so does a localiser in force: its setting and its field stay
     if (int rc = loc_reset(h, sl, h->lc.B, nullptr)) return rc;
+  }
+  if (h->cm.B > 0) {              // ... and a commitment in force keeps its setting; the memory is emptied, the counters start over
+    if (int rc = commitment_reset(h, sl)) return rc;
   }
   return aud_reset(h, B);         // ... and so does the audit (mpmpc_footprint.hpp)
 }

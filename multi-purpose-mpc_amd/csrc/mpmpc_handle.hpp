@@ -319,6 +319,21 @@ struct LocState {
   bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_localiser)
 };
 
+// corridor commitment of the rollout (mpmpc_rollout_set_commitment; the law: commitment_core.hpp): the setting, every car's memory
+// of its last row - twice: a step of K0c<., ., ., true> reads buffer `cur` and writes the other, then they swap - and the counters;
+// one block of its own, sized by the setting's B
+struct CmtState {
+  int B = 0;                // > 0: the commitment is in force for B cars
+  unsigned gen = 0;         // base_gen the setting was made against
+  Buf<char> block;          // keep [B] doubles, rows [2][B][N][COR_WPC] doubles, wp [2][B][N] ints, counts [CMT_COUNTS][B] ints
+  int cur = 0;              // the buffer that holds the memory of the last step
+  bool ran = false;         // a step ran under the setting in force (mpmpc_rollout_commitment)
+  double* keep() const { return (double*)block.get(); }
+  double* rows(int which, int N) const { return keep() + B + (size_t)which * B * N * COR_WPC; }
+  int* wp(int which, int N) const { return (int*)(keep() + B + (size_t)2 * B * N * COR_WPC) + (size_t)which * B * N; }
+  int* counts(int N) const { return wp(0, N) + (size_t)2 * B * N; }
+};
+
 // per-batch inputs and host staging
 struct IoState {
   // the inputs of a batch lie back to back in ONE device block (wp_id, x0, cc, lb, ub, laid out for the batch size
@@ -369,6 +384,7 @@ struct mpmpc_handle_s {
   DynState dy;
   EstState es;
   LocState lc;
+  CmtState cm;
   IoState io;
   // ---- Launch slots: what ONE solve launch in flight owns - its stream, its output block, its tail lists and its deferred-tail
   // state.  slot[0] is made by mpmpc_create (its stream before anything else touches the device) and is all a handle needs that

@@ -25,7 +25,7 @@
 //   K0 / K3 / K4                corridor tables from the map and the closed-loop rollout (mpmpc_closed_loop.hpp: the kernels, the
 //                               setters and getters; mpmpc_rollout_step.hpp, behind the features it drives: the step itself - its
 //                               plan, one enqueue function per kernel, the loop), the plant K3n / K3p (mpmpc_plant.hpp), the
-//                               actuation delay K3d / K3q (mpmpc_delay.hpp), the dynamic plant K3y (mpmpc_dynamics.hpp), the pose estimator K3e (mpmpc_estimator.hpp), the lidar localisation K0d / K3l (mpmpc_localiser.hpp), the lookaheads' entry points (mpmpc_lookahead.hpp), perception K0s (mpmpc_perception.hpp),
+//                               actuation delay K3d / K3q (mpmpc_delay.hpp), the dynamic plant K3y (mpmpc_dynamics.hpp), the pose estimator K3e (mpmpc_estimator.hpp), the lidar localisation K0d / K3l (mpmpc_localiser.hpp), the corridor commitment K0k (mpmpc_commitment.hpp), the lookaheads' entry points (mpmpc_lookahead.hpp), perception K0s (mpmpc_perception.hpp),
 //                               the speed profile (mpmpc_speed_profile.hpp), the lidar K0l (mpmpc_lidar.hpp), the
 //                               footprint audit K0f (mpmpc_footprint.hpp), the walls K0w and K-world (mpmpc_walls.hpp), the
 //                               reference paths' static width K0p (mpmpc_path.hpp), the pose projection and the re-route of a
@@ -83,6 +83,7 @@ __device__ long long g_phase[4096 * 32];
 #include "dynamics_core.hpp"
 #include "estimator_core.hpp"
 #include "localiser_core.hpp"
+#include "commitment_core.hpp"
 
 using namespace mpmpc;
 
@@ -993,6 +994,7 @@ static int check_wp_ids(mpmpc_handle h, int B, const int32_t* wp_id) {
 #include "mpmpc_dynamics.hpp"
 #include "mpmpc_estimator.hpp"
 #include "mpmpc_localiser.hpp"
+#include "mpmpc_commitment.hpp"
 #include "mpmpc_closed_loop.hpp"
 #include "mpmpc_lookahead.hpp"
 #include "mpmpc_lidar.hpp"

@@ -143,6 +143,10 @@ int mpmpc_rollout_reroute(mpmpc_handle h, int32_t B, const int32_t* route, doubl
   HIP_TRY(hipStreamSynchronize(sl.stream));      // `rhdr` and `acc` leave scope; the mirror needs the verdicts
   t.routes.rerouted(B, route, acc.data());
   h->tlk.forget();      // (traffic lookahead: a plan track lies on the route it was made on - the whole fleet's start over)
+  if (h->cm.B > 0) {    // (commitment: a memory lies on the route it was made on - the accepted cars' are emptied)
+    if (int rc = commitment_rerouted(h, sl, B, acc.data())) return rc;
+    HIP_TRY(hipStreamSynchronize(sl.stream));
+  }
   if (accepted_out) std::memcpy(accepted_out, acc.data(), sizeof(int32_t) * (size_t)B);
   return MPMPC_OK;
 }

@@ -1,5 +1,5 @@
 // mpmpc_rollout_step of libmpmpc.so, part of the one translation unit mpmpc_hip.hip (included there behind every feature of a
-// step: mpmpc_closed_loop.hpp - the kernels K0c, K0m, K0t, K3a, K3b, K3r -, mpmpc_plant.hpp, mpmpc_delay.hpp, mpmpc_estimator.hpp, mpmpc_localiser.hpp, mpmpc_lookahead.hpp, mpmpc_lidar.hpp,
+// step: mpmpc_closed_loop.hpp - the kernels K0c, K0m, K0t, K3a, K3b, K3r -, mpmpc_plant.hpp, mpmpc_delay.hpp, mpmpc_estimator.hpp, mpmpc_localiser.hpp, mpmpc_commitment.hpp, mpmpc_lookahead.hpp, mpmpc_lidar.hpp,
 // mpmpc_perception.hpp and mpmpc_footprint.hpp).  A step is decided once (plan_step: every check and lay-out, in a fixed order),
 // then its kernels are enqueued in stream order, each from the one enqueue_* function that launches it, then the handle
 // remembers what ran (step_ran).  DESIGN.md section 4, "A rollout step", is the same list.
@@ -7,7 +7,7 @@
 
 // What the step loop needs, and nothing else (host only).
 struct StepPlan {
-  bool per_car, discs, walls, traffic, perceiving, plant, delaying, dynamic, estimating, localising, auditing, looking, ahead_traffic, recording;
+  bool per_car, discs, walls, traffic, perceiving, plant, delaying, dynamic, estimating, localising, auditing, looking, ahead_traffic, keeping, recording;
   int movers;
   MapView map;
   PathGeom geom;
@@ -22,7 +22,7 @@ struct StepPlan {
 // Every check and lay-out of a step of B cars, in this order (the first refusal that applies is the call's): the rollout's
 // state, n_steps, the per-car settings' B, stale generations, the recorder's B and capacity, the plant's B, the delay's B, the
 // dynamics' B, plant and stability, the estimator's B, the localiser's B, map and generation, the beams of a recorded scan, the audit, perception, the routes, the lookahead, the delay under a
-// lookahead, the estimator and the localiser under an assumed delay of DL_MAX.
+// lookahead, the estimator and the localiser under an assumed delay of DL_MAX, the commitment.
 static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
   if (int rc = h->ro.check(B, "the rollout's state was overwritten by an upload / solve / assemble on this handle: "
                               "call mpmpc_rollout_init again (or use a second handle for single solves)")) return rc;
@@ -102,6 +102,11 @@ static int plan_step(mpmpc_handle h, int B, int n_steps, StepPlan& p) {
     return fail(MPMPC_E_STATE, "a localiser is in force and a car's assumed delay is " + std::to_string(DL_MAX) +
                                ": the command that reached the wheels in the last step has left the register by then "
                                "(mpmpc_rollout_set_localiser / mpmpc_rollout_set_delay: assume at most " + std::to_string(DL_MAX - 1) + ")");
+  p.keeping = h->cm.B > 0;
+  if (p.keeping) {
+    if (int rc = commitment_check_step(h, B, p.per_car)) return rc;
+    p.car_lds += sizeof(int) * N;      // (the waypoints of the car's memory)
+  }
   return MPMPC_OK;
 }
 
@@ -187,18 +192,23 @@ static void enqueue_localise(mpmpc_handle h, Slot& sl, int B, const StepPlan& p)
                      h->ro.cum, h->cor.gx, h->cor.gy, h->cor.gpsi, s, pose, h->ro.alive, h->io.wp_id, h->io.x0, h->ro.shift, p.route);
 }
 
-// K0c: one argument pack, and one choice of its six instantiations by (walls, looking, ahead_traffic)
-template <bool WALLS, bool LEAD, bool TRAF, class Look>
-static void launch_car_corridor(mpmpc_handle h, Slot& sl, int B, const StepPlan& p, Look lk) {
-  hipLaunchKernelGGL((mpmpc_car_corridor_kernel<WALLS, LEAD, TRAF>), dim3(B), dim3(64), p.car_lds, sl.stream, p.map, p.geom, h->cfg.N,
+// K0c: one argument pack, and one choice of its eight instantiations by (walls, looking, ahead_traffic, keeping); a step that
+// keeps swaps the two buffers of the commitment's memory
+template <bool WALLS, bool LEAD, bool TRAF, bool KEEP = false, class Look, class Keep = KeepNone>
+static void launch_car_corridor(mpmpc_handle h, Slot& sl, int B, const StepPlan& p, Look lk, Keep km = KeepNone{}) {
+  hipLaunchKernelGGL((mpmpc_car_corridor_kernel<WALLS, LEAD, TRAF, KEEP>), dim3(B), dim3(64), p.car_lds, sl.stream, p.map, p.geom, h->cfg.N,
                      h->cor.built_min_width, h->cor.built_sm, h->cor.segs, h->cor.nseg, h->cor.forced_rows(h->tab), h->cor.line_cells,
                      h->cor.line_box, p.discs ? h->obs.obst_off.get() : nullptr /* a world of walls only */, p.plan_discs, h->io.wp_id,
-                     h->ro.alive.get(), h->obs.ro_flag.get(), h->io.lb, h->io.ub, p.plan_walls, p.route, lk);
+                     h->ro.alive.get(), h->obs.ro_flag.get(), h->io.lb, h->io.ub, p.plan_walls, p.route, lk, km);
 }
 static void enqueue_car_corridor(mpmpc_handle h, Slot& sl, int B, const StepPlan& p) {
   const LookView lk{p.look.car, p.look.tab};
   if (p.ahead_traffic) p.walls ? launch_car_corridor<true, true, true>(h, sl, B, p, p.look) : launch_car_corridor<false, true, true>(h, sl, B, p, p.look);
   else if (p.looking) p.walls ? launch_car_corridor<true, true, false>(h, sl, B, p, lk) : launch_car_corridor<false, true, false>(h, sl, B, p, lk);
+  else if (p.keeping) {
+    const KeepView km = commitment_view_and_swap(h);
+    p.walls ? launch_car_corridor<true, false, false, true>(h, sl, B, p, LookNone{}, km) : launch_car_corridor<false, false, false, true>(h, sl, B, p, LookNone{}, km);
+  }
   else p.walls ? launch_car_corridor<true, false, false>(h, sl, B, p, LookNone{}) : launch_car_corridor<false, false, false>(h, sl, B, p, LookNone{});
 }
 
@@ -274,6 +284,7 @@ static void step_ran(mpmpc_handle h, int B, const StepPlan& p) {
   if (p.dynamic) h->dy.ran = true;
   if (p.estimating) h->es.ran = true;
   if (p.localising) h->lc.ran = true;
+  if (p.keeping) h->cm.ran = true;
   h->look.ran_B = p.looking ? B : 0;
   h->look.ran_n = p.looking ? p.movers : 0;
   h->tlk.ran_B = p.ahead_traffic ? B : 0;

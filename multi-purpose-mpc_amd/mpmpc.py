@@ -189,6 +189,8 @@ def load_library(path: str | None = None):
     lib.mpmpc_plant_noise.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _dp]
     lib.mpmpc_rollout_set_delay.argtypes = [h, C.c_int32, _ip, _ip, _dp]
     lib.mpmpc_rollout_delay.argtypes = [h, C.c_int32, _dp, _dp, _dp, _dp]
+    lib.mpmpc_rollout_set_commitment.argtypes = [h, C.c_int32, _dp, _ip, _dp]
+    lib.mpmpc_rollout_commitment.argtypes = [h, C.c_int32, _ip, _ip, _dp]
     lib.mpmpc_rollout_set_dynamics.argtypes = [h, C.c_int32, _dp, _dp]
     lib.mpmpc_rollout_dynamics.argtypes = [h, C.c_int32, _dp, _ip, _dp]
     lib.mpmpc_dynamics_drive.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]
@@ -273,6 +275,7 @@ EXPORTS = ["mpmpc_version", "mpmpc_last_error", "mpmpc_device_count", "mpmpc_def
            "mpmpc_rollout_set_dynamics", "mpmpc_rollout_dynamics", "mpmpc_dynamics_drive",
            "mpmpc_rollout_set_estimator", "mpmpc_rollout_estimator",
            "mpmpc_distance_field", "mpmpc_scan_match", "mpmpc_rollout_set_localiser", "mpmpc_rollout_localiser",
+           "mpmpc_rollout_set_commitment", "mpmpc_rollout_commitment",
            "mpmpc_solve_staged", "mpmpc_staged_begin", "mpmpc_staged_end"]
 
 
@@ -742,6 +745,38 @@ class Handle:
         state, counts, peaks = np.zeros((B, 3)), np.zeros((3, B), np.int32), np.zeros((3, B))
         self._check(self.lib.mpmpc_rollout_dynamics(self._h, B, _d(state), _i(counts), _d(peaks)))
         return _dynamics_dict(state, counts, peaks)
+
+    # --- corridor commitment of the rollout, per car
+    COMMITMENT_FIELDS = ("kept", "switched", "moved", "wp", "rows")
+
+    def rollout_set_commitment(self, keep, memory=None):
+        """The corridor commitment of the rollouts that follow (K0k; the law: csrc/commitment_core.hpp): keep [B] per car -
+        commitment.Commitment.keep(B): 0 off, else the switch_ratio in [1, inf] - or None for none (the default).  A car that is
+        on lets every waypoint that was in its horizon in the step before choose, among its free segments, the one nearest to
+        what it chose then.  memory: None (empty) or (wp [B, N], rows [B, N, 6]) - rollout_commitment()'s of the run that is
+        resumed.  Needs a per-car world in force for the same cars at the step (rollout_set_obstacles with empty lists will
+        do); not together with rollout_set_lookahead.  May be called between rollout_step calls; rollout_init empties the
+        memory, so a resumed run sets the commitment after it."""
+        if keep is None:
+            self._check(self.lib.mpmpc_rollout_set_commitment(self._h, 0, None, None, None))
+            return
+        k = np.ascontiguousarray(keep, dtype=np.float64).reshape(-1)
+        wp = rows = None
+        if memory is not None:
+            wp = np.ascontiguousarray(memory[0], dtype=np.int32).reshape(k.size, self.cfg.N)
+            rows = np.ascontiguousarray(memory[1], dtype=np.float64).reshape(k.size, self.cfg.N, 6)
+        self._check(self.lib.mpmpc_rollout_set_commitment(self._h, k.size, _d(k), _i(wp), _d(rows)))
+
+    def rollout_commitment(self):
+        """-> dict of the commitment's per-car state: kept / switched / moved [B] - the columns decided from memory, those of
+        them where the ratio left the nearest candidate, and the columns whose corridor jumped to a disjoint interval, summed
+        over the steps since the setting or rollout_init; wp [B, N], rows [B, N, 6]: the memory the next step reads (wp -1: an
+        empty entry)."""
+        B = int(getattr(self, "_ro_B", 0))      # (0 before the first rollout_init: the library refuses it)
+        N = self.cfg.N
+        counts, wp, rows = np.zeros((3, B), np.int32), np.zeros((B, N), np.int32), np.zeros((B, N, 6))
+        self._check(self.lib.mpmpc_rollout_commitment(self._h, B, _i(counts), _i(wp), _d(rows)))
+        return dict(kept=counts[0], switched=counts[1], moved=counts[2], wp=wp, rows=rows)
 
     # --- pose estimator of the rollout, per car
     ESTIMATOR_FIELDS = ("est", "cov", "err2_max", "err2_sum", "meas2_sum", "head2_sum", "used", "steps")
